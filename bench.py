@@ -2,9 +2,14 @@
 """Headline benchmark: frames/sec of STFT -> mel-cepstrum (fl=400 fp=80 nfft=512 M=24,
 alpha=0.42, n_iter=10) on synthetic 16 kHz waveforms, one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]           (N = 1)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]           (N = 1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`metric`, `value`, `unit`, `ms_per_step`, `dtype`,
+`config`, ...).  `--full` adds every other measurement below (rooflines, the side measurements after the timed region, the other
+configs, the CPU baselines).  `--dump-outputs DIR` writes the mel-cepstra of the last timed step to DIR/mcep.npy (float32; the
+input is seeded, so two builds can be compared output for output).
 
 A "step" is one pass of the hot path over this rank's shard of utterances (inputs resident in
 HBM): fused STFT kernel -> mel-cepstral analysis kernel -> (N > 1) ONE in-place all-gather of the
@@ -16,7 +21,7 @@ Timing: an untimed clock ramp (--ramp-seconds, default 0.3 s of the same steps: 
 10 % slower), W warmup steps, then exactly K steps between barrier + synchronize; defaults K = 200, W = 20
 (0.2 s of GPU time).  HIP events bracket the two launches of every fourth timed step (per-kernel averages).
 
-Rank 0 prints ONE JSON line (contract in the task statement).  Besides the headline value it carries
+Rank 0 prints ONE JSON line (contract in the task statement).  With --full, besides the headline value it carries
   roofline        the dominant kernel (mel-cepstral analysis): bound "valu_issue" -- vector wave-instructions
                   issued per second against the machine's issue rate -- with the algorithmic-flop figure beside it;
   roofline_stft   the fused Frame+Window+rFFT stage (HBM bound, 1348 B/frame): the north star's ">= 50 %" number;
@@ -661,6 +666,26 @@ def emit(res: dict) -> str:
     return compact_line(res)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, out: torch.Tensor) -> None:
+    """--dump-outputs: what the timed step returned in its last step -- the (utterances, 200, 25) mel-cepstra -- as
+    <path>/mcep.npy (float32).  Above DUMP_LIMIT_BYTES a fixed, seeded sample of utterances is written instead, with their row
+    indices in <path>/mcep_rows.npy (float64)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    a = out.detach().float().cpu().numpy()
+    row_bytes = a[0].nbytes + 8 if a.shape[0] else 1
+    n_max = (DUMP_LIMIT_BYTES - (1 << 20)) // row_bytes   # (1 MB left for the headers)
+    if a.shape[0] > n_max:
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], n_max, replace=False))
+        np.save(os.path.join(path, "mcep_rows.npy"), rows.astype(np.float64))
+        a = a[rows]
+    np.save(os.path.join(path, "mcep.npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -686,12 +711,18 @@ def main():
                          "duration (what the roofline objects divide by).  2: every launch carries DSA_ALGO_OVERLAPPED_LAUNCHES -- its "
                          "short last round of tiles (204 800 frames = 6.25 rounds of the 2 048 wave slots) is packed onto 64 workgroups and "
                          "the other 192 CUs go to the next step's launch, which waits on the other stream (round 6: 0.5945 -> 0.5685 ms per "
-                         "step at 200 steps, -2 % at 20).  At N = 1 the default run measures this mode too, AFTER the timed region, and "
+                         "step at 200 steps, -2 % at 20).  At N = 1 a --full run measures this mode too, AFTER the timed region, and "
                          "carries it in the line as `two_streams`")
     ap.add_argument("--record-every", type=int, default=4,
                     help="HIP events bracket the two launches of every n-th step of the timed region")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the config 2/3/4 sub-benchmarks (N = 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beyond the headline figure: rooflines, the reference "
+                         "steps of the STFT stage, the two-stream / module-API / speech-like side measurements, the other "
+                         "configs and the CPU baselines (N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the mel-cepstra of the last timed step to DIR/mcep.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the config 2/3/4 sub-benchmarks (N = 1)")
     ap.add_argument("--algo", choices=["auto", "generic", "tuned"], default="auto")
     args = ap.parse_args()
 
@@ -850,48 +881,11 @@ def main():
     elapsed = float(t.item())
     assert out.shape == (B * world, FRAMES_PER_UTT, M1) and bool(torch.isfinite(out).all())
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+
     frames_rank = B * FRAMES_PER_UTT
-    # average duration and frame count of ONE launch (a launch covers one chunk)
-    t_stft = statistics.mean(e[0].elapsed_time(e[1]) for e, _ in ev_log) * 1e-3
-    t_mcep = statistics.mean(e[1].elapsed_time(e[2]) for e, _ in ev_log) * 1e-3
-    frames_launch = statistics.mean(nb for _, nb in ev_log) * FRAMES_PER_UTT
-    stft_measured_in = "the timed region (HIP events around single launches)"
-    k_stft_ref = None
-    if args.path == "fused" and rank == 0:
-        # The timed step is ONE launch whose prologue is the frame + window + rFFT stage: there is no STFT launch to bracket.  The
-        # stage's own record (`roofline_stft`) comes from reference steps of the two-kernel path run AFTER the timed region,
-        # bracketed exactly as the two-kernel path brackets them inside it (event, STFT, event, mel-cepstral kernel, event).
-        ref_log = []
-        nref = int(frames_launch // FRAMES_PER_UTT)
-        with torch.no_grad():
-            for i in range(12):
-                e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-                e[0].record()
-                Xr = ops.StftFn.apply(x[:nref], stft.window, stft.twiddle, FL, FP, NFFT, True, False, "constant", 1e-9, None, 3, algo)
-                e[1].record()
-                k_stft_ref = _lib.last_kernel()
-                ops.McepFn.apply(Xr, mcep.G, mcep.D, mcep.E, mcep.alpha_vector, NFFT, M, N_ITER, algo)
-                e[2].record()
-                if i >= 2:
-                    ref_log.append(e)
-            torch.cuda.synchronize()
-        t_stft = statistics.mean(e[0].elapsed_time(e[1]) for e in ref_log) * 1e-3
-        t_mcep_two = statistics.mean(e[1].elapsed_time(e[2]) for e in ref_log) * 1e-3
-        stft_measured_in = ("reference steps of the two-kernel path after the timed region (event, STFT, event, mel-cepstral kernel, event): "
-                            "the timed step is ONE launch, this stage is its prologue and writes no spectrogram")
     if rank == 0:
-        # the same two kernels back to back (no dispatch gap between an event and the launch): what a rocprofv3 kernel
-        # trace reports as the kernels' own durations
-        xl = x[: int(frames_launch // FRAMES_PER_UTT)]
-        with torch.no_grad():
-            Xl = stft(xl)
-            t_stft_b2b = gpu_time(lambda: ops.StftFn.apply(xl, stft.window, stft.twiddle, FL, FP, NFFT, True, False, "constant",
-                                                           1e-9, None, 3, algo), n=40) * 1e-3
-            t_mcep_b2b = gpu_time(lambda: ops.McepFn.apply(Xl, mcep.G, mcep.D, mcep.E, mcep.alpha_vector, NFFT, M, N_ITER, algo),
-                                  n=10) * 1e-3
-        k_stft = k_stft_ref or kernels["stft"]   # (one-launch step: the stage's stand-alone kernel from the reference steps)
-        pm_m, pm_s = pmc_static(kernels["mcep"]), pmc_static(k_stft)
-        ipf = pm_m["derived"]["valu_insts_per_frame"] if pm_m else None
         res = {
             "metric": "frames/sec STFT->mcep (fl=400 fp=80 nfft=512 M=24)",
             "value": frames_rank * world * args.steps / elapsed,
@@ -915,52 +909,93 @@ def main():
                 "arith": "float32 in / out / accumulate; the matrix chains of the mel-cepstral kernel run as 3-term "
                          "binary16 MFMA splits (hi/lo, dropped lo*lo: ~22-bit products), the STFT in packed float32",
             },
-            "roofline": (lambda dp: {
-                "kernel": kernels["mcep"], "bound": "f32_datapath (vector ALU + float32 matrix instructions share it)",
-                "achieved": dp["achieved"] if dp else None, "peak": F32_DATAPATH_PEAK_GCPS, "unit": "G datapath-cycles/s",
-                "frac": dp["frac"] if dp else None,
-                "traffic": pmc_traffic(kernels["mcep"], frames_launch), "avg_launch_ms": t_mcep * 1e3,
-                "algorithmic_frac": max((MCEP_F32_FLOP_PER_FRAME + (STFT_F32_FLOP_PER_FRAME if args.path == "fused" else 0)) / (FP32_PEAK_TFLOPS * 1e12),
-                                        MCEP_F16_FLOP_PER_FRAME / (F16_MFMA_PEAK_TFLOPS * 1e12)) * frames_launch / t_mcep,
-                "back_to_back_ms": t_mcep_b2b * 1e3, "frames_per_launch": frames_launch,
-                "datapath": dp,
-                "nominal_valu_issue": {"achieved": (ipf * frames_launch / t_mcep / 1e9) if ipf else None, "peak": VALU_ISSUE_PEAK_GIPS,
-                                       "unit": "G wave-instr/s", "frac": (ipf * frames_launch / t_mcep / 1e9 / VALU_ISSUE_PEAK_GIPS) if ipf else None,
-                                       "valu_insts_per_frame": ipf,
-                                       "note": "vector wave-instructions (static: rocprofv3 SQ_INSTS_VALU, profiles/) against the guide's 2 cycles per "
-                                               "wave64 instruction; the multiply-add class measures 4 cycles on this chip "
-                                               "(profiles/r03_issue_calibration.txt), so this figure cannot reach 1 for FMA-heavy code"},
-                "algorithmic": {"achieved": MCEP_FLOP_PER_FRAME * frames_launch / t_mcep / 1e12, "peak": FP32_PEAK_TFLOPS,
-                                "unit": "TFLOP/s", "frac": MCEP_FLOP_PER_FRAME * frames_launch / t_mcep / 1e12 / FP32_PEAK_TFLOPS,
-                                "flop_per_frame": MCEP_FLOP_PER_FRAME,
-                                "note": "flops of the composed-matrix algorithm (DESIGN.md 3.2), each counted once; NOT a unit utilisation: "
-                                        "the two matrix chains execute as binary16 products on the separate matrix pipe"},
-                "pmc": pm_m["derived"] if pm_m else None, "pmc_source": (pm_m["_source"] + " (static)") if pm_m else None,
-                "arith": "f16x3 split chains (fp32 accumulate) on the matrix pipe; 25x25 elimination as v_mfma_f32_4x4x1 rank-1 updates "
-                         "+ fp32 VALU",
-                "note": "achieved = float32-datapath cycles the kernel's instruction mix occupies (mix of the Newton-step loop read off the "
-                        "code object, tools/isa_mix.py; per-instruction cycles measured with rocprofv3 --pmc on tools/bench_issue.cpp, "
-                        "profiles/r03_issue_calibration.txt: multiply-add class 4, two-operand class 2, transcendental 8, 4x4x1 product 8) "
-                        "x frames / measured launch time; peak = 1024 SIMDs x 2.4 GHz.  Two waves per SIMD (256 registers)",
-                "power": {"socket_W_under_this_kernel": [1371, 1379], "socket_W_under_stft": [1316, 1333], "cap_W": 1400,
-                          "source": "profiles/r03_power_probe.txt (static: tools/power_probe.sh, rocm-smi while the kernel loops)",
-                          "note": "both headline kernels run at the socket's power cap; the kernel's cycle counter averages "
-                                  "1.99-2.09 GHz over a launch, so the nominal-clock peak above is not reachable"},
-            })(datapath_roofline(isa_mix("mcep_mfma_fwd_kernel_hILi8ELb1ELb0ELb0E" if args.path == "fused" else "mcep_mfma_fwd_kernel_hILi8ELb0ELb0ELb0E"), N_ITER, frames_launch, t_mcep)),
-            "roofline_stft": {
-                "kernel": k_stft, "bound": "hbm",
-                "achieved": STFT_BYTES_PER_FRAME * frames_launch / t_stft / 1e9,
-                "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": STFT_BYTES_PER_FRAME * frames_launch / t_stft / 1e9 / HBM_PEAK_GBS,
-                "traffic": pmc_traffic(k_stft, frames_launch), "avg_launch_ms": t_stft * 1e3,
-                "back_to_back_ms": t_stft_b2b * 1e3,
-                "frac_back_to_back": STFT_BYTES_PER_FRAME * frames_launch / t_stft_b2b / 1e9 / HBM_PEAK_GBS,
-                "pmc": pm_s["derived"] if pm_s else None, "pmc_source": (pm_s["_source"] + " (static)") if pm_s else None,
-                "bytes_per_frame": STFT_BYTES_PER_FRAME,
-                "measured_in": stft_measured_in,
-                "note": "avg_launch_ms: HIP events around single launches (what `frac` uses), between two mel-cepstral launches; "
-                        "back_to_back_ms: the same launch repeated between two events (module API, no mel-cepstral kernel in between)",
-            },
+        }
+    if rank == 0 and args.full:   # everything beyond the headline figure
+        # average duration and frame count of ONE launch (a launch covers one chunk)
+        t_stft = statistics.mean(e[0].elapsed_time(e[1]) for e, _ in ev_log) * 1e-3
+        t_mcep = statistics.mean(e[1].elapsed_time(e[2]) for e, _ in ev_log) * 1e-3
+        frames_launch = statistics.mean(nb for _, nb in ev_log) * FRAMES_PER_UTT
+        stft_measured_in = "the timed region (HIP events around single launches)"
+        k_stft_ref = None
+        if args.path == "fused":
+            # The timed step is ONE launch whose prologue is the frame + window + rFFT stage: there is no STFT launch to bracket.  The
+            # stage's own record (`roofline_stft`) comes from reference steps of the two-kernel path run AFTER the timed region,
+            # bracketed exactly as the two-kernel path brackets them inside it (event, STFT, event, mel-cepstral kernel, event).
+            ref_log = []
+            nref = int(frames_launch // FRAMES_PER_UTT)
+            with torch.no_grad():
+                for i in range(12):
+                    e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+                    e[0].record()
+                    Xr = ops.StftFn.apply(x[:nref], stft.window, stft.twiddle, FL, FP, NFFT, True, False, "constant", 1e-9, None, 3, algo)
+                    e[1].record()
+                    k_stft_ref = _lib.last_kernel()
+                    ops.McepFn.apply(Xr, mcep.G, mcep.D, mcep.E, mcep.alpha_vector, NFFT, M, N_ITER, algo)
+                    e[2].record()
+                    if i >= 2:
+                        ref_log.append(e)
+                torch.cuda.synchronize()
+            t_stft = statistics.mean(e[0].elapsed_time(e[1]) for e in ref_log) * 1e-3
+            t_mcep_two = statistics.mean(e[1].elapsed_time(e[2]) for e in ref_log) * 1e-3
+            stft_measured_in = ("reference steps of the two-kernel path after the timed region (event, STFT, event, mel-cepstral kernel, event): "
+                                "the timed step is ONE launch, this stage is its prologue and writes no spectrogram")
+        # the same two kernels back to back (no dispatch gap between an event and the launch): what a rocprofv3 kernel
+        # trace reports as the kernels' own durations
+        xl = x[: int(frames_launch // FRAMES_PER_UTT)]
+        with torch.no_grad():
+            Xl = stft(xl)
+            t_stft_b2b = gpu_time(lambda: ops.StftFn.apply(xl, stft.window, stft.twiddle, FL, FP, NFFT, True, False, "constant",
+                                                           1e-9, None, 3, algo), n=40) * 1e-3
+            t_mcep_b2b = gpu_time(lambda: ops.McepFn.apply(Xl, mcep.G, mcep.D, mcep.E, mcep.alpha_vector, NFFT, M, N_ITER, algo),
+                                  n=10) * 1e-3
+        k_stft = k_stft_ref or kernels["stft"]   # (one-launch step: the stage's stand-alone kernel from the reference steps)
+        pm_m, pm_s = pmc_static(kernels["mcep"]), pmc_static(k_stft)
+        ipf = pm_m["derived"]["valu_insts_per_frame"] if pm_m else None
+        res["roofline"] = (lambda dp: {
+            "kernel": kernels["mcep"], "bound": "f32_datapath (vector ALU + float32 matrix instructions share it)",
+            "achieved": dp["achieved"] if dp else None, "peak": F32_DATAPATH_PEAK_GCPS, "unit": "G datapath-cycles/s",
+            "frac": dp["frac"] if dp else None,
+            "traffic": pmc_traffic(kernels["mcep"], frames_launch), "avg_launch_ms": t_mcep * 1e3,
+            "algorithmic_frac": max((MCEP_F32_FLOP_PER_FRAME + (STFT_F32_FLOP_PER_FRAME if args.path == "fused" else 0)) / (FP32_PEAK_TFLOPS * 1e12),
+                                    MCEP_F16_FLOP_PER_FRAME / (F16_MFMA_PEAK_TFLOPS * 1e12)) * frames_launch / t_mcep,
+            "back_to_back_ms": t_mcep_b2b * 1e3, "frames_per_launch": frames_launch,
+            "datapath": dp,
+            "nominal_valu_issue": {"achieved": (ipf * frames_launch / t_mcep / 1e9) if ipf else None, "peak": VALU_ISSUE_PEAK_GIPS,
+                                   "unit": "G wave-instr/s", "frac": (ipf * frames_launch / t_mcep / 1e9 / VALU_ISSUE_PEAK_GIPS) if ipf else None,
+                                   "valu_insts_per_frame": ipf,
+                                   "note": "vector wave-instructions (static: rocprofv3 SQ_INSTS_VALU, profiles/) against the guide's 2 cycles per "
+                                           "wave64 instruction; the multiply-add class measures 4 cycles on this chip "
+                                           "(profiles/r03_issue_calibration.txt), so this figure cannot reach 1 for FMA-heavy code"},
+            "algorithmic": {"achieved": MCEP_FLOP_PER_FRAME * frames_launch / t_mcep / 1e12, "peak": FP32_PEAK_TFLOPS,
+                            "unit": "TFLOP/s", "frac": MCEP_FLOP_PER_FRAME * frames_launch / t_mcep / 1e12 / FP32_PEAK_TFLOPS,
+                            "flop_per_frame": MCEP_FLOP_PER_FRAME,
+                            "note": "flops of the composed-matrix algorithm (DESIGN.md 3.2), each counted once; NOT a unit utilisation: "
+                                    "the two matrix chains execute as binary16 products on the separate matrix pipe"},
+            "pmc": pm_m["derived"] if pm_m else None, "pmc_source": (pm_m["_source"] + " (static)") if pm_m else None,
+            "arith": "f16x3 split chains (fp32 accumulate) on the matrix pipe; 25x25 elimination as v_mfma_f32_4x4x1 rank-1 updates "
+                     "+ fp32 VALU",
+            "note": "achieved = float32-datapath cycles the kernel's instruction mix occupies (mix of the Newton-step loop read off the "
+                    "code object, tools/isa_mix.py; per-instruction cycles measured with rocprofv3 --pmc on tools/bench_issue.cpp, "
+                    "profiles/r03_issue_calibration.txt: multiply-add class 4, two-operand class 2, transcendental 8, 4x4x1 product 8) "
+                    "x frames / measured launch time; peak = 1024 SIMDs x 2.4 GHz.  Two waves per SIMD (256 registers)",
+            "power": {"socket_W_under_this_kernel": [1371, 1379], "socket_W_under_stft": [1316, 1333], "cap_W": 1400,
+                      "source": "profiles/r03_power_probe.txt (static: tools/power_probe.sh, rocm-smi while the kernel loops)",
+                      "note": "both headline kernels run at the socket's power cap; the kernel's cycle counter averages "
+                              "1.99-2.09 GHz over a launch, so the nominal-clock peak above is not reachable"},
+        })(datapath_roofline(isa_mix("mcep_mfma_fwd_kernel_hILi8ELb1ELb0ELb0E" if args.path == "fused" else "mcep_mfma_fwd_kernel_hILi8ELb0ELb0ELb0E"), N_ITER, frames_launch, t_mcep))
+        res["roofline_stft"] = {
+            "kernel": k_stft, "bound": "hbm",
+            "achieved": STFT_BYTES_PER_FRAME * frames_launch / t_stft / 1e9,
+            "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": STFT_BYTES_PER_FRAME * frames_launch / t_stft / 1e9 / HBM_PEAK_GBS,
+            "traffic": pmc_traffic(k_stft, frames_launch), "avg_launch_ms": t_stft * 1e3,
+            "back_to_back_ms": t_stft_b2b * 1e3,
+            "frac_back_to_back": STFT_BYTES_PER_FRAME * frames_launch / t_stft_b2b / 1e9 / HBM_PEAK_GBS,
+            "pmc": pm_s["derived"] if pm_s else None, "pmc_source": (pm_s["_source"] + " (static)") if pm_s else None,
+            "bytes_per_frame": STFT_BYTES_PER_FRAME,
+            "measured_in": stft_measured_in,
+            "note": "avg_launch_ms: HIP events around single launches (what `frac` uses), between two mel-cepstral launches; "
+                    "back_to_back_ms: the same launch repeated between two events (module API, no mel-cepstral kernel in between)",
         }
         if world == 1 and args.path == "fused":
             try:   # the other path of the same step, back to back (detail file only)
@@ -1078,6 +1113,7 @@ def main():
                 res["cpu_baseline_c_oracle"] = c_oracle_baseline()
             except Exception as e:  # the oracle is optional test infrastructure
                 res["cpu_baseline_c_oracle"] = {"error": str(e)}
+    if rank == 0:
         line = emit(res)
         print(line, flush=True)
     if world > 1:

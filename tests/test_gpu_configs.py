@@ -591,6 +591,56 @@ def test_bench_launches_its_own_ranks():
     assert d["n_gpus"] == 2 and d["steps"] == 4 and d["value"] > 0 and d["config"]["global_batch"] == 64
 
 
+def _bench_line(args, cwd):
+    import json
+    import subprocess
+    import sys
+
+    out = subprocess.run([sys.executable, os.path.join(cwd, "bench.py"), *args], cwd=cwd, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_dumps_the_outputs_of_its_last_step(tmp_path):
+    """A plain run (no --full) prints the headline line only -- none of the side measurements -- and --dump-outputs DIR holds what
+    the timed step returned in its last step: the mel-cepstra of bench.py's seeded input, bit for bit what fuse(stft, mcep) returns
+    for the same input through the module API."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B = 64
+    d = _bench_line(["--gpus", "1", "--steps", "5", "--warmup", "2", "--batch", str(B), "--ramp-seconds", "0",
+                     "--dump-outputs", str(tmp_path)], root)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 5 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["value"] == pytest.approx(B * 200 / (d["ms_per_step"] * 1e-3), rel=1e-3)
+    for k in ("roofline", "roofline_stft", "cpu_baseline", "two_streams", "module_api", "speech_like"):
+        assert k not in d, k
+    assert sorted(os.listdir(tmp_path)) == ["mcep.npy"]
+    got = np.load(tmp_path / "mcep.npy")
+    assert got.dtype == np.float32 and got.shape == (B, 200, 25)
+    x = torch.randn(B, 16000, device=DEV, generator=torch.Generator(device=DEV).manual_seed(1234))
+    stft, mcep = _modules()
+    fused = dsp.fuse(stft, mcep)
+    with torch.no_grad():
+        want = host(fused(x))
+    assert fused.last_path == "fused"
+    np.testing.assert_array_equal(got, want)
+
+
+def test_bench_full_run_carries_the_side_measurements():
+    """--full (without the long config / CPU legs) adds the rooflines and the side measurements after the timed region."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = _bench_line(["--gpus", "1", "--steps", "4", "--warmup", "1", "--batch", "64", "--ramp-seconds", "0", "--full",
+                     "--no-configs", "--no-cpu-baseline"], root)
+    assert d["steps"] == 4 and d["value"] > 0
+    for k in ("roofline", "roofline_stft", "two_streams", "module_api", "speech_like"):
+        assert k in d, k
+    assert d["roofline"]["avg_launch_ms"] > 0 and d["roofline_stft"]["avg_launch_ms"] > 0
+    assert "cpu_baseline" not in d
+
+
 @pytest.mark.parametrize("fl,fp,nfft,M,alpha", [(1200, 240, 2048, 49, 0.55), (1024, 256, 1024, 34, 0.55), (512, 128, 512, 30, 0.42)])
 def test_untuned_geometries_forward_as_whole_batch_launches(monkeypatch, fl, fp, nfft, M, alpha):
     """The 48 kHz set-ups of the reference's get_alpha table (fft_length 1024 / 2048, orders 34 .. 60) and any other

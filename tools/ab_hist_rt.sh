@@ -1,5 +1,5 @@
 for v in 1 0 1 0; do
-DSA_MCEP_HIST_RT=$v python bench.py --steps 20 --warmup 5 --no-cpu-baseline > /dev/null 2>&1
+DSA_MCEP_HIST_RT=$v python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > /dev/null 2>&1
 python - <<PY
 import json
 d=json.load(open('bench_detail.json'))['configs']

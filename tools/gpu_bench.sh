@@ -1,14 +1,14 @@
-# default bench (as the driver runs it) + kernel trace + PMC passes; outputs under gpurun_out/$1; ROUND (default r06) names the
+# the driver's bench command, the full bench (--full) + kernel trace + PMC passes; outputs under $OUT (named by $1); ROUND (default r06) names the
 # profile files the traffic record points at (copy gpurun_out/$1/pmc_<what>.txt to profiles/${ROUND}_pmc_<what>_$1.txt)
 ROUND=${ROUND:-r06}
 OUT=gpurun_out/$1
 mkdir -p $OUT
 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 cp bench_detail.json $OUT/bench_detail.json 2>/dev/null
 R=$PWD
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $R/$OUT/trace -o trace -- python $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-configs > $R/$OUT/trace.log 2>&1
+rocprofv3 --kernel-trace --stats -d $R/$OUT/trace -o trace -- python $R/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-configs > $R/$OUT/trace.log 2>&1
 cd $R
 DB=$(find $OUT/trace -name "*.db" | head -1)
 [ -n "$DB" ] && python tools/rocprof_db_summary.py $DB > $OUT/kernel_trace.txt

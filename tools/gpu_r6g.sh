@@ -2,7 +2,7 @@
 OUT=$GRAFT_REPO_ROOT/gpurun_out/r6g; mkdir -p $OUT
 for m in 1 2; do
 for s in 2 1; do
-  DSA_OVERLAP_MODE=$m timeout 300 python bench.py --streams $s --no-configs --no-cpu-baseline > $OUT/bench_m${m}_s$s.json 2> $OUT/err.txt
+  DSA_OVERLAP_MODE=$m timeout 300 python bench.py --full --streams $s --no-configs --no-cpu-baseline > $OUT/bench_m${m}_s$s.json 2> $OUT/err.txt
   python - <<PY
 import json
 d=json.load(open("$OUT/bench_m${m}_s$s.json"))
