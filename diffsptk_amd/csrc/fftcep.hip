@@ -349,10 +349,9 @@ static int fftcep_launch(bool bwd, const void* gout, const void* x, int64_t F, i
     }();
     if (n_iter > 0 && L >= 32 && (L & (L - 1)) == 0 && !direct_only) {   // full H x H products: FFT in LDS
         const size_t lds_fft = lds + sizeof(T) * (2 * (size_t)L + H);   // transform halves, real results, twiddles
-        // one wave per frame (DSA_FFTCEP_BLOCK overrides for A/B): the barriers between the butterfly passes become single-wave
-        // barriers and a compute unit holds four times as many frames
-        static const int forced = [] { const char* e = getenv("DSA_FFTCEP_BLOCK"); return e ? atoi(e) : 0; }();
-        const int block = forced > 0 ? forced : 64;
+        // one wave per frame: the barriers between the butterfly passes become single-wave barriers and a compute unit holds
+        // four times as many frames
+        const int block = 64;
         if (!bwd)
             hipLaunchKernelGGL((fftcep_fwd_kernel<T, true>), dim3((unsigned)F), dim3(block), lds_fft, st, (const T*)x, (long)F, H, N,
                                (const T*)A, (T)accel, n_iter, (T*)out, (unsigned long long*)masks);

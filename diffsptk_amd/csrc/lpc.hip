@@ -496,7 +496,7 @@ typedef float lp_f4a4 __attribute__((ext_vector_type(4), aligned(4)));
 template <int NE, int LC>   // NE = 8: operand elements per lane (512 samples); LC: the frame length at compile time (0: run time)
 __global__ __launch_bounds__(256, 3) void frame_window_lpc24_mfma_kernel(
     const float* __restrict__ x, long Tlen, long N, int L_rt, int P, int left, int mode, const float* __restrict__ w, double eps,
-    float* __restrict__ out, long total_sc, int sc_per_utt, unsigned* __restrict__ queue, int fpi)
+    float* __restrict__ out, long total_sc, int sc_per_utt, int fpi)
 {
     typedef float f4 __attribute__((ext_vector_type(4)));
     typedef _Float16 lp_h8 __attribute__((ext_vector_type(8)));
@@ -533,28 +533,11 @@ __global__ __launch_bounds__(256, 3) void frame_window_lpc24_mfma_kernel(
             const int i = 4 * g + r, lag = 16 * s_ + j - i;
             addr[s_][r] = (lag >= 0 && lag < kLpcM1) ? lag * DS + i : kLsArea - 64 + lane;
         }
-    // Items are dealt out statically, item = wave + k (number of waves), unless a counter is given (queue != NULL: tickets).  With
-    // the ticket counter every item and every wave's exit was an atomic on ONE address -- 5120 + 3072 of them per launch at the
-    // bench size, about one per 16 ns: the counter's throughput, not the arithmetic, set the launch time (0.105 of 0.135 ms were
-    // left with everything but the loads removed, tools/gpu_abl_lpc.sh).
+    // Items are dealt out statically, item = wave + k (number of waves).  (A ticket counter put an atomic on ONE address behind every
+    // item and every wave's exit -- 5120 + 3072 of them per launch at the bench size, about one per 16 ns: the counter's throughput,
+    // not the arithmetic, set the launch time: 0.135 against 0.087 ms.)
     const long nwaves_g = (long)gridDim.x * (blockDim.x >> 6);
-    long next_static = (long)blockIdx.x * (blockDim.x >> 6) + wave;
-    for (;;) {
-        long tk;
-        if (queue) {
-            unsigned ticket = 0;
-            if (lane == 0) ticket = atomicAdd(queue, 1u);
-            tk = (long)__builtin_amdgcn_readfirstlane(ticket);
-        } else {
-            tk = next_static;
-            next_static += nwaves_g;
-        }
-        if (tk >= total_sc) {
-            // (tickets: every wave draws exactly one past the end, so the counter stops at total_sc + the number of waves; the wave
-            // that drew the last of those hands it back zeroed -- DSA_LPC_SCRATCH_IS_CLEAN: no fill launch before the next call)
-            if (queue && lane == 0 && tk == total_sc + nwaves_g - 1) __hip_atomic_store(queue, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
-        }
+    for (long tk = (long)blockIdx.x * (blockDim.x >> 6) + wave; tk < total_sc; tk += nwaves_g) {
         const long b = tk / sc_per_utt;
         const long ci = tk - b * sc_per_utt;
         const long fbase = ci * fpi;
@@ -1683,11 +1666,10 @@ DSA_EXPORT int dsa_frame_window_lpc_fwd(const void* x, int64_t B, int64_t T, int
             // lag sums: float32 matrix instruction (default) or the float64 vector unit (DSA_LPC_LAGSUMS=f64: exact sums)
             static const bool exact_env = [] { const char* e = getenv("DSA_LPC_LAGSUMS"); return e && e[0] == 'f' && e[1] == '6'; }();
             const bool exact = exact_env || exact_flag;
-            static const bool tickets = [] { const char* e = getenv("DSA_LPC_TICKETS"); return e && e[0] == '1'; }();   // A/B: the ticket counter
             // ticket counter (the float64 kernel; the default kernel deals its items out statically and needs none): the first word of
             // the caller's scratch, zeroed in stream order before the launch unless the caller says it is
             unsigned* queue = (unsigned*)scratch;
-            if ((exact || tickets) && !scratch_clean && hipMemsetAsync(queue, 0, sizeof(unsigned), st) != hipSuccess)
+            if (exact && !scratch_clean && hipMemsetAsync(queue, 0, sizeof(unsigned), st) != hipSuccess)
                 return fail(DSA_ERR_LAUNCH, "frame_window_lpc: cannot reset the ticket counter%s");
             if (!exact && L <= 512) {
                 // three workgroups per CU need 4 (200 fpi + 5312) <= 53 KB: at most 41 frames per item, utterances split evenly.
@@ -1711,7 +1693,7 @@ DSA_EXPORT int dsa_frame_window_lpc_fwd(const void* x, int64_t B, int64_t T, int
         if (lds_m > 48 * 1024 && !ensure_dynamic_lds((const void*)frame_window_lpc24_mfma_kernel<NEV, LCV>, lds_m, attr_m))        \
             return fail(DSA_ERR_LAUNCH, "frame_window_lpc: cannot reserve LDS%s");                                                 \
         hipLaunchKernelGGL((frame_window_lpc24_mfma_kernel<NEV, LCV>), dim3((unsigned)wgs), dim3(256), lds_m, st, (const float*)x, \
-                           (long)T, (long)N, L, P, left, pad_mode, (const float*)w, eps, (float*)out, total_sc, sc_per_utt, tickets ? queue : nullptr, fpi); \
+                           (long)T, (long)N, L, P, left, pad_mode, (const float*)w, eps, (float*)out, total_sc, sc_per_utt, fpi); \
     } while (0)
                 if (L == 400) DSA_LPC_MFMA(8, 400);   // the 25 ms window at 16 kHz
                 else DSA_LPC_MFMA(8, 0);

@@ -595,9 +595,6 @@ int thsolve_quad24_fwd(const void* p, const void* q, const void* r, int64_t F, v
 #include "mcep_glogx_f16.h"
 #include "mcep_big_f16.h"
 #include "mcep_big4_f16.h"
-#ifdef DSA_MCEP_BWD_PAIR_EXPERIMENT   // round 5: built, measured, not adopted (tools/experiments/mcep_mfma_bwd_pair.h)
-#include "../../tools/experiments/mcep_mfma_bwd_pair.h"
-#endif
 namespace dsa {
 
 int mcep_mfma_supported(int nfft, int M, int dtype) { return dtype == DSA_F32 && nfft == 512 && M == 24; }
@@ -835,22 +832,6 @@ int mcep_mfma_bwd(const void* gmc, const void* X, const void* hist, int64_t F, i
                   const void* images, void* scratch, void* gX, hipStream_t st, bool has_workspace = false, bool hist_has_rt = false)
 {
     const float* hist_rt = hist_has_rt ? (const float*)hist + (size_t)(n_iter + 1) * (size_t)F * mm::M1 : nullptr;
-#ifdef DSA_MCEP_BWD_PAIR_EXPERIMENT
-    // round-5 experiment: pairs of waves that split the bins of a tile, two waves per SIMD (2.9 ms against 1.57: not adopted)
-    static const bool pair_on = [] { const char* e = getenv("DSA_MCEP_BWD_PAIR"); return !(e && e[0] == '0'); }();
-    if (pair_on) {
-        const int lds_p = mhp::P_LDS_FLOATS * 4;
-        static std::atomic<uint64_t> attr_p{0};
-        if (!ensure_dynamic_lds((const void*)mcep_mfma_bwd_pair_kernel, lds_p, attr_p))
-            return fail(DSA_ERR_LAUNCH, "mcep_mfma_bwd: cannot reserve the LDS operand images%s");
-        const long nt = (long)((F + 15) / 16);
-        long blocks_p = (nt + mhp::PAIRS - 1) / mhp::PAIRS;
-        if (blocks_p > 256) blocks_p = 256;
-        hipLaunchKernelGGL(mcep_mfma_bwd_pair_kernel, dim3((unsigned)blocks_p), dim3(512), lds_p, st, (const float*)gmc, (const float*)X,
-                           (const float*)hist, (long)F, n_iter, (const float*)av, (float*)gX, nt, (const _Float16*)images);
-        return check_launch("mcep_mfma_bwd_pair");
-    }
-#endif
     // With the forward's rt rows at hand the sweep runs on the two-waves-per-SIMD kernel (mcep_mfma_bwd2_f16.h); DSA_MCEP_BWD2=0: A/B
     const char* e2 = getenv("DSA_MCEP_BWD2");   // (read per call: the tests switch it)
     const bool bwd2_on = !(e2 && e2[0] == '0');
@@ -866,16 +847,14 @@ int mcep_mfma_bwd(const void* gmc, const void* X, const void* hist, int64_t F, i
     long blocks = (ntiles16 + waves - 1) / waves;
     long grid = blocks < 256 ? blocks : 256;
     // A last round that fills at most half of the wave slots is cut into pieces of Newton steps (see the kernel) when the caller's
-    // scratch carries the hand-over workspace behind the counters (DSA_ALGO_SCRATCH_HAS_WORKSPACE); DSA_MCEP_SPLIT=0: A/B
-    static const bool split_on = [] { const char* e = getenv("DSA_MCEP_SPLIT"); return !(e && e[0] == '0'); }();
+    // scratch carries the hand-over workspace behind the counters (DSA_ALGO_SCRATCH_HAS_WORKSPACE)
     const long slots = grid * waves, rounds = ntiles16 / slots, rest = ntiles16 - rounds * slots;
     int split_tiles = 0, split_pieces = 0;
-    if (!two && has_workspace && split_on && rounds >= 1 && rest > 0 && rest <= slots / 2 && rest <= 512 && n_iter >= 2) {
+    if (!two && has_workspace && rounds >= 1 && rest > 0 && rest <= slots / 2 && rest <= 512 && n_iter >= 2) {
         long pieces = slots / rest;
         if (pieces > n_iter) pieces = n_iter;
         if (pieces > rounds + 1) pieces = rounds + 1;
         if (pieces > 9) pieces = 9;   // one counter word of the scratch per piece level
-        if (const char* ep = getenv("DSA_MCEP_SPLIT_PIECES")) { const long cap = atol(ep); if (cap >= 2 && pieces > cap) pieces = cap; }   // (A/B)
         split_tiles = (int)rest;
         split_pieces = (int)pieces;
     }

@@ -186,10 +186,6 @@ static int th_launch(bool bwd, const void* gg, const void* p, const void* q, con
 {
     const size_t lds = sizeof(T) * ((size_t)n * (n + 1) + 2 * kThMax) + sizeof(int) * kThMax;
     long grid = F < 256L * 16 ? (long)F : 256L * 16;
-    static const bool lds_only = [] {
-        const char* e = getenv("DSA_THSOLVE_LDS");
-        return e && atoi(e) != 0;
-    }();
 #define DSA_TH_LAUNCH(NM)                                                                                                  \
     do {                                                                                                                   \
         if (!bwd)                                                                                                          \
@@ -199,10 +195,10 @@ static int th_launch(bool bwd, const void* gg, const void* p, const void* q, con
             hipLaunchKernelGGL((th_solve_bwd_kernel<T, NM>), dim3((unsigned)grid), dim3(64), lds, st, (const T*)gg, (const T*)p, \
                                (const T*)q, (const T*)r_or_g, (long)F, n, (T*)o1, (T*)o2, (T*)o3);                         \
     } while (0)
-    if (!lds_only && n <= 24) DSA_TH_LAUNCH(24);
-    else if (!lds_only && n <= 32) DSA_TH_LAUNCH(32);
-    else if (!lds_only && n <= 48) DSA_TH_LAUNCH(48);   // the orders of the 48 kHz set-ups (34 .. 60): rows in registers too
-    else if (!lds_only && n <= 64) DSA_TH_LAUNCH(64);
+    if (n <= 24) DSA_TH_LAUNCH(24);
+    else if (n <= 32) DSA_TH_LAUNCH(32);
+    else if (n <= 48) DSA_TH_LAUNCH(48);   // the orders of the 48 kHz set-ups (34 .. 60): rows in registers too
+    else if (n <= 64) DSA_TH_LAUNCH(64);
     else DSA_TH_LAUNCH(0);
 #undef DSA_TH_LAUNCH
     return check_launch(bwd ? "th_solve_bwd" : "th_solve_fwd");
@@ -729,11 +725,10 @@ template <typename T>
 static int zerodf_launch_fwd(const void* x, const void* b, int64_t B, int64_t Tlen, int64_t N, int M, int P, int z0, int ig,
                              void* y, hipStream_t st, double scale = 1.0, const void* acc = nullptr, void* ysum = nullptr)
 {
-    static const int variant = [] { const char* e = getenv("DSA_ZERODF"); return e ? atoi(e) : 0; }();   // 1: round-2 kernels (A/B)
     {
         int S, nf, G;
         size_t lds_r;
-        if ((variant == 0 || ysum || scale != 1.0) && zerodf_rows_plan(M, P, sizeof(T), S, nf, G, lds_r)) {
+        if (zerodf_rows_plan(M, P, sizeof(T), S, nf, G, lds_r)) {
             const long chunks = (N + nf - 1) / nf;
             // (the kernel is written for S = 4 or 8 samples per thread; 8 measured the same at P = 80 and is not instantiated)
             hipLaunchKernelGGL((zerodf_fwd_rows_kernel<T, 4>), dim3((unsigned)(B * chunks)), dim3(256), lds_r, st, (const T*)x,
@@ -742,14 +737,10 @@ static int zerodf_launch_fwd(const void* x, const void* b, int64_t B, int64_t Tl
         }
         if (ysum || scale != 1.0) return fail(DSA_ERR_UNSUPPORTED, "zerodf: the scaled / accumulating form needs P % 4 == 0 and M >= 16%s");
     }
-    {   // long filters: taps and samples blocked by four (DSA_ZERODF_SLICED=1 keeps the older sliced kernel: A/B)
-        static const bool sliced_only = [] {
-            const char* e = getenv("DSA_ZERODF_SLICED");
-            return e && atoi(e) != 0;
-        }();
+    {   // long filters: taps and samples blocked by four (the sliced kernel below takes what does not fit)
         const int NB = (M + 4) / 4, nt = (P + 3) / 4;
         const size_t lds_b = sizeof(T) * ((size_t)8 * NB + (size_t)(4 * nt + 4 * NB + 4) + (size_t)(256 / (nt > 0 ? nt : 1)) * 2 * 4 * nt);
-        if (!sliced_only && M >= 64 && P >= 4 && P <= 128 && lds_b <= 64 * 1024) {
+        if (M >= 64 && P >= 4 && P <= 128 && lds_b <= 64 * 1024) {
             hipLaunchKernelGGL((zerodf_fwd_blocked_kernel<T>), dim3((unsigned)(B * N)), dim3(256), lds_b, st, (const T*)x, (const T*)b,
                                (long)Tlen, (long)N, M, P, z0, ig, (T*)y);
             return check_launch("zerodf_blocked_fwd");
@@ -946,8 +937,7 @@ static int zerodf_launch_bwd(const void* gy, const void* x, const void* b, const
                              bool gb_accumulate = false)
 {
     const bool plain = scale == 1.0 && gx_add == nullptr && !gb_accumulate;
-    static const int variant = [] { const char* e = getenv("DSA_ZERODF"); return e ? atoi(e) : 0; }();   // 1: round-2 kernels (A/B)
-    const bool rows_ok = variant == 0 && !ig && P % 4 == 0 && P / 4 <= 64 && M >= 16;
+    const bool rows_ok = !ig && P % 4 == 0 && P / 4 <= 64 && M >= 16;
     if (rows_ok) {
         // filters of more than ~200 taps as a sum of pieces (the kernels keep one piece's rows of a few frames in LDS): piece c
         // = taps [c KC, c KC + Mc], zeroth index z0 - c KC; gx accumulates over the pieces, gb's columns are disjoint
@@ -1458,30 +1448,7 @@ DSA_EXPORT int dsa_mcep_newton_update(const void* rt, int64_t F, int32_t n, cons
 //   u = A^-1 gs (A is symmetric: the same batched solve), then per system
 //   grt[k] = -sum_{i + j = k} u_i s_j  -  [k < n] sum_{|i - j| = k} u_i s_j  +  [k < n] u_k      (Hankel, Toeplitz, right-hand side)
 namespace dsa {
-__global__ __launch_bounds__(256) void newton_update_bwd_sums_kernel(const float* __restrict__ u, const float* __restrict__ s, long F, int n,
-                                                                    float* __restrict__ grt)
-{
-    __shared__ float us[4][64], ss[4][64];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long f = (long)blockIdx.x * 4 + w;
-    const bool ok = f < F;
-    us[w][lane] = ok && lane < n ? u[f * n + lane] : 0.f;
-    ss[w][lane] = ok && lane < n ? s[f * n + lane] : 0.f;
-    __syncthreads();
-    if (!ok) return;
-    for (int k = lane; k < 2 * n - 1; k += 64) {
-        float acc = 0.f;
-        const int lo = k - (n - 1) > 0 ? k - (n - 1) : 0, hi = k < n - 1 ? k : n - 1;
-        for (int i = lo; i <= hi; ++i) acc -= us[w][i] * ss[w][k - i];
-        if (k < n) {
-            for (int i = 0; i + k < n; ++i) acc -= us[w][i] * ss[w][i + k] + (k > 0 ? us[w][i + k] * ss[w][i] : 0.f);
-            acc += us[w][k];
-        }
-        grt[f * (2 * n - 1) + k] = acc;
-    }
-}
-
-// Round 6: the same sums with ONE FRAME PER LANE, everything in registers.  The kernel above gives a wave to a frame and a lane one or two
+// Round 6: the sums with ONE FRAME PER LANE, everything in registers.  The round-5 kernel gave a wave to a frame and a lane one or two
 // of its 2 n - 1 sums, every multiply-add behind two LDS reads (143 us per 102 400 frames of order 49: a tenth of the 48 kHz analysis'
 // forward + backward).  Here a lane loads its frame's u and s rows (zero-padded to NMAX), runs the three sums fully unrolled at compile
 // time -- 2 NMAX^2 + NMAX multiply-adds, no memory access, no cross-lane operation -- and stores four results at a time.  The rows of a
@@ -1569,20 +1536,14 @@ DSA_EXPORT int dsa_mcep_newton_update_bwd(const void* gs, const void* rt, const 
     if (F == 0) return DSA_OK;
     if (int rc = thsolve_quadn_fwd(rt, 2 * n - 1, rt, 2 * n - 1, gs, n, nullptr, nullptr, F, n, u, (hipStream_t)stream)) return rc;
     // one frame per lane (round 6), whatever the batch: the two kernels sum in different orders, and a frame's bits must not depend on
-    // how many frames travel with it; DSA_SUMS_LANE=0: the wave-per-frame kernel (A/B)
-    static const bool lane_on = [] { const char* e = getenv("DSA_SUMS_LANE"); return !(e && e[0] == '0'); }();
-    if (lane_on) {
-        const dim3 g((unsigned)((F + 255) / 256));
-        if (n <= 36)
-            hipLaunchKernelGGL((dsa::newton_update_bwd_sums_lane_kernel<36>), g, dim3(256), 0, (hipStream_t)stream, (const float*)u, (const float*)sol,
-                               (long)F, (int)n, (float*)grt);
-        else
-            hipLaunchKernelGGL((dsa::newton_update_bwd_sums_lane_kernel<56>), g, dim3(256), 0, (hipStream_t)stream, (const float*)u, (const float*)sol,
-                               (long)F, (int)n, (float*)grt);
-        return dsa::check_launch("mcep_newton_update_bwd");
-    }
-    hipLaunchKernelGGL(dsa::newton_update_bwd_sums_kernel, dim3((unsigned)((F + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const float*)u,
-                       (const float*)sol, (long)F, (int)n, (float*)grt);
+    // how many frames travel with it
+    const dim3 g((unsigned)((F + 255) / 256));
+    if (n <= 36)
+        hipLaunchKernelGGL((dsa::newton_update_bwd_sums_lane_kernel<36>), g, dim3(256), 0, (hipStream_t)stream, (const float*)u, (const float*)sol,
+                           (long)F, (int)n, (float*)grt);
+    else
+        hipLaunchKernelGGL((dsa::newton_update_bwd_sums_lane_kernel<56>), g, dim3(256), 0, (hipStream_t)stream, (const float*)u, (const float*)sol,
+                           (long)F, (int)n, (float*)grt);
     return dsa::check_launch("mcep_newton_update_bwd");
 }
 

@@ -264,13 +264,7 @@ static void rows_gemm_launch_t(const void* c, int64_t F, int K, const void* A, i
     // rows of fewer than four values (of c, or of A): the single-load variant, one instantiation
     if (K < 4 || N < 4) return rows_gemm_launch_nt<FLAGS, 2, true>(c, F, K, A, lda, N, aux, ldaux, out, ldo, st);
     // column tiles per workgroup: the whole width when it fits eight tiles (every value of c is then read once), else eight.
-    // DSA_ROWS_GEMM_NT = 2 / 4 / 6 / 8 caps it (more, narrower workgroups for small batches: measurement knob).
-    int nt = (N + 15) / 16;
-    static const int cap = [] {
-        const char* e = getenv("DSA_ROWS_GEMM_NT");
-        return e ? atoi(e) : 0;
-    }();
-    if (cap >= 2 && nt > cap) nt = cap;
+    const int nt = (N + 15) / 16;
     if (nt <= 2) rows_gemm_launch_nt<FLAGS, 2, false>(c, F, K, A, lda, N, aux, ldaux, out, ldo, st);
     else if (nt <= 4) rows_gemm_launch_nt<FLAGS, 4, false>(c, F, K, A, lda, N, aux, ldaux, out, ldo, st);
     else if (nt <= 6) rows_gemm_launch_nt<FLAGS, 6, false>(c, F, K, A, lda, N, aux, ldaux, out, ldo, st);

@@ -773,8 +773,6 @@ __device__ unsigned long long g_stft_stamps[16];
 //                        (c) then the spectra Z in natural order, (d) finally the staged 4 x 257
 //                        output tile -- each use is dead before the next begins;
 //   t256[16][16] cf    : W256^(j k1), shared by the 4 frames;   fmax[kFPW].
-// ABL: 0 production | 1 no output stores | 2 no FFT butterflies | 3 no input staging
-//      (ablation knob for tools/bench_stft.cpp)
 // The workgroup IS one wave: LDS operations of a wave execute in order, so the phases only need a compiler
 // fence.  (__syncthreads() = s_waitcnt vmcnt(0) lgkmcnt(0) + s_barrier: its vmcnt(0) made every pass wait for the
 // previous pass's output stores before touching LDS.)
@@ -788,7 +786,7 @@ __device__ unsigned long long g_stft_stamps[16];
 // waves fit a SIMD; LDS is what limits them then, so two waves share a workgroup and with it the 2 KB twiddle table
 // (8 workgroups x 19.5 KB per CU).  The waves stay autonomous: each fills the whole table itself (identical values)
 // before its first use, and no barrier is ever needed.
-template <int ABL, bool ZMEAN, bool PLAIN = false, int LC = 0>
+template <bool ZMEAN, bool PLAIN = false, int LC = 0>
 __global__ __launch_bounds__(128, 4) void stft512_fwd_kernel(
     const float* __restrict__ x, long Tlen, long N, int L, int P, int left, int mode_arg,
     const float* __restrict__ w, const float* __restrict__ twiddle, float eps, int use_floor_arg,
@@ -854,7 +852,7 @@ __global__ __launch_bounds__(128, 4) void stft512_fwd_kernel(
         DSA_WAVE_SYNC();  // previous pass is done with the LDS tile (single-wave workgroup)
         STFT_STAMP(0);
         // ---- stage the shared waveform stretch (each sample read from HBM once) ----
-        if (ABL != 3) {
+        {
             const long g0 = frame0 * P - left;
             const int need = (nvalid - 1) * P + L;  // samples the valid frames touch
             const bool interior = g0 >= 0 && g0 + need <= Tlen;
@@ -876,7 +874,7 @@ __global__ __launch_bounds__(128, 4) void stft512_fwd_kernel(
         }
         DSA_WAVE_SYNC();
         STFT_STAMP(1);
-        if (PLAIN && ABL != 3) {   // issue the next pass's loads (no wait here)
+        if (PLAIN) {   // issue the next pass's loads (no wait here)
             long b2 = b + b_step;
             int ci2 = ci + ci_step;
             if (ci2 >= chunks_per_utt) {
@@ -940,7 +938,7 @@ __global__ __launch_bounds__(128, 4) void stft512_fwd_kernel(
         }
         DSA_WAVE_SYNC();  // every lane has its samples: the stretch may be overwritten
         STFT_STAMP(2);
-        if (ABL != 2) fft16<false>(v);
+        fft16<false>(v);
         STFT_STAMP(3);
 #pragma unroll
         for (int k1 = 0; k1 < 16; ++k1)  // twiddle, then transposed store: (k1, j) -> k1*17 + j (row stride 17: every
@@ -951,7 +949,7 @@ __global__ __launch_bounds__(128, 4) void stft512_fwd_kernel(
         for (int i = 0; i < 16; ++i) v[i] = zf[j * 17 + i];  // lane k1 = j reads A[i][k1]: 34 j floats apart, 16 distinct bank pairs
         DSA_WAVE_SYNC();
         STFT_STAMP(5);
-        if (ABL != 2) fft16<false>(v);
+        fft16<false>(v);
         STFT_STAMP(6);
 #pragma unroll
         for (int k0 = 0; k0 < 16; ++k0) zf[j + 16 * k0] = v[FFT16_OUT(k0)];  // Z[k1 + 16 k0], natural order
@@ -992,7 +990,7 @@ __global__ __launch_bounds__(128, 4) void stft512_fwd_kernel(
                 const cf X1 = {S.re + Pp.im, S.im - Pp.re};     // Z arrives halved (see t256)
                 const cf X2 = {S.re - Pp.im, -S.im - Pp.re};
                 if (complex_out) {
-                    if (f < nvalid && ABL != 1) {
+                    if (f < nvalid) {
                         y2[out0 + f * K + k] = make_float2(X1.re * osc, X1.im * osc);
                         y2[out0 + f * K + 256 - k] = make_float2(X2.re * osc, X2.im * osc);
                     }
@@ -1010,7 +1008,7 @@ __global__ __launch_bounds__(128, 4) void stft512_fwd_kernel(
             // the two real-valued end bins
             const float x0 = 2.f * (z0[f].re + z0[f].im), x256 = 2.f * (z0[f].re - z0[f].im);   // these two take Z[0] whole
             if (complex_out) {
-                if (f < nvalid && ABL != 1 && lane == 0) {
+                if (f < nvalid && lane == 0) {
                     y2[out0 + f * K] = make_float2(x0 * osc_edge, 0.f);
                     y2[out0 + f * K + 256] = make_float2(x256 * osc_edge, 0.f);
                 }
@@ -1062,7 +1060,7 @@ __global__ __launch_bounds__(128, 4) void stft512_fwd_kernel(
                         }
                         q = make_float4(o4[0], o4[1], o4[2], o4[3]);
                     }
-                    if (ABL != 1 || q.x == 123.456f) y4[t] = q;
+                    y4[t] = q;
                 }
             }
         } else {
@@ -1380,10 +1378,8 @@ static int gc2gc_launch(const void* c1, int64_t F, int n_in, int out_order, doub
     static std::atomic<uint64_t> lds_set{0};
     if (lds > 48 * 1024 && !ensure_dynamic_lds(reinterpret_cast<const void*>(&gc2gc_fused_kernel<T>), 150 * 1024, lds_set))
         return fail(DSA_ERR_LAUNCH, "gc2gc: cannot raise the dynamic LDS limit%s");
-    // short transforms: one wave per row (two butterflies per lane and pass, the passes' barriers are single-wave barriers);
-    // DSA_GC2GC_BLOCK overrides for A/B runs
-    static const int forced = [] { const char* e = getenv("DSA_GC2GC_BLOCK"); return e ? atoi(e) : 0; }();
-    const int block = forced > 0 ? forced : (nfft <= 1024 ? 64 : 256);
+    // short transforms: one wave per row (two butterflies per lane and pass, the passes' barriers are single-wave barriers)
+    const int block = nfft <= 1024 ? 64 : 256;
     hipLaunchKernelGGL((gc2gc_fused_kernel<T>), dim3((unsigned)F), dim3(block), lds, st, (const T*)c1, n_in, out_order, (T)g1, (T)g2, nfft,
                        (const T*)tw, flags, (T*)c2);
     return check_launch("gc2gc_fused");
@@ -1688,80 +1684,6 @@ static int stft512_lds_bytes(int L, int P, int* io_floats)
 }
 
 static int stft512_lds_bytes2() { return 2 * kFPW * kZS * 8 + 256 * 8 + 2 * kFPW * 4; }   // two waves + the shared table
-
-template <int ABL>
-static void stft512_launch(bool zmean, dim3 grid, int lds, hipStream_t st, const float* x, long T, long N, int L,
-                           int P, int left, int mode, const float* w, const float* tw, float eps, int use_floor,
-                           float floor_lin, int fmt, float* y, long total_chunks, int chunks_per_utt, int io_floats)
-{
-    // `grid` counts waves; they are paired into 128-thread workgroups that share the twiddle table
-    (void)lds;
-    const bool plain = !use_floor && fmt == DSA_SPEC_POWER && mode == DSA_PAD_CONSTANT;
-    const dim3 g2((grid.x + 1) / 2);
-    const int lds2 = stft512_lds_bytes2();
-    // DSA_STFT_PK (A/B knob): 2 = packed-float32 kernel with register-direct stores (stft_pk.h) where it applies
-    // (default), 1 = the same with the staged output tile, 0 = scalar-float32 kernel
-    static const int use_pk = [] {
-        const char* e = getenv("DSA_STFT_PK");
-        return e ? atoi(e) : 2;
-    }();
-    // (round 6: every pad mode -- the mode only changes what the passes that reach over an utterance's end read -- and, as an
-    //  instantiation of its own, zmean and the relative floor)
-    if (use_pk && ABL == 0 && fmt == DSA_SPEC_POWER && L == 400 && (P & 1) == 0 && 3 * P + 512 <= kFPW * kZS * 2) {
-        if (zmean || use_floor) {
-            hipLaunchKernelGGL((stft512_fwd_pk_kernel<0, 400, true, 0, false, 0, true>), g2, dim3(128), lds2, st, x, T, N, L, P, left, w, tw, eps, y,
-                               total_chunks, chunks_per_utt, (const float*)nullptr, 0.f, 0.f, 0, 0, mode, (int)zmean, use_floor ? floor_lin : -1.f);
-            return;
-        }
-        // a wave walks a RUN of consecutive passes (their shared samples come from its CU's cache, not from memory twice);
-        // DSA_STFT_RUN=0: the round-robin order of rounds 1-4 (A/B)
-        static const int run_env = [] { const char* e = getenv("DSA_STFT_RUN"); return e ? atoi(e) : 0; }();
-        const int run_len = run_env;
-        if (use_pk == 1)   // staged 16-byte stores (A/B)
-            hipLaunchKernelGGL((stft512_fwd_pk_kernel<0, 400, false>), g2, dim3(128), lds2, st, x, T, N, L, P, left, w, tw, eps, y,
-                               total_chunks, chunks_per_utt, (const float*)nullptr, 0.f, 0.f, 0, run_len, mode);
-#define DSA_PK_XCD(ABLV)                                                                                              \
-    hipLaunchKernelGGL((stft512_fwd_pk_kernel<ABLV, 400, true>), g2, dim3(128), lds2, st, x, T, N, L, P, left, w, tw, eps, y, \
-                       total_chunks, chunks_per_utt, (const float*)nullptr, 0.f, 0.f, 0, 0, mode)
-        else if (use_pk == 3) DSA_PK_XCD(1024);   // experiments (A/B): XCD-chunked workgroup order, C = 4 / 8 / 2, XCD-contiguous
-        else if (use_pk == 4) DSA_PK_XCD(4096);
-        else if (use_pk == 5) DSA_PK_XCD(2048);
-        else if (use_pk == 6) DSA_PK_XCD(256);
-        else if (use_pk == 8)   // four-wave workgroups: four adjacent passes per workgroup
-            hipLaunchKernelGGL((stft512_fwd_pk_kernel<0, 400, true, 0, false, 4>), dim3((grid.x + 3) / 4), dim3(256),
-                               4 * kFPW * kZS * 8 + 256 * 8 + 64, st, x, T, N, L, P, left, w, tw, eps, y, total_chunks,
-                               chunks_per_utt, (const float*)nullptr, 0.f, 0.f, 0, run_len, mode);
-        else if (use_pk == 9) {   // eight-wave workgroups
-            static std::atomic<uint64_t> a9{0};
-            ensure_dynamic_lds(reinterpret_cast<const void*>(&stft512_fwd_pk_kernel<0, 400, true, 0, false, 8>), 8 * kFPW * kZS * 8 + 256 * 8 + 64, a9);
-            hipLaunchKernelGGL((stft512_fwd_pk_kernel<0, 400, true, 0, false, 8>), dim3((grid.x + 7) / 8), dim3(512),
-                               8 * kFPW * kZS * 8 + 256 * 8 + 64, st, x, T, N, L, P, left, w, tw, eps, y, total_chunks,
-                               chunks_per_utt, (const float*)nullptr, 0.f, 0.f, 0, run_len, mode);
-        } else if (use_pk == 10) {   // sixteen-wave workgroups: a CU's whole complement of waves on sixteen adjacent passes
-            static std::atomic<uint64_t> a10{0};
-            ensure_dynamic_lds(reinterpret_cast<const void*>(&stft512_fwd_pk_kernel<0, 400, true, 0, false, 16>), 16 * kFPW * kZS * 8 + 256 * 8 + 64, a10);
-            hipLaunchKernelGGL((stft512_fwd_pk_kernel<0, 400, true, 0, false, 16>), dim3((grid.x + 15) / 16), dim3(1024),
-                               16 * kFPW * kZS * 8 + 256 * 8 + 64, st, x, T, N, L, P, left, w, tw, eps, y, total_chunks,
-                               chunks_per_utt, (const float*)nullptr, 0.f, 0.f, 0, run_len, mode);
-        } else if (use_pk == 7)   // the stretch fetched two passes ahead (two register sets, window table in LDS, four-wave workgroups)
-            hipLaunchKernelGGL((stft512_fwd_pk_kernel<0, 400, true, 0, true>), dim3((grid.x + 3) / 4), dim3(256),
-                               4 * kFPW * kZS * 8 + 256 * 8 + 16 * 13 * 8 + 64, st, x, T, N, L, P, left, w, tw, eps, y, total_chunks,
-                               chunks_per_utt, (const float*)nullptr, 0.f, 0.f, 0, run_len, mode);
-#undef DSA_PK_XCD
-        else               // 8-byte stores straight from the split's registers (default)
-            hipLaunchKernelGGL((stft512_fwd_pk_kernel<0, 400, true>), g2, dim3(128), lds2, st, x, T, N, L, P, left, w, tw, eps, y,
-                               total_chunks, chunks_per_utt, (const float*)nullptr, 0.f, 0.f, 0, run_len, mode);
-        return;
-    }
-#define DSA_STFT_FWD_LAUNCH(ZM, PL, LCV)                                                                                 \
-    hipLaunchKernelGGL((stft512_fwd_kernel<ABL, ZM, PL, LCV>), g2, dim3(128), lds2, st, x, T, N, L, P, left, mode, w, tw, \
-                       eps, use_floor, floor_lin, fmt, y, total_chunks, chunks_per_utt, io_floats)
-    if (zmean) DSA_STFT_FWD_LAUNCH(true, false, 0);
-    else if (plain && L == 400) DSA_STFT_FWD_LAUNCH(false, true, 400);
-    else if (plain) DSA_STFT_FWD_LAUNCH(false, true, 0);
-    else DSA_STFT_FWD_LAUNCH(false, false, 0);
-#undef DSA_STFT_FWD_LAUNCH
-}
 
 // ---- inverse path helpers ----
 // irfft(Y)[n] = sum_k c_k / N Re(Y_k e^{+2 pi i k n / N}), c = 1 at DC / Nyquist, 2 in between (ifftr.py:138):
@@ -2088,6 +2010,35 @@ DSA_EXPORT int dsa_spec_fwd(const void* b, int32_t lb, const void* a, int32_t la
     return fail(DSA_ERR_UNSUPPORTED, "spec: unsupported dtype%s");
 }
 
+static void stft512_launch(bool zmean, dim3 grid, hipStream_t st, const float* x, long T, long N, int L, int P, int left, int mode,
+                           const float* w, const float* tw, float eps, int use_floor, float floor_lin, int fmt, float* y,
+                           long total_chunks, int chunks_per_utt, int io_floats)
+{
+    // `grid` counts waves; they are paired into 128-thread workgroups that share the twiddle table
+    const bool plain = !use_floor && fmt == DSA_SPEC_POWER && mode == DSA_PAD_CONSTANT;
+    const dim3 g2((grid.x + 1) / 2);
+    const int lds2 = stft512_lds_bytes2();
+    // the packed-float32 kernel with register-direct stores (stft_pk.h) where it applies -- round 6: every pad mode (the mode only
+    // changes what the passes that reach over an utterance's end read) and, as an instantiation of its own, zmean and the relative floor
+    if (fmt == DSA_SPEC_POWER && L == 400 && (P & 1) == 0 && 3 * P + 512 <= kFPW * kZS * 2) {
+        if (zmean || use_floor)
+            hipLaunchKernelGGL((stft512_fwd_pk_kernel<400, 0, true>), g2, dim3(128), lds2, st, x, T, N, L, P, left, w, tw, eps, y,
+                               total_chunks, chunks_per_utt, (const float*)nullptr, 0.f, 0.f, 0, mode, (int)zmean, use_floor ? floor_lin : -1.f);
+        else
+            hipLaunchKernelGGL((stft512_fwd_pk_kernel<400>), g2, dim3(128), lds2, st, x, T, N, L, P, left, w, tw, eps, y,
+                               total_chunks, chunks_per_utt, (const float*)nullptr, 0.f, 0.f, 0, mode);
+        return;
+    }
+#define DSA_STFT_FWD_LAUNCH(ZM, PL, LCV)                                                                                 \
+    hipLaunchKernelGGL((stft512_fwd_kernel<ZM, PL, LCV>), g2, dim3(128), lds2, st, x, T, N, L, P, left, mode, w, tw,      \
+                       eps, use_floor, floor_lin, fmt, y, total_chunks, chunks_per_utt, io_floats)
+    if (zmean) DSA_STFT_FWD_LAUNCH(true, false, 0);
+    else if (plain && L == 400) DSA_STFT_FWD_LAUNCH(false, true, 400);
+    else if (plain) DSA_STFT_FWD_LAUNCH(false, true, 0);
+    else DSA_STFT_FWD_LAUNCH(false, false, 0);
+#undef DSA_STFT_FWD_LAUNCH
+}
+
 DSA_EXPORT int dsa_stft_fwd(const void* x, int64_t B, int64_t T, int32_t L, int32_t P, int32_t nfft,
                             const void* w, const void* twiddle, int32_t center, int32_t zmean,
                             int32_t pad_mode, double eps, int32_t use_floor, double relative_floor_db,
@@ -2113,18 +2064,13 @@ DSA_EXPORT int dsa_stft_fwd(const void* x, int64_t B, int64_t T, int32_t L, int3
     if (tuned_ok && algo != DSA_ALGO_GENERIC) {
         int chunks_per_utt = (int)((N + kFPW - 1) / kFPW);
         long total_chunks = (long)B * chunks_per_utt;
-        // persistent single-wave workgroups; every one of them must be resident from the start, so
-        // leave headroom under the 160 KB of LDS (12 x 13.3 KB does not always fit: measured slower)
-        int waves_per_cu = 144 * 1024 / lds;
-        if (waves_per_cu > 12) waves_per_cu = 12;
-        if (waves_per_cu < 1) waves_per_cu = 1;
-        waves_per_cu = 16;   // four waves per SIMD (two-wave workgroups, 19.5 KB of LDS each)
-        long grid = 256L * waves_per_cu;  // persistent waves
+        // persistent waves, every one of them resident from the start: four per SIMD (two-wave workgroups, 19.5 KB of LDS each)
+        long grid = 256L * 16;
         if (grid > total_chunks) grid = total_chunks;
         float floor_lin = use_floor ? (float)pow(10.0, relative_floor_db / 10.0) : 0.f;
-        stft512_launch<0>(zmean != 0, dim3((unsigned)grid), lds, st, (const float*)x, (long)T, (long)N, L, P, left,
-                          pad_mode, (const float*)w, (const float*)twiddle, (float)eps, use_floor, floor_lin,
-                          out_format, (float*)y, total_chunks, chunks_per_utt, in_floats);
+        stft512_launch(zmean != 0, dim3((unsigned)grid), st, (const float*)x, (long)T, (long)N, L, P, left,
+                       pad_mode, (const float*)w, (const float*)twiddle, (float)eps, use_floor, floor_lin,
+                       out_format, (float*)y, total_chunks, chunks_per_utt, in_floats);
         return check_launch("stft512_fwd");
     }
     // fft_length 1024 / 2048 (the 44.1 / 48 kHz set-ups of utils/public.py:61-104), power format, constant padding, no zmean, no
@@ -2165,7 +2111,7 @@ DSA_EXPORT int dsa_stft_fwd(const void* x, int64_t B, int64_t T, int32_t L, int3
 }
 
 // --------------------------------------------------------------------------- fused STFT -> mel filter bank
-// Host side of the filter-bank epilogue of stft512_fwd_pk_kernel<.., FB = true> (stft_pk.h).
+// Host side of the filter-bank epilogue of stft512_fwd_pk_kernel<.., FBM = 1 / 2> (stft_pk.h).
 // dsa_fbank_scan_plan turns H (host, float64, 257 x C) into the (64, 32) float32 per-lane table; it is the C
 // statement of diffsptk_amd/utils/tables.py:fbank_scan_plan / fbank_scan_table (tests compare the two bit for bit).
 DSA_EXPORT int dsa_fbank_scan_plan(const double* H, int32_t K, int32_t C, float* table)
@@ -2270,9 +2216,9 @@ DSA_EXPORT int dsa_stft_fbank_fwd(const void* x, int64_t B, int64_t T, int32_t L
     if (waves > total_chunks) waves = total_chunks;
     const int lds = 4 * kFPW * kZS * 8 + 256 * 8 + 16 * 13 * 8 + 128 * 8;
 #define DSA_FB_LAUNCH(MODE)                                                                                                  \
-    hipLaunchKernelGGL((stft512_fwd_pk_kernel<0, 400, true, MODE>), dim3((unsigned)((waves + 3) / 4)), dim3(256), lds, st,     \
+    hipLaunchKernelGGL((stft512_fwd_pk_kernel<400, MODE>), dim3((unsigned)((waves + 3) / 4)), dim3(256), lds, st,              \
                        (const float*)x, (long)T, (long)N, L, P, left, (const float*)w, (const float*)twiddle, (float)eps,      \
-                       (float*)y, total_chunks, chunks_per_utt, (const float*)plan, (float)floor, (float)gamma, C, 0, (int)DSA_PAD_CONSTANT)
+                       (float*)y, total_chunks, chunks_per_utt, (const float*)plan, (float)floor, (float)gamma, C, (int)DSA_PAD_CONSTANT)
     if (use_power) DSA_FB_LAUNCH(1);
     else DSA_FB_LAUNCH(2);
 #undef DSA_FB_LAUNCH
@@ -2465,23 +2411,15 @@ static int stft_bwd_impl(const void* gy, const void* x, int64_t B, int64_t T, in
             int chunks_per_utt = (int)((N + kFPW - 1) / kFPW);
             long total_chunks = (long)B * chunks_per_utt;
             int span = (kFPW - 1) * P + L;
-            // the packed kernel with the overlap-add carried in registers (stft_bwd_pk.h): one launch, no workspace.
-            // DSA_STFT_BWD_PK=0 keeps the two-kernel path (A/B)
+            // the packed kernel with the overlap-add carried in registers (stft_bwd_pk.h): one launch, no workspace
             {
             const bool cplx = out_format == DSA_SPEC_COMPLEX || out_format == DSA_SPEC_COMPLEX_INV;
             const int left = center ? L / 2 : 0;
-            static const int use_pk = [] {
-                const char* e = getenv("DSA_STFT_BWD_PK");
-                return e ? atoi(e) : 1;
-            }();
-            if (use_pk && !zmean && L == 400 && (P == 80 || P == 160) && (cplx || out_format == DSA_SPEC_POWER || out_format == DSA_SPEC_MAG)) {
+            if (!zmean && L == 400 && (P == 80 || P == 160) && (cplx || out_format == DSA_SPEC_POWER || out_format == DSA_SPEC_MAG)) {
                 const int ppu = chunks_per_utt;                       // passes of four frames per utterance
                 const long waves = 256L * 16;
                 long want = (waves + B - 1) / B;                       // runs per utterance that fill the chip ...
-                static const int min_run = [] {   // A/B knob: shortest run of passes a wave takes (each run adds one warm-up pass)
-                    const char* e = getenv("DSA_STFT_BWD_MINRUN");
-                    return e && atoi(e) > 0 ? atoi(e) : 4;
-                }();
+                constexpr int min_run = 4;                             // shortest run of passes a wave takes (each run adds one warm-up pass)
                 const long longest = ppu / min_run > 0 ? ppu / min_run : 1;
                 const int runs = (int)(want < longest ? want : longest);
                 const long items = (long)B * runs;

@@ -21,32 +21,20 @@
 
 namespace dsa {
 
-// ABL (ablation bit mask, tools/bench_stft.cpp only; 0 in the product): 1 no output stores | 2 no butterflies |
-// 4 no waveform loads / staging | 8 no twiddle-table reads | 16 no transposes through LDS | 32 no spectrum
-// round trip (Z write + pair reads) | 64 no staged tile | 128 cycle stamps of wave 0
-#ifdef DSA_STFT_TIMING
-__device__ unsigned long long g_stft_pk_stamps[64];
-#define PK_STAMP(i)                                                                                     \
-    do {                                                                                                \
-        if ((ABL & 128) && blockIdx.x == 0 && threadIdx.x == 0) g_stft_pk_stamps[i] = __builtin_readcyclecounter();  \
-    } while (0)
-#else
-#define PK_STAMP(i)
-#endif
 // The packed forward kernel.  Same pass structure, LDS carve-up, launch geometry and output as
-// stft512_fwd_kernel<0, false, true, LC> (see there); P must be even (8-byte aligned sample pairs in LDS).
+// stft512_fwd_kernel<false, true, LC> (see there); P must be even (8-byte aligned sample pairs in LDS).
 // (stft.hip is built with the compiler's packed-float32 selection switched off, which also makes the assembler
 // reject v_pk_*_f32 in inline assembly: the target attribute switches the feature back on for this kernel only)
 // (DSA_PK_TARGET: common.h)
-// DIRECT: the power values leave the split's registers as 4-byte stores (lane = bin: every store instruction writes 64
-// consecutive floats of one row) instead of being staged in LDS for 16-byte stores: the kernel is bound by LDS
-// cycles, and the staged tile costs 18 four-byte LDS writes + 5 sixteen-byte reads per pass (a fifth of them).
+// The power values leave the split's registers as 8-byte stores (a lane holds two neighbouring bins: every store instruction
+// writes 512 consecutive bytes of one row) instead of being staged in LDS for 16-byte stores: the kernel is bound by LDS
+// cycles, and a staged tile cost 18 four-byte LDS writes + 5 sixteen-byte reads per pass (a fifth of them).
 //
 // FB: the mel filter bank in the epilogue (SURVEY 8(f) row 1 without the spectrum's round trip through memory,
 // fbank.py:306-321 on top of stft.py): `y` is then the (B N, C) filter-bank output glog(max(s H, floor)), s = the
 // power values or their square roots.  H must have the two-adjacent-channels-per-bin structure of the mel filters;
 // the host turns it into the per-lane plan `fbt` (dsa_fbank_scan_plan; tools/proto_fbank_scan.py is a lane-level
-// model): with the DIRECT split a lane holds the neighbouring bins (2l+1, 2l+2) and (255-2l, 254-2l) of a frame,
+// model): with the register-direct split a lane holds the neighbouring bins (2l+1, 2l+2) and (255-2l, 254-2l) of a frame,
 // so the bins between two channel centres are a RUN of lanes and the channel sums are segmented scans over lanes
 // (v_fmac_f32_dpp with a 0/1 mask per lane and step: no transposition through LDS, no matrix operand images --
 // neither would fit beside four waves per SIMD).  Four-wave workgroups: the window moves from registers to a
@@ -59,90 +47,53 @@ __device__ __attribute__((noinline)) float fb_slow_glog(float v, float gamma) { 
 
 // OPTS (round 6): zmean (frame.py:139-140) and the relative floor (spec.py:174-176) -- an instantiation of its own, the plain kernel's
 // code is untouched.  `opt_zmean`, `opt_floor` (< 0: none, else the linear factor 10^(dB / 10)) are its run-time switches.
-template <int ABL, int LC, bool DIRECT = false, int FBM = 0, bool PF2 = false, int WPBX = 0, bool OPTS = false>   // FBM: 0 spectrum out, 1 filter bank of the power values, 2 of the amplitudes;
-                                                                            // PF2: the stretch fetched TWO passes ahead (two register sets, window from LDS)
-                                                                            // WPBX: waves per workgroup (0: 2, or 4 with FBM / PF2) -- the waves of a workgroup take ADJACENT
-                                                                            // passes, which share L - P of their samples: on one CU the second fetch of those is a cache hit
-__global__ __launch_bounds__(WPBX ? WPBX * 64 : ((FBM || PF2) ? 256 : 128), WPBX ? 16 / WPBX : 4) DSA_PK_TARGET void stft512_fwd_pk_kernel(
+// FBM: 0 spectrum out, 1 filter bank of the power values, 2 of the amplitudes.  Workgroups of two waves (four with FBM); they share the
+// twiddle (and window) tables, nothing else.
+template <int LC, int FBM = 0, bool OPTS = false>
+__global__ __launch_bounds__(FBM ? 256 : 128, 4) DSA_PK_TARGET void stft512_fwd_pk_kernel(
     const float* __restrict__ x, long Tlen, long N, int L, int P, int left, const float* __restrict__ w,
     const float* __restrict__ twiddle, float eps, float* __restrict__ y, long total_chunks, int chunks_per_utt,
-    const float* __restrict__ fbt, float fb_floor, float fb_gamma, int fbC, int run_len, int pad_mode, int opt_zmean = 0, float opt_floor = -1.f)
+    const float* __restrict__ fbt, float fb_floor, float fb_gamma, int fbC, int pad_mode, int opt_zmean = 0, float opt_floor = -1.f)
 {
-    static_assert(!OPTS || (DIRECT && LC > 0 && !FBM && !PF2), "zmean / relative floor build on the register-direct plain kernel");
+    static_assert(!OPTS || (LC > 0 && !FBM), "zmean / relative floor build on the plain kernel");
     // pad_mode (round 6; frame.py:130-137): reflect / replicate / circular padding only changes which sample a position outside the
     // utterance reads -- the passes that reach over an end (stage_sync's element-wise path); interior passes never see it
-    // run_len > 1 (round 5): a wave takes RUNS of run_len consecutive passes instead of every (number of waves)-th pass.  Consecutive
-    // passes of an utterance share L - P of their 3 P + L samples; dealt round-robin those were fetched by two waves on two XCDs at
-    // two times -- 1.73 x the waveform's bytes from memory (FETCH_SIZE) -- while a wave that walks its own run finds them in its
-    // CU's cache a pass later.  Same passes, same arithmetic, same stores: only the order changes.
     constexpr bool FB = FBM != 0;
-    static_assert(!FB || (DIRECT && LC > 0), "the filter-bank epilogue builds on the register-direct split");
+    static_assert(!FB || LC > 0, "the filter-bank epilogue needs the frame length at compile time");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    constexpr bool WL = FB || PF2;    // window pairs from a shared LDS table instead of 26 registers per lane
-    static_assert(!PF2 || (DIRECT && LC > 0 && !FB), "PF2 builds on the register-direct plain kernel");
-    constexpr int WPB = WPBX ? WPBX : (WL ? 4 : 2);   // waves per workgroup (they share the twiddle / window tables, nothing else)
+    constexpr int WPB = FB ? 4 : 2;   // waves per workgroup (FB: window pairs from a shared LDS table instead of 26 registers per lane)
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     v2f* zbuf = reinterpret_cast<v2f*>(smem_raw) + wv * kFPW * kZS;
-    float* io_buf = reinterpret_cast<float*>(zbuf);  // aliases zbuf: stretch -> tiles -> spectra -> staged output
+    float* io_buf = reinterpret_cast<float*>(zbuf);  // aliases zbuf: stretch -> tiles -> spectra -> filter-bank slots
     v2f* t256 = reinterpret_cast<v2f*>(smem_raw) + WPB * kFPW * kZS;
     v2f* wtab = t256 + 256;                          // FB: [16][NR] window pairs
     v2f* hend = wtab + 16 * (LC ? (LC + 31) / 32 : 16);   // FB: [128] (H[0][c], H[256][c])
     const long nw = (long)gridDim.x * WPB;
-    long wid = (long)blockIdx.x * WPB + wv;
-    if (ABL & 256) {   // experiment: workgroups are dealt round-robin to the 8 XCDs; give every XCD a contiguous eighth of a round
-        const long per = gridDim.x / 8;
-        if (per * 8 == gridDim.x) wid = ((blockIdx.x & 7) * per + (blockIdx.x >> 3)) * WPB + wv;
-    }
-
-    if (ABL & (1024 | 2048 | 4096)) {
-        // experiment: consecutive workgroup ids sit on different XCDs (id % 8), so neighbouring passes -- which share L - P samples --
-        // never share an L2.  Here the workgroups of one XCD take C CONSECUTIVE logical workgroups out of every 8 C (the passes
-        // in flight stay one contiguous window of the output, unlike the XCD-contiguous order above)
-        constexpr unsigned C = (ABL & 1024) ? 4 : ((ABL & 2048) ? 2 : 8);
-        const unsigned bq = blockIdx.x, xcd = bq & 7, r = bq >> 3;
-        if (gridDim.x % (8 * C) == 0) wid = (long)((r / C) * (8 * C) + xcd * C + (r % C)) * WPB + wv;
-    }
+    const long wid = (long)blockIdx.x * WPB + wv;
     const int lane = threadIdx.x & 63;
     const int j = lane & 15;   // lane within the frame group
     const int fl = lane >> 4;  // frame slot within the pass (0..3)
-    PK_STAMP(0);
-    // pass k of wave `wid` is chunk (wid + (k / R) nw) R + k % R (R = run_len; R <= 0: wid + k nw): runs of R consecutive chunks, the runs
-    // themselves dealt round-robin, so the passes in flight stay one compact window of the output
-    const int R = run_len > 0 ? run_len : 1;
-    const long jump = nw * R - (R - 1);                                       // from the last chunk of a run to the next run's first
-    const long c_first = wid * R;
+    // pass k of wave `wid` is chunk wid + k nw: the passes in flight stay one compact window of the output
+    const long c_first = wid;
     const long c_end = total_chunks;
     if (c_first >= c_end) return;
     constexpr int NR = LC ? (LC + 31) / 32 : 16;   // sample pairs a lane reads (the rest is zero padding)
     constexpr int K = 257;
     // (utterance, chunk) of a pass advance incrementally: one 64-bit division per wave
     // (32-bit: the wave count and the chunks of an utterance are far below 2^31; 64-bit divisions are ~150 instructions)
-    const long b_step = (long)((unsigned long)jump / (unsigned)chunks_per_utt);
-    const int ci_step = (int)(jump - b_step * chunks_per_utt);
-    // (kin: position of the pass inside its run; a step is +1 inside a run, `jump` at its end)
-    auto advance = [&](long& bb, int& cc, long& cq, int& kin) __attribute__((always_inline)) {
-        if (kin + 1 < R) {
-            ++kin;
-            ++cq;
-            ++cc;
-            if (cc >= chunks_per_utt) {
-                cc = 0;
-                ++bb;
-            }
-        } else {
-            kin = 0;
-            cq += jump;
-            bb += b_step;
-            cc += ci_step;
-            if (cc >= chunks_per_utt) {
-                cc -= chunks_per_utt;
-                ++bb;
-            }
+    const long b_step = (long)((unsigned long)nw / (unsigned)chunks_per_utt);
+    const int ci_step = (int)(nw - b_step * chunks_per_utt);
+    auto advance = [&](long& bb, int& cc, long& cq) __attribute__((always_inline)) {
+        cq += nw;
+        bb += b_step;
+        cc += ci_step;
+        if (cc >= chunks_per_utt) {
+            cc -= chunks_per_utt;
+            ++bb;
         }
     };
     // the stretch of samples the (up to) four frames of pass (bb, cc) share, straight from memory into the tile
     auto stage_sync = [&](long bb, int cc) __attribute__((always_inline)) {
-        if (ABL & 4) return;
         const long frame0 = (long)cc * kFPW;
         const int nvalid = (int)((N - frame0) < kFPW ? (N - frame0) : kFPW);
         const float* xb = x + bb * Tlen;
@@ -169,9 +120,7 @@ __global__ __launch_bounds__(WPBX ? WPBX * 64 : ((FBM || PF2) ? 256 : 128), WPBX
     // order, and a wait placed after the stores cannot tell them from the loads -- every pass would wait for its
     // own stores (measured: the pass period then follows the store latency).
     v4f pre0 = v4f{0.f, 0.f, 0.f, 0.f}, pre1 = pre0, pre2 = pre0;
-    v4f prb0 = pre0, prb1 = pre0, prb2 = pre0;   // PF2: the second register set
     auto prefetch_into = [&](long bb, int cc, v4f& q0, v4f& q1, v4f& q2) __attribute__((always_inline)) -> bool {
-        if (ABL & 4) return false;
         const long fr2 = (long)cc * kFPW;
         const int nv2 = (int)((N - fr2) < kFPW ? (N - fr2) : kFPW);
         const long g2 = fr2 * P - left;
@@ -195,33 +144,11 @@ __global__ __launch_bounds__(WPBX ? WPBX * 64 : ((FBM || PF2) ? 256 : 128), WPBX
     int ci = (int)(c_first - b * chunks_per_utt);
     long c = c_first;
     bool pre_ok = prefetch(b, ci);
-    bool prb_ok = false;
-    long bn1 = b;      // PF2: coordinates of the pass after this wave's first one
-    int cin1 = ci;
-    long cn1 = c;
-    int kn1 = 0;
-    if (PF2) {
-        advance(bn1, cin1, cn1, kn1);
-        prb_ok = (cn1 < c_end) ? prefetch_into(bn1, cin1, prb0, prb1, prb2) : false;
-    }
-    PK_STAMP(3);
 
     v2f wreg[NR];
     v2f f_wd0, f_wu0, f_wd1, f_wu1, f_nb, f_mM;   // FB: the lane's plan (lower-half bin pair in .x, upper-half pair in .y)
     float f_mk[12];
     int f_addr[4], f_valid = 0;
-    if (WL && !FB) {   // the window table alone (every wave writes the whole, identical table: no barrier needed)
-        v2f wt[4];
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) {
-            const int i = lane + 64 * q4;
-            const int l = 2 * (i / NR) + 32 * (i % NR);
-            wt[q4] = v2f{(i < 16 * NR && l < L) ? w[l < L ? l : 0] : 0.f, (i < 16 * NR && l + 1 < L) ? w[l + 1 < L ? l + 1 : 0] : 0.f};
-        }
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4)
-            if (lane + 64 * q4 < 16 * NR) wtab[lane + 64 * q4] = wt[q4];
-    }
     if (FB) {
         // every wave writes the whole (identical) tables, like the twiddle table below: no workgroup barrier needed
         v2f wt[4], he[2];
@@ -254,7 +181,7 @@ __global__ __launch_bounds__(WPBX ? WPBX * 64 : ((FBM || PF2) ? 256 : 128), WPBX
         f_addr[1] = 4 * ((flags_w & 2) ? ((slots_w >> 8) & 255) : 127);     //              upper half
         f_addr[2] = 4 * ((flags_w & 4) ? ((slots_w >> 16) & 255) : 127);    // interval closed inside the lane, lower half
         f_addr[3] = 4 * ((flags_w & 8) ? ((slots_w >> 24) & 255) : 127);    //                                  upper half
-    } else if (!WL) {
+    } else {
 #pragma unroll
         for (int m1 = 0; m1 < NR; ++m1) {
             const int l = 2 * j + 32 * m1;
@@ -275,9 +202,8 @@ __global__ __launch_bounds__(WPBX ? WPBX * 64 : ((FBM || PF2) ? 256 : 128), WPBX
 #pragma unroll
         for (int q4 = 0; q4 < 4; ++q4) t256[lane + 64 * q4] = t4[q4] * 0.5f;
     }
-    // split twiddles W512^k of this lane's two pairs (k, 256 - k): k = lane + 1, lane + 65 (staged output: a store
-    // covers 64 consecutive bins) or k = 2 lane + 1, 2 lane + 2 (DIRECT: the lane's two bins are neighbours)
-    const int kA = DIRECT ? 2 * lane + 1 : lane + 1, kB = DIRECT ? 2 * lane + 2 : lane + 65;
+    // split twiddles W512^k of this lane's two pairs (k, 256 - k): k = 2 lane + 1, 2 lane + 2 (the lane's two bins are neighbours)
+    const int kA = 2 * lane + 1, kB = 2 * lane + 2;
     v2f twA = v2f{twiddle[2 * kA], twiddle[2 * kA + 1]};
     v2f twB = v2f{twiddle[2 * kB], twiddle[2 * kB + 1]};
     const v2f eps2 = v2f{eps, eps};
@@ -289,12 +215,11 @@ __global__ __launch_bounds__(WPBX ? WPBX * 64 : ((FBM || PF2) ? 256 : 128), WPBX
 #pragma unroll
         for (int i = 0; i < 12; ++i) asm volatile("" : "+v"(f_mk[i]));
         asm volatile("" : "+v"(f_addr[0]), "+v"(f_addr[1]), "+v"(f_addr[2]), "+v"(f_addr[3]), "+v"(f_valid));
-    } else if (!WL) {
+    } else {
 #pragma unroll
         for (int m1 = 0; m1 < NR; ++m1) asm volatile("" : "+v"(wreg[m1]));
     }
     asm volatile("" : "+v"(twA), "+v"(twB));
-    PK_STAMP(4);
     if (pre_ok) {
         const long fr0 = (long)ci * kFPW;
         const int nv0 = (int)((N - fr0) < kFPW ? (N - fr0) : kFPW);
@@ -307,38 +232,18 @@ __global__ __launch_bounds__(WPBX ? WPBX * 64 : ((FBM || PF2) ? 256 : 128), WPBX
     } else {
         stage_sync(b, ci);
     }
-    PK_STAMP(5);
     long b1 = b;
     int ci1 = ci;
     long c1 = c;
-    int k1n = 0;
-    advance(b1, ci1, c1, k1n);
+    advance(b1, ci1, c1);
     bool has1 = c1 < c_end;
-    if (PF2) {   // pass 1 is already on its way into the second register set; the first set now takes pass 2
-        long b2 = b1, c2 = c1;
-        int ci2 = ci1, k2n = k1n;
-        advance(b2, ci2, c2, k2n);
-        pre_ok = (c2 < c_end) ? prefetch_into(b2, ci2, pre0, pre1, pre2) : false;
-    } else {
-        pre_ok = has1 ? prefetch(b1, ci1) : false;
-    }
-    PK_STAMP(1);
-    int pass_no = 0;
-    (void)pass_no;
+    pre_ok = has1 ? prefetch(b1, ci1) : false;
     // One pass.  (q0, q1, q2, qok): the register set that holds the NEXT pass's stretch -- waited for before this pass's stores,
-    // staged into the tile at the end of the pass, then re-used for the fetch one (PF2: two) passes further on.
+    // staged into the tile at the end of the pass, then re-used for the fetch one pass further on.
     auto run_pass = [&](v4f& q0, v4f& q1, v4f& q2, bool& qok) __attribute__((always_inline)) -> bool {
         const long frame0 = (long)ci * kFPW;
         const int nvalid = (int)((N - frame0) < kFPW ? (N - frame0) : kFPW);
         DSA_WAVE_SYNC();
-#ifdef DSA_STFT_TIMING
-        if ((ABL & 128) && pass_no < 24) PK_STAMP(8 + pass_no);
-        const bool stamp_pass = pass_no == 3;
-        ++pass_no;
-#define PK_PHASE(i) do { if (stamp_pass) PK_STAMP(40 + i); } while (0)
-#else
-#define PK_PHASE(i)
-#endif
         // ---- per frame: window (window.py:190), 256-point complex FFT (16 lanes x 16 points) ----
         v2f v[16];
         {
@@ -358,7 +263,7 @@ __global__ __launch_bounds__(WPBX ? WPBX * 64 : ((FBM || PF2) ? 256 : 128), WPBX
                 }
                 if (opt_zmean) pk_zero_mean<NR>(raw, in0, in1, LC);
 #pragma unroll
-                for (int m1 = 0; m1 < NR; ++m1) v[m1] = pk_mul(raw[m1], WL ? wtab[j * NR + m1] : wreg[m1]);
+                for (int m1 = 0; m1 < NR; ++m1) v[m1] = pk_mul(raw[m1], FB ? wtab[j * NR + m1] : wreg[m1]);
 #pragma unroll
                 for (int m1 = NR; m1 < 16; ++m1) v[m1] = v2f{0.f, 0.f};
             } else if (LC) {
@@ -368,7 +273,7 @@ __global__ __launch_bounds__(WPBX ? WPBX * 64 : ((FBM || PF2) ? 256 : 128), WPBX
                     const bool in0 = 32 * m1 + 30 < LC || 32 * m1 + 2 * j < LC;
                     const bool in1 = 32 * m1 + 31 < LC || 32 * m1 + 1 + 2 * j < LC;
                     const v2f r = v2f{in0 ? raw[m1].x : 0.f, in1 ? raw[m1].y : 0.f};
-                    v[m1] = pk_mul(r, WL ? wtab[j * NR + m1] : wreg[m1]);
+                    v[m1] = pk_mul(r, FB ? wtab[j * NR + m1] : wreg[m1]);
                 }
 #pragma unroll
                 for (int m1 = NR; m1 < 16; ++m1) v[m1] = v2f{0.f, 0.f};
@@ -383,42 +288,25 @@ __global__ __launch_bounds__(WPBX ? WPBX * 64 : ((FBM || PF2) ? 256 : 128), WPBX
             }
         }
         DSA_WAVE_SYNC();  // every lane has its samples: the stretch may be overwritten
-        PK_PHASE(1);
-        if (!(ABL & 2)) pk_fft16<(LC > 0 && NR <= 13)>(v);
-        PK_PHASE(2);
-        if (ABL & 16) {
+        pk_fft16<(LC > 0 && NR <= 13)>(v);
 #pragma unroll
-            for (int k1 = 0; k1 < 16; ++k1) v[k1] = pk_cmul(v[k1], (ABL & 8) ? twA : t256[k1 * 16 + j]);
-        } else {
+        for (int k1 = 0; k1 < 16; ++k1)  // twiddle, then transposed store: (k1, j) -> k1*17 + j
+            zf[k1 * 17 + j] = pk_cmul(v[FFT16_OUT(k1)], t256[k1 * 16 + j]);
+        DSA_WAVE_SYNC();
 #pragma unroll
-            for (int k1 = 0; k1 < 16; ++k1)  // twiddle, then transposed store: (k1, j) -> k1*17 + j
-                zf[k1 * 17 + j] = pk_cmul(v[FFT16_OUT(k1)], (ABL & 8) ? twA : t256[k1 * 16 + j]);
-            DSA_WAVE_SYNC();
-            PK_PHASE(3);
+        for (int i = 0; i < 16; ++i) v[i] = zf[j * 17 + i];  // lane k1 = j reads A[i][k1]
+        DSA_WAVE_SYNC();
+        pk_fft16<false>(v);
 #pragma unroll
-            for (int i = 0; i < 16; ++i) v[i] = zf[j * 17 + i];  // lane k1 = j reads A[i][k1]
-            DSA_WAVE_SYNC();
-        }
-        PK_PHASE(4);
-        if (!(ABL & 2)) pk_fft16<false>(v);
-        PK_PHASE(5);
-        if (!(ABL & 32)) {
-#pragma unroll
-            for (int k0 = 0; k0 < 16; ++k0) {
-                if (DIRECT) {
-                    // Z[k], k = j + 16 k0, at position k + 1 (k <= 128) or k + 2 (k >= 128; Z[128] at both 129 and 130):
-                    // the split below then reads its two neighbouring pairs (Z[2l+1], Z[2l+2]) and
-                    // (Z[254-2l], Z[255-2l]) as ONE 16-byte aligned access each (as 8-byte reads at a 16-byte lane
-                    // stride they were two-way bank conflicts: 15 % of the kernel's LDS cycles)
-                    zf[j + 16 * k0 + (k0 < 8 ? 1 : 2)] = v[FFT16_OUT(k0)];
-                    if (k0 == 8 && j == 0) zf[129] = v[FFT16_OUT(k0)];
-                } else {
-                    zf[j + 16 * k0] = v[FFT16_OUT(k0)];  // Z[k1 + 16 k0], natural order
-                }
-            }
+        for (int k0 = 0; k0 < 16; ++k0) {
+            // Z[k], k = j + 16 k0, at position k + 1 (k <= 128) or k + 2 (k >= 128; Z[128] at both 129 and 130):
+            // the split below then reads its two neighbouring pairs (Z[2l+1], Z[2l+2]) and
+            // (Z[254-2l], Z[255-2l]) as ONE 16-byte aligned access each (as 8-byte reads at a 16-byte lane
+            // stride they were two-way bank conflicts: 15 % of the kernel's LDS cycles)
+            zf[j + 16 * k0 + (k0 < 8 ? 1 : 2)] = v[FFT16_OUT(k0)];
+            if (k0 == 8 && j == 0) zf[129] = v[FFT16_OUT(k0)];
         }
         DSA_WAVE_SYNC();
-        PK_PHASE(6);
         // ---- real-FFT split, two bins (k, 256-k) per lane from one pair (a, b) = (Z[k], Z[256-k]) ----
         //   S = a + conj(b), Dd = a - conj(b), Pp = W^k Dd   (Z arrives halved, see t256):
         //   X[k] = (S.re + Pp.im, S.im - Pp.re),  X[256-k] = (S.re - Pp.im, -S.im - Pp.re)
@@ -426,39 +314,22 @@ __global__ __launch_bounds__(WPBX ? WPBX * 64 : ((FBM || PF2) ? 256 : 128), WPBX
         // |X|^2 + eps of BOTH bins is two packed fused multiply-adds (spec.py:173).
         const long row0 = b * N + frame0;
         const long out0 = row0 * K;
-        float* stage = io_buf;
         v2f pa[kFPW][2], pb[kFPW][2], z0[kFPW];
 #pragma unroll
         for (int f = 0; f < kFPW; ++f) {
             const v2f* z = zbuf + f * kZS;
-            if (ABL & 32) {
-                pa[f][0] = v[4 * f], pb[f][0] = v[4 * f + 1], pa[f][1] = v[4 * f + 2], pb[f][1] = v[4 * f + 3], z0[f] = v[f];
-            } else {
-                if (DIRECT) {
-                    const v4f a2 = *reinterpret_cast<const v4f*>(z + 2 * lane + 2);     // Z[2l+1], Z[2l+2]
-                    const v4f b2 = *reinterpret_cast<const v4f*>(z + 256 - 2 * lane);   // Z[254-2l], Z[255-2l]
-                    pa[f][0] = v2f{a2.x, a2.y};
-                    pa[f][1] = v2f{a2.z, a2.w};
-                    pb[f][1] = v2f{b2.x, b2.y};   // partner of kB = 2l+2: Z[254-2l]
-                    pb[f][0] = v2f{b2.z, b2.w};   // partner of kA = 2l+1: Z[255-2l]
-                    z0[f] = z[1];
-                } else {
-                    pa[f][0] = z[kA];
-                    pb[f][0] = z[256 - kA];
-                    pa[f][1] = z[kB];
-                    pb[f][1] = z[256 - kB];
-                    z0[f] = z[0];
-                }
-            }
+            const v4f a2 = *reinterpret_cast<const v4f*>(z + 2 * lane + 2);     // Z[2l+1], Z[2l+2]
+            const v4f b2 = *reinterpret_cast<const v4f*>(z + 256 - 2 * lane);   // Z[254-2l], Z[255-2l]
+            pa[f][0] = v2f{a2.x, a2.y};
+            pa[f][1] = v2f{a2.z, a2.w};
+            pb[f][1] = v2f{b2.x, b2.y};   // partner of kB = 2l+2: Z[254-2l]
+            pb[f][0] = v2f{b2.z, b2.w};   // partner of kA = 2l+1: Z[255-2l]
+            z0[f] = z[1];
         }
-        DSA_WAVE_SYNC();   // all pairs are read before anything is written: the staged tile reuses the same LDS
-        PK_PHASE(7);
-        v2f sink = v2f{0.f, 0.f};
-        (void)sink;
-        const bool tile_aligned = nvalid == kFPW && (row0 & 3) == 0;   // 16-byte aligned because row0 % 4 == 0
+        DSA_WAVE_SYNC();   // all pairs are read before anything is written: the filter-bank slots reuse the same LDS
         // the fetch for the NEXT pass has had this whole pass to arrive; it is waited for here, before the stores
         // (unconditional: on a conditional path the compiler would still schedule its own wait at the register use below)
-        if (DIRECT) asm volatile("" : "+v"(q0), "+v"(q1), "+v"(q2) : : "memory");
+        asm volatile("" : "+v"(q0), "+v"(q1), "+v"(q2) : : "memory");
         v2f ends[kFPW];
 #pragma unroll
         for (int f = 0; f < kFPW; ++f) {
@@ -468,16 +339,9 @@ __global__ __launch_bounds__(WPBX ? WPBX * 64 : ((FBM || PF2) ? 256 : 128), WPBX
             const v2f E4 = pk_mul_s(E, v2f{4.f, 4.f});
             const v2f se = pk_fma_sc(E4, E, eps2);
             ends[f] = se;
-            if (ABL & 64) {
-                sink = pk_add(sink, se);
-            } else if (!DIRECT && lane == 0) {
-                stage[f * K] = se.x;
-                stage[f * K + 256] = se.y;
-            }
             v2f sp[2];
 #pragma unroll
             for (int part = 0; part < 2; ++part) {
-                const int k = part == 0 ? kA : kB;
                 const v2f S = pk_add_conj(pa[f][part], pb[f][part]);
                 const v2f Dd = pk_sub_conj(pa[f][part], pb[f][part]);
                 const v2f Pp = pk_cmul(Dd, part == 0 ? twA : twB);
@@ -487,12 +351,6 @@ __global__ __launch_bounds__(WPBX ? WPBX * 64 : ((FBM || PF2) ? 256 : 128), WPBX
                 s = pk_fma_sc(R, R, eps2);
                 s = pk_fma(I, I, s);
                 sp[part] = s;
-                if (ABL & 64) {
-                    sink = pk_add(sink, s);
-                } else if (!DIRECT) {
-                    stage[f * K + k] = s.x;
-                    stage[f * K + 256 - k] = s.y;
-                }
             }
             if (OPTS && opt_floor >= 0.f) {
                 // spec.py:174-176: every bin of the frame at least (the frame's largest value) x 10^(dB / 10)
@@ -560,17 +418,12 @@ __global__ __launch_bounds__(WPBX ? WPBX * 64 : ((FBM || PF2) ? 256 : 128), WPBX
                 *reinterpret_cast<float*>(sl + 1024 + f_addr[2]) = m2;
                 *reinterpret_cast<float*>(sl + 512 + f_addr[3]) = m1;
                 *reinterpret_cast<float*>(sl + 1536 + f_addr[3]) = m3;
-            } else if (DIRECT && !(ABL & 64) && !(ABL & 1) && f < nvalid) {
+            } else if (f < nvalid) {
                 // bins (2 lane + 1, 2 lane + 2) and (254 - 2 lane, 255 - 2 lane): two 8-byte stores, 512 consecutive
                 // bytes of the row per instruction (lane 63 writes bin 128 twice, the same pair either way)
                 float* yr = y + out0 + f * K;
-                if (ABL & 512) {
-                    __builtin_nontemporal_store(v2f{sp[0].x, sp[1].x}, reinterpret_cast<v2f_u4*>(yr + kA));
-                    __builtin_nontemporal_store(v2f{sp[1].y, sp[0].y}, reinterpret_cast<v2f_u4*>(yr + 256 - kB));
-                } else {
-                    *reinterpret_cast<v2f_u4*>(yr + kA) = v2f{sp[0].x, sp[1].x};
-                    *reinterpret_cast<v2f_u4*>(yr + 256 - kB) = v2f{sp[1].y, sp[0].y};
-                }
+                *reinterpret_cast<v2f_u4*>(yr + kA) = v2f{sp[0].x, sp[1].x};
+                *reinterpret_cast<v2f_u4*>(yr + 256 - kB) = v2f{sp[1].y, sp[0].y};
             }
         }
         if (FB) {
@@ -621,9 +474,9 @@ __global__ __launch_bounds__(WPBX ? WPBX * 64 : ((FBM || PF2) ? 256 : 128), WPBX
                 }
 #pragma unroll
                 for (int f = 0; f < kFPW; ++f)
-                    if (ch < fbC && f < nvalid && !(ABL & 1)) y[(row0 + f) * fbC + ch] = sums[f];
+                    if (ch < fbC && f < nvalid) y[(row0 + f) * fbC + ch] = sums[f];
             }
-        } else if (DIRECT && !(ABL & 1) && !(ABL & 64)) {   // bins 0 and 256 of the (up to) four frames: lanes 0..7, one instruction
+        } else {   // bins 0 and 256 of the (up to) four frames: lanes 0..7, one instruction
             const int fe = lane >> 1;
             v2f e = ends[0];
             e = fe == 1 ? ends[1] : e;
@@ -632,32 +485,9 @@ __global__ __launch_bounds__(WPBX ? WPBX * 64 : ((FBM || PF2) ? 256 : 128), WPBX
             if (fe < nvalid) y[out0 + fe * K + ((lane & 1) ? 256 : 0)] = (lane & 1) ? e.y : e.x;
         }
         DSA_WAVE_SYNC();
-        PK_PHASE(8);
-        // ---- coalesced write of the staged 4 x 257 tile ----
-        v4f q[5];
-        if (!DIRECT && !(ABL & 64) && tile_aligned) {
-            const v4f* s4 = reinterpret_cast<const v4f*>(stage);
-#pragma unroll
-            for (int jj = 0; jj < 5; ++jj) q[jj] = s4[jj < 4 ? lane + 64 * jj : 256];
-        }
-        if (!DIRECT) asm volatile("" : "+v"(q0), "+v"(q1), "+v"(q2) : : "memory");   // see above
-        if (ABL & 64) {
-            if (sink.x + sink.y == 123.456f) y[out0 + lane] = sink.x;   // keeps the arithmetic alive, never true
-        } else if (DIRECT) {
-        } else if (tile_aligned) {
-            v4f* y4 = reinterpret_cast<v4f*>(y + out0);
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj)
-                if (!(ABL & 1) || q[jj].x == 123.456f) y4[lane + 64 * jj] = q[jj];
-            if (lane == 0 && (!(ABL & 1) || q[4].x == 123.456f)) y4[256] = q[4];
-        } else {
-            const int total = nvalid * K;
-            for (int idx = lane; idx < total; idx += 64) y[out0 + idx] = stage[idx];
-        }
-        PK_PHASE(9);
         if (!has1) return false;
-        // ---- the next pass's stretch into the tile (LDS operations of a wave execute in order: the staged output
-        // has been read), then the fetch for the pass after it ----
+        // ---- the next pass's stretch into the tile (LDS operations of a wave execute in order: the filter-bank slots
+        // have been read), then the fetch for the pass after it ----
         DSA_WAVE_SYNC();
         if (qok) {
             const long fr1 = (long)ci1 * kFPW;
@@ -673,28 +503,12 @@ __global__ __launch_bounds__(WPBX ? WPBX * 64 : ((FBM || PF2) ? 256 : 128), WPBX
         c = c1;
         b = b1;
         ci = ci1;
-        advance(b1, ci1, c1, k1n);
+        advance(b1, ci1, c1);
         has1 = c1 < c_end;
-        if (PF2) {   // the set just staged takes the stretch two passes ahead
-            long b2 = b1, c2 = c1;
-            int ci2 = ci1, k2n = k1n;
-            advance(b2, ci2, c2, k2n);
-            qok = (c2 < c_end) ? prefetch_into(b2, ci2, q0, q1, q2) : false;
-        } else {
-            qok = has1 ? prefetch_into(b1, ci1, q0, q1, q2) : false;
-        }
-        PK_PHASE(0);
+        qok = has1 ? prefetch_into(b1, ci1, q0, q1, q2) : false;
         return true;
     };
-    if (PF2) {
-        for (;;) {
-            if (!run_pass(prb0, prb1, prb2, prb_ok)) break;
-            if (!run_pass(pre0, pre1, pre2, pre_ok)) break;
-        }
-    } else {
-        while (run_pass(pre0, pre1, pre2, pre_ok)) {}
-    }
-    PK_STAMP(2);
+    while (run_pass(pre0, pre1, pre2, pre_ok)) {}
 }
 
 }  // namespace dsa

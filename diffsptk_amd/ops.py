@@ -1236,15 +1236,23 @@ class reserve_cus:
 
 
 def _mcep_scratch(device):
-    """(scratch, algo flag) of a tuned mel-cepstral forward launch: the per-(device, stream) kept-zero counters
-    (DSA_ALGO_SCRATCH_IS_CLEAN, no fill launch per call) -- except while a HIP graph is being captured: a graph replays on whatever
-    stream is current, possibly next to an eager call that uses the capture stream's counters, so a captured launch gets its
-    own block and the library's reset (a captured memset node) instead."""
+    """(scratch, clean) of a tuned persistent launch: the per-(device, stream) kept-zero counters (clean = True: no fill launch per
+    call) -- except while a HIP graph is being captured: a graph replays on whatever stream is current, possibly next to an eager
+    call that uses the capture stream's counters, so a captured launch gets its own block and the library's reset (a captured
+    memset node) instead."""
     with torch.cuda.device(device):
-        if torch.cuda.is_current_stream_capturing() or os.environ.get("DSA_CLEAN_SCRATCH", "1") == "0":   # (the variable: A/B runs)
-            return _scratch(device), _lib.algo_reserve_cus(_reserved_cus[0])
-        return _clean_scratch(device), (_lib.ALGO_SCRATCH_IS_CLEAN | (_lib.ALGO_OVERLAPPED_LAUNCHES if _overlapped[0] else 0)
-                                        | _lib.algo_reserve_cus(_reserved_cus[0]))
+        if torch.cuda.is_current_stream_capturing():
+            return _scratch(device), False
+        return _clean_scratch(device), True
+
+
+def _mcep_algo(clean: bool) -> int:
+    """The algo bits of a tuned mel-cepstral forward launch: DSA_ALGO_SCRATCH_IS_CLEAN with DSA_ALGO_OVERLAPPED_LAUNCHES
+    (overlapped_launches()) on the kept-zero scratch, and DSA_ALGO_RESERVE_CUS (reserve_cus())."""
+    flag = _lib.algo_reserve_cus(_reserved_cus[0])
+    if clean:
+        flag |= _lib.ALGO_SCRATCH_IS_CLEAN | (_lib.ALGO_OVERLAPPED_LAUNCHES if _overlapped[0] else 0)
+    return flag
 
 
 def stft_mcep_fusable(x, window, G, L, P, fft_length, M) -> bool:
@@ -1283,7 +1291,8 @@ class StftMcepFn(torch.autograd.Function):
         images = mcep_images(G, D, E, fft_length, M)
         if images is None:
             raise _lib.BackendError("stft_mcep: no tuned kernel for this configuration (check stft_mcep_fusable first)")
-        scratch, flag = _mcep_scratch(x.device)
+        scratch, clean = _mcep_scratch(x.device)
+        flag = _mcep_algo(clean)
         if with_rt:
             flag |= _lib.ALGO_HIST_HAS_RT
         with torch.cuda.device(x.device):
@@ -1346,7 +1355,8 @@ class McepFn(torch.autograd.Function):
         scratch = None
         flag = 0
         if images is not None:
-            scratch, flag = _mcep_scratch(X.device)
+            scratch, clean = _mcep_scratch(X.device)
+            flag = _mcep_algo(clean)
         if with_rt:
             flag |= _lib.ALGO_HIST_HAS_RT
         with torch.cuda.device(X.device):
@@ -1856,8 +1866,10 @@ def frame_window_lpc(x, window, L, P, M, eps, center=True, mode="constant", exac
     B = xc.numel() // T
     out = torch.empty(*xc.shape[:-1], num_frames(T, P), M + 1, device=x.device, dtype=x.dtype)
     # the kept-zero per-(device, stream) counters of the persistent kernels (the kernel hands them back zeroed: no fill launch per call;
-    # under graph capture a private block and the library's own reset, see _mcep_scratch)
-    scratch, flag = _mcep_scratch(x.device)
+    # under graph capture a private block and the library's own reset, see _mcep_scratch).  The mel-cepstral launch bits
+    # (overlapped launches, reserved CUs) are not the LPC entry's: only its own flags go with the pad mode.
+    scratch, clean = _mcep_scratch(x.device)
+    flag = _lib.LPC_SCRATCH_IS_CLEAN if clean else 0
     if exact_lag_sums:
         flag |= _lib.LPC_EXACT_LAGSUMS
     with torch.cuda.device(x.device):

@@ -111,6 +111,30 @@ def test_fused_lpc_bench_size_properties():
     assert float(g0.abs().max()) == 0.0
 
 
+@pytest.mark.parametrize("exact", [False, True])
+def test_fused_lpc_under_mcep_launch_flags(exact):
+    """ops.reserve_cus / ops.overlapped_launches set launch bits of the mel-cepstral kernels only (dist.analyze_chunked_overlap
+    reserves CUs in every multi-rank run): the fused LPC branch inside them runs and gives the same bits, forward and backward"""
+    gen = torch.Generator().manual_seed(12)
+    x = torch.randn(8, 8000, generator=gen).to(DEV)
+    gy = torch.randn(8, 100, 25, generator=gen).to(DEV)
+    fl = dsp.fuse(*_mods(400, 80), exact_lag_sums=exact)
+
+    def run():
+        xg = x.clone().requires_grad_(True)
+        y = fl(xg)
+        assert fl.last_path == "fused"
+        (y * gy).sum().backward()
+        return y.detach(), xg.grad
+
+    y0, g0 = run()
+    for ctx in (ops.reserve_cus(8), ops.overlapped_launches()):
+        with ctx:
+            y1, g1 = run()
+        assert torch.equal(y1, y0) and torch.equal(g1, g0), type(ctx).__name__
+    assert ops._reserved_cus[0] == 0 and not ops._overlapped[0]
+
+
 def test_fused_lpc_fallbacks_and_errors():
     f, w, l = _mods(400, 80)
     with pytest.raises(ValueError):

@@ -1,5 +1,5 @@
 // Calibration microbenchmark (dev tool): what one tick of __builtin_readcyclecounter() is worth on this GPU, in vector
-// instructions and in LDS instructions, with 1 / 4 waves per SIMD -- the unit the stamps of tools/bench_stft_pk.cpp are in.
+// instructions and in LDS instructions, with 1 / 4 waves per SIMD -- the unit of the kernels' phase stamps.
 //   hipcc --offload-arch=gfx950 -O3 tools/bench_clock.cpp -o build/bench_clock
 #include <hip/hip_runtime.h>
 

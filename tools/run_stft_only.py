@@ -1,4 +1,4 @@
-"""A few launches of the stand-alone packed STFT kernel at the bench size (for counter collection; DSA_STFT_RUN picks the pass order)."""
+"""A few launches of the stand-alone packed STFT kernel at the bench size (for counter collection)."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import diffsptk_amd as dsp
