@@ -185,6 +185,11 @@ def zerodf(x: Tensor, b: Tensor, frame_period: int = 80, ignore_gain: bool = Fal
                                          zeroth_index=zeroth_index, mode=mode)
 
 
+def poledf(x: Tensor, a: Tensor, frame_period: int = 80, ignore_gain: bool = False) -> Tensor:
+    """Time-variant all-pole filter (functional.py: poledf)."""
+    return nn.AllPoleDigitalFilter._func(x, a, frame_period=frame_period, ignore_gain=ignore_gain)
+
+
 def linear_intpl(x: Tensor, upsampling_factor: int = 80) -> Tensor:
     """Linear interpolation of frame-wise parameters (functional.py: linear_intpl)."""
     return nn.LinearInterpolation._func(x, upsampling_factor=upsampling_factor)

@@ -24,6 +24,7 @@ from .mgc2sp import MelGeneralizedCepstrumToSpectrum
 from .mgcep import MelGeneralizedCepstralAnalysis
 from .mglsadf import PseudoMGLSADigitalFilter
 from .mglsadf import PseudoMGLSADigitalFilter as MLSA
+from .poledf import AllPoleDigitalFilter
 from .zerodf import AllZeroDigitalFilter, LinearInterpolation
 from .mfcc import MelFrequencyCepstralCoefficientsAnalysis
 from .mfcc import MelFrequencyCepstralCoefficientsAnalysis as MFCC
@@ -40,7 +41,7 @@ __all__ = [
     "GeneralizedCepstrumGainNormalization", "GeneralizedCepstrumInverseGainNormalization",
     "MelCepstrumToMLSADigitalFilterCoefficients", "MLSADigitalFilterCoefficientsToMelCepstrum",
     "MelGeneralizedCepstrumToMelGeneralizedCepstrum", "MelGeneralizedCepstrumToSpectrum", "MelGeneralizedCepstralAnalysis",
-    "PseudoMGLSADigitalFilter", "MLSA", "AllZeroDigitalFilter", "LinearInterpolation",
+    "PseudoMGLSADigitalFilter", "MLSA", "AllPoleDigitalFilter", "AllZeroDigitalFilter", "LinearInterpolation",
     "FusedFrameWindowLPC", "FusedSTFTFilterBank", "FusedSTFTMelCepstralAnalysis", "fuse",
     "RealValuedFastFourierTransform", "STFT", "ShortTimeFourierTransform", "Spectrum", "Window",
 ]

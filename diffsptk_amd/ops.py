@@ -1698,6 +1698,61 @@ def zerodf(x, b, P, zeroth_index, ignore_gain):
     return ZerodfFn.apply(x, b, P, zeroth_index, ignore_gain)
 
 
+class PoledfFn(torch.autograd.Function):
+    """Time-variant all-pole filter (poledf.py:117-140, the recursion of torchlpc.sample_wise_lpc): x:(..., T),
+    a:(..., T/P, M+1) -> y:(..., T).  Forward one launch (dsa_poledf_fwd); backward the adjoint recursion, then ga in a
+    second launch when a needs a gradient (dsa_poledf_bwd)."""
+
+    @staticmethod
+    def forward(ctx, x, a, P, ignore_gain):
+        _require_device(x, a)
+        _same_dtype(x, a)
+        xc, ac = x.contiguous(), a.contiguous()
+        T = xc.size(-1)
+        M = ac.size(-1) - 1
+        B = xc.numel() // max(T, 1)
+        if ac.dim() < 2 or ac.shape[:-2] != xc.shape[:-1] or ac.size(-2) * P != T:
+            raise ValueError(f"poledf: coefficients {tuple(ac.shape)} do not match the signal {tuple(xc.shape)} at frame period {P}")
+        y = torch.empty_like(xc)
+        with torch.cuda.device(x.device):
+            _call("dsa_poledf_fwd", _p(xc), _p(ac), B, T, M, P, int(bool(ignore_gain)), _dtype_code(xc), _p(y), _stream())
+        ctx.save_for_backward(xc, ac, y)
+        ctx.cfg = (P, int(bool(ignore_gain)))
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        xc, ac, y = ctx.saved_tensors
+        P, ig = ctx.cfg
+        T = xc.size(-1)
+        M = ac.size(-1) - 1
+        B = xc.numel() // max(T, 1)
+        gyc = gy.contiguous()
+        u = torch.empty_like(xc)   # the adjoint state (the library owns no device memory)
+        gx = torch.empty_like(xc) if ctx.needs_input_grad[0] else None
+        ga = torch.empty_like(ac) if ctx.needs_input_grad[1] else None
+        with torch.cuda.device(gy.device):
+            _call("dsa_poledf_bwd", _p(gyc), _p(xc), _p(ac), _p(y), B, T, M, P, ig, _dtype_code(xc), _p(u), _p(gx), _p(ga), _stream())
+        return gx, ga, None, None
+
+
+def poledf(x, a, P, ignore_gain):
+    """PoledfFn with the leading dimensions of x:(..., T) and a:(..., T/P, M+1) broadcast against each other first (as zerodf()
+    does; the gradient of a broadcast operand is summed back by autograd)."""
+    if a.dim() < 2:
+        raise ValueError("poledf: a must have at least two dimensions (frames, coefficients).")
+    try:
+        batch = torch.broadcast_shapes(x.shape[:-1], a.shape[:-2])
+    except RuntimeError as e:
+        raise ValueError(f"poledf: leading dimensions of x {tuple(x.shape)} and a {tuple(a.shape)} do not broadcast") from e
+    if tuple(x.shape[:-1]) != tuple(batch):
+        x = x.expand(*batch, x.size(-1))
+    if tuple(a.shape[:-2]) != tuple(batch):
+        a = a.expand(*batch, *a.shape[-2:])
+    return PoledfFn.apply(x, a, P, ignore_gain)
+
+
 def zerodf_taylor_shapes_ok(x, b, P) -> bool:
     """Shapes the fused Taylor-stage launches cover, forward and backward (csrc/mgc.hip:zerodf_rows_plan, zerodf_launch_bwd)."""
     return (P % 4 == 0 and 16 <= P <= 256 and b.size(-1) - 1 >= 16 and b.dim() >= 2 and tuple(b.shape[:-2]) == tuple(x.shape[:-1])

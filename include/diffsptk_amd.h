@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define DSA_VERSION 129 /* 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
+#define DSA_VERSION 130 /* 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
 
 typedef enum {
     DSA_OK = 0,
@@ -480,6 +480,23 @@ int dsa_zerodf_taylor_fwd(const void* x, const void* b, int64_t B, int64_t T, in
  * Same shape limits as dsa_zerodf_taylor_fwd. */
 int dsa_zerodf_taylor_bwd(const void* G, const void* x, const void* b, int64_t B, int64_t T, int32_t M, int32_t P,
                           int32_t zeroth_index, double scale, const void* gy, int32_t dtype, void* G_out, void* gb, void* stream);
+
+/* ------------------------------------------------------------------ f5  time-variant all-pole filter (0.2.4)
+ * AllPoleDigitalFilter._forward, poledf.py:117-140 (the reference delegates the recursion to torchlpc.sample_wise_lpc): the LPC
+ * synthesis filter.  x:(B,T), a:(B,N,M+1) with T = N P, a row [K, a_1 .. a_M] -> y:(B,T), zero initial state:
+ *   c_t = lerp(a[t / P], a[min(t / P + 1, N - 1)], (t % P) / P),  g_t = c_t[0] (1 with ignore_gain),
+ *   y[t] = g_t x[t] - sum_{k=1..M} c_t[k] y[t - k].
+ * Backward: gy, and the forward's x, a, y -> the adjoint state u:(B,T) (always written: a caller-owned buffer, the library owns no
+ * device memory), gx:(B,T) and / or ga:(B,N,M+1) (either may be NULL; x and y are only read for ga):
+ *   u[t] = gy[t] - sum_{k=1..M} c_{t+k}[k] u[t + k],  gx[t] = g_t u[t],
+ *   dc_t[k] = -u[t] y[t - k] (k >= 1),  dc_t[0] = u[t] x[t] (0 with ignore_gain),  ga = the adjoint of the interpolation of dc.
+ * One wave per utterance for 1 <= M <= 63 (a row window of 63 / P + 3 frames of M + 1 values within 512); other shapes take a
+ * plain one-thread-per-utterance kernel.  0 <= M <= DSA_POLEDF_MAX_ORDER. */
+#define DSA_POLEDF_MAX_ORDER 4096
+int dsa_poledf_fwd(const void* x, const void* a, int64_t B, int64_t T, int32_t M, int32_t P, int32_t ignore_gain, int32_t dtype,
+                   void* y, void* stream);
+int dsa_poledf_bwd(const void* gy, const void* x, const void* a, const void* y, int64_t B, int64_t T, int32_t M, int32_t P,
+                   int32_t ignore_gain, int32_t dtype, void* u, void* gx, void* ga, void* stream);
 
 /* ------------------------------------------------------------------ a11  autocorrelation
  * Autocorrelation._forward, acorr.py:110-120.  x:(F,L) -> r:(F,M+1).  Computed as direct lag
