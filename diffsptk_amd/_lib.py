@@ -16,7 +16,7 @@ _ROOT = os.path.dirname(_PKG)
 CSRC = os.path.join(_PKG, "csrc")
 LIB_DIR = os.path.join(_PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libdiffsptk_amd.so")
-SOURCES = ("stft.hip", "mcep.hip", "mcep_mfma.hip", "lpc.hip", "fbank.hip", "fftcep.hip", "mgc.hip", "rows_gemm.hip", "thsolve_quad.hip", "poledf.hip")
+SOURCES = ("stft.hip", "mcep.hip", "mcep_mfma.hip", "lpc.hip", "fbank.hip", "fftcep.hip", "mgc.hip", "rows_gemm.hip", "thsolve_quad.hip", "poledf.hip", "plp.hip")
 HIPCC_FLAGS = (
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
     "-mcode-object-version=5", "-Wno-unused-value", "-ffp-contract=on",
@@ -34,12 +34,14 @@ SOURCE_FLAGS = {
     "mgc.hip": _NO_PK,
     "thsolve_quad.hip": _NO_PK,
     "poledf.hip": _NO_PK,
+    "plp.hip": _NO_PK,
     "mcep_mfma.hip": _NO_PK,   # (its kernels carry DSA_PK_TARGET -- measured faster with the compiler's pairing -- except mgcep_step_h)
 }
 
 F32, F64 = 0, 1
 SCRATCH_BYTES = 64   # DSA_SCRATCH_BYTES
 FBANK_PLAN_FLOATS = 2048   # DSA_FBANK_PLAN_FLOATS
+PLP_MAX_ORDER = 62         # DSA_PLP_MAX_ORDER
 ERR_UNSUPPORTED = -2       # DSA_ERR_UNSUPPORTED
 LPC_SCRATCH_IS_CLEAN = 0x100  # DSA_LPC_SCRATCH_IS_CLEAN
 LPC_EXACT_LAGSUMS = 0x200  # DSA_LPC_EXACT_LAGSUMS
@@ -184,6 +186,8 @@ SIGNATURES = {
     "dsa_zerodf_taylor_bwd": (C.c_int, [_P, _P, _P, _L, _L, _I, _I, _I, C.c_double, _P, _I, _P, _P, _P]),
     "dsa_poledf_fwd": (C.c_int, [_P, _P, _L, _L, _I, _I, _I, _I, _P, _P]),
     "dsa_poledf_bwd": (C.c_int, [_P, _P, _P, _P, _L, _L, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "dsa_plp_fwd": (C.c_int, [_P, _P, _L, _I, _I, _I, _D, _I, _P, _I, _P, _P, _P]),
+    "dsa_plp_bwd": (C.c_int, [_P, _P, _P, _L, _I, _I, _I, _D, _I, _P, _I, _P, _P, _P]),
     "dsa_acorr_fwd": (C.c_int, [_P, _L, _I, _I, _I, _I, _P, _P]),
     "dsa_acorr_bwd": (C.c_int, [_P, _P, _L, _I, _I, _I, _I, _P, _P]),
     "dsa_levdur_fwd": (C.c_int, [_P, _L, _I, _D, _I, _P, _P]),

@@ -185,6 +185,16 @@ def zerodf(x: Tensor, b: Tensor, frame_period: int = 80, ignore_gain: bool = Fal
                                          zeroth_index=zeroth_index, mode=mode)
 
 
+def plp(x: Tensor, plp_order: int, n_channel: int, sample_rate: int, compression_factor: float = 0.33, lifter: int = 1,
+        f_min: float = 0, f_max: float | None = None, floor: float = 1e-5, gamma: float = 0, scale: str = "htk",
+        erb_factor: float | None = None, n_fft: int = 512, out_format: str = "y") -> Tensor:
+    """PLP analysis of power spectra x:(..., L/2+1) -> (..., M) (+ C0 / energy) (functional.py: plp)."""
+    return nn.PerceptualLinearPredictiveCoefficientsAnalysis._func(
+        x, plp_order=plp_order, n_channel=n_channel, sample_rate=sample_rate, compression_factor=compression_factor,
+        lifter=lifter, f_min=f_min, f_max=f_max, floor=floor, gamma=gamma, scale=scale, erb_factor=erb_factor, n_fft=n_fft,
+        out_format=out_format)
+
+
 def poledf(x: Tensor, a: Tensor, frame_period: int = 80, ignore_gain: bool = False) -> Tensor:
     """Time-variant all-pole filter (functional.py: poledf)."""
     return nn.AllPoleDigitalFilter._func(x, a, frame_period=frame_period, ignore_gain=ignore_gain)

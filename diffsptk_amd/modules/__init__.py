@@ -24,6 +24,8 @@ from .mgc2sp import MelGeneralizedCepstrumToSpectrum
 from .mgcep import MelGeneralizedCepstralAnalysis
 from .mglsadf import PseudoMGLSADigitalFilter
 from .mglsadf import PseudoMGLSADigitalFilter as MLSA
+from .plp import PerceptualLinearPredictiveCoefficientsAnalysis
+from .plp import PerceptualLinearPredictiveCoefficientsAnalysis as PLP
 from .poledf import AllPoleDigitalFilter
 from .zerodf import AllZeroDigitalFilter, LinearInterpolation
 from .mfcc import MelFrequencyCepstralCoefficientsAnalysis
@@ -41,7 +43,7 @@ __all__ = [
     "GeneralizedCepstrumGainNormalization", "GeneralizedCepstrumInverseGainNormalization",
     "MelCepstrumToMLSADigitalFilterCoefficients", "MLSADigitalFilterCoefficientsToMelCepstrum",
     "MelGeneralizedCepstrumToMelGeneralizedCepstrum", "MelGeneralizedCepstrumToSpectrum", "MelGeneralizedCepstralAnalysis",
-    "PseudoMGLSADigitalFilter", "MLSA", "AllPoleDigitalFilter", "AllZeroDigitalFilter", "LinearInterpolation",
+    "PseudoMGLSADigitalFilter", "MLSA", "PerceptualLinearPredictiveCoefficientsAnalysis", "PLP", "AllPoleDigitalFilter", "AllZeroDigitalFilter", "LinearInterpolation",
     "FusedFrameWindowLPC", "FusedSTFTFilterBank", "FusedSTFTMelCepstralAnalysis", "fuse",
     "RealValuedFastFourierTransform", "STFT", "ShortTimeFourierTransform", "Spectrum", "Window",
 ]

@@ -18,6 +18,7 @@ from .frame import Frame
 from .lpc import LinearPredictiveCodingAnalysis
 from .mcep import MelCepstralAnalysis
 from .mfcc import MelFrequencyCepstralCoefficientsAnalysis
+from .plp import PerceptualLinearPredictiveCoefficientsAnalysis
 from .stft import ShortTimeFourierTransform
 from .window import Window
 
@@ -25,7 +26,9 @@ _SPEC_POWER, _FFT, _FRAME = 3, 512, 400
 
 
 class FusedSTFTFilterBank(nn.Module):
-    """``analysis(stft(x))`` for ``analysis`` a MelFilterBankAnalysis or a MelFrequencyCepstralCoefficientsAnalysis.
+    """``analysis(stft(x))`` for ``analysis`` a MelFilterBankAnalysis, a MelFrequencyCepstralCoefficientsAnalysis or a
+    PerceptualLinearPredictiveCoefficientsAnalysis (out_format y / yc: the one-launch filter bank on power values, then the PLP
+    tail's launch, dsa_plp_fwd -- two launches, no spectrogram in memory; the fused kernel has no E, so yE / ycE take two stages).
 
     ``last_path`` tells which route the last call took ("fused" / "two-stage") -- for tests and profiles."""
 
@@ -33,7 +36,8 @@ class FusedSTFTFilterBank(nn.Module):
         super().__init__()
         if not isinstance(stft, ShortTimeFourierTransform):
             raise ValueError("stft must be a ShortTimeFourierTransform.")
-        if not isinstance(analysis, (MelFilterBankAnalysis, MelFrequencyCepstralCoefficientsAnalysis)):
+        if not isinstance(analysis, (MelFilterBankAnalysis, MelFrequencyCepstralCoefficientsAnalysis,
+                                     PerceptualLinearPredictiveCoefficientsAnalysis)):
             raise ValueError("analysis must be a MelFilterBankAnalysis or a MelFrequencyCepstralCoefficientsAnalysis.")
         if stft.fft_length // 2 + 1 != analysis.in_dim:
             raise ValueError("stft and analysis disagree on fft_length.")
@@ -51,7 +55,8 @@ class FusedSTFTFilterBank(nn.Module):
                 and s.fft_length == _FFT and s.frame_length == _FRAME and s.frame_period % 2 == 0
                 and 3 * s.frame_period + 512 <= 2176):
             return False
-        return a.out_format == "y" and ops.fbank_scan_plan(a.H) is not None and ops.fbank_bins_table(a.H) is not None
+        formats = ("y", "yc") if isinstance(a, PerceptualLinearPredictiveCoefficientsAnalysis) else ("y",)
+        return a.out_format in formats and ops.fbank_scan_plan(a.H) is not None and ops.fbank_bins_table(a.H) is not None
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         s, a = self.stft, self.analysis
@@ -60,13 +65,16 @@ class FusedSTFTFilterBank(nn.Module):
             return a(s(x))
         self.last_path = "fused"
         is_mfcc = isinstance(a, MelFrequencyCepstralCoefficientsAnalysis)
-        use_power = False if is_mfcc else a.use_power          # mfcc.py:200: amplitude domain
+        is_plp = isinstance(a, PerceptualLinearPredictiveCoefficientsAnalysis)
+        use_power = False if is_mfcc else True if is_plp else a.use_power   # mfcc.py:200: amplitude domain; plp.py:248: power
         # with a gradient needed the same launch runs as an autograd Function (backward: channel cotangents -> bins -> the
         # STFT backward kernel; ops.StftFbankFn)
         y = ops.StftFbankFn.apply(x, s.window, s.twiddle, a.H, ops.fbank_scan_plan(a.H), s.frame_length, s.frame_period,
                                   s.fft_length, s.center, s.eps, a.floor, a.gamma, use_power)
         if is_mfcc:   # DCT-II x truncation x lifter (mfcc.py:249-252): one row product on (.., C) values; C0 dropped ("y")
             y = ops.MatmulRowsFn.apply(y, a.W)[..., 1:]
+        elif is_plp:  # the PLP tail on the (.., C) log filter-bank values (plp.py:315-320), backward into StftFbankFn's
+            y = ops.PlpFn.apply(y, None, a.table, a.plp_order, a.n_fft, a.compression_factor, a.out_format)
         return y
 
 
@@ -162,7 +170,7 @@ def fuse(first: nn.Module, *rest: nn.Module, **options) -> nn.Module:
     """One launch where a fused kernel applies, the modules themselves elsewhere:
 
     * ``fuse(stft, analysis)(x) == analysis(stft(x))`` for ``analysis`` a MelCepstralAnalysis (the hot path), a
-      MelFilterBankAnalysis or a MelFrequencyCepstralCoefficientsAnalysis;
+      MelFilterBankAnalysis, a MelFrequencyCepstralCoefficientsAnalysis or a PerceptualLinearPredictiveCoefficientsAnalysis;
     * ``fuse(frame, window, lpc)(x) == lpc(window(frame(x)))`` -- the LPC branch, forward and backward."""
     if isinstance(first, Frame):
         if len(rest) != 2:

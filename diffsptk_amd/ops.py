@@ -831,6 +831,51 @@ class MfccFn(torch.autograd.Function):
         return gx, None, None, None, None, None
 
 
+PLP_FORMATS = {"y": 0, "yE": 1, "yc": 2, "ycE": 3}
+
+
+class PlpFn(torch.autograd.Function):
+    """PLP after the filter bank (plp.py:315-320): y:(..., C) log filter-bank outputs and E:(..., 1) (None unless out_format
+    carries it) -> (..., M + {0, 1, 1, 2}).  Equal loudness, compression, replicate1, hfft, Levinson (eps = 0), the n_fft-point
+    LPC -> cepstrum sum, lifter and formatter in one launch (dsa_plp_fwd); the adjoint of all of it in one launch (dsa_plp_bwd)
+    from the saved [K, a].  `table` is the packed constant table (tables.plp_table) in the dtype of y."""
+
+    @staticmethod
+    def forward(ctx, y, E, table, M, n_fft, compression_factor, fmt):
+        _require_device(y, E, table)
+        _same_dtype(y, E, table)
+        code = PLP_FORMATS[fmt]
+        if (code & 1) and E is None:
+            raise ValueError(f"plp: out_format {fmt} needs E")
+        yc = y.contiguous()
+        Ec = E.contiguous() if code & 1 else None
+        C = yc.size(-1)
+        F = yc.numel() // C
+        Mo = M + (code & 1) + (code >> 1)
+        out = torch.empty(*yc.shape[:-1], Mo, device=y.device, dtype=y.dtype)
+        save = torch.empty(F, M + 1, device=y.device, dtype=y.dtype) if ctx.needs_input_grad[0] else None
+        with torch.cuda.device(y.device):
+            _call("dsa_plp_fwd", _p(yc), _p(Ec), F, C, M, n_fft, float(compression_factor), code, _p(table), _dtype_code(yc),
+                  _p(out), _p(save), _stream())
+        ctx.save_for_backward(yc, table, save)
+        ctx.cfg = (M, n_fft, float(compression_factor), code, E is not None)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        yc, table, save = ctx.saved_tensors
+        M, n_fft, cf, code, has_E = ctx.cfg
+        C = yc.size(-1)
+        F = yc.numel() // C
+        gy = torch.empty_like(yc)
+        gE = torch.empty(*yc.shape[:-1], 1, device=yc.device, dtype=yc.dtype) if has_E and ctx.needs_input_grad[1] else None
+        with torch.cuda.device(yc.device):
+            _call("dsa_plp_bwd", _p(gout.contiguous()), _p(yc), _p(save), F, C, M, n_fft, cf, code, _p(table), _dtype_code(yc),
+                  _p(gy), _p(gE), _stream())
+        return gy, gE, None, None, None, None, None
+
+
 # ----------------------------------------------------------------------------------- mcep
 def _mcep_composed_applies(Xc, M) -> bool:
     """Geometries without a tuned kernel (48 kHz set-ups: fft_length 1024 / 2048, orders 34 .. 60).  A function of the geometry

@@ -715,3 +715,59 @@ def fbank_bins_table(H: np.ndarray):
                 out[k, 2] = H[k, nz[1]]
     out[:, 0] = idx.view(np.float32)
     return out
+
+
+# ------------------------------------------------------------------ PLP (plp.py:192-320)
+def plp_equal_loudness(n_channel: int, sample_rate: int, f_min: float = 0.0, f_max: float | None = None,
+                       scale: str = "htk") -> np.ndarray:
+    """Equal-loudness curve q:(C,) of plp.py:272-285: the auditory-scale centres 1..C+1 (the last one dropped), f = hz^2."""
+    if f_max is None:
+        f_max = sample_rate / 2
+    z_min = hz_to_auditory(np.asarray(f_min), scale)
+    z_max = hz_to_auditory(np.asarray(f_max), scale)
+    seed = np.arange(1, n_channel + 2)
+    f = auditory_to_hz((z_max - z_min) / (n_channel + 1) * seed + z_min, scale)[:-1] ** 2
+    return (f / (f + 1.6e5)) ** 2 * (f + 1.44e6) / (f + 9.61e6)
+
+
+def plp_lifter(plp_order: int, lifter: int) -> np.ndarray:
+    """Liftering vector of plp.py:287-289 (entry 0 is 2; lifter = 0: ZeroDivisionError, as in the reference)."""
+    r = np.arange(plp_order + 1, dtype=np.float64)
+    v = 1.0 + (lifter / 2) * np.sin((math.pi / lifter) * r)
+    v[0] = 2.0
+    return v
+
+
+def plp_hfft_matrix(n_channel: int, plp_order: int) -> np.ndarray:
+    """(C+2, M+1): r = u @ Q is hfft(u, norm="forward")[:M+1] of a real u:(C+2) (plp.py:317):
+    Q[n, k] = e_n cos(pi n k / (C+1)) / (2C+2), e_n = 1 at n = 0 and n = C+1, else 2."""
+    n = np.arange(n_channel + 2, dtype=np.float64)[:, None]
+    k = np.arange(plp_order + 1, dtype=np.float64)[None, :]
+    e = np.full((n_channel + 2, 1), 2.0)
+    e[0] = e[-1] = 1.0
+    return e * np.cos(math.pi * n * k / (n_channel + 1)) / (2 * n_channel + 2)
+
+
+def plp_spectrum_tables(plp_order: int, n_fft: int):
+    """The n_fft-point LPC -> cepstrum sum of plp.py:318 (mgc2mgc.py:207-300 with in_gamma = -1, in_norm, in_mul -> gamma 0)
+    over the half spectrum j = 0..n_fft/2: cos, sin (M+1, J) of 2 pi j m / n_fft, and the weights -(2 / n_fft) {1, 2, .., 2, (1)}
+    (the last one 1 only for even n_fft), so that c_m = sum_j w_j log|A_j| cos_mj for m >= 1."""
+    J = n_fft // 2 + 1
+    m = np.arange(plp_order + 1, dtype=np.float64)[:, None]
+    j = np.arange(J, dtype=np.float64)[None, :]
+    ph = 2.0 * math.pi * ((m * j) % n_fft) / n_fft
+    w = np.full(J, 2.0)
+    w[0] = 1.0
+    if n_fft % 2 == 0:
+        w[-1] = 1.0
+    return np.cos(ph), np.sin(ph), w * (-2.0 / n_fft)
+
+
+def plp_table(n_channel: int, plp_order: int, n_fft: int, sample_rate: int, f_min: float = 0.0, f_max: float | None = None,
+              scale: str = "htk", lifter: int = 1) -> np.ndarray:
+    """The packed per-configuration table of dsa_plp_fwd / dsa_plp_bwd (include/diffsptk_amd.h), float64:
+    [q (C) | Q (C+2, M+1) | cos (M+1, J) | sin (M+1, J) | w (J) | lifter (M+1)], J = n_fft/2 + 1."""
+    cs, sn, w = plp_spectrum_tables(plp_order, n_fft)
+    return np.concatenate([plp_equal_loudness(n_channel, sample_rate, f_min, f_max, scale),
+                           plp_hfft_matrix(n_channel, plp_order).reshape(-1), cs.reshape(-1), sn.reshape(-1), w,
+                           plp_lifter(plp_order, lifter)])

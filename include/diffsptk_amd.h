@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define DSA_VERSION 130 /* 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
+#define DSA_VERSION 131 /* 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
 
 typedef enum {
     DSA_OK = 0,
@@ -497,6 +497,26 @@ int dsa_poledf_fwd(const void* x, const void* a, int64_t B, int64_t T, int32_t M
                    void* y, void* stream);
 int dsa_poledf_bwd(const void* gy, const void* x, const void* a, const void* y, int64_t B, int64_t T, int32_t M, int32_t P,
                    int32_t ignore_gain, int32_t dtype, void* u, void* gx, void* ga, void* stream);
+
+/* ------------------------------------------------------------------ f6  perceptual linear prediction after the filter bank (0.2.5)
+ * PerceptualLinearPredictiveCoefficientsAnalysis._forward, plp.py:313-320, from `y, E = fbank(x)` on (plp.py:314), with
+ * levdur.py:114-127 (eps = 0) and mgc2mgc.py:207-300 (in_gamma = -1, in_norm, in_mul -> gamma 0: lpc2c).  y:(F,C) log filter-bank
+ * outputs, E:(F) log energy (read only when out_format carries it; may be NULL otherwise) -> out:(F, Mo), Mo = M + {0, 1, 1, 2}
+ * for out_format 0 y, 1 yE, 2 yc, 3 ycE:
+ *   v_c = (exp(y_c) q_c)^cf,  u = [v_0, v, v_{C-1}],  r_k = sum_n u_n Q[n][k] (hfft(u, norm="forward")[:M+1]),  [K, a] = levdur(r),
+ *   c_0 = log K,  c_m = sum_{j=0..N/2} w_j log|1 + sum_l a_l e^{-2 pi i j l / N}| cos(2 pi j m / N)  (the reference's aliased
+ *   N-point sum),  c *= lifter,  out row = [c_1 .. c_M] (+ c_0) (+ E).
+ * table: the packed float64-built constants in the data's dtype (utils/tables.py: plp_table), J = N/2 + 1:
+ *   [q (C) | Q (C+2, M+1) | cos (M+1, J) | sin (M+1, J) | w (J) = -(2/N) {1, 2, .., 2, (1)} | lifter (M+1)].
+ * save:(F, M+1) (may be NULL) receives [K, a] for the backward.  Backward: gout:(F, Mo), the forward's y and save -> gy:(F,C) (the
+ * cotangent of the filter-bank outputs, for dsa_fbank_bwd / dsa_fbank_bins_bwd) and gE:(F) (may be NULL; the pass-through of E's
+ * column, 0 without one).  One wave per frame: a frame's bits do not depend on F.  0 <= M <= DSA_PLP_MAX_ORDER, C > M, N > M + 1;
+ * float32 and float64; F = 0 is a no-op; no allocation, no host synchronisation. */
+#define DSA_PLP_MAX_ORDER 62
+int dsa_plp_fwd(const void* y, const void* E, int64_t F, int32_t C, int32_t M, int32_t N, double compression_factor,
+                int32_t out_format, const void* table, int32_t dtype, void* out, void* save, void* stream);
+int dsa_plp_bwd(const void* gout, const void* y, const void* save, int64_t F, int32_t C, int32_t M, int32_t N,
+                double compression_factor, int32_t out_format, const void* table, int32_t dtype, void* gy, void* gE, void* stream);
 
 /* ------------------------------------------------------------------ a11  autocorrelation
  * Autocorrelation._forward, acorr.py:110-120.  x:(F,L) -> r:(F,M+1).  Computed as direct lag
