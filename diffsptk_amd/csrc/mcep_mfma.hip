@@ -312,13 +312,14 @@ __device__ __forceinline__ f32x4 mfma441(float a, float b, f32x4 c)
 }
 
 // rows of R + Q in block layout; slot 6 through the two per-lane pointers of col_build_rows_p (column 24 | right-hand side
-// | second right-hand side or zero | zero).  Rows 25 .. 27 are padding: never pivots, never read.
-template <int rg>
-__device__ __forceinline__ void blk_build_rows(f32x4 (&a)[blk::NBLK], const float* rt0, const float* rr0, const float* pa6,
+// | second right-hand side or zero | zero).  Rows 25 .. 27 are padding: never pivots, never read.  (A set of N = NBLK - 1
+// quadruples leaves out block (6, 6): the forward kernels keep row 24 in one register of its own, blk_elim_all_r24.)
+template <int rg, int N>
+__device__ __forceinline__ void blk_build_rows(f32x4 (&a)[N], const float* rt0, const float* rr0, const float* pa6,
                                                const float* pb6, int gs)
 {
     using namespace mm;
-    if constexpr (rg < blk::NG) {
+    if constexpr (rg < blk::NG && blk::at(rg, rg) < N) {
         const float* rt_g = rt0 + gs;
         const float* rr_g = rr0 + 27 - gs;
 #ifndef DSA_BLK_BUILD_SCALAR   // the four rows of a block as ONE 16-byte read per window (dword-aligned) and two packed additions
@@ -347,10 +348,10 @@ __device__ __forceinline__ void blk_build_rows(f32x4 (&a)[blk::NBLK], const floa
     }
 }
 
-template <int k, int rg>
-__device__ __forceinline__ void blk_update_groups(f32x4 (&a)[blk::NBLK], const float (&m)[blk::NG])
+template <int k, int rg, int N>
+__device__ __forceinline__ void blk_update_groups(f32x4 (&a)[N], const float (&m)[blk::NG])
 {
-    if constexpr (rg < blk::NG) {
+    if constexpr (rg < blk::NG && blk::at(rg, rg) < N) {
         // A = the multipliers of rows 4 rg .. 4 rg + 3 (slot rg of the scaled pivot row), B = the pivot row where it stands
 #pragma unroll
         for (int c = rg; c < blk::NG; ++c) a[blk::at(rg, c)] = mfma441(m[rg], a[blk::at(k >> 2, c)][k & 3], a[blk::at(rg, c)]);
@@ -399,8 +400,8 @@ __device__ __forceinline__ void blk_elim_all(f32x4 (&a)[blk::NBLK], const GroupM
 // Row group by row group: the sums over the FINISHED column groups (c > rg) of the group's four rows are packed two rows to
 // an instruction (a register pair of the quadruple times the broadcast x slot); only the row's own column group, the quad
 // reduction and the division are serial.
-template <int rg>
-__device__ __forceinline__ void blk_backsub_group(const f32x4 (&a)[blk::NBLK], float (&xq)[mm::KS], const GroupMask& gq,
+template <int rg, int N>
+__device__ __forceinline__ void blk_backsub_group(const f32x4 (&a)[N], float (&xq)[mm::KS], const GroupMask& gq,
                                                   const float (&ninvs)[mm::M1])
 {
     typedef float f2 __attribute__((ext_vector_type(2)));
@@ -430,6 +431,65 @@ __device__ __forceinline__ void blk_backsub_all(const f32x4 (&a)[blk::NBLK], flo
                                                 const float (&ninvs)[mm::M1], std::integer_sequence<int, Gs...>)
 {
     (blk_backsub_group<blk::NG - 1 - Gs>(a, xq, gq, ninvs), ...);
+}
+
+// The forward kernels' elimination (one right-hand side).  Bit-identical to blk_elim_all + blk_backsub_all: every element
+// still takes the same fmaf(multiplier, pivot-row entry, entry) in the same order, only work on dead lanes goes.
+//  - Row 24 is one register r24 (lane 0: column 24, lane 1: the right-hand side, lanes 2, 3: zero -- slot 6 of the row as in
+//    the block set) instead of block (6, 6), whose rows 25 .. 27 are padding: its update in each of the steps 0 .. 23 is one
+//    vector multiply-add with the multiplier of lane 0 of m[6] instead of a 4 x 4 x 1 product (8 cycles of the float32
+//    datapath for 4 + 2 of the broadcast), and the quadruple's three dead registers go.
+//  - At q == 2 the only live row of the pivot's own row group is 4 c0 + 3: 7 - c0 vector multiply-adds on element 3 of the
+//    group's blocks (the multiplier broadcast from lane 3) instead of 7 - c0 products with three quarters of A zero.
+// Both stay in the step's vector run, ahead of its products (a vector instruction between two products costs ~9 cycles).
+template <int k>
+__device__ __forceinline__ void blk_elim_step_r24(f32x4 (&a)[blk::NBLK - 1], float& r24, const GroupMask& gq,
+                                                  float (&ninvs)[mm::M1])
+{
+    using namespace blk;
+    constexpr int c0 = k >> 2, q = k & 3;
+    if constexpr (k == mm::M1 - 1) ninvs[k] = -__builtin_amdgcn_rcpf(quad_bcast<0>(r24));
+    if constexpr (k < mm::M1 - 1) {
+        const float ninv = -__builtin_amdgcn_rcpf(quad_bcast<q>(a[at(c0, c0)][q]));
+        ninvs[k] = ninv;
+        float m[NG];
+#pragma unroll
+        for (int c = 0; c < NG; ++c) m[c] = c >= c0 ? a[at(c0, c >= c0 ? c : c0)][q] * ninv : 0.f;
+        r24 = __builtin_fmaf(quad_bcast<0>(m[6]), a[at(c0, 6)][q], r24);
+        if constexpr (q == 2) {
+            const float m3 = quad_bcast<3>(m[c0]);
+#pragma unroll
+            for (int c = c0; c < NG; ++c) a[at(c0, c)][3] = __builtin_fmaf(m3, a[at(c0, c)][2], a[at(c0, c)][3]);
+        }
+        const float m0 = keep_if(gq.gt[q], m[c0]);
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (q < 2) {
+#pragma unroll
+            for (int c = c0; c < NG; ++c) a[at(c0, c)] = mfma441(m0, a[at(c0, c)][q], a[at(c0, c)]);
+        }
+        blk_update_groups<k, c0 + 1>(a, m);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+template <int... Ks>
+__device__ __forceinline__ void blk_elim_all_r24(f32x4 (&a)[blk::NBLK - 1], float& r24, const GroupMask& gq,
+                                                 float (&ninvs)[mm::M1], std::integer_sequence<int, Ks...>)
+{
+    (blk_elim_step_r24<Ks>(a, r24, gq, ninvs), ...);
+}
+
+// back substitution of blk_elim_all_r24: row 24 (blk_backsub_group<6> with its one live row read from r24), then groups 5 .. 0
+template <int... Gs>
+__device__ __forceinline__ void blk_backsub_all_r24(const f32x4 (&a)[blk::NBLK - 1], float r24, float (&xq)[mm::KS],
+                                                    const GroupMask& gq, const float (&ninvs)[mm::M1],
+                                                    std::integer_sequence<int, Gs...>)
+{
+    float sl = __builtin_fmaf(r24, xq[6], 0.f);
+    sl += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(sl), 0xB1, 0xf, 0xf, true));  // quad_perm [1,0,3,2]
+    sl += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(sl), 0x4E, 0xf, 0xf, true));  // quad_perm [2,3,0,1]
+    const float x24 = sl * ninvs[mm::M1 - 1];
+    xq[6] = gq.m[0] ? x24 : xq[6];
+    (blk_backsub_group<blk::NG - 2 - Gs>(a, xq, gq, ninvs), ...);
 }
 
 // The same back substitution taking the pivots' reciprocals again instead of reading the 25 kept by the elimination (the

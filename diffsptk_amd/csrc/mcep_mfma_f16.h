@@ -930,7 +930,10 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) DSA_PK_TARGET void mcep_mfma
 #ifdef DSA_MCEP_SOLVE_VALU   // the column-cyclic v_fmac_f32_dpp elimination of rounds 1-2 (A/B builds; bit-identical results)
             float a[colm::TOTAL];
 #else
-            f32x4 a[blk::NBLK];
+            // every block but (6, 6): row 24 is r24 (blk_elim_all_r24).  The options instantiation keeps all 28 and the shared
+            // elimination (the same results): with r24 it needs 20 bytes of scratch per lane.
+            f32x4 a[PADM ? blk::NBLK : blk::NBLK - 1];
+            float r24 = 0.f;
 #endif
             {
                 // slot c = 6 of every row through two per-lane pointers (see col_build_rows_p); re-derived every step so
@@ -943,6 +946,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) DSA_PK_TARGET void mcep_mfma
                 col_build_rows_p<0>(a, rt_q, rr_q, pa6, pb6, gs);
 #else
                 blk_build_rows<0>(a, rt_q, rr_q, pa6, pb6, gs);
+                if constexpr (!PADM) r24 = pa6[24] + pb6[24];
 #endif
             }
             __builtin_amdgcn_wave_barrier();
@@ -954,10 +958,16 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) DSA_PK_TARGET void mcep_mfma
             col_backsub_all(a, xq, gq, std::make_integer_sequence<int, M1>{});
 #else
             float ninvs[M1];
-            blk_elim_all(a, gq, ninvs, std::make_integer_sequence<int, M1>{});
+            if constexpr (PADM)
+                blk_elim_all(a, gq, ninvs, std::make_integer_sequence<int, M1>{});
+            else
+                blk_elim_all_r24(a, r24, gq, ninvs, std::make_integer_sequence<int, M1>{});
             DSA_STAMP(4);
 #if !(DSA_FUSED_DBG & 4)
-            blk_backsub_all(a, xq, gq, ninvs, std::make_integer_sequence<int, blk::NG>{});
+            if constexpr (PADM)
+                blk_backsub_all(a, xq, gq, ninvs, std::make_integer_sequence<int, blk::NG>{});
+            else
+                blk_backsub_all_r24(a, r24, xq, gq, ninvs, std::make_integer_sequence<int, blk::NG - 1>{});
 #else
             xq[0] = ninvs[0] + a[0][0];
 #endif
