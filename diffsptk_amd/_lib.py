@@ -16,7 +16,8 @@ _ROOT = os.path.dirname(_PKG)
 CSRC = os.path.join(_PKG, "csrc")
 LIB_DIR = os.path.join(_PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libdiffsptk_amd.so")
-SOURCES = ("stft.hip", "mcep.hip", "mcep_mfma.hip", "lpc.hip", "fbank.hip", "fftcep.hip", "mgc.hip", "rows_gemm.hip", "thsolve_quad.hip", "poledf.hip", "plp.hip")
+SOURCES = ("stft.hip", "mcep.hip", "mcep_mfma.hip", "lpc.hip", "fbank.hip", "fftcep.hip", "mgc.hip", "rows_gemm.hip", "thsolve_quad.hip", "poledf.hip", "plp.hip",
+           "pqmf.hip")
 HIPCC_FLAGS = (
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
     "-mcode-object-version=5", "-Wno-unused-value", "-ffp-contract=on",
@@ -35,6 +36,7 @@ SOURCE_FLAGS = {
     "thsolve_quad.hip": _NO_PK,
     "poledf.hip": _NO_PK,
     "plp.hip": _NO_PK,
+    "pqmf.hip": _NO_PK,
     "mcep_mfma.hip": _NO_PK,   # (its kernels carry DSA_PK_TARGET -- measured faster with the compiler's pairing -- except mgcep_step_h)
 }
 
@@ -188,6 +190,12 @@ SIGNATURES = {
     "dsa_poledf_bwd": (C.c_int, [_P, _P, _P, _P, _L, _L, _I, _I, _I, _I, _P, _P, _P, _P]),
     "dsa_plp_fwd": (C.c_int, [_P, _P, _L, _I, _I, _I, _D, _I, _P, _I, _P, _P, _P]),
     "dsa_plp_bwd": (C.c_int, [_P, _P, _P, _L, _I, _I, _I, _D, _I, _P, _I, _P, _P, _P]),
+    "dsa_pqmf_fwd": (C.c_int, [_P, _P, _L, _L, _I, _I, _I, _I, _I, _P, _P]),
+    "dsa_pqmf_bwd": (C.c_int, [_P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "dsa_ipqmf_fwd": (C.c_int, [_P, _P, _L, _L, _I, _I, _I, _I, _I, _P, _P]),
+    "dsa_ipqmf_bwd": (C.c_int, [_P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "dsa_interpolate_fwd": (C.c_int, [_P, _L, _L, _L, _I, _I, _I, _P, _P]),
+    "dsa_interpolate_bwd": (C.c_int, [_P, _L, _L, _L, _I, _I, _I, _P, _P]),
     "dsa_acorr_fwd": (C.c_int, [_P, _L, _I, _I, _I, _I, _P, _P]),
     "dsa_acorr_bwd": (C.c_int, [_P, _P, _L, _I, _I, _I, _I, _P, _P]),
     "dsa_levdur_fwd": (C.c_int, [_P, _L, _I, _D, _I, _P, _P]),

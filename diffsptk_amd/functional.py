@@ -200,6 +200,16 @@ def poledf(x: Tensor, a: Tensor, frame_period: int = 80, ignore_gain: bool = Fal
     return nn.AllPoleDigitalFilter._func(x, a, frame_period=frame_period, ignore_gain=ignore_gain)
 
 
+def decimate(x: Tensor, period: int = 1, start: int = 0, dim: int = -1) -> Tensor:
+    """Decimation (functional.py: decimate): the view x[..., start::period, ...] along dim."""
+    return nn.Decimation._func(x, period=period, start=start, dim=dim)
+
+
+def interpolate(x: Tensor, period: int = 1, start: int = 0, dim: int = -1) -> Tensor:
+    """Interpolation (functional.py: interpolate): zeros with x[n] at start + n period along dim."""
+    return nn.Interpolation._func(x, period=period, start=start, dim=dim)
+
+
 def linear_intpl(x: Tensor, upsampling_factor: int = 80) -> Tensor:
     """Linear interpolation of frame-wise parameters (functional.py: linear_intpl)."""
     return nn.LinearInterpolation._func(x, upsampling_factor=upsampling_factor)

@@ -2,6 +2,7 @@ from .acorr import Autocorrelation
 from .base import BaseFunctionalModule, Precomputed
 from .dct import DiscreteCosineTransform
 from .dct import DiscreteCosineTransform as DCT
+from .decimate import Decimation, Interpolation
 from .fbank import MelFilterBankAnalysis
 from .fbank import MelFilterBankAnalysis as FBANK
 from .fftcep import CepstralAnalysis
@@ -15,7 +16,7 @@ from .freqt import FrequencyTransform
 from .levdur import LevinsonDurbin
 from .lpc import LinearPredictiveCodingAnalysis
 from .lpc import LinearPredictiveCodingAnalysis as LPC
-from .fused import FusedFrameWindowLPC, FusedSTFTFilterBank, FusedSTFTMelCepstralAnalysis, fuse
+from .fused import FusedFrameWindowLPC, FusedInterpolationIPQMF, FusedPQMFDecimation, FusedSTFTFilterBank, FusedSTFTMelCepstralAnalysis, fuse
 from .gnorm import GeneralizedCepstrumGainNormalization, GeneralizedCepstrumInverseGainNormalization
 from .mc2b import MelCepstrumToMLSADigitalFilterCoefficients, MLSADigitalFilterCoefficientsToMelCepstrum
 from .mcep import MelCepstralAnalysis
@@ -27,6 +28,9 @@ from .mglsadf import PseudoMGLSADigitalFilter as MLSA
 from .plp import PerceptualLinearPredictiveCoefficientsAnalysis
 from .plp import PerceptualLinearPredictiveCoefficientsAnalysis as PLP
 from .poledf import AllPoleDigitalFilter
+from .pqmf import PseudoQuadratureMirrorFilterBankAnalysis, PseudoQuadratureMirrorFilterBankSynthesis
+from .pqmf import PseudoQuadratureMirrorFilterBankAnalysis as PQMF
+from .pqmf import PseudoQuadratureMirrorFilterBankSynthesis as IPQMF
 from .zerodf import AllZeroDigitalFilter, LinearInterpolation
 from .mfcc import MelFrequencyCepstralCoefficientsAnalysis
 from .mfcc import MelFrequencyCepstralCoefficientsAnalysis as MFCC
@@ -45,5 +49,7 @@ __all__ = [
     "MelGeneralizedCepstrumToMelGeneralizedCepstrum", "MelGeneralizedCepstrumToSpectrum", "MelGeneralizedCepstralAnalysis",
     "PseudoMGLSADigitalFilter", "MLSA", "PerceptualLinearPredictiveCoefficientsAnalysis", "PLP", "AllPoleDigitalFilter", "AllZeroDigitalFilter", "LinearInterpolation",
     "FusedFrameWindowLPC", "FusedSTFTFilterBank", "FusedSTFTMelCepstralAnalysis", "fuse",
+    "Decimation", "Interpolation", "PQMF", "IPQMF", "PseudoQuadratureMirrorFilterBankAnalysis",
+    "PseudoQuadratureMirrorFilterBankSynthesis", "FusedPQMFDecimation", "FusedInterpolationIPQMF",
     "RealValuedFastFourierTransform", "STFT", "ShortTimeFourierTransform", "Spectrum", "Window",
 ]

@@ -13,12 +13,14 @@ import torch
 from torch import nn
 
 from .. import ops
+from .decimate import Decimation, Interpolation
 from .fbank import MelFilterBankAnalysis
 from .frame import Frame
 from .lpc import LinearPredictiveCodingAnalysis
 from .mcep import MelCepstralAnalysis
 from .mfcc import MelFrequencyCepstralCoefficientsAnalysis
 from .plp import PerceptualLinearPredictiveCoefficientsAnalysis
+from .pqmf import PseudoQuadratureMirrorFilterBankAnalysis, PseudoQuadratureMirrorFilterBankSynthesis
 from .stft import ShortTimeFourierTransform
 from .window import Window
 
@@ -166,12 +168,70 @@ class FusedFrameWindowLPC(nn.Module):
         return lp(wn(f(x)))
 
 
+class FusedPQMFDecimation(nn.Module):
+    """``decimate(pqmf(x))`` -- the subband analysis of the reference's README (README.md:280-283) -- as ONE launch that computes
+    only the outputs the decimation keeps (dsa_pqmf_fwd with (period, start)): 1/P of the multiply-adds and of the bytes written,
+    forward and backward.  The values are the module chain's, bit for bit, in a new tensor where the chain returns a view.  A
+    decimation along another axis than time runs the two modules.  ``last_path``: "fused" / "two-stage"."""
+
+    def __init__(self, pqmf: PseudoQuadratureMirrorFilterBankAnalysis, decimate: Decimation) -> None:
+        super().__init__()
+        if not isinstance(pqmf, PseudoQuadratureMirrorFilterBankAnalysis):
+            raise ValueError("pqmf must be a PseudoQuadratureMirrorFilterBankAnalysis.")
+        if not isinstance(decimate, Decimation):
+            raise ValueError("decimate must be a Decimation.")
+        self.pqmf, self.decimate = pqmf, decimate
+        self.last_path = None
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        p, d = self.pqmf, self.decimate
+        if 1 <= x.dim() <= 3 and d.dim in (-1, 2):   # the time axis of the (B, K, T) analysis
+            self.last_path = "fused"
+            return p._analyze(x, d.period, d.start)
+        self.last_path = "two-stage"
+        return d(p(x))
+
+
+class FusedInterpolationIPQMF(nn.Module):
+    """``ipqmf(interpolate(y))`` -- the subband synthesis of the reference's README (README.md:286-288) -- as ONE launch that
+    evaluates only the taps landing on interpolated samples, about (M+1)/P per band, and never writes the zero-stuffed signal
+    (dsa_ipqmf_fwd with (period, start)).  The values are the module chain's, bit for bit.  An interpolation along another axis
+    than time runs the two modules.  ``last_path``: "fused" / "two-stage"."""
+
+    def __init__(self, interpolate: Interpolation, ipqmf: PseudoQuadratureMirrorFilterBankSynthesis) -> None:
+        super().__init__()
+        if not isinstance(interpolate, Interpolation):
+            raise ValueError("interpolate must be an Interpolation.")
+        if not isinstance(ipqmf, PseudoQuadratureMirrorFilterBankSynthesis):
+            raise ValueError("ipqmf must be a PseudoQuadratureMirrorFilterBankSynthesis.")
+        self.interpolate, self.ipqmf = interpolate, ipqmf
+        self.last_path = None
+
+    def forward(self, y: torch.Tensor, keepdim: bool = True) -> torch.Tensor:
+        i, q = self.interpolate, self.ipqmf
+        if y.dim() in (2, 3) and i.dim in (-1, y.dim() - 1):
+            self.last_path = "fused"
+            return q._synthesize(y, i.period, i.start, keepdim)
+        self.last_path = "two-stage"
+        return q(i(y), keepdim=keepdim)
+
+
 def fuse(first: nn.Module, *rest: nn.Module, **options) -> nn.Module:
     """One launch where a fused kernel applies, the modules themselves elsewhere:
 
     * ``fuse(stft, analysis)(x) == analysis(stft(x))`` for ``analysis`` a MelCepstralAnalysis (the hot path), a
       MelFilterBankAnalysis, a MelFrequencyCepstralCoefficientsAnalysis or a PerceptualLinearPredictiveCoefficientsAnalysis;
-    * ``fuse(frame, window, lpc)(x) == lpc(window(frame(x)))`` -- the LPC branch, forward and backward."""
+    * ``fuse(frame, window, lpc)(x) == lpc(window(frame(x)))`` -- the LPC branch, forward and backward;
+    * ``fuse(pqmf, decimate)(x) == decimate(pqmf(x))`` and ``fuse(interpolate, ipqmf)(y) == ipqmf(interpolate(y))`` -- the
+      subband analysis and synthesis, forward and backward."""
+    if isinstance(first, PseudoQuadratureMirrorFilterBankAnalysis):
+        if len(rest) != 1 or options:
+            raise ValueError("fuse(pqmf, decimate) takes a PseudoQuadratureMirrorFilterBankAnalysis and a Decimation.")
+        return FusedPQMFDecimation(first, rest[0])
+    if isinstance(first, Interpolation):
+        if len(rest) != 1 or options:
+            raise ValueError("fuse(interpolate, ipqmf) takes an Interpolation and a PseudoQuadratureMirrorFilterBankSynthesis.")
+        return FusedInterpolationIPQMF(first, rest[0])
     if isinstance(first, Frame):
         if len(rest) != 2:
             raise ValueError("fuse(frame, window, lpc) takes a Frame, a Window and a LinearPredictiveCodingAnalysis.")

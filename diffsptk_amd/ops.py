@@ -7,6 +7,7 @@ hand-written backward kernels).
 """
 from __future__ import annotations
 
+import math
 import os
 import weakref
 
@@ -1796,6 +1797,116 @@ def poledf(x, a, P, ignore_gain):
     if tuple(a.shape[:-2]) != tuple(batch):
         a = a.expand(*batch, *a.shape[-2:])
     return PoledfFn.apply(x, a, P, ignore_gain)
+
+
+def pqmf_out_length(T: int, period: int, start: int) -> int:
+    """len(range(start, T, period)): the samples Decimation(period, start) keeps (decimate.py:92)."""
+    return (T - start + period - 1) // period if T > start else 0
+
+
+class PqmfFn(torch.autograd.Function):
+    """Pseudo-QMF analysis (pqmf.py:250-258: conv1d over the zero / replicate padded signal) with the Decimation(period, start)
+    that may follow it folded in: x:(B, T), f:(K, M+1) the stored (time-flipped) filters -> y:(B, K, len(range(start, T, period))).
+    (1, 0) is the plain analysis.  Backward (dsa_pqmf_bwd): gx, the replicate pad's copies summed into x[T-1], and for learnable
+    filters gf from per-utterance partials in a workspace, summed in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, x, f, period, start):
+        _require_device(x, f)
+        _same_dtype(x, f)
+        xc, fc = x.contiguous(), f.contiguous()
+        B, T = xc.shape
+        K, M1 = fc.shape
+        y = torch.empty(B, K, pqmf_out_length(T, period, start), device=x.device, dtype=x.dtype)
+        with torch.cuda.device(x.device):
+            _call("dsa_pqmf_fwd", _p(xc), _p(fc), B, T, K, M1 - 1, period, start, _dtype_code(xc), _p(y), _stream())
+        ctx.save_for_backward(xc if ctx.needs_input_grad[1] else None, fc)
+        ctx.cfg = (B, T, period, start)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        xc, fc = ctx.saved_tensors
+        B, T, period, start = ctx.cfg
+        K, M1 = fc.shape
+        gx = torch.empty(B, T, device=fc.device, dtype=fc.dtype) if ctx.needs_input_grad[0] else None
+        gf = torch.zeros_like(fc) if ctx.needs_input_grad[1] else None   # (an empty batch leaves it zero)
+        if gx is None and gf is None:
+            return None, None, None, None
+        work = torch.empty(B * K * M1, device=fc.device, dtype=fc.dtype) if gf is not None else None
+        gyc = gy.contiguous()
+        with torch.cuda.device(fc.device):
+            _call("dsa_pqmf_bwd", _p(gyc), _p(xc), _p(fc), B, T, K, M1 - 1, period, start, _dtype_code(fc), _p(gx), _p(gf), _p(work),
+                  _stream())
+        return gx, gf, None, None
+
+
+class IpqmfFn(torch.autograd.Function):
+    """Pseudo-QMF synthesis (ipqmf.py:132-141) with the Interpolation(up, start) that may precede it folded in: y:(B, K, T),
+    f:(K, M+1) the stored (time-flipped) filters -> x:(B, T up + start).  (1, 0) is the plain synthesis; otherwise only the taps on
+    the interpolated samples are evaluated and the zero-stuffed signal is never written.  Backward (dsa_ipqmf_bwd): gy at the kept
+    positions, and gf for learnable filters."""
+
+    @staticmethod
+    def forward(ctx, y, f, up, start):
+        _require_device(y, f)
+        _same_dtype(y, f)
+        yc, fc = y.contiguous(), f.contiguous()
+        B, K, T = yc.shape
+        x = torch.empty(B, T * up + start, device=y.device, dtype=y.dtype)
+        with torch.cuda.device(y.device):
+            _call("dsa_ipqmf_fwd", _p(yc), _p(fc), B, T, K, fc.size(1) - 1, up, start, _dtype_code(yc), _p(x), _stream())
+        ctx.save_for_backward(yc if ctx.needs_input_grad[1] else None, fc)
+        ctx.cfg = (B, T, up, start)
+        return x
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gx):
+        yc, fc = ctx.saved_tensors
+        B, T, up, start = ctx.cfg
+        K, M1 = fc.shape
+        gy = torch.empty(B, K, T, device=fc.device, dtype=fc.dtype) if ctx.needs_input_grad[0] else None
+        gf = torch.zeros_like(fc) if ctx.needs_input_grad[1] else None
+        if gy is None and gf is None:
+            return None, None, None, None
+        work = torch.empty(B * K * M1, device=fc.device, dtype=fc.dtype) if gf is not None else None
+        gxc = gx.contiguous()
+        with torch.cuda.device(fc.device):
+            _call("dsa_ipqmf_bwd", _p(gxc), _p(yc), _p(fc), B, T, K, M1 - 1, up, start, _dtype_code(fc), _p(gy), _p(gf), _p(work),
+                  _stream())
+        return gy, gf, None, None
+
+
+class InterpolateFn(torch.autograd.Function):
+    """Interpolation._forward (interpolate.py:85-96): zeros with x[..., n, ...] at start + n period along dim, one launch that
+    writes every output element (dsa_interpolate_fwd); backward the strided gather (dsa_interpolate_bwd)."""
+
+    @staticmethod
+    def forward(ctx, x, period, start, dim):
+        _require_device(x)
+        d = dim % x.dim()
+        xc = x.contiguous()
+        shape = tuple(xc.shape)
+        outer, T, inner = math.prod(shape[:d]), shape[d], math.prod(shape[d + 1:])
+        out_shape = list(shape)
+        out_shape[d] = T * period + start
+        y = torch.empty(out_shape, device=x.device, dtype=x.dtype)
+        with torch.cuda.device(x.device):
+            _call("dsa_interpolate_fwd", _p(xc), outer, T, inner, period, start, _dtype_code(xc), _p(y), _stream())
+        ctx.cfg = (shape, outer, T, inner, period, start)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        shape, outer, T, inner, period, start = ctx.cfg
+        gyc = gy.contiguous()
+        gx = torch.empty(shape, device=gy.device, dtype=gy.dtype)
+        with torch.cuda.device(gy.device):
+            _call("dsa_interpolate_bwd", _p(gyc), outer, T, inner, period, start, _dtype_code(gyc), _p(gx), _stream())
+        return gx, None, None, None
 
 
 def zerodf_taylor_shapes_ok(x, b, P) -> bool:

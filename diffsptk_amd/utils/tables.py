@@ -771,3 +771,71 @@ def plp_table(n_channel: int, plp_order: int, n_fft: int, sample_rate: int, f_mi
     return np.concatenate([plp_equal_loudness(n_channel, sample_rate, f_min, f_max, scale),
                            plp_hfft_matrix(n_channel, plp_order).reshape(-1), cs.reshape(-1), sn.reshape(-1), w,
                            plp_lifter(plp_order, lifter)])
+
+
+def _kaiser_beta(attenuation_db: float) -> float:
+    """Kaiser's empirical window parameter for a stopband attenuation in dB."""
+    if attenuation_db > 50:
+        return 0.1102 * (attenuation_db - 8.7)
+    if attenuation_db > 21:
+        d = attenuation_db - 21
+        return 0.5842 * np.power(d, 0.4) + 0.07886 * d
+    return 0.0
+
+
+def pqmf_filters(n_band: int, filter_order: int, mode: str = "analysis", alpha: float = 100, n_iter: int = 100,
+                 step_size: float = 1e-2, decay: float = 0.5, eps: float = 1e-6) -> tuple[np.ndarray, bool]:
+    """The cosine-modulated pseudo-QMF bank (pqmf.py: make_filter_banks), float64 (K, M+1), and whether the prototype search
+    converged.  The prototype is a Kaiser-windowed ideal low-pass of cutoff w; w is searched (Cruz-Roldan et al. 2002) until
+    the squared magnitude at pi / 2K -- read from an FFT of the next power of two of M+1 points -- is 1/2 within eps: each step
+    moves w against the sign of the error, and a step that does not improve the best error is first shrunk by `decay`.  Band k
+    is 2 p(n) cos((2k+1) pi / 2K (n - M/2) +- (-1)^k pi/4), + for analysis and - for synthesis (Nguyen 1994)."""
+    K, M = n_band, filter_order
+    if K <= 0:
+        raise ValueError("n_band must be positive.")
+    if M <= 1:
+        raise ValueError("filter_order must be greater than or equal to 2.")
+    if n_iter <= 0:
+        raise ValueError("n_iter must be positive.")
+    if alpha <= 0:
+        raise ValueError("alpha must be positive.")
+    if step_size <= 0:
+        raise ValueError("step_size must be positive.")
+    if decay <= 0:
+        raise ValueError("decay must be positive.")
+    if eps < 0:
+        raise ValueError("eps must be non-negative.")
+    n = np.arange(M + 1) - 0.5 * M           # time from the centre of the filter
+    win = np.kaiser(M + 1, _kaiser_beta(alpha))
+    nfft = 1 << M.bit_length()               # the next power of two >= M + 1
+    probe = nfft // (4 * K)                  # the bin of pi / 2K
+    centre = M // 2 if M % 2 == 0 else None
+
+    def prototype(w):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            p = np.sin(w * n) / (np.pi * n)
+        if centre is not None:
+            p[centre] = w / np.pi
+        return p * win
+
+    w, step, best = np.pi / (2 * K), step_size, np.inf
+    converged = False
+    for _ in range(n_iter):
+        p = prototype(w)
+        err = np.square(np.abs(np.fft.rfft(p, n=nfft)[probe])) - 0.5
+        if np.abs(err) < eps:
+            converged = True
+            break
+        if np.abs(err) < best:
+            best = np.abs(err)
+        else:
+            step *= decay
+        w -= np.sign(err) * step
+    if mode == "analysis":
+        phase = np.pi / 4
+    elif mode == "synthesis":
+        phase = -np.pi / 4
+    else:
+        raise ValueError("analysis or synthesis is expected.")
+    rows = [2 * p * np.cos(((2 * k + 1) * np.pi / (2 * K)) * n + (-1) ** k * phase) for k in range(K)]
+    return np.asarray(rows), converged

@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define DSA_VERSION 131 /* 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
+#define DSA_VERSION 132 /* 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
 
 typedef enum {
     DSA_OK = 0,
@@ -517,6 +517,45 @@ int dsa_plp_fwd(const void* y, const void* E, int64_t F, int32_t C, int32_t M, i
                 int32_t out_format, const void* table, int32_t dtype, void* out, void* save, void* stream);
 int dsa_plp_bwd(const void* gout, const void* y, const void* save, int64_t F, int32_t C, int32_t M, int32_t N,
                 double compression_factor, int32_t out_format, const void* table, int32_t dtype, void* gy, void* gE, void* stream);
+
+/* ------------------------------------------------------------------ f7  pseudo-QMF subband analysis and synthesis (0.2.6)
+ * PseudoQuadratureMirrorFilterBankAnalysis.forward, pqmf.py:250-258 (ConstantPad1d, ReplicationPad1d and conv1d with K output
+ * channels), with the Decimation that may follow it (decimate.py:88-93, x[..., start::period]) folded in; and
+ * PseudoQuadratureMirrorFilterBankSynthesis.forward, ipqmf.py:132-141, with the Interpolation that may precede it
+ * (interpolate.py:85-96, zeros + index_copy_) folded in.  f:(K, M+1) are the filters in the reference's stored, time-flipped layout
+ * (its conv1d weights, (K,1,M+1) / (1,K,M+1), without the unit axis):
+ *   dsa_pqmf_fwd   x:(B,T) -> y:(B,K,Tout), Tout = len(range(start, T, period)):
+ *                  y[b,k,m] = sum_i f[k,i] xp[b, start + m period + i],  xp = dl zeros | x | dr copies of x[T-1]
+ *                  (dl, dr) = (M/2, M/2) for even M, ((M+1)/2, (M-1)/2) for odd M;  only the kept outputs are computed.
+ *   dsa_ipqmf_fwd  y:(B,K,T) -> x:(B,Tu), Tu = T up + start:  x[b,t] = sum_k sum_i f[k,i] yp[b,k,t + i],  yp = dl zeros | yu |
+ *                  dr copies of yu[Tu-1], yu = y zero-stuffed (y[b,k,m] at start + m up), (dl, dr) = ((M-1)/2, (M+1)/2) for odd M;
+ *                  only the taps on non-zero samples are evaluated and yu is never written.
+ *   (period, start) = (1, 0) and (up, start) = (1, 0) are the plain modules.
+ * Backward: dsa_pqmf_bwd gy:(B,K,Tout) -> gx:(B,T) (the replicate pad's gradients summed into x[T-1]) and / or gf:(K,M+1);
+ * dsa_ipqmf_bwd gx:(B,Tu) -> gy:(B,K,T) (at the kept positions only) and / or gf.  Either output may be NULL.  gf needs the forward's
+ * input (x / y) and `work`, a caller-owned workspace of B K (M+1) elements of the dtype: per-utterance partials, each a sum over
+ * time in ascending order, then summed in a fixed order -- no atomics, the same bits run to run.
+ * Each output element is one fma chain in a fixed tap order whatever the tiling: a row's bits do not depend on B, and the folded
+ * routes give the bits of the module chain for finite data (a skipped tap is an exact zero product).  Tuned kernels for K <= 8,
+ * M <= 127, period / up <= 16, generic ones otherwise; float32 and float64; no allocation, no host synchronisation.
+ * 1 <= K <= DSA_PQMF_MAX_BANDS, 2 <= M <= DSA_PQMF_MAX_ORDER. */
+#define DSA_PQMF_MAX_BANDS 1024
+#define DSA_PQMF_MAX_ORDER 2047
+int dsa_pqmf_fwd(const void* x, const void* f, int64_t B, int64_t T, int32_t K, int32_t M, int32_t period, int32_t start, int32_t dtype,
+                 void* y, void* stream);
+int dsa_pqmf_bwd(const void* gy, const void* x, const void* f, int64_t B, int64_t T, int32_t K, int32_t M, int32_t period, int32_t start,
+                 int32_t dtype, void* gx, void* gf, void* work, void* stream);
+int dsa_ipqmf_fwd(const void* y, const void* f, int64_t B, int64_t T, int32_t K, int32_t M, int32_t up, int32_t start, int32_t dtype,
+                  void* x, void* stream);
+int dsa_ipqmf_bwd(const void* gx, const void* y, const void* f, int64_t B, int64_t T, int32_t K, int32_t M, int32_t up, int32_t start,
+                  int32_t dtype, void* gy, void* gf, void* work, void* stream);
+/* Interpolation._forward, interpolate.py:85-96, over the (outer, T, inner) view of a contiguous tensor (any `dim`): y:(outer, T period
+ * + start, inner) is zero except y[o, start + n period, i] = x[o, n, i] (every element written: no separate zero fill).  Backward:
+ * the strided gather gx[o, n, i] = gy[o, start + n period, i]. */
+int dsa_interpolate_fwd(const void* x, int64_t outer, int64_t T, int64_t inner, int32_t period, int32_t start, int32_t dtype, void* y,
+                        void* stream);
+int dsa_interpolate_bwd(const void* gy, int64_t outer, int64_t T, int64_t inner, int32_t period, int32_t start, int32_t dtype, void* gx,
+                        void* stream);
 
 /* ------------------------------------------------------------------ a11  autocorrelation
  * Autocorrelation._forward, acorr.py:110-120.  x:(F,L) -> r:(F,M+1).  Computed as direct lag
