@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import shutil
 import subprocess
 
@@ -40,30 +41,58 @@ SOURCE_FLAGS = {
     "mcep_mfma.hip": _NO_PK,   # (its kernels carry DSA_PK_TARGET -- measured faster with the compiler's pairing -- except mgcep_step_h)
 }
 
-F32, F64 = 0, 1
-SCRATCH_BYTES = 64   # DSA_SCRATCH_BYTES
-FBANK_PLAN_FLOATS = 2048   # DSA_FBANK_PLAN_FLOATS
-PLP_MAX_ORDER = 62         # DSA_PLP_MAX_ORDER
-ERR_UNSUPPORTED = -2       # DSA_ERR_UNSUPPORTED
-LPC_SCRATCH_IS_CLEAN = 0x100  # DSA_LPC_SCRATCH_IS_CLEAN
-LPC_EXACT_LAGSUMS = 0x200  # DSA_LPC_EXACT_LAGSUMS
-ALGO_AUTO, ALGO_GENERIC, ALGO_TUNED = 0, 1, 2
-ALGO_SCRATCH_IS_CLEAN = 0x100   # DSA_ALGO_SCRATCH_IS_CLEAN
-ALGO_SCRATCH_HAS_WORKSPACE = 0x200   # DSA_ALGO_SCRATCH_HAS_WORKSPACE
-ALGO_HIST_HAS_RT = 0x400             # DSA_ALGO_HIST_HAS_RT
-ALGO_OVERLAPPED_LAUNCHES = 0x800     # DSA_ALGO_OVERLAPPED_LAUNCHES
-
-
-def algo_reserve_cus(n: int) -> int:
-    """DSA_ALGO_RESERVE_CUS(n)"""
-    return (int(n) & 63) << 16
-MCEP_BWD_WORKSPACE_BYTES = SCRATCH_BYTES + 512 * 16 * 32 * 4   # DSA_MCEP_BWD_WORKSPACE_BYTES
-
 _lib = None
 
 
 class BackendError(RuntimeError):
     """The HIP library is missing, failed to load, or a call returned an error status."""
+
+
+# bindings and constants: read at import from the C header, which the compiler checks against the definitions in every .hip file
+HEADER = os.path.join(_ROOT, "include", "diffsptk_amd.h")
+_RETURNS = {"int": C.c_int, "int64_t": C.c_int64, "const char*": C.c_char_p}
+_VALUES = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double}
+_PROTOTYPE = re.compile(r"\s*([\w\s*]+?)\s*\b(dsa_[a-z0-9_]+)\s*\(([^()]*)\)\s*")
+
+
+def parse_header(text: str):
+    """(signatures, constants) of the header's text: name -> (restype, [argtypes]) of every `dsa_*` prototype, and name -> int of
+    every enumerator and object-like `#define DSA_*` (function-like macros are not evaluated).  Raises BackendError on whatever
+    looks like a prototype and is not fully understood; a constant that is no integer expression raises from eval() / int()."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    signatures, constants = {}, {}
+    for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(DSA_\w+)[ \t]+(.+)$|\benum\s*\{([^}]*)\}", text, flags=re.M):
+        last = -1   # an enumerator without a value is one more than the one before it
+        for item in [f"{m.group(1)} = {m.group(2)}"] if m.group(1) else filter(str.strip, m.group(3).split(",")):
+            name, _, expr = map(str.strip, item.partition("="))
+            constants[name] = last = int(eval(expr or str(last + 1), {"__builtins__": {}}, constants))   # may name earlier ones
+    looks_like_a_prototype = re.compile(r"\bdsa_[a-z0-9_]+\s*\(").search
+    for stmt in filter(looks_like_a_prototype, re.sub(r"^[ \t]*#.*$", "", text, flags=re.M).split(";")):
+        m = _PROTOTYPE.fullmatch(stmt)
+        restype = m and _RETURNS.get(re.sub(r"\s*\*", "*", " ".join(m.group(1).split())))
+        if not restype:
+            raise BackendError(f"{HEADER}: cannot parse the prototype `{' '.join(stmt.split())[:200]}`")
+        argtypes = []
+        for param in [] if m.group(3).strip() in ("", "void") else m.group(3).split(","):
+            p = re.fullmatch(r"\s*(.+?)\s*\b\w+\s*", param)   # `<type> <parameter name>`
+            ctype = p and (C.c_void_p if p.group(1).endswith("*") else _VALUES.get(p.group(1)))   # any pointer: an address
+            if not ctype:
+                raise BackendError(f"{HEADER}: {m.group(2)}: parameter `{param.strip()}` has no ctypes mapping")
+            argtypes.append(ctype)
+        signatures[m.group(2)] = (restype, argtypes)
+    return signatures, constants
+
+
+if not os.path.isfile(HEADER):
+    raise BackendError(f"the C header {HEADER} is missing: the ctypes bindings are read from it")
+SIGNATURES, CONSTANTS = parse_header(open(HEADER).read())   # name -> (restype, [argtypes]); "DSA_..." -> int
+# every constant under its header name without the prefix: F32, SCRATCH_BYTES, ERR_UNSUPPORTED, ALGO_TUNED, ROWS_TRANS, PAD_REFLECT, ...
+globals().update({name[len("DSA_"):]: value for name, value in CONSTANTS.items()})
+
+
+def algo_reserve_cus(n: int) -> int:
+    """DSA_ALGO_RESERVE_CUS(n)"""
+    return (int(n) & 63) << 16
 
 
 def _sources():
@@ -115,96 +144,6 @@ def build(force: bool = False, verbose: bool = False) -> str:
     global _lib
     _lib = None
     return LIB_PATH
-
-
-# name -> (restype, argtypes); mirrors include/diffsptk_amd.h
-_P, _I, _L, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_double
-SIGNATURES = {
-    "dsa_version": (C.c_int, []),
-    "dsa_last_error": (C.c_char_p, []),
-    "dsa_device_count": (C.c_int, []),
-    "dsa_last_kernel": (C.c_char_p, []),
-    "dsa_num_frames": (C.c_int64, [_L, _I]),
-    "dsa_frame_fwd": (C.c_int, [_P, _L, _L, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "dsa_frame_bwd": (C.c_int, [_P, _L, _L, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "dsa_window_fwd": (C.c_int, [_P, _L, _I, _P, _I, _I, _P, _P]),
-    "dsa_window_bwd": (C.c_int, [_P, _P, _L, _I, _P, _I, _I, _P, _P, _P]),
-    "dsa_fftr_fwd": (C.c_int, [_P, _L, _I, _I, _I, _P, _I, _P, _P]),
-    "dsa_fftr_bwd": (C.c_int, [_P, _P, _L, _I, _I, _I, _P, _I, _P, _P]),
-    "dsa_spec_fwd": (C.c_int, [_P, _I, _P, _I, _L, _I, _D, _I, _D, _I, _P, _I, _P, _P]),
-    "dsa_spec_bwd": (C.c_int, [_P, _P, _I, _P, _I, _L, _I, _D, _I, _D, _I, _P, _I, _P, _P, _P]),
-    "dsa_stft_fwd": (C.c_int, [_P, _L, _L, _I, _I, _I, _P, _P, _I, _I, _I, _D, _I, _D, _I, _I, _I, _P, _P]),
-    "dsa_stft_bwd": (C.c_int, [_P, _P, _L, _L, _I, _I, _I, _P, _P, _I, _I, _I, _D, _I, _D, _I, _I, _I, _P, _P, _P]),
-    "dsa_freqt_fwd": (C.c_int, [_P, _L, _I, _P, _I, _I, _P, _P]),
-    "dsa_freqt_bwd": (C.c_int, [_P, _L, _I, _P, _I, _I, _P, _P]),
-    "dsa_rows_gemm": (C.c_int, [_P, _L, _I, _P, _I, _I, _I, _P, _I, _I, _P, _I, _P]),
-    "dsa_mcep_newton_update": (C.c_int, [_P, _L, _I, _P, _I, _P, _P, _P]),
-    "dsa_gnorm_fwd": (C.c_int, [_P, _L, _I, _D, _I, _I, _P, _P]),
-    "dsa_mgcep_gain": (C.c_int, [_P, _P, _P, _L, _I, _D, _I, _P, _P]),
-    "dsa_mcep_newton_update_bwd": (C.c_int, [_P, _P, _P, _L, _I, _I, _P, _P, _P]),
-    "dsa_mcep_newton_resid": (C.c_int, [_P, _L, _I, _P, _I, _P, _I, _P, _I, _I, _P, _P]),
-    "dsa_mcep_resid_images_bytes": (C.c_int64, [_I, _I]),
-    "dsa_mcep_resid_prepare": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _P, _P]),
-    "dsa_mcep_newton_resid_h": (C.c_int, [_P, _L, _I, _P, _I, _P, _I, _P, _P]),
-    "dsa_mcep_resid_bwd_images_bytes": (C.c_int64, [_I, _I]),
-    "dsa_mcep_resid_bwd_prepare": (C.c_int, [_P, _I, _P, _I, _I, _I, _I, _P, _P]),
-    "dsa_mcep_newton_resid_h_bwd": (C.c_int, [_P, _L, _I, _P, _I, _P, _P, _I, _P, _P, _P]),
-    "dsa_mcep_newton_glogx_h": (C.c_int, [_P, _L, _I, _P, _I, _P, _I, _P, _I, _P, _P]),
-    "dsa_mcep_newton_steps": (C.c_int, [_P, _L, _I, _P, _I, _P, _P, _I, _I, _P, _P]),
-    "dsa_rows_ew": (C.c_int, [_I, _I, _P, _P, _P, _L, _I, _P, _P, _P]),
-    "dsa_irfft_scale": (C.c_int, [_P, _L, _I, _I, _P, _P]),
-    "dsa_div_rows": (C.c_int, [_P, _L, _L, _P, _D, _I, _P, _P]),
-    "dsa_istft_fwd": (C.c_int, [_P, _L, _L, _I, _I, _I, _P, _P, _I, _P, _D, _I, _I, _P, _P]),
-    "dsa_fbank_dct_fwd": (C.c_int, [_P, _L, _I, _P, _I, _P, _I, _D, _D, _I, _I, _P, _P, _P]),
-    "dsa_fftcep_fwd": (C.c_int, [_P, _L, _I, _I, _P, _D, _I, _I, _P, _P, _P]),
-    "dsa_fftcep_bwd": (C.c_int, [_P, _P, _L, _I, _I, _P, _D, _I, _P, _I, _P, _P]),
-    "dsa_griffin_update": (C.c_int, [_P, _L, _L, _L, _I, _P, _P, _P, _P, _I, _D, _D, _D, _D, _I, _P, _P]),
-    "dsa_fbank_fwd": (C.c_int, [_P, _L, _I, _P, _I, _D, _D, _I, _I, _P, _P, _P]),
-    "dsa_fbank_scan_plan": (C.c_int, [_P, _I, _I, _P]),
-    "dsa_mgcep_spectra": (C.c_int, [_P, _P, _L, _I, _I, _P, _P, _D, _I, _P, _P]),
-    "dsa_stft_fbank_fwd": (C.c_int, [_P, _L, _L, _I, _I, _I, _P, _P, _I, _D, _P, _I, _D, _D, _I, _I, _P, _P]),
-    "dsa_fbank_bins_plan": (C.c_int, [_P, _I, _I, _P]),
-    "dsa_fbank_bins_bwd": (C.c_int, [_P, _P, _L, _I, _I, _P, _D, _D, _I, _P, _P]),
-    "dsa_fbank_bwd": (C.c_int, [_P, _P, _P, _L, _I, _P, _I, _D, _D, _I, _I, _P, _P]),
-    "dsa_mcep_images_bytes": (C.c_int64, [_I, _I, _I]),
-    "dsa_mcep_prepare": (C.c_int, [_P, _P, _P, _I, _I, _I, _P, _P]),
-    "dsa_mcep_fwd": (C.c_int, [_P, _L, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
-    "dsa_stft_mcep_fwd": (C.c_int, [_P, _L, _L, _I, _I, _I, _P, _P, _I, _D, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
-    "dsa_stft_mcep_opts_fwd": (C.c_int, [_P, _L, _L, _I, _I, _I, _P, _P, _I, _I, _I, _D, _I, _D, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P,
-                                         _P, _P]),
-    "dsa_mcep_bwd": (C.c_int, [_P, _P, _P, _L, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
-    "dsa_thsolve_fwd": (C.c_int, [_P, _P, _P, _L, _I, _I, _P, _P]),
-    "dsa_mgcep_step": (C.c_int, [_P, _P, _L, _I, _I, _D, _P, _I, _P, _P, _P, _P]),
-    "dsa_mgcep_step_solve": (C.c_int, [_P, _P, _L, _I, _I, _D, _P, _I, _P, _P, _P, _P, _I, _P, _P]),
-    "dsa_mgcep_step_bwd_h": (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _I, _D, _P, _I, _P, _P, _P, _P]),
-    "dsa_mgcep_step_bwd": (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _I, _D, _P, _I, _P, _P, _P, _P]),
-    "dsa_gc2gc_fwd": (C.c_int, [_P, _L, _I, _I, _D, _D, _I, _P, _I, _I, _P, _P]),
-    "dsa_gc2gc_bwd": (C.c_int, [_P, _P, _L, _I, _I, _D, _D, _I, _P, _I, _P, _P]),
-    "dsa_thsolve_bwd": (C.c_int, [_P, _P, _P, _P, _L, _I, _I, _P, _P, _P, _P]),
-    "dsa_thsolve_update_fwd": (C.c_int, [_P, _P, _P, _L, _L, _L, _I, _I, _P, _P, _P]),
-    "dsa_zerodf_fwd": (C.c_int, [_P, _P, _L, _L, _I, _I, _I, _I, _I, _P, _P]),
-    "dsa_zerodf_bwd": (C.c_int, [_P, _P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _P, _P, _P]),
-    "dsa_zerodf_taylor_fwd": (C.c_int, [_P, _P, _L, _L, _I, _I, _I, C.c_double, _P, _I, _P, _P, _P]),
-    "dsa_zerodf_taylor_bwd": (C.c_int, [_P, _P, _P, _L, _L, _I, _I, _I, C.c_double, _P, _I, _P, _P, _P]),
-    "dsa_poledf_fwd": (C.c_int, [_P, _P, _L, _L, _I, _I, _I, _I, _P, _P]),
-    "dsa_poledf_bwd": (C.c_int, [_P, _P, _P, _P, _L, _L, _I, _I, _I, _I, _P, _P, _P, _P]),
-    "dsa_plp_fwd": (C.c_int, [_P, _P, _L, _I, _I, _I, _D, _I, _P, _I, _P, _P, _P]),
-    "dsa_plp_bwd": (C.c_int, [_P, _P, _P, _L, _I, _I, _I, _D, _I, _P, _I, _P, _P, _P]),
-    "dsa_pqmf_fwd": (C.c_int, [_P, _P, _L, _L, _I, _I, _I, _I, _I, _P, _P]),
-    "dsa_pqmf_bwd": (C.c_int, [_P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
-    "dsa_ipqmf_fwd": (C.c_int, [_P, _P, _L, _L, _I, _I, _I, _I, _I, _P, _P]),
-    "dsa_ipqmf_bwd": (C.c_int, [_P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
-    "dsa_interpolate_fwd": (C.c_int, [_P, _L, _L, _L, _I, _I, _I, _P, _P]),
-    "dsa_interpolate_bwd": (C.c_int, [_P, _L, _L, _L, _I, _I, _I, _P, _P]),
-    "dsa_acorr_fwd": (C.c_int, [_P, _L, _I, _I, _I, _I, _P, _P]),
-    "dsa_acorr_bwd": (C.c_int, [_P, _P, _L, _I, _I, _I, _I, _P, _P]),
-    "dsa_levdur_fwd": (C.c_int, [_P, _L, _I, _D, _I, _P, _P]),
-    "dsa_levdur_bwd": (C.c_int, [_P, _P, _P, _L, _I, _D, _I, _P, _P]),
-    "dsa_lpc_fwd": (C.c_int, [_P, _L, _I, _I, _D, _I, _P, _P, _P]),
-    "dsa_lpc_bwd": (C.c_int, [_P, _P, _P, _L, _I, _I, _D, _I, _P, _P]),
-    "dsa_frame_window_lpc_fwd": (C.c_int, [_P, _L, _L, _I, _I, _P, _I, _I, _I, _D, _I, _P, _P, _P]),
-    "dsa_frame_window_lpc_bwd": (C.c_int, [_P, _P, _L, _L, _I, _I, _P, _I, _I, _I, _D, _I, _P, _P]),
-}
 
 
 def load():

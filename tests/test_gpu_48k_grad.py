@@ -163,9 +163,9 @@ def test_48khz_glogx_in_one_pass_equals_the_in_place_accumulation_bit_for_bit(nf
     # a non-finite frame stays in its own row
     # by default the pass takes over from ops.MCEP_GLOGX_MIN_FRAMES frames on -- the same bits either side of the threshold
     monkeypatch.delenv("DSA_MCEP_GLOGX_PASS")
-    monkeypatch.setattr(ops, "MCEP_GLOGX_MIN_FRAMES", 300)
+    monkeypatch.setattr(ops.mcep, "MCEP_GLOGX_MIN_FRAMES", 300)
     assert torch.equal(_grads(m, X, w)[1], g1)
-    monkeypatch.setattr(ops, "MCEP_GLOGX_MIN_FRAMES", 400)
+    monkeypatch.setattr(ops.mcep, "MCEP_GLOGX_MIN_FRAMES", 400)
     assert torch.equal(_grads(m, X, w)[1], g1)
     Xb = X.clone()
     Xb[5, 3] = float("nan")

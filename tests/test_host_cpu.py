@@ -30,10 +30,99 @@ def test_library_exports_every_header_symbol():
     lib = ctypes.CDLL(_lib.LIB_PATH)
     missing = [n for n in sorted(declared) if not hasattr(lib, n)]
     assert not missing, f"declared in the header but not exported: {missing}"
-    assert declared == set(_lib.SIGNATURES), "ctypes signature table out of sync with the header"
+    assert declared == set(_lib.SIGNATURES), "the header parser of _lib missed or invented a prototype"
+    exported = {n for n in _dynamic_symbols(_lib.LIB_PATH) if n.startswith("dsa_")}
+    assert exported == declared, f"exported without a prototype in the header (no binding): {sorted(exported - declared)}"
     assert _lib.load().dsa_version() == int(re.search(r"#define DSA_VERSION (\d+)", header).group(1)) >= 120
     assert _lib.load().dsa_num_frames(16000, 80) == 200
     assert _lib.load().dsa_num_frames(19200, 80) == 240
+
+
+def _dynamic_symbols(path):
+    """Names of the symbols an ELF64 (little-endian) shared object defines in its dynamic symbol table."""
+    import struct
+
+    blob = open(path, "rb").read()
+    assert blob[:6] == b"\x7fELF\x02\x01"
+    shoff, = struct.unpack_from("<Q", blob, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", blob, 0x3A)
+    sections = [struct.unpack_from("<IIQQQQIIQQ", blob, shoff + i * shentsize) for i in range(shnum)]
+    names = set()
+    for _, sh_type, _, _, offset, size, link, _, _, entsize in sections:
+        if sh_type == 11:   # SHT_DYNSYM; `link` is its string table
+            for at in range(offset, offset + size, entsize):
+                st_name, _, _, st_shndx = struct.unpack_from("<IBBH", blob, at)
+                if st_shndx != 0:   # defined here, not imported
+                    start = sections[link][4] + st_name
+                    names.add(blob[start:blob.index(b"\0", start)].decode())
+    return names
+
+
+def test_header_parser_type_mapping_spot_check():
+    """Three rows spelt out by hand, so that the parser's type mapping is pinned by something that is not the parser:
+    int32_t / int64_t / double / pointers, an int64_t return, typed HOST pointers (const double*, float*) as addresses."""
+    P, L, I, D = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double
+    stft = _lib.SIGNATURES["dsa_stft_fwd"]
+    assert stft == (ctypes.c_int, [P, L, L, I, I, I, P, P, I, I, I, D, I, D, I, I, I, P, P])
+    assert len(stft[1]) == 19 and stft[1][11] is D and stft[1][12] is I and stft[1][13] is D
+    assert _lib.SIGNATURES["dsa_num_frames"] == (ctypes.c_int64, [L, I])
+    assert _lib.SIGNATURES["dsa_fbank_scan_plan"] == (ctypes.c_int, [P, I, I, P])
+    assert _lib.SIGNATURES["dsa_last_error"] == (ctypes.c_char_p, [])
+    assert L is not I and ctypes.sizeof(L) == 8 and ctypes.sizeof(I) == 4
+    header = open(os.path.join(ROOT, "include", "diffsptk_amd.h")).read()
+    assert re.search(r"int dsa_fbank_scan_plan\(const double\* H_host, int32_t K, int32_t C, float\* plan_host\);", header)
+    # constants: an enumerator, a negative one, a hex define and the one define that is an expression
+    assert (_lib.F64, _lib.ERR_UNSUPPORTED, _lib.ALGO_HIST_HAS_RT, _lib.ALGO_TUNED) == (1, -2, 0x400, 2)
+    assert _lib.MCEP_BWD_WORKSPACE_BYTES == 64 + 512 * 16 * 32 * 4 and _lib.SCRATCH_BYTES == 64
+    assert "DSA_ALGO_RESERVE_CUS" not in _lib.CONSTANTS and _lib.algo_reserve_cus(65) == 1 << 16   # function-like: stays Python
+
+
+def test_header_parser_on_snippets(tmp_path):
+    sig, const = _lib.parse_header("""
+        /* int dsa_in_a_comment(float x); */
+        #define DSA_A 0x10   // int dsa_also_a_comment(float x);
+        #define DSA_B (DSA_A + 2 * 3)
+        #define DSA_F(n) ((n) << 1)
+        typedef enum { DSA_P = -1, DSA_Q, DSA_R = 7, DSA_S } dsa_status;
+        const char * dsa_name(void);
+        int64_t dsa_two_lines(const void* x, int64_t n,
+                              double eps, float* out_host, void* stream);
+    """)
+    assert const == {"DSA_A": 16, "DSA_B": 22, "DSA_P": -1, "DSA_Q": 0, "DSA_R": 7, "DSA_S": 8}
+    assert sig == {"dsa_name": (ctypes.c_char_p, []),
+                   "dsa_two_lines": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p])}
+    for bad in ("int dsa_x(const void* a, float b);",                     # a parameter type without a mapping
+                "int dsa_x(const void* a, int32_t n\nint dsa_y(void);",   # unterminated
+                "int dsa_x(const void* a, int32_t n",                     # unterminated at the end of the file
+                "dsa_x(int32_t n);",                                      # no return type
+                "unsigned dsa_x(int32_t n);",                             # a return type without a mapping
+                "int dsa_x(int32_t);",                                    # a parameter without a name
+                "int dsa_x(int32_t n, void (*done)(int));"):              # nested parentheses
+        with pytest.raises(_lib.BackendError, match="diffsptk_amd.h"):
+            _lib.parse_header("#define DSA_A 1\nint dsa_ok(void);\n" + bad)
+    # a tree without the header fails at import, naming the path
+    import importlib.util
+
+    os.makedirs(tmp_path / "pkg")
+    (tmp_path / "pkg" / "_lib.py").write_text(open(_lib.__file__).read())
+    spec = importlib.util.spec_from_file_location("_lib_without_header", str(tmp_path / "pkg" / "_lib.py"))
+    with pytest.raises(RuntimeError, match=re.escape(str(tmp_path / "include" / "diffsptk_amd.h"))) as e:
+        spec.loader.exec_module(importlib.util.module_from_spec(spec))
+    assert type(e.value).__name__ == "BackendError"
+
+
+def test_names_the_driver_uses_resolve():
+    """bench.py and __graft_entry__.py reach into ops and _lib by name (ops._call, ops.McepFn, _lib.ALGO_AUTO, ...): every such
+    name must resolve, wherever the code behind it lives."""
+    from diffsptk_amd import ops
+
+    used = set()
+    for f in ("bench.py", "__graft_entry__.py"):
+        used |= set(re.findall(r"\b(ops|_lib)\.([A-Za-z_]\w*)", open(os.path.join(ROOT, f)).read()))
+    assert {("ops", "_call"), ("ops", "_stream"), ("ops", "McepFn"), ("_lib", "F32"), ("_lib", "last_kernel")} <= used
+    missing = [f"{m}.{n}" for m, n in sorted(used) if not hasattr({"ops": ops, "_lib": _lib}[m], n)]
+    assert not missing, missing
+    assert ops._reserved_cus is ops.mcep._reserved_cus and ops._overlapped is ops.mcep._overlapped   # the lists, not copies
 
 
 def test_no_cpu_fallback():
