@@ -213,3 +213,38 @@ def interpolate(x: Tensor, period: int = 1, start: int = 0, dim: int = -1) -> Te
 def linear_intpl(x: Tensor, upsampling_factor: int = 80) -> Tensor:
     """Linear interpolation of frame-wise parameters (functional.py: linear_intpl)."""
     return nn.LinearInterpolation._func(x, upsampling_factor=upsampling_factor)
+
+
+def lpc2par(a: Tensor, gamma: float = 1, c: int | None = None) -> Tensor:
+    """LPC -> PARCOR coefficients a:(..., M+1) -> (..., M+1) (functional.py: lpc2par)."""
+    return nn.LinearPredictiveCoefficientsToParcorCoefficients._func(a, gamma=gamma, c=c)
+
+
+def par2lpc(k: Tensor, gamma: float = 1, c: int | None = None) -> Tensor:
+    """PARCOR -> LPC coefficients k:(..., M+1) -> (..., M+1) (functional.py: par2lpc)."""
+    return nn.ParcorCoefficientsToLinearPredictiveCoefficients._func(k, gamma=gamma, c=c)
+
+
+def lpccheck(a: Tensor, margin: float = 1e-16, warn_type: str = "warn") -> Tensor:
+    """Stability check of LPC coefficients a:(..., M+1) -> (..., M+1) (functional.py: lpccheck)."""
+    return nn.LinearPredictiveCoefficientsStabilityCheck._func(a, margin=margin, warn_type=warn_type)
+
+
+def par2lar(k: Tensor) -> Tensor:
+    """PARCOR coefficients -> log area ratio (functional.py: par2lar)."""
+    return nn.ParcorCoefficientsToLogAreaRatio._func(k)
+
+
+def lar2par(g: Tensor) -> Tensor:
+    """Log area ratio -> PARCOR coefficients (functional.py: lar2par)."""
+    return nn.LogAreaRatioToParcorCoefficients._func(g)
+
+
+def par2is(k: Tensor) -> Tensor:
+    """PARCOR coefficients -> inverse sine coefficients (functional.py: par2is)."""
+    return nn.ParcorCoefficientsToInverseSine._func(k)
+
+
+def is2par(s: Tensor) -> Tensor:
+    """Inverse sine coefficients -> PARCOR coefficients (functional.py: is2par)."""
+    return nn.InverseSineToParcorCoefficients._func(s)

@@ -28,6 +28,13 @@ from .mglsadf import PseudoMGLSADigitalFilter as MLSA
 from .plp import PerceptualLinearPredictiveCoefficientsAnalysis
 from .plp import PerceptualLinearPredictiveCoefficientsAnalysis as PLP
 from .poledf import AllPoleDigitalFilter
+from .lpc2par import LinearPredictiveCoefficientsToParcorCoefficients
+from .par2lpc import ParcorCoefficientsToLinearPredictiveCoefficients
+from .lpccheck import LinearPredictiveCoefficientsStabilityCheck
+from .par2lar import ParcorCoefficientsToLogAreaRatio
+from .lar2par import LogAreaRatioToParcorCoefficients
+from .par2is import ParcorCoefficientsToInverseSine
+from .is2par import InverseSineToParcorCoefficients
 from .pqmf import PseudoQuadratureMirrorFilterBankAnalysis, PseudoQuadratureMirrorFilterBankSynthesis
 from .pqmf import PseudoQuadratureMirrorFilterBankAnalysis as PQMF
 from .pqmf import PseudoQuadratureMirrorFilterBankSynthesis as IPQMF
@@ -51,5 +58,8 @@ __all__ = [
     "FusedFrameWindowLPC", "FusedSTFTFilterBank", "FusedSTFTMelCepstralAnalysis", "fuse",
     "Decimation", "Interpolation", "PQMF", "IPQMF", "PseudoQuadratureMirrorFilterBankAnalysis",
     "PseudoQuadratureMirrorFilterBankSynthesis", "FusedPQMFDecimation", "FusedInterpolationIPQMF",
+    "LinearPredictiveCoefficientsToParcorCoefficients", "ParcorCoefficientsToLinearPredictiveCoefficients",
+    "LinearPredictiveCoefficientsStabilityCheck", "ParcorCoefficientsToLogAreaRatio", "LogAreaRatioToParcorCoefficients",
+    "ParcorCoefficientsToInverseSine", "InverseSineToParcorCoefficients",
     "RealValuedFastFourierTransform", "STFT", "ShortTimeFourierTransform", "Spectrum", "Window",
 ]

@@ -149,3 +149,103 @@ class FrameWindowLpcFn(torch.autograd.Function):
             _call("dsa_frame_window_lpc_bwd", _p(gc), _p(xc), xc.numel() // T, T, L, P, _p(wc), int(center), pad_mode_code("constant"),
                   M, float(eps), _dtype_code(xc), _p(gx), _stream())
         return gx, None, None, None, None, None, None, None
+
+
+def _rows(t):
+    """(contiguous tensor, F, M) of a (..., M+1) tensor of coefficient rows."""
+    tc = t.contiguous()
+    M1 = tc.size(-1)
+    return tc, tc.numel() // M1, M1 - 1
+
+
+class Lpc2ParFn(torch.autograd.Function):
+    """lpc2par.py:103-120 (the step-down recursion) in one launch; the backward works from the output k alone."""
+
+    @staticmethod
+    def forward(ctx, a, gamma):
+        _require_device(a)
+        ac, F, M = _rows(a)
+        k = torch.empty_like(ac)
+        with torch.cuda.device(a.device):
+            _call("dsa_lpc2par_fwd", _p(ac), F, M, float(gamma), _dtype_code(ac), _p(k), _stream())
+        ctx.save_for_backward(k)
+        ctx.gamma = gamma
+        return k
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gk):
+        (k,) = ctx.saved_tensors
+        gk, F, M = _rows(gk)
+        ga = torch.empty_like(k)
+        with torch.cuda.device(gk.device):
+            _call("dsa_lpc2par_bwd", _p(gk), _p(k), F, M, float(ctx.gamma), _dtype_code(k), _p(ga), _stream())
+        return ga, None
+
+
+class Par2LpcFn(torch.autograd.Function):
+    """par2lpc.py:101-107 (the step-up recursion) in one launch; the backward recomputes from the input k."""
+
+    @staticmethod
+    def forward(ctx, k, gamma):
+        _require_device(k)
+        kc, F, M = _rows(k)
+        a = torch.empty_like(kc)
+        with torch.cuda.device(k.device):
+            _call("dsa_par2lpc_fwd", _p(kc), F, M, float(gamma), _dtype_code(kc), _p(a), _stream())
+        ctx.save_for_backward(kc)
+        ctx.gamma = gamma
+        return a
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, ga):
+        (kc,) = ctx.saved_tensors
+        ga, F, M = _rows(ga)
+        gk = torch.empty_like(kc)
+        with torch.cuda.device(ga.device):
+            _call("dsa_par2lpc_bwd", _p(ga), _p(kc), F, M, float(ctx.gamma), _dtype_code(kc), _p(gk), _stream())
+        return gk, None
+
+
+class LpcCheckFn(torch.autograd.Function):
+    """lpccheck.py:104-121 (step-down, clip, step-up) in one launch.  `unstable`: a zeroed int32 tensor of one element that the
+    kernel sets when any |k_m| >= 1, or None.  Saves the unclipped PARCOR, and only when a gradient is wanted."""
+
+    @staticmethod
+    def forward(ctx, a, bound, unstable):
+        _require_device(a)
+        ac, F, M = _rows(a)
+        out = torch.empty_like(ac)
+        k = torch.empty_like(ac) if ctx.needs_input_grad[0] else None
+        with torch.cuda.device(a.device):
+            _call("dsa_lpccheck_fwd", _p(ac), F, M, float(bound), _dtype_code(ac), _p(out), _p(k), _p(unstable), _stream())
+        if k is not None:
+            ctx.save_for_backward(k)
+        ctx.bound = bound
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        (k,) = ctx.saved_tensors
+        gout, F, M = _rows(gout)
+        ga = torch.empty_like(k)
+        with torch.cuda.device(gout.device):
+            _call("dsa_lpccheck_bwd", _p(gout), _p(k), F, M, float(ctx.bound), _dtype_code(k), _p(ga), _stream())
+        return ga, None, None
+
+
+def lpc2par(a, gamma=1.0):
+    return Lpc2ParFn.apply(a, gamma)
+
+
+def par2lpc(k, gamma=1.0):
+    return Par2LpcFn.apply(k, gamma)
+
+
+def lpccheck(a, bound, detect=False):
+    """(out, unstable): unstable is None unless detect, else a one-element int32 tensor (non-zero: some |k_m| >= 1) that the
+    caller reads back -- the only synchronisation, and only when asked for."""
+    unstable = torch.zeros(1, dtype=torch.int32, device=a.device) if detect else None
+    return LpcCheckFn.apply(a, bound, unstable), unstable

@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define DSA_VERSION 132 /* 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
+#define DSA_VERSION 133 /* 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
 
 typedef enum {
     DSA_OK = 0,
@@ -602,6 +602,35 @@ int dsa_frame_window_lpc_fwd(const void* x, int64_t B, int64_t T, int32_t L, int
 int dsa_frame_window_lpc_bwd(const void* gout, const void* x, int64_t B, int64_t T, int32_t L, int32_t P,
                              const void* w, int32_t center, int32_t pad_mode, int32_t M, double eps,
                              int32_t dtype, void* gx, void* stream);
+
+/* ------------------------------------------------------------------ a14  LPC <-> PARCOR and the LPC stability check (0.2.7)
+ * Rows are (F, M+1) = [K, c_1 .. c_M]; K is carried, never part of a recursion.  One launch each, float32 and float64 (the
+ * recursions run in float64 either way), int64 indexing, no allocation, no host synchronisation; F = 0 is a no-op before any pointer
+ * is looked at.  A row's bits depend on (M, dtype) and the row alone, not on F or on its position.  One frame per lane with the
+ * recursion unrolled in registers for M <= DSA_PARCOR_MAX_ORDER, one wave per frame with the row in LDS up to
+ * DSA_PARCOR_ROW_MAX_ORDER; a larger M is DSA_ERR_INVALID_ARGUMENT.
+ *   dsa_lpc2par_fwd   LinearPredictiveCoefficientsToParcorCoefficients._forward, lpc2par.py:103-120: a -> k by the step-down
+ *                     recursion on gamma a_1 .. gamma a_M (a^(m-1)_j = (a^(m)_j - k_m a^(m)_{m-j}) / (1 - k_m^2), k_m = a^(m)_m).
+ *   dsa_lpc2par_bwd   its adjoint from the OUTPUT k alone (the intermediates are regenerated by stepping up): gk -> ga.
+ *   dsa_par2lpc_fwd   ParcorCoefficientsToLinearPredictiveCoefficients._forward, par2lpc.py:101-107: k -> a by the step-up recursion
+ *                     (a^(m)_j = a^(m-1)_j + k_m a^(m-1)_{m-j}), the WHOLE row -- K included -- divided by gamma (par2lpc.py:102).
+ *   dsa_par2lpc_bwd   its adjoint from the input k: ga -> gk.  Each a^(m-1) is recomputed by stepping up from k, never by stepping
+ *                     down from the output: the gradient is finite at |k_m| = 1.
+ *   dsa_lpccheck_fwd  LinearPredictiveCoefficientsStabilityCheck._forward, lpccheck.py:104-121: step-down (gamma 1), the PARCOR
+ *                     rounded to the dtype, k_1 .. k_M clipped to +-bound (bound rounded to the dtype, as torch.clip does with a
+ *                     Python scalar), step-up -> out.  k:(F, M+1) or NULL receives the UNCLIPPED PARCOR for the backward.
+ *                     unstable: one int32 or NULL, zeroed by the caller, set to 1 (an ordinary vector store) when any |k_m| >= 1.
+ *   dsa_lpccheck_bwd  gout and the forward's k -> ga: the step-up adjoint on the clipped k, torch.clip's mask (1 inside and on the
+ *                     bound), the step-down adjoint on the unclipped k. */
+#define DSA_PARCOR_MAX_ORDER 32
+#define DSA_PARCOR_ROW_MAX_ORDER 1023
+int dsa_lpc2par_fwd(const void* a, int64_t F, int32_t M, double gamma, int32_t dtype, void* k, void* stream);
+int dsa_lpc2par_bwd(const void* gk, const void* k, int64_t F, int32_t M, double gamma, int32_t dtype, void* ga, void* stream);
+int dsa_par2lpc_fwd(const void* k, int64_t F, int32_t M, double gamma, int32_t dtype, void* a, void* stream);
+int dsa_par2lpc_bwd(const void* ga, const void* k, int64_t F, int32_t M, double gamma, int32_t dtype, void* gk, void* stream);
+int dsa_lpccheck_fwd(const void* a, int64_t F, int32_t M, double bound, int32_t dtype, void* out, void* k, int32_t* unstable,
+                     void* stream);
+int dsa_lpccheck_bwd(const void* gout, const void* k, int64_t F, int32_t M, double bound, int32_t dtype, void* ga, void* stream);
 
 #ifdef __cplusplus
 }
