@@ -17,8 +17,8 @@ _ROOT = os.path.dirname(_PKG)
 CSRC = os.path.join(_PKG, "csrc")
 LIB_DIR = os.path.join(_PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libdiffsptk_amd.so")
-SOURCES = ("stft.hip", "mcep.hip", "mcep_mfma.hip", "lpc.hip", "fbank.hip", "fftcep.hip", "mgc.hip", "rows_gemm.hip", "thsolve_quad.hip", "poledf.hip", "plp.hip",
-           "pqmf.hip", "parcor.hip")
+SOURCES = ("core.hip", "stft.hip", "spec.hip", "griffin.hip", "mcep.hip", "mcep_mfma.hip", "lpc.hip", "fbank.hip", "fftcep.hip", "mgc.hip", "thsolve.hip",
+           "zerodf.hip", "rows_gemm.hip", "thsolve_quad.hip", "poledf.hip", "plp.hip", "pqmf.hip", "parcor.hip")
 HIPCC_FLAGS = (
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
     "-mcode-object-version=5", "-Wno-unused-value", "-ffp-contract=on",
@@ -31,9 +31,14 @@ HIPCC_FLAGS = (
 # tests/test_host_cpu.py::test_no_crossed_packed_float32); kernels with hand-placed packed instructions carry DSA_PK_TARGET.
 _NO_PK = ("-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops")
 SOURCE_FLAGS = {
+    "core.hip": _NO_PK,
     "stft.hip": _NO_PK,
+    "spec.hip": _NO_PK,
+    "griffin.hip": _NO_PK,
     "fbank.hip": _NO_PK,
     "mgc.hip": _NO_PK,
+    "thsolve.hip": _NO_PK,
+    "zerodf.hip": _NO_PK,
     "thsolve_quad.hip": _NO_PK,
     "poledf.hip": _NO_PK,
     "plp.hip": _NO_PK,

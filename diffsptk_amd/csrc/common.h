@@ -68,6 +68,13 @@ inline bool ensure_dynamic_lds(const void* kernel, int bytes, std::atomic<uint64
 // matrix-core "transform of the spectrum x (K x C) matrix" launcher of fbank.hip, shared with fftcep.hip
 // (use_power: 0 sqrt x | 1 x | 2 log x;  post_mode 0: floor + glog, 1: scale with the first column halved,
 //  3: first and last column halved;  needs float32, C <= 48, C < K <= 320)
+// the generic route of the STFT (csrc/spec.hip), the fallback of dsa_stft_fwd / dsa_stft_bwd (csrc/stft.hip): float32 and float64
+int stft_generic_fwd(int dtype, const void* x, int64_t B, int64_t Tlen, int64_t N, int L, int P, int left, int mode, int zmean,
+                     const void* w, int nfft, const void* twiddle, int fmt, double eps, int use_floor, double floor_db, void* y,
+                     hipStream_t st);
+int stft_generic_bwd(int dtype, const void* gy, const void* x, int64_t B, int64_t Tlen, int L, int P, int nfft, const void* w,
+                     const void* twiddle, int center, int zmean, int pad_mode, double eps, int use_floor, double floor_db, int fmt,
+                     void* gx, void* gw, hipStream_t st);
 // 24 x 24 Toeplitz-plus-Hankel systems, float32, 16 per wave in the quad layout (csrc/mcep_mfma.hip)
 int thsolve_quad24_fwd(const void* p, const void* q, const void* r, int64_t F, void* g, hipStream_t st, int r_stride = 24,
                        int r_off = 0, const void* add = nullptr);

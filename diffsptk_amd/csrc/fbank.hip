@@ -731,6 +731,90 @@ DSA_EXPORT int dsa_fbank_bins_plan(const double* H, int32_t K, int32_t C, float*
     return DSA_OK;
 }
 
+// Host side of the filter-bank epilogue of stft512_fwd_pk_kernel<.., FBM = 1 / 2> (stft_pk.h; launched by dsa_stft_fbank_fwd, stft.hip).
+// dsa_fbank_scan_plan turns H (host, float64, 257 x C) into the (64, 32) float32 per-lane table; it is the C
+// statement of diffsptk_amd/utils/tables.py:fbank_scan_plan / fbank_scan_table (tests compare the two bit for bit).
+DSA_EXPORT int dsa_fbank_scan_plan(const double* H, int32_t K, int32_t C, float* table)
+{
+    DSA_REQUIRE(H && table, "fbank_scan_plan: null pointer");
+    if (K != 257 || C < 1 || C > 126) return fail(DSA_ERR_UNSUPPORTED, "fbank_scan_plan: needs 257 bins and at most 126 channels%s");
+    int jk[257] = {0};
+    double wd[257] = {0.0}, wu[257] = {0.0};
+    int prev = 0;
+    for (int k = 1; k < K - 1; ++k) {
+        int nz[3], n = 0;
+        for (int c = 0; c < C; ++c) {
+            const double h = H[(size_t)k * C + c];
+            if (!std::isfinite(h)) return fail(DSA_ERR_UNSUPPORTED, "fbank_scan_plan: non-finite weight%s");
+            if (h != 0.0) {
+                if (n < 3) nz[n] = c;
+                ++n;
+            }
+        }
+        int j;
+        if (n == 0) {
+            j = prev;
+        } else if (n == 1) {
+            const int c = nz[0];
+            if (c >= prev) j = c, wu[k] = H[(size_t)k * C + c];
+            else if (c + 1 >= prev) j = c + 1, wd[k] = H[(size_t)k * C + c];
+            else return fail(DSA_ERR_UNSUPPORTED, "fbank_scan_plan: channels are not ordered along the bins%s");
+        } else if (n == 2 && nz[1] == nz[0] + 1 && nz[1] >= prev) {
+            j = nz[1], wd[k] = H[(size_t)k * C + nz[0]], wu[k] = H[(size_t)k * C + nz[1]];
+        } else {
+            return fail(DSA_ERR_UNSUPPORTED, "fbank_scan_plan: a bin feeds more than two adjacent channels%s");
+        }
+        jk[k] = prev = j;
+    }
+    for (int c = 0; c < C; ++c)
+        if (!std::isfinite(H[c]) || !std::isfinite(H[(size_t)(K - 1) * C + c]))
+            return fail(DSA_ERR_UNSUPPORTED, "fbank_scan_plan: non-finite weight%s");
+    memset(table, 0, sizeof(float) * 64 * 32);
+    int32_t* ti = reinterpret_cast<int32_t*>(table);
+    bool valid[2][128] = {{false}};
+    for (int h = 0; h < 2; ++h) {
+        int j0[64], j1[64], run[64];
+        for (int l = 0; l < 64; ++l) {
+            const int b0 = h == 0 ? 2 * l + 1 : 255 - 2 * l, b1 = h == 0 ? 2 * l + 2 : 254 - 2 * l;
+            j0[l] = jk[b0], j1[l] = jk[b1];
+            float* t = table + l * 32;
+            t[0 + h] = (float)wd[b0], t[2 + h] = (float)wu[b0];
+            t[4 + h] = (float)wd[b1], t[6 + h] = (float)wu[b1];
+            if (h == 1 && l == 63) t[4 + h] = t[6 + h] = 0.f;   // bin 128 belongs to the lower half
+            t[8 + h] = j0[l] != j1[l] ? 0.f : 1.f;
+        }
+        run[0] = 0;
+        for (int l = 1; l < 64; ++l) run[l] = (j0[l] == j1[l] && j1[l - 1] == j0[l]) ? run[l - 1] + 1 : 0;
+        for (int l = 0; l < 64; ++l) {
+            float* t = table + l * 32;
+            float* m = t + 10 + 6 * h;
+            m[0] = run[l] >= 1, m[1] = run[l] >= 2, m[2] = run[l] >= 4, m[3] = run[l] >= 8;
+            m[4] = ((l / 16) % 2 == 1) && run[l] >= l % 16 + 1;
+            m[5] = l >= 32 && run[l] >= l - 31;
+            t[22 + h] = (l > 0 && j1[l - 1] == j0[l]) ? 1.f : 0.f;
+            const bool isE = l == 63 || j0[l + 1] != j1[l], isM = j0[l] != j1[l];
+            ti[l * 32 + 24] |= (j1[l] << (8 * h)) | (j0[l] << (16 + 8 * h));
+            ti[l * 32 + 25] |= ((int)isE << h) | ((int)isM << (2 + h));
+            if (isE) valid[h][j1[l]] = true;
+            if (isM) valid[h][j0[l]] = true;
+        }
+    }
+    for (int l = 0; l < 64; ++l)
+        for (int r = 0; r < 2; ++r) {
+            const int c = l + 64 * r;
+            if (c >= C) continue;
+            table[l * 32 + 26 + 2 * r] = (float)H[c];
+            table[l * 32 + 27 + 2 * r] = (float)H[(size_t)(K - 1) * C + c];
+            // channel c reads the up-slope sums of interval c and the down-slope sums of interval c + 1
+            ti[l * 32 + 30] |= ((int)valid[0][c] | ((int)valid[1][c] << 1) | ((int)valid[0][c + 1] << 2) | ((int)valid[1][c + 1] << 3)) << (4 * r);
+        }
+    bool has_ends = false;
+    for (int c = 0; c < C; ++c) has_ends = has_ends || H[c] != 0.0 || H[(size_t)(K - 1) * C + c] != 0.0;
+    if (has_ends)
+        for (int l = 0; l < 64; ++l) ti[l * 32 + 30] |= 256;   // bit 8 (every lane): bins 0 / 256 carry weight
+    return DSA_OK;
+}
+
 DSA_EXPORT int dsa_fbank_bins_bwd(const void* gy, const void* y, int64_t F, int32_t K, int32_t C, const void* table, double floor,
                                   double gamma, int32_t dtype, void* g, void* stream)
 {

@@ -70,7 +70,7 @@ __device__ __forceinline__ void fc_fft_product(const T* src, int klim, int H, T*
         fim[m] = k1 < klim ? src[k1] : T(0);
     }
     __syncthreads();
-    // lds_fft_pow2 of stft.hip, restated here for this translation unit (forward sign, natural in, bit-reversed out): two
+    // lds_fft_pow2 of lds_fft.h, restated here for this translation unit (forward sign, natural in, bit-reversed out): two
     // radix-2 stages per pass through registers (the four points i0, i0 + h/2, i0 + h, i0 + h + h/2 are closed under
     // stages s and s - 1): half the LDS traffic and barriers; the second pair's twiddle is -i times the first's, stage
     // s - 1's is its square.  The twiddle table is the L-point one: W_n^(j n / 2h) = W_L^(j L / 2h).

@@ -536,7 +536,7 @@ __device__ __forceinline__ void blk_backsub_all_r(const f32x4 (&a)[blk::NBLK], f
 // without pivoting for the same reason).  The 24 x 24 system rides in the 25 x 25 machinery with row / column 24 as an
 // identity pair: row 24 stores slot 6 only (diagonal 1 on lane 0, right-hand side 0 on lane 1) and column 24 of the other
 // rows comes through the slot-6 pointers as zeros, so it never couples.  One system per wave with a pivot search
-// (th_solve_reg, csrc/mgc.hip) took 0.2 ms per 51 200 systems; this takes 0.02 ms.
+// (th_solve_reg, csrc/thsolve.hip) took 0.2 ms per 51 200 systems; this takes 0.02 ms.
 // ---------------------------------------------------------------------------------------------
 constexpr int kTq = 132;   // floats per system in LDS: q window [0, 52) | mirrored p window [52, 104) | r [104, 132); 132 % 32 = 4: the four lanes of a
                            // system read four consecutive banks and the eight systems of a 32-lane half cover the 32 banks once (136: two systems per bank range)

@@ -1,1018 +1,10 @@
-// Toeplitz-plus-Hankel solve of the mel-generalized cepstral analysis:
-//   MelGeneralizedCepstralAnalysis.forward, mgcep.py:226-229:  R = symmetric_toeplitz(pt), Q = hankel(qt),
-//   gradient = torch.linalg.solve(R + Q, rt)     (utils/private.py:291-302 for the two builders).
-// One wave per frame: the M x (M + 1) augmented system lives in LDS, lane i owns row i; Gauss-Jordan elimination
-// with row pivoting by magnitude (the reference's LAPACK call pivots too; the system is not guaranteed positive
-// definite for gamma != 0).  Backward: with A = T(p) + H(q) symmetric, u = A^{-1} gbar, rbar = u, Abar = -u g^T,
-// pbar[k] = sum over |i - j| = k of Abar[i][j], qbar[k] = sum over i + j = k.  float32 and float64; M <= 64.
-// The rest of the analysis (warping / FFT stages composed into row products, pointwise spectrum arithmetic) is
-// assembled by the host layer from the library's row-product kernel (modules/mgcep.py).
+// Mel-generalized cepstra: the spectrum arithmetic of the Newton step of the mel-generalized cepstral analysis (mgcep_spectra,
+// mgcep_step, mgcep_step_bwd; the step's solve is thsolve.hip / thsolve_quad.hip), gain normalisation (gnorm, mgcep_gain) and the
+// generalized cepstral transformation gc2gc.
 #include "common.h"
-#include "th_solve_reg.h"
-
-#include <cstdlib>
+#include "lds_fft.h"
 
 namespace dsa {
-
-constexpr int kThMax = 64;
-
-// Solves the n x n system in LDS (row stride W >= n + nrhs) for nrhs right-hand sides; on return column n + c of row
-// piv_row[k] divided by its pivot is x_c[k].  One wave, lane i owns row i (n <= 64).
-template <typename T>
-__device__ void th_gauss_jordan(T* Aug, int n, int W, int nrhs, int* rowof, int lane)
-{
-    unsigned long long used = 0ull;   // rows already chosen as pivots (uniform)
-    for (int k = 0; k < n; ++k) {
-        // pivot: the unused row with the largest |Aug[i][k]|
-        T mag = (lane < n && !((used >> lane) & 1ull)) ? (Aug[lane * W + k] < T(0) ? -Aug[lane * W + k] : Aug[lane * W + k]) : T(-1);
-        int arg = lane;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const T m2 = __shfl_xor(mag, o, 64);
-            const int a2 = __shfl_xor(arg, o, 64);
-            if (m2 > mag || (m2 == mag && a2 < arg)) {
-                mag = m2;
-                arg = a2;
-            }
-        }
-        const int p = arg;   // uniform
-        used |= 1ull << p;
-        if (lane == 0) rowof[k] = p;
-        const T inv = T(1) / Aug[p * W + k];
-        const T fac = (lane < n && lane != p) ? Aug[lane * W + k] * inv : T(0);
-        __builtin_amdgcn_wave_barrier();
-        if (lane < n && lane != p)
-            for (int j = k + 1; j < n + nrhs; ++j) Aug[lane * W + j] -= fac * Aug[p * W + j];
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-
-template <typename T>
-__device__ void th_build(T* Aug, const T* p, const T* q, int n, int W, int lane)
-{
-    if (lane < n)
-        for (int j = 0; j < n; ++j) {
-            const int d = lane > j ? lane - j : j - lane;
-            Aug[lane * W + j] = p[d] + q[lane + j];
-        }
-}
-
-template <typename T, int NMAX = 0>   // NMAX > 0: register version (n <= NMAX)
-__global__ __launch_bounds__(64) void th_solve_fwd_kernel(const T* __restrict__ p, const T* __restrict__ q,
-                                                          const T* __restrict__ r, long F, int n, T* __restrict__ g)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    T* Aug = reinterpret_cast<T*>(smem_raw);
-    const int W = n + 1;
-    int* rowof = reinterpret_cast<int*>(Aug + (size_t)n * W);
-    const int lane = threadIdx.x;
-    for (long f = blockIdx.x; f < F; f += gridDim.x) {
-        __builtin_amdgcn_wave_barrier();
-        if (NMAX > 0) {
-            T* ps = Aug;          // [n]
-            T* qs = Aug + n;      // [2n - 1]
-            if (lane < n) ps[lane] = p[f * n + lane];
-            for (int i = lane; i < 2 * n - 1; i += 64) qs[i] = q[f * (2 * n - 1) + i];
-            const T rhs = lane < n ? r[f * n + lane] : T(0);
-            __builtin_amdgcn_wave_barrier();
-            int col;
-            T sol;
-            th_solve_reg<T, (NMAX > 0 ? NMAX : 1)>(ps, qs, rhs, n, lane, col, sol);
-            if (lane < n) g[f * n + col] = sol;
-            continue;
-        }
-        th_build(Aug, p + f * n, q + f * (2 * n - 1), n, W, lane);
-        if (lane < n) Aug[lane * W + n] = r[f * n + lane];
-        __builtin_amdgcn_wave_barrier();
-        th_gauss_jordan(Aug, n, W, 1, rowof, lane);
-        if (lane < n) {
-            const int row = rowof[lane];
-            g[f * n + lane] = Aug[row * W + n] / Aug[row * W + lane];
-        }
-    }
-}
-
-template <typename T, int NMAX = 0>
-__global__ __launch_bounds__(64) void th_solve_bwd_kernel(const T* __restrict__ gg, const T* __restrict__ p,
-                                                          const T* __restrict__ q, const T* __restrict__ g, long F, int n,
-                                                          T* __restrict__ gp, T* __restrict__ gq, T* __restrict__ gr)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    T* Aug = reinterpret_cast<T*>(smem_raw);
-    const int W = n + 1;
-    int* rowof = reinterpret_cast<int*>(Aug + (size_t)n * W);
-    T* u = reinterpret_cast<T*>(rowof + kThMax);
-    T* gs = u + kThMax;
-    const int lane = threadIdx.x;
-    for (long f = blockIdx.x; f < F; f += gridDim.x) {
-        __builtin_amdgcn_wave_barrier();
-        if (NMAX > 0) {
-            T* ps = Aug;
-            T* qs = Aug + n;
-            if (lane < n) {
-                ps[lane] = p[f * n + lane];
-                gs[lane] = g[f * n + lane];
-            }
-            for (int i = lane; i < 2 * n - 1; i += 64) qs[i] = q[f * (2 * n - 1) + i];
-            const T rhs = lane < n ? gg[f * n + lane] : T(0);   // A is symmetric: u = A^{-T} gbar = A^{-1} gbar
-            __builtin_amdgcn_wave_barrier();
-            int col;
-            T sol;
-            th_solve_reg<T, (NMAX > 0 ? NMAX : 1)>(ps, qs, rhs, n, lane, col, sol);
-            if (lane < n) {
-                u[col] = sol;
-                gr[f * n + col] = sol;
-            }
-        } else {
-            th_build(Aug, p + f * n, q + f * (2 * n - 1), n, W, lane);
-            if (lane < n) {
-                Aug[lane * W + n] = gg[f * n + lane];   // A is symmetric: u = A^{-T} gbar = A^{-1} gbar
-                gs[lane] = g[f * n + lane];
-            }
-            __builtin_amdgcn_wave_barrier();
-            th_gauss_jordan(Aug, n, W, 1, rowof, lane);
-            if (lane < n) {
-                const int row = rowof[lane];
-                const T ul = Aug[row * W + n] / Aug[row * W + lane];
-                u[lane] = ul;
-                gr[f * n + lane] = ul;
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-        // Abar = -u g^T on the Toeplitz diagonals |i - j| = k (k < n) and the Hankel anti-diagonals i + j = k (k < 2n-1)
-        for (int k = lane; k < 2 * n - 1; k += 64) {
-            T sq = 0;
-            const int lo = k - (n - 1) > 0 ? k - (n - 1) : 0, hi = k < n - 1 ? k : n - 1;
-            for (int i = lo; i <= hi; ++i) sq -= u[i] * gs[k - i];
-            gq[f * (2 * n - 1) + k] = sq;
-            if (k < n) {
-                T sp = 0;
-                for (int i = 0; i + k < n; ++i) sp -= u[i] * gs[i + k] + (k > 0 ? u[i + k] * gs[i] : T(0));
-                gp[f * n + k] = sp;
-            }
-        }
-    }
-}
-
-// Cotangents of the Toeplitz column p and the Hankel sequence q from u = A^{-1} gbar and the forward's solution g:
-// Abar = -u g^T summed along the diagonals |i - j| = k and the anti-diagonals i + j = k.  64 threads per system.
-__global__ __launch_bounds__(256) void th_bwd_sums_kernel(const float* __restrict__ u, const float* __restrict__ g, long F, int n,
-                                                         float* __restrict__ gp, float* __restrict__ gq)
-{
-    __shared__ float us[4][64], gs[4][64];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long f = (long)blockIdx.x * 4 + w;
-    const bool ok = f < F;
-    us[w][lane] = ok && lane < n ? u[f * n + lane] : 0.f;
-    gs[w][lane] = ok && lane < n ? g[f * n + lane] : 0.f;
-    __syncthreads();
-    if (!ok) return;
-    for (int k = lane; k < 2 * n - 1; k += 64) {
-        float sq = 0.f;
-        const int lo = k - (n - 1) > 0 ? k - (n - 1) : 0, hi = k < n - 1 ? k : n - 1;
-        for (int i = lo; i <= hi; ++i) sq -= us[w][i] * gs[w][k - i];
-        gq[f * (2 * n - 1) + k] = sq;
-        if (k < n) {
-            float sp = 0.f;
-            for (int i = 0; i + k < n; ++i) sp -= us[w][i] * gs[w][i + k] + (k > 0 ? us[w][i + k] * gs[w][i] : 0.f);
-            gp[f * n + k] = sp;
-        }
-    }
-}
-
-template <typename T>
-static int th_launch(bool bwd, const void* gg, const void* p, const void* q, const void* r_or_g, int64_t F, int n, void* o1,
-                     void* o2, void* o3, hipStream_t st)
-{
-    const size_t lds = sizeof(T) * ((size_t)n * (n + 1) + 2 * kThMax) + sizeof(int) * kThMax;
-    long grid = F < 256L * 16 ? (long)F : 256L * 16;
-#define DSA_TH_LAUNCH(NM)                                                                                                  \
-    do {                                                                                                                   \
-        if (!bwd)                                                                                                          \
-            hipLaunchKernelGGL((th_solve_fwd_kernel<T, NM>), dim3((unsigned)grid), dim3(64), lds, st, (const T*)p, (const T*)q, \
-                               (const T*)r_or_g, (long)F, n, (T*)o1);                                                      \
-        else                                                                                                               \
-            hipLaunchKernelGGL((th_solve_bwd_kernel<T, NM>), dim3((unsigned)grid), dim3(64), lds, st, (const T*)gg, (const T*)p, \
-                               (const T*)q, (const T*)r_or_g, (long)F, n, (T*)o1, (T*)o2, (T*)o3);                         \
-    } while (0)
-    if (n <= 24) DSA_TH_LAUNCH(24);
-    else if (n <= 32) DSA_TH_LAUNCH(32);
-    else if (n <= 48) DSA_TH_LAUNCH(48);   // the orders of the 48 kHz set-ups (34 .. 60): rows in registers too
-    else if (n <= 64) DSA_TH_LAUNCH(64);
-    else DSA_TH_LAUNCH(0);
-#undef DSA_TH_LAUNCH
-    return check_launch(bwd ? "th_solve_bwd" : "th_solve_fwd");
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// Time-variant all-zero filter: AllZeroDigitalFilter._forward_efficient, zerodf.py:207-243 -- the
-// FIR core of the multi-stage / single-stage MLSA filter (mglsadf.py:254-527).
-//   y[t] = sum_{k=0}^{M} h_t[k] x[t - k + z0],   h_t = (1 - w) b[n] + w b[min(n + 1, N - 1)],  n = t / P, w = (t % P) / P
-// (x is zero outside [0, T); z0 = zeroth_index: taps k < z0 look ahead).  ignore_gain divides by the interpolated b[.][0]
-// (z0 < M) or b[.][M] (z0 = M).  One workgroup per frame: both coefficient rows and the frame's stretch of x in LDS.
-template <typename T>
-__global__ __launch_bounds__(256) void zerodf_fwd_kernel(const T* __restrict__ x, const T* __restrict__ b, long Tlen, long N,
-                                                         int M, int P, int z0, int ignore_gain, T* __restrict__ y)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    T* b0 = reinterpret_cast<T*>(smem_raw);   // [M + 1]
-    T* b1 = b0 + (M + 1);                     // [M + 1]
-    T* xs = b1 + (M + 1);                     // [P + M]: x[t0 - M + z0 .. t0 + P - 1 + z0]
-    const long f = blockIdx.x;                // flattened (utterance, frame)
-    const long u = f / N, n = f - u * N;
-    const long n1 = n + 1 < N ? n + 1 : N - 1;
-    const T* br0 = b + (u * N + n) * (M + 1);
-    const T* br1 = b + (u * N + n1) * (M + 1);
-    for (int k = threadIdx.x; k <= M; k += blockDim.x) {
-        b0[k] = br0[k];
-        b1[k] = br1[k];
-    }
-    const long t0 = n * P;
-    const T* xu = x + u * Tlen;
-    for (int i = threadIdx.x; i < P + M; i += blockDim.x) {
-        const long s = t0 - M + z0 + i;
-        xs[i] = (s >= 0 && s < Tlen) ? xu[s] : T(0);
-    }
-    __syncthreads();
-    const int gk = z0 == M ? M : 0;
-    for (int i = threadIdx.x; i < P; i += blockDim.x) {
-        const T w = (T)i / (T)P;
-        T a0 = 0, a1 = 0;
-        // x[t - k + z0] = xs[i + M - k]
-        for (int k = 0; k <= M; ++k) {
-            const T xv = xs[i + M - k];
-            a0 += b0[k] * xv;
-            a1 += b1[k] * xv;
-        }
-        T v = a0 + w * (a1 - a0);             // torch.lerp(y1, y2, ramp)
-        if (ignore_gain) v /= b0[gk] + w * (b1[gk] - b0[gk]);
-        y[u * Tlen + t0 + i] = v;
-    }
-}
-
-// gx[s] = sum_k gyn[t] h_t[k], t = s - z0 + k (gather: deterministic); gyn = gy / gain when ignore_gain
-template <typename T>
-__global__ __launch_bounds__(256) void zerodf_bwd_x_kernel(const T* __restrict__ gy, const T* __restrict__ b, long B, long Tlen,
-                                                           long N, int M, int P, int z0, int ignore_gain, T* __restrict__ gx)
-{
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long u = idx / Tlen, s = idx - u * Tlen;
-    if (u >= B) return;
-    const int gk = z0 == M ? M : 0;
-    T acc = 0;
-    for (int k = 0; k <= M; ++k) {
-        const long t = s - z0 + k;
-        if (t < 0 || t >= Tlen) continue;
-        const long n = t / P;
-        const long n1 = n + 1 < N ? n + 1 : N - 1;
-        const T w = (T)(t - n * P) / (T)P;
-        const T* r0 = b + (u * N + n) * (M + 1);
-        const T* r1 = b + (u * N + n1) * (M + 1);
-        T g = gy[u * Tlen + t];
-        if (ignore_gain) g /= r0[gk] + w * (r1[gk] - r0[gk]);
-        acc += g * (r0[k] + w * (r1[k] - r0[k]));
-    }
-    gx[idx] = acc;
-}
-
-// gb[n][k] = sum over the samples of frame n (weight 1 - w) and of frame n - 1 (weight w; the last frame also takes its
-// own w part) of gyn[t] x[t - k + z0]; with ignore_gain the gain tap additionally receives -gy y / gain.
-template <typename T>
-__global__ __launch_bounds__(256) void zerodf_bwd_b_kernel(const T* __restrict__ gy, const T* __restrict__ x, const T* __restrict__ b,
-                                                           const T* __restrict__ y, long Tlen, long N, int M, int P, int z0,
-                                                           int ignore_gain, T* __restrict__ gb)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    T* gs = reinterpret_cast<T*>(smem_raw);   // [2P]: normalised cotangent times the frame weight, frames n - 1 and n
-    T* xs = gs + 2 * P;                       // [2P + M]
-    T* red = xs + 2 * P + M;                  // [blockDim.x] reduction scratch for the gain tap
-    const long f = blockIdx.x;
-    const long u = f / N, n = f - u * N;
-    const int gk = z0 == M ? M : 0;
-    const long tbase = (n - 1) * P;           // first sample of frame n - 1
-    T gain_part = 0;
-    for (int i = threadIdx.x; i < 2 * P; i += blockDim.x) {
-        const long t = tbase + i;
-        T v = 0;
-        if (t >= 0 && t < Tlen) {
-            const long nt = t / P;            // n - 1 or n
-            const long nt1 = nt + 1 < N ? nt + 1 : N - 1;
-            const T w = (T)(t - nt * P) / (T)P;
-            T wt = 0;                         // weight with which b[n] enters h_t
-            if (nt == n) wt += T(1) - w;
-            if (nt1 == n) wt += w;
-            T g = gy[u * Tlen + t];
-            if (ignore_gain) {
-                const T* r0 = b + (u * N + nt) * (M + 1);
-                const T* r1 = b + (u * N + nt1) * (M + 1);
-                const T gain = r0[gk] + w * (r1[gk] - r0[gk]);
-                g /= gain;
-                gain_part -= wt * g * y[u * Tlen + t];   // d/d gain of (u / gain) = -y / gain, gain = sum wt b[.][gk]
-            }
-            v = wt * g;
-        }
-        gs[i] = v;
-    }
-    const T* xu = x + u * Tlen;
-    for (int i = threadIdx.x; i < 2 * P + M; i += blockDim.x) {
-        const long s = tbase - M + z0 + i;
-        xs[i] = (s >= 0 && s < Tlen) ? xu[s] : T(0);
-    }
-    red[threadIdx.x] = gain_part;
-    __syncthreads();
-    for (int k = threadIdx.x; k <= M; k += blockDim.x) {
-        T acc = 0;
-        for (int i = 0; i < 2 * P; ++i) acc += gs[i] * xs[i + M - k];
-        if (ignore_gain && k == gk)
-            for (int q = 0; q < (int)blockDim.x; ++q) acc += red[q];
-        gb[(u * N + n) * (M + 1) + k] = acc;
-    }
-}
-
-// Long filters (M >= 64: the 200-tap cepstra of the multi-stage MLSA filter, the 2000-tap impulse responses of the
-// single-stage one) with P <= 128: the taps are dealt to 8 slices of 32 threads, a thread keeps up to four output samples
-// (i = l, l + 32, ..) in registers -- two coefficient reads feed eight multiply-adds instead of two, and all 256 threads work
-// where the kernel above keeps P of them busy -- and the slices' partial sums meet in LDS (fixed order: deterministic).
-template <typename T>
-__global__ __launch_bounds__(256) void zerodf_fwd_sliced_kernel(const T* __restrict__ x, const T* __restrict__ b, long Tlen, long N,
-                                                                int M, int P, int z0, int ignore_gain, T* __restrict__ y)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    T* b0 = reinterpret_cast<T*>(smem_raw);   // [M + 1]
-    T* b1 = b0 + (M + 1);                     // [M + 1]
-    T* xs = b1 + (M + 1);                     // [128 + M]: x[t0 - M + z0 ..], zero beyond the frame's stretch
-    T* part = xs + (128 + M);                 // [8][2][128]
-    const long f = blockIdx.x;
-    const long u = f / N, n = f - u * N;
-    const long n1 = n + 1 < N ? n + 1 : N - 1;
-    const T* br0 = b + (u * N + n) * (M + 1);
-    const T* br1 = b + (u * N + n1) * (M + 1);
-    for (int k = threadIdx.x; k <= M; k += blockDim.x) {
-        b0[k] = br0[k];
-        b1[k] = br1[k];
-    }
-    const long t0 = n * P;
-    const T* xu = x + u * Tlen;
-    for (int i = threadIdx.x; i < 128 + M; i += blockDim.x) {
-        const long s = t0 - M + z0 + i;
-        xs[i] = (i < P + M && s >= 0 && s < Tlen) ? xu[s] : T(0);
-    }
-    __syncthreads();
-    const int g = threadIdx.x >> 5, l = threadIdx.x & 31;
-    const int per = (M + 8) / 8;              // ceil((M + 1) / 8)
-    const int k0 = g * per, k1 = (k0 + per < M + 1) ? k0 + per : M + 1;
-    T a0[4] = {T(0), T(0), T(0), T(0)}, a1[4] = {T(0), T(0), T(0), T(0)};
-    for (int k = k0; k < k1; ++k) {
-        const T c0 = b0[k], c1 = b1[k];
-        const T* xp = xs + (M - k) + l;       // x[t - k + z0] = xs[i + M - k]
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const T xv = xp[32 * j];
-            a0[j] += c0 * xv;
-            a1[j] += c1 * xv;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        part[(g * 2 + 0) * 128 + l + 32 * j] = a0[j];
-        part[(g * 2 + 1) * 128 + l + 32 * j] = a1[j];
-    }
-    __syncthreads();
-    const int gk = z0 == M ? M : 0;
-    for (int i = threadIdx.x; i < P; i += blockDim.x) {
-        T s0 = 0, s1 = 0;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            s0 += part[(q * 2 + 0) * 128 + i];
-            s1 += part[(q * 2 + 1) * 128 + i];
-        }
-        const T w = (T)i / (T)P;
-        T v = s0 + w * (s1 - s0);             // torch.lerp(y1, y2, ramp)
-        if (ignore_gain) v /= b0[gk] + w * (b1[gk] - b0[gk]);
-        y[u * Tlen + t0 + i] = v;
-    }
-}
-
-// The same filters with the taps AND the samples blocked by four: a thread owns four consecutive output samples and a
-// contiguous range of 4-tap blocks; with the taps stored reversed (br[kk] = b[M - kk]) a block needs the eight samples
-// xs[4 (l + m) .. + 7] -- two aligned 16-byte reads, one of them carried over from the previous block -- and two
-// 16-byte coefficient reads (broadcasts): 3 LDS reads per 32 multiply-adds (the kernel above: 6 per 8, which bound it).
-// The tap ranges of the 256 / ceil(P / 4) thread groups meet in LDS in a fixed order (deterministic).
-template <typename T>
-__global__ __launch_bounds__(256) void zerodf_fwd_blocked_kernel(const T* __restrict__ x, const T* __restrict__ b, long Tlen, long N,
-                                                                 int M, int P, int z0, int ignore_gain, T* __restrict__ y)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int NB = (M + 4) / 4;               // 4-tap blocks: ceil((M + 1) / 4)
-    const int nt = (P + 3) / 4;               // threads per group (four samples each)
-    const int G = 256 / nt;                   // tap-range groups
-    const int PP = nt * 4;
-    T* br0 = reinterpret_cast<T*>(smem_raw);  // [4 NB] reversed taps of frame n, zero-padded
-    T* br1 = br0 + 4 * NB;                    // [4 NB] ... of frame n + 1
-    T* xs = br1 + 4 * NB;                     // [PP + 4 NB + 4]: x[t0 - M + z0 ..], zero beyond the frame's stretch
-    T* part = xs + (PP + 4 * NB + 4);         // [G][2][PP]
-    const long f = blockIdx.x;
-    const long u = f / N, n = f - u * N;
-    const long n1 = n + 1 < N ? n + 1 : N - 1;
-    const T* r0 = b + (u * N + n) * (M + 1);
-    const T* r1 = b + (u * N + n1) * (M + 1);
-    // (four independent loads per round: a load -> store loop waits out one round trip to memory per element)
-    const long t0 = n * P;
-    const T* xu = x + u * Tlen;
-    for (int kb = threadIdx.x; kb < 4 * NB; kb += 4 * blockDim.x) {
-        T v0[4], v1[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int kk = kb + q * blockDim.x;
-            const bool ok = kk <= M;
-            v0[q] = ok ? r0[M - (ok ? kk : M)] : T(0);
-            v1[q] = ok ? r1[M - (ok ? kk : M)] : T(0);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int kk = kb + q * blockDim.x;
-            if (kk < 4 * NB) {
-                br0[kk] = v0[q];
-                br1[kk] = v1[q];
-            }
-        }
-    }
-    for (int ib = threadIdx.x; ib < PP + 4 * NB + 4; ib += 4 * blockDim.x) {
-        T v[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int i = ib + q * blockDim.x;
-            const long sidx = t0 - M + z0 + i;
-            const bool ok = i < P + M && sidx >= 0 && sidx < Tlen;
-            v[q] = ok ? xu[ok ? sidx : 0] : T(0);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int i = ib + q * blockDim.x;
-            if (i < PP + 4 * NB + 4) xs[i] = v[q];
-        }
-    }
-    __syncthreads();
-    const int g = threadIdx.x / nt, l = threadIdx.x - g * nt;
-    if (g < G) {
-        const int per = (NB + G - 1) / G;
-        const int m0 = g * per, m1 = (m0 + per < NB) ? m0 + per : NB;
-        T a0[4] = {T(0), T(0), T(0), T(0)}, a1[4] = {T(0), T(0), T(0), T(0)};
-        T wv[8];
-        if (m0 < m1) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) wv[q] = xs[4 * (l + m0) + q];
-        }
-        for (int m = m0; m < m1; ++m) {
-            T c0[4], c1[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                wv[4 + q] = xs[4 * (l + m + 1) + q];
-                c0[q] = br0[4 * m + q];
-                c1[q] = br1[4 * m + q];
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    a0[q] += c0[r] * wv[q + r];
-                    a1[q] += c1[r] * wv[q + r];
-                }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) wv[q] = wv[4 + q];
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            part[(g * 2 + 0) * PP + 4 * l + q] = a0[q];
-            part[(g * 2 + 1) * PP + 4 * l + q] = a1[q];
-        }
-    }
-    __syncthreads();
-    const int gk = z0 == M ? M : 0;
-    const T g0 = r0[gk], g1 = r1[gk];
-    for (int i = threadIdx.x; i < P; i += blockDim.x) {
-        T s0 = 0, s1 = 0;
-        for (int q = 0; q < G; ++q) {
-            s0 += part[(q * 2 + 0) * PP + i];
-            s1 += part[(q * 2 + 1) * PP + i];
-        }
-        const T w = (T)i / (T)P;
-        T v = s0 + w * (s1 - s0);             // torch.lerp(y1, y2, ramp)
-        if (ignore_gain) v /= g0 + w * (g1 - g0);
-        y[u * Tlen + t0 + i] = v;
-    }
-}
-
-// Round 3: several frames per workgroup, every tap of a sample block in ONE thread, float32 on packed multiply-adds.
-// The blocked kernel above spends most of a launch around its inner loop (one frame per workgroup: two barriers, the
-// partial sums of twelve tap ranges through LDS, ~5 blocks of taps per thread).  Here a workgroup takes `nf` consecutive
-// frames of one utterance: a thread owns four consecutive output samples of one frame and (G = 1) all of its taps, so the
-// sums stay in registers; the rows of frame n and n + 1 are stored INTERLEAVED in LDS -- (b_n[k], b_n+1[k]) as one 8-byte
-// pair -- so that the two filters of the interpolation are the two halves of one v_pk_fma_f32 whose other factor is the
-// sample, broadcast by op_sel: 16 packed instructions per 4 taps x 4 samples x 2 rows instead of 32 v_fma_f32 (the packed
-// form is the only one that issues two float32 multiply-adds per lane in 4 cycles: DESIGN 3.2).  Long filters (the
-// 2000-tap impulse responses of the single-stage form) split the taps over G groups of threads that meet in LDS in a fixed
-// order.  Optional epilogue for the Taylor stages of the multi-stage form: y = scale * filter(x), ysum = acc + y.
-// NaN containment: taps beyond M (padding of the last block of four) are skipped, not multiplied by zero.
-typedef float zd_v2f __attribute__((ext_vector_type(2)));
-typedef float zd_v4f __attribute__((ext_vector_type(4)));
-typedef float zd_v4f_u __attribute__((ext_vector_type(4), aligned(4)));
-typedef double zd_v2d __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void zd_fma_lo(zd_v2f& acc, zd_v2f c, zd_v2f w)   // acc += c * w.x (both halves)
-{
-    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(acc) : "v"(c), "v"(w));
-}
-__device__ __forceinline__ void zd_fma_hi(zd_v2f& acc, zd_v2f c, zd_v2f w)   // acc += c * w.y (both halves)
-{
-    // the odd sample as the LOW half of its own pair (a move the compiler shares between the uses of a ring slot), then the
-    // low-half broadcast of zd_fma_lo: the one-instruction form "op_sel:[0,1,0] op_sel_hi:[1,1,1]" has a set op_sel bit -- its
-    // low result reads a high source half -- and no shipped kernel executes that class (pk_math.h, DSA_PK_CROSSED)
-    const zd_v2f wh = __builtin_shufflevector(w, w, 1, 1);
-    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(acc) : "v"(c), "v"(wh));
-}
-// two adjacent pairs from a 16-byte aligned LDS address (float: one ds_read_b128); `both` false: only the first is wanted
-__device__ __forceinline__ void zd_load2(const zd_v2f* p, zd_v2f& a, zd_v2f& b, bool both)
-{
-    if (both) {
-        const zd_v4f v = *reinterpret_cast<const zd_v4f*>(p);
-        a = zd_v2f{v.x, v.y};
-        b = zd_v2f{v.z, v.w};
-    } else {
-        a = p[0];
-    }
-}
-__device__ __forceinline__ void zd_load2(const zd_v2d* p, zd_v2d& a, zd_v2d& b, bool both)
-{
-    a = p[0];
-    if (both) b = p[1];
-}
-__device__ __forceinline__ void zd_fma2(zd_v2f& acc, zd_v2f c, zd_v2f w)     // acc += c * w, half by half
-{
-    asm("v_pk_fma_f32 %0, %1, %2, %0" : "+v"(acc) : "v"(c), "v"(w));
-}
-__device__ __forceinline__ void zd_fma2(zd_v2d& acc, zd_v2d c, zd_v2d w) { acc += c * w; }
-__device__ __forceinline__ void zd_fma_lo(zd_v2d& acc, zd_v2d c, zd_v2d w) { acc += c * w.x; }
-__device__ __forceinline__ void zd_fma_hi(zd_v2d& acc, zd_v2d c, zd_v2d w) { acc += c * w.y; }
-
-template <typename T, int S>
-__global__ __launch_bounds__(256) DSA_PK_TARGET void zerodf_fwd_rows_kernel(const T* __restrict__ x, const T* __restrict__ b, long Tlen, long N,
-                                                              int M, int P, int z0, int ignore_gain, int nf, int G, T scale,
-                                                              const T* acc, T* __restrict__ y, T* ysum)
-{
-    using V2 = T __attribute__((ext_vector_type(2)));
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int NB = (M + 4) / 4;                 // 4-tap blocks
-    const int nt = P / S;                       // threads per (frame, tap group): S consecutive samples each
-    V2* brp = reinterpret_cast<V2*>(smem_raw);  // [nf][4 NB]: (b[n][M - kk], b[n + 1][M - kk]), zero beyond kk = M
-    T* xs = reinterpret_cast<T*>(brp + (size_t)nf * 4 * NB);   // [nf P + 4 NB + 8]: x[t0 - M + z0 ..]
-    V2* part = reinterpret_cast<V2*>(xs + ((size_t)nf * P + 4 * NB + 8));   // [nf][G][P] when G > 1
-    const long chunks = (N + nf - 1) / nf;
-    const long u = blockIdx.x / chunks, n0 = (blockIdx.x - u * chunks) * nf;
-    const int frames = (int)((N - n0 < nf) ? N - n0 : nf);
-    const T* bu = b + u * N * (M + 1);
-    // (all loads of a batch first, then the stores: a load -> store loop waits out one trip to memory per element)
-    for (int kk = threadIdx.x; kk < 4 * NB; kk += blockDim.x) {   // a thread walks down one tap: every row is read once
-        const bool tap = kk <= M;
-        const T* col = bu + (M - (tap ? kk : M));
-        T cv[17];
-#pragma unroll
-        for (int p = 0; p <= 16; ++p) {
-            const long row = n0 + p < N ? n0 + p : N - 1;
-            cv[p] = (tap && p <= frames) ? col[row * (M + 1)] : T(0);
-        }
-#pragma unroll
-        for (int p = 0; p < 16; ++p)
-            if (p < frames) brp[(size_t)p * 4 * NB + kk] = V2{cv[p], cv[p + 1]};
-    }
-    const long t0 = n0 * P;
-    const T* xu = x + u * Tlen;
-    const int xlen = frames * P + 4 * NB + 8;
-    for (int i0 = threadIdx.x; i0 < xlen; i0 += 8 * blockDim.x) {
-        T xv[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const long sidx = t0 - M + z0 + i0 + q * (int)blockDim.x;
-            xv[q] = (i0 + q * (int)blockDim.x < xlen && sidx >= 0 && sidx < Tlen) ? xu[sidx] : T(0);
-        }
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-            if (i0 + q * (int)blockDim.x < xlen) xs[i0 + q * (int)blockDim.x] = xv[q];
-    }
-    __syncthreads();
-    const int grp = threadIdx.x / nt, l = threadIdx.x - grp * nt;   // grp = fr * G + g
-    const int fr = grp / G, g = grp - fr * G;
-    const bool active = fr < frames;
-    V2 a[S];
-#pragma unroll
-    for (int q = 0; q < S; ++q) a[q] = V2{0, 0};
-    if (active) {
-        // (host: G divides the number of full blocks, so the loop count is the same for every thread of the launch)
-        const int rem = (M + 1) & 3;                       // taps in the last block when it is a partial one
-        const int per = (rem ? NB - 1 : NB) / G;
-        const int m0 = g * per, m_full = m0 + per;
-        const int m1 = (rem != 0 && g == G - 1) ? m_full + 1 : m_full;
-        const V2* cp = brp + (size_t)fr * 4 * NB;
-        const T* xf = xs + fr * P + S * l;
-        // A block of four taps on S samples reads the S + 4 samples xf[4 m .. 4 m + S + 3]: NP = (S + 4) / 2 pairs kept in a
-        // ring of NP registers pairs that advances by two pairs per block -- after NP / 2 blocks (a trip, unrolled) every pair
-        // is back in its slot, so nothing is copied; per block two 16-byte tap reads (broadcasts) and one 16-byte sample read
-        // feed 4 S packed multiply-adds (S = 8: the LDS pipe, which the S = 4 form loads as much as the vector unit, idles).
-        constexpr int NP = (S + 4) / 2, TRIP = NP / 2;
-        V2 R[NP];
-#pragma unroll
-        for (int i = 0; i < NP - 2; ++i) R[i] = *reinterpret_cast<const V2*>(xf + 4 * m0 + 2 * i);
-        auto block = [&](int m, int b) __attribute__((always_inline)) {   // b = (m - m0) % TRIP: the ring's phase
-            V2 c[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) c[r] = cp[4 * m + r];
-            zd_load2(reinterpret_cast<const V2*>(xf + 4 * m + 2 * (NP - 2)), R[(2 * b + NP - 2) % NP], R[(2 * b + NP - 1) % NP], true);
-#pragma unroll
-            for (int q = 0; q < S; ++q)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if ((q + r) & 1) zd_fma_hi(a[q], c[r], R[(2 * b + ((q + r) >> 1)) % NP]);
-                    else zd_fma_lo(a[q], c[r], R[(2 * b + ((q + r) >> 1)) % NP]);
-                }
-        };
-        int j = 0;
-        for (; j + TRIP <= per; j += TRIP) {   // (uniform trip count: a scalar loop)
-#pragma unroll
-            for (int b = 0; b < TRIP; ++b) block(m0 + j + b, b);
-        }
-        int tail_b = 0;   // blocks left after the last whole trip (the ring's phase restarts at 0 there)
-#pragma unroll
-        for (int b = 0; b < TRIP - 1; ++b)
-            if (j + b < per) {
-                block(m0 + j + b, b);
-                tail_b = b + 1;
-            }
-        if (m_full < m1) {   // the partial last block: only its real taps
-            const int m = m_full;
-            // bring the ring back to phase 0 (at most once per thread)
-            V2 Wn[NP];
-#pragma unroll
-            for (int i = 0; i < NP; ++i) Wn[i] = tail_b == 0 ? R[i] : (tail_b == 1 ? R[(i + 2) % NP] : R[(i + 4) % NP]);
-            Wn[NP - 2] = *reinterpret_cast<const V2*>(xf + 4 * m + 2 * (NP - 2));
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-                if (r < rem) {
-                    const V2 cr = cp[4 * m + r];
-#pragma unroll
-                    for (int q = 0; q < S; ++q) {
-                        if ((q + r) & 1) zd_fma_hi(a[q], cr, Wn[(q + r) >> 1]);
-                        else zd_fma_lo(a[q], cr, Wn[(q + r) >> 1]);
-                    }
-                }
-        }
-    }
-    if (G > 1) {
-        if (active) {
-#pragma unroll
-            for (int q = 0; q < S; ++q) part[((size_t)fr * G + g) * P + S * l + q] = a[q];
-        }
-        __syncthreads();
-        if (active && g == 0) {
-#pragma unroll
-            for (int q = 0; q < S; ++q) {
-                V2 sacc = part[((size_t)fr * G) * P + S * l + q];
-                for (int gg = 1; gg < G; ++gg) sacc += part[((size_t)fr * G + gg) * P + S * l + q];
-                a[q] = sacc;
-            }
-        }
-    }
-    if (active && g == 0) {
-        const int gk = z0 == M ? M : 0;
-        const V2 gain = brp[(size_t)fr * 4 * NB + (M - gk)];
-        const long o = u * Tlen + t0 + (long)fr * P + S * l;
-        T v[S];
-#pragma unroll
-        for (int q = 0; q < S; ++q) {
-            const T wt = (T)(S * l + q) / (T)P;
-            T r = a[q].x + wt * (a[q].y - a[q].x);          // torch.lerp(y1, y2, ramp)
-            if (ignore_gain) r /= gain.x + wt * (gain.y - gain.x);
-            v[q] = r * scale;
-        }
-        if (y) {
-#pragma unroll
-            for (int q = 0; q < S; ++q) y[o + q] = v[q];
-        }
-        if (ysum) {
-#pragma unroll
-            for (int q = 0; q < S; ++q) ysum[o + q] = acc[o + q] + v[q];
-        }
-    }
-}
-
-// nf frames x G tap groups of P / S threads per 256-thread workgroup within 64 KB of LDS; false: shape not covered
-static bool zerodf_rows_plan(int M, int P, size_t elt, int& S, int& nf, int& G, size_t& lds)
-{
-    if (P % 4 != 0 || P / 4 > 256 || M < 16) return false;
-    S = 4;   // (S = 8 -- half the LDS reads per multiply-add, 160 of 256 threads busy at P = 80 -- measured the same: 1.50 vs 1.46 ms)
-    const int NB = (M + 4) / 4, nt = P / S, groups = 256 / nt;
-    const int nb_full = ((M + 1) & 3) ? NB - 1 : NB;
-    for (nf = groups < 16 ? groups : 16; nf >= 1; --nf) {
-        G = groups / nf;
-        while (G > 1 && nb_full % G != 0) --G;   // equal tap ranges: one loop count for the whole launch
-        lds = (size_t)nf * 4 * NB * 2 * elt + ((size_t)nf * P + 4 * NB + 8) * elt + (G > 1 ? (size_t)nf * G * P * 2 * elt : 0);
-        lds = (lds + 15) & ~(size_t)15;
-        if (lds <= 64 * 1024) return true;
-    }
-    return false;
-}
-
-template <typename T>
-static int zerodf_launch_fwd(const void* x, const void* b, int64_t B, int64_t Tlen, int64_t N, int M, int P, int z0, int ig,
-                             void* y, hipStream_t st, double scale = 1.0, const void* acc = nullptr, void* ysum = nullptr)
-{
-    {
-        int S, nf, G;
-        size_t lds_r;
-        if (zerodf_rows_plan(M, P, sizeof(T), S, nf, G, lds_r)) {
-            const long chunks = (N + nf - 1) / nf;
-            // (the kernel is written for S = 4 or 8 samples per thread; 8 measured the same at P = 80 and is not instantiated)
-            hipLaunchKernelGGL((zerodf_fwd_rows_kernel<T, 4>), dim3((unsigned)(B * chunks)), dim3(256), lds_r, st, (const T*)x,
-                               (const T*)b, (long)Tlen, (long)N, M, P, z0, ig, nf, G, (T)scale, (const T*)acc, (T*)y, (T*)ysum);
-            return check_launch("zerodf_rows_fwd");
-        }
-        if (ysum || scale != 1.0) return fail(DSA_ERR_UNSUPPORTED, "zerodf: the scaled / accumulating form needs P % 4 == 0 and M >= 16%s");
-    }
-    {   // long filters: taps and samples blocked by four (the sliced kernel below takes what does not fit)
-        const int NB = (M + 4) / 4, nt = (P + 3) / 4;
-        const size_t lds_b = sizeof(T) * ((size_t)8 * NB + (size_t)(4 * nt + 4 * NB + 4) + (size_t)(256 / (nt > 0 ? nt : 1)) * 2 * 4 * nt);
-        if (M >= 64 && P >= 4 && P <= 128 && lds_b <= 64 * 1024) {
-            hipLaunchKernelGGL((zerodf_fwd_blocked_kernel<T>), dim3((unsigned)(B * N)), dim3(256), lds_b, st, (const T*)x, (const T*)b,
-                               (long)Tlen, (long)N, M, P, z0, ig, (T*)y);
-            return check_launch("zerodf_blocked_fwd");
-        }
-    }
-    const size_t lds_s = sizeof(T) * (2 * (size_t)(M + 1) + 128 + M + 8 * 2 * 128);
-    if (M >= 64 && P <= 128 && lds_s <= 64 * 1024) {
-        hipLaunchKernelGGL((zerodf_fwd_sliced_kernel<T>), dim3((unsigned)(B * N)), dim3(256), lds_s, st, (const T*)x, (const T*)b,
-                           (long)Tlen, (long)N, M, P, z0, ig, (T*)y);
-        return check_launch("zerodf_sliced_fwd");
-    }
-    const size_t lds = sizeof(T) * (2 * (size_t)(M + 1) + P + M);
-    if (lds > 64 * 1024) return fail(DSA_ERR_UNSUPPORTED, "zerodf: filter too long for LDS%s");
-    hipLaunchKernelGGL((zerodf_fwd_kernel<T>), dim3((unsigned)(B * N)), dim3(P >= 192 ? 256 : (P >= 96 ? 128 : 64)), lds, st,
-                       (const T*)x, (const T*)b, (long)Tlen, (long)N, M, P, z0, ig, (T*)y);
-    return check_launch("zerodf_fwd");
-}
-
-// Round 3: the backward of the time-variant FIR on the forward's pattern (rows of frames n and n + 1 interleaved as pairs,
-// several frames per workgroup, four consecutive samples / taps per thread).  Without ignore_gain:
-//   gx[s] = sum_k gy[t] h_t[k],  t = s - z0 + k  =  sum_t (b[n(t)][k], b[n(t) + 1][k]) . ((1 - w_t) gy[t], w_t gy[t])
-// -- the dot product of two pairs, i.e. ONE packed multiply-add into a pair accumulator whose halves are added at the end.
-// A thread owns four consecutive s and walks t in blocks of four that never straddle a frame (P % 4 == 0; z0 is rounded up
-// to a multiple of 4 by shifting the taps): block m needs the tap pairs 4 m - 3 .. 4 m + 3 of ITS frame's row (stored from
-// position 3, so the window starts 16-byte aligned) and the four weighted cotangent pairs.  Lanes cross frame boundaries at
-// different m, so the window is re-read every block (the kernel is bound by LDS reads, ~1.4 x the multiply-adds).
-// The old kernel: a thread per sample over all taps with two row reads from memory per tap.
-template <typename T, int S>
-__global__ __launch_bounds__(256) DSA_PK_TARGET void zerodf_bwd_x_rows_kernel(const T* __restrict__ gy, const T* __restrict__ b, long Tlen, long N,
-                                                                int M, int P, int z0, int nf, int nrows, int ldb, int accumulate,
-                                                                T scale, const T* add, T* gx)
-{
-    // gx = (accumulate ? gx : (add ? add : 0)) + scale * (the sum): `add` / `scale` serve the Taylor stages of the multi-stage
-    // MLSA filter's backward (G_{i-1} = gy + F^T G_i / i)
-    // (`b` may point at a run of M + 1 taps inside rows of ldb coefficients -- long filters are handled as a sum of
-    // 200-tap pieces: piece c has z0 - c KC as its (possibly negative) zeroth index and accumulates into gx)
-    using V2 = T __attribute__((ext_vector_type(2)));
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int dz = (4 - (((z0 % 4) + 4) & 3)) & 3, Mp = M + dz, z0p = z0 + dz;
-    const int NBt = (Mp + S - 1) / 4 + 1;              // blocks of four t per block of S output samples
-    const int RW = (Mp + S + 6 + 3) & ~3;              // pairs per row: tap k' at position k' + S - 1, zeros around
-    const int nt = P / S;
-    V2* rows = reinterpret_cast<V2*>(smem_raw);        // [nrows][RW]
-    V2* up = rows + (size_t)nrows * RW;                // [nf P + 4 NBt]: ((1 - w) gy, w gy) of t = Tstart + j
-    const long chunks = (N + nf - 1) / nf;
-    const long u = blockIdx.x / chunks, n0 = (blockIdx.x - u * chunks) * nf;
-    const int frames = (int)((N - n0 < nf) ? N - n0 : nf);
-    const long Tstart = n0 * P - z0p;                  // t of up[0]
-    // floor division by P for a possibly negative Tstart
-    const long nlo = Tstart >= 0 ? Tstart / P : -((-Tstart + P - 1) / P);
-    const int r0 = (int)(Tstart - nlo * P);            // in [0, P)
-    const T* bu = b + u * N * ldb;
-    for (int pos = threadIdx.x; pos < RW; pos += blockDim.x) {
-        const int k = pos - (S - 1) - dz;
-        const bool tap = k >= 0 && k <= M;
-        T cv[25];
-#pragma unroll
-        for (int i = 0; i <= 24; ++i) {
-            const long nn = nlo + i;
-            const long row = nn < 0 ? 0 : (nn < N ? nn : N - 1);
-            cv[i] = (tap && i <= nrows) ? bu[row * ldb + (tap ? k : 0)] : T(0);
-        }
-#pragma unroll
-        for (int i = 0; i < 24; ++i)
-            if (i < nrows) rows[(size_t)i * RW + pos] = V2{cv[i], cv[i + 1]};
-    }
-    const int ulen = frames * P + 4 * NBt;
-    const T* gyu = gy + u * Tlen;
-    for (int j0 = threadIdx.x; j0 < ulen; j0 += 8 * blockDim.x) {
-        T gv[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int j = j0 + q * (int)blockDim.x;
-            const long t = Tstart + j;
-            gv[q] = (j < ulen && t >= 0 && t < Tlen) ? gyu[t] : T(0);
-        }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int j = j0 + q * (int)blockDim.x;
-            if (j < ulen) {
-                const int ph = (r0 + j) % P;
-                const T w = (T)ph / (T)P;
-                up[j] = V2{gv[q] - w * gv[q], w * gv[q]};
-            }
-        }
-    }
-    __syncthreads();
-    const int fr = threadIdx.x / nt, l = threadIdx.x - fr * nt;
-    if (fr >= frames) return;
-    const int jb0 = fr * P + S * l;                    // this thread's samples are s = n0 P + jb0 + q; block m reads up[jb0 + 4 m ..]
-    int ph = (r0 + jb0) % P;
-    const V2* rp = rows + (size_t)((r0 + jb0) / P) * RW;
-    const V2* upp = up + jb0;
-    V2 a[S];
-#pragma unroll
-    for (int q = 0; q < S; ++q) a[q] = V2{0, 0};
-    for (int m = 0; m < NBt; ++m) {                    // (uniform trip count: a scalar loop)
-        // (two pairs per 16-byte aligned read: the rows and `up` start 32-byte aligned and advance by four pairs a block;
-        // left as pair reads the compiler emits ds_read2_b64, which moves half as many bytes per LDS cycle as ds_read_b128)
-        V2 w[S + 4], uu[4];
-#pragma unroll
-        for (int i = 0; i < S + 3; i += 2) zd_load2(rp + 4 * m + i, w[i], w[i + 1], i + 1 < S + 3);
-#pragma unroll
-        for (int i = 0; i < 4; i += 2) zd_load2(upp + 4 * m + i, uu[i], uu[i + 1], true);
-#pragma unroll
-        for (int q = 0; q < S; ++q)
-#pragma unroll
-            for (int jt = 0; jt < 4; ++jt) zd_fma2(a[q], w[jt - q + S - 1], uu[jt]);
-        ph += 4;
-        if (ph >= P) {
-            ph -= P;
-            rp += RW;
-        }
-    }
-    T* dst = gx + u * Tlen + n0 * P + jb0;
-#pragma unroll
-    for (int q = 0; q < S; ++q) {
-        const T base = accumulate ? dst[q] : (add ? add[u * Tlen + n0 * P + jb0 + q] : T(0));
-        dst[q] = base + scale * (a[q].x + a[q].y);
-    }
-}
-
-// gb[n][k] = sum over the samples i of frames n - 1 and n of gs[i] x[t - k + z0], gs = the frame weight of b[n] in h_t times gy
-// (frame n: 1 - w, frame n - 1: w; the last frame also takes its own w part).  A thread owns four consecutive taps and walks
-// the 2 P samples in blocks of four on a sliding window of seven x values (one aligned 16-byte read of x and one of gs per 16
-// multiply-adds); 256 / ceil((M + 1) / 4) frames per workgroup.  The old kernel: a thread per tap, two LDS reads per
-// multiply-add, one frame per workgroup.
-template <typename T>
-__global__ __launch_bounds__(256) void zerodf_bwd_b_rows_kernel(const T* __restrict__ gy, const T* __restrict__ x, long Tlen, long N,
-                                                                long BN, int M, int P, int z0, int nfw, int ldb, T scale, int accumulate,
-                                                                T* __restrict__ gb)
-{
-    using V4 = T __attribute__((ext_vector_type(4)));
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int NBk = (M + 4) / 4;                       // 4-tap blocks
-    const int o = (3 - M) & 3;                         // shift that aligns the x window: (M - k0 - 3 + o) % 4 == 0
-    const int XL = (2 * P + M + 8 + 3) & ~3;           // floats of x per frame
-    T* gs = reinterpret_cast<T*>(smem_raw);            // [nfw][2 P]
-    T* xs = gs + (size_t)nfw * 2 * P;                  // [nfw][XL]: xs[j + o] = x[(n - 1) P - M + z0 + j]
-    const long f0 = (long)blockIdx.x * nfw;
-    for (int fw = 0; fw < nfw; ++fw) {                 // (frame indices per frame, not per element: 64-bit divisions)
-        const long f = f0 + fw;
-        const bool fok = f < BN;
-        const long u = fok ? f / N : 0, n = fok ? f - u * N : 0;
-        const T* gyu = gy + u * Tlen;
-        const T* xu = x + u * Tlen;
-        for (int i = threadIdx.x; i < 2 * P; i += blockDim.x) {
-            const long t = (n - 1) * P + i;
-            T v = 0;
-            if (fok && t >= 0) {
-                // frame of t: n - 1 for i < P, n otherwise; the row b[n] enters h_t with 1 - w in its own frame, with w in the
-                // frame before, and the clamped last frame takes both
-                const int ph = i < P ? i : i - P;
-                const T w = (T)ph / (T)P;
-                const T wt = i < P ? w : ((n == N - 1) ? T(1) : T(1) - w);
-                v = wt * gyu[t];
-            }
-            gs[(size_t)fw * 2 * P + i] = v;
-        }
-        for (int jj = threadIdx.x; jj < XL; jj += blockDim.x) {
-            const int j = jj - o;
-            const long sidx = (n - 1) * P - M + z0 + j;
-            xs[(size_t)fw * XL + jj] = (fok && j >= 0 && sidx >= 0 && sidx < Tlen) ? xu[sidx] : T(0);
-        }
-    }
-    __syncthreads();
-    const int fw = threadIdx.x / NBk, kb = threadIdx.x - fw * NBk;
-    const long f = f0 + fw;
-    if (fw >= nfw || f >= BN) return;
-    const int k0 = 4 * kb;
-    // acc[q] (tap k0 + q) += gs[i + j] xs[i + j + M - k0 - q]: window xw[c] = xs[i + e + c], e = M - k0 - 3, c = j - q + 3
-    const T* gp = gs + (size_t)fw * 2 * P;
-    const T* xp = xs + (size_t)fw * XL + (M - k0 - 3 + o);   // 16-byte aligned
-    T acc[4] = {T(0), T(0), T(0), T(0)};
-    V4 lo = *reinterpret_cast<const V4*>(xp);
-    for (int i = 0; i < 2 * P; i += 4) {
-        const V4 hi = *reinterpret_cast<const V4*>(xp + i + 4);
-        const V4 gv = *reinterpret_cast<const V4*>(gp + i);
-        const T xw[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[q] += gv[j] * xw[j - q + 3];
-        lo = hi;
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-        if (k0 + q <= M) gb[f * ldb + k0 + q] = (accumulate ? gb[f * ldb + k0 + q] : T(0)) + scale * acc[q];
-}
-
-template <typename T>
-static int zerodf_launch_bwd(const void* gy, const void* x, const void* b, const void* y, int64_t B, int64_t Tlen, int64_t N, int M,
-                             int P, int z0, int ig, void* gx, void* gb, hipStream_t st, double scale = 1.0, const void* gx_add = nullptr,
-                             bool gb_accumulate = false)
-{
-    const bool plain = scale == 1.0 && gx_add == nullptr && !gb_accumulate;
-    const bool rows_ok = !ig && P % 4 == 0 && P / 4 <= 64 && M >= 16;
-    if (rows_ok) {
-        // filters of more than ~200 taps as a sum of pieces (the kernels keep one piece's rows of a few frames in LDS): piece c
-        // = taps [c KC, c KC + Mc], zeroth index z0 - c KC; gx accumulates over the pieces, gb's columns are disjoint
-        const int npieces = (M + 1 + 199) / 200;
-        const int KC = (((M + 1 + npieces - 1) / npieces) + 3) & ~3;
-        // feasibility of BOTH kernels for EVERY piece is decided before anything is launched (round 3 launched gx first and could
-        // then find that gb's rows did not fit LDS: P = 252 / 256 in float32, P >= 124 in float64 -- a half-written backward)
-        struct PiecePlan { int Mc, z0c, nf, nrows, nfw; size_t lds_x, lds_b; };
-        PiecePlan plan[64];
-        bool ok = npieces <= 64;
-        int np_used = 0;
-        constexpr int S = 4;   // (eight samples per thread -- 2/3 of the LDS reads per multiply-add, 160 of 256 threads at P = 80 -- measured slower)
-        for (int c = 0; c < npieces && ok; ++c) {
-            PiecePlan& pl = plan[c];
-            pl.Mc = ((M + 1 - c * KC) < KC ? (M + 1 - c * KC) : KC) - 1;
-            pl.z0c = z0 - c * KC;
-            if (pl.Mc < 0) break;
-            np_used = c + 1;
-            pl.nf = pl.nrows = pl.nfw = 0;
-            pl.lds_x = pl.lds_b = 0;
-            if (gx) {
-                const int dz = (4 - (((pl.z0c % 4) + 4) & 3)) & 3, Mp = pl.Mc + dz, NBt = (Mp + S - 1) / 4 + 1, RW = (Mp + S + 6 + 3) & ~3, nt = P / S;
-                int nf = 256 / nt;
-                if (nf > 16) nf = 16;
-                for (; nf >= 1; --nf) {
-                    pl.nrows = nf + (Mp + P - 1) / P + 2;      // frames the t range of nf output frames can touch
-                    pl.lds_x = sizeof(T) * 2 * ((size_t)pl.nrows * RW + (size_t)nf * P + 4 * NBt);
-                    if (pl.nrows <= 24 && pl.lds_x <= 64 * 1024) break;
-                }
-                if (nf < 1) { ok = false; break; }
-                pl.nf = nf;
-            }
-            if (gb) {
-                const int NBk = (pl.Mc + 4) / 4;
-                const int XL = (2 * P + pl.Mc + 8 + 3) & ~3;
-                int nfw = 256 / NBk;
-                if (nfw > 16) nfw = 16;
-                for (; nfw >= 1; --nfw) {                      // fewer frames per workgroup until their rows fit LDS
-                    pl.lds_b = sizeof(T) * (size_t)nfw * (2 * P + XL);
-                    if (pl.lds_b <= 64 * 1024) break;
-                }
-                if (nfw < 1) { ok = false; break; }
-                pl.nfw = nfw;
-            }
-        }
-        for (int c = 0; c < np_used && ok; ++c) {
-            const PiecePlan& pl = plan[c];
-            if (gx) {
-                const long chunks = (N + pl.nf - 1) / pl.nf;
-                hipLaunchKernelGGL((zerodf_bwd_x_rows_kernel<T, S>), dim3((unsigned)(B * chunks)), dim3(256), pl.lds_x, st, (const T*)gy,
-                                   (const T*)b + c * KC, (long)Tlen, (long)N, pl.Mc, P, pl.z0c, pl.nf, pl.nrows, M + 1, c > 0 ? 1 : 0, (T)scale,
-                                   (const T*)gx_add, (T*)gx);
-            }
-            if (gb) {
-                hipLaunchKernelGGL((zerodf_bwd_b_rows_kernel<T>), dim3((unsigned)((B * N + pl.nfw - 1) / pl.nfw)), dim3(256), pl.lds_b, st,
-                                   (const T*)gy, (const T*)x, (long)Tlen, (long)N, (long)(B * N), pl.Mc, P, pl.z0c, pl.nfw, M + 1, (T)scale,
-                                   gb_accumulate ? 1 : 0, (T*)gb + c * KC);
-            }
-        }
-        // (nothing was launched unless every piece of both kernels fits)
-        if (ok) return check_launch("zerodf_rows_bwd");
-    }
-    if (!plain) return fail(DSA_ERR_UNSUPPORTED, "zerodf_bwd: the scaled / accumulating form needs P % 4 == 0 and M >= 16%s");
-    if (gx) {
-        hipLaunchKernelGGL((zerodf_bwd_x_kernel<T>), dim3((unsigned)((B * Tlen + 255) / 256)), dim3(256), 0, st, (const T*)gy,
-                           (const T*)b, (long)B, (long)Tlen, (long)N, M, P, z0, ig, (T*)gx);
-    }
-    if (gb) {
-        const size_t lds = sizeof(T) * ((size_t)2 * P + 2 * P + M + 256);
-        if (lds > 64 * 1024) return fail(DSA_ERR_UNSUPPORTED, "zerodf_bwd: filter too long for LDS%s");
-        hipLaunchKernelGGL((zerodf_bwd_b_kernel<T>), dim3((unsigned)(B * N)), dim3(256), lds, st, (const T*)gy, (const T*)x,
-                           (const T*)b, (const T*)y, (long)Tlen, (long)N, M, P, z0, ig, (T*)gb);
-    }
-    return check_launch("zerodf_bwd");
-}
 
 // ---------------------------------------------------------------------------------------------
 // The spectrum arithmetic of one Newton step of MelGeneralizedCepstralAnalysis (mgcep.py:199-209), gamma not in {0, -1},
@@ -1353,242 +345,273 @@ static int mgcep_spectra_launch(const void* x, const void* b1, int64_t F, int K,
     return check_launch("mgcep_spectra");
 }
 
+// ---------------------------------------------------------------------------------------------
+// Generalized cepstral transformation in ONE launch (GeneralizedCepstrumToGeneralizedCepstrum._forward, mgc2mgc.py:333-361):
+//   c01 = (0, c1[1:]) -> C1 = fft(c01, n) -> s = (1 + g1 C1)^(1/g1) (g1 = 0: exp C1) -> C2 = (|s|^g2 cos(g2 angle(s)) - 1) / g2
+//   (g2 = 0: log |s|) -> c02 = ifft(C2).real[: M2 + 1] -> c2 = (c1[0], 2 c02[1:]).
+// One workgroup per row, the n complex points in LDS; both transforms are the radix-2 LDS transform of lds_fft.h: c01 is real, so C1 is
+// Hermitian and C2 is real and even -- its inverse transform IS its forward transform / n, and only the real parts leave.
+// As separate launches (row transform -> five element-wise operators -> adjoint row transform, modules/mgc2mgc.py) the
+// 4096-point spectra of the MLSA filter's impulse responses went through memory seven times (profiles/r02_mlsa_single_stage_trace.txt:
+// 7.2 of the 8.3 ms of the single-stage mode).  Forward only (the module composes the differentiable operators when a gradient is
+// wanted).
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void gc2gc_fused_kernel(const T* __restrict__ c1, int n_in, int out_order, T g1, T g2, int nfft,
+                                                         const T* __restrict__ tw, int flags, T* __restrict__ c2)
+{
+    // Both transforms act on REAL data (c01, and the real even C2), so each runs as a complex transform of HALF the length on
+    // the packed sequence z[n] = x[2n] + i x[2n+1], followed by the split  X[k] = (Z[k] + conj Z[H-k]) / 2 - i W^k (Z[k] - conj Z[H-k]) / 2
+    // (H = n / 2): half the butterflies and half the LDS traffic of the full-length version (2.59 -> see DESIGN ms per 51 200 rows
+    // of 4096 points).  LDS: re[H] | im[H] | cb[H + 1] (the mapped half spectrum, natural order).
+    extern __shared__ unsigned char smem_raw[];
+    const int H = nfft >> 1;
+    T* re = reinterpret_cast<T*>(smem_raw);
+    T* im = re + H;
+    T* cb = im + H;
+    const long f = blockIdx.x;
+    const T* row = c1 + f * n_in;
+    const int lgh = 30 - __clz(nfft);   // log2(H)
+    // flags: the per-row scalar steps mgc2mgc.py:217-300 wraps around the transformation, folded in (each was a pass over the
+    // row in memory): 1 gnorm(in_gamma) before, 2 ignorm(out_gamma) after, 4 tail times out_gamma, 8 zeroth coefficient * out_gamma + 1
+    T k0 = row[0], tin = T(1);
+    if (flags & 1) {   // gnorm.py:99-109
+        if (g1 == T(0)) k0 = dsa_exp(row[0]);
+        else {
+            const T z = T(1) + g1 * row[0];
+            k0 = dsa_pow(z, T(1) / g1);
+            tin = T(1) / z;
+        }
+    }
+    for (int n = threadIdx.x; n < H; n += blockDim.x) {   // fft(c01, n): longer rows are cropped, c01[0] = 0
+        const int i0 = 2 * n, i1 = 2 * n + 1;
+        re[n] = (i0 >= 1 && i0 < n_in) ? row[i0] * tin : T(0);
+        im[n] = i1 < n_in ? row[i1] * tin : T(0);
+    }
+    __syncthreads();
+    lds_fft_pow2(re, im, H, lgh, tw, 2);   // Z[k] at position brev(k)
+    constexpr T kPi = T(3.14159265358979323846);
+    auto gmap = [&](T cr, T ci) -> T {
+        T lmag, ang;   // log |s|, angle(s) (wrapped to (-pi, pi] as .angle() of the reference's polar(r, theta) is)
+        if (g1 == T(0)) {
+            lmag = cr;
+            ang = ci;
+        } else {
+            const T zr = T(1) + g1 * cr, zi = g1 * ci;
+            lmag = T(0.5) * dsa_log(zr * zr + zi * zi) / g1;
+            ang = atan2(zi, zr) / g1;
+        }
+        if (g2 == T(0)) return lmag;
+        ang -= T(2) * kPi * rint(ang / (T(2) * kPi));
+        return (dsa_exp(g2 * lmag) * cos(ang * g2) - T(1)) / g2;
+    };
+    // split into X[k], X[H - k] and map both (C2 is real and even: cb[k], k = 0 .. H, carries it all)
+    for (int k = threadIdx.x; k <= (H >> 1); k += blockDim.x) {
+        if (k == 0) {
+            const T zr = re[0], zi = im[0];
+            cb[0] = gmap(zr + zi, T(0));
+            cb[H] = gmap(zr - zi, T(0));
+        } else {
+            const int pa = fft_brev(k, lgh), pb = fft_brev(H - k, lgh);
+            const T ar = re[pa], ai = im[pa], br = re[pb], bi = -im[pb];          // A = Z[k], B = conj Z[H - k]
+            const T sr = T(0.5) * (ar + br), si = T(0.5) * (ai + bi), dr = T(0.5) * (ar - br), di = T(0.5) * (ai - bi);
+            const T wr = tw[2 * k], wi = tw[2 * k + 1];                            // W_n^k = (cos, -sin)(2 pi k / n)
+            const T pr = wr * dr - wi * di, pi_ = wr * di + wi * dr;              // W D
+            cb[k] = gmap(sr + pi_, si - pr);                                       // X[k]     = S - i W D
+            cb[H - k] = gmap(sr - pi_, -si - pr);                                  // X[H - k] = conj(S + i W D)
+        }
+    }
+    __syncthreads();
+    for (int m = threadIdx.x; m < H; m += blockDim.x) {   // pack the even sequence C2[0 .. n - 1]: C2[j] = cb[j <= H ? j : n - j]
+        const int j0 = 2 * m, j1 = 2 * m + 1;
+        re[m] = cb[j0 <= H ? j0 : nfft - j0];
+        im[m] = cb[j1 <= H ? j1 : nfft - j1];
+    }
+    __syncthreads();
+    lds_fft_pow2(re, im, H, lgh, tw, 2);
+    T* out = c2 + f * (long)(out_order + 1);
+    T sc = T(2) / T(nfft), o0 = k0;
+    if (flags & 2) {   // ignorm.py:99-109
+        if (g2 == T(0)) o0 = dsa_log(k0);
+        else {
+            const T zz = dsa_pow(k0, g2);
+            o0 = (zz - T(1)) / g2;
+            sc *= zz;
+        }
+    }
+    if (flags & 4) sc *= g2;
+    if (flags & 8) o0 = o0 * g2 + T(1);
+    for (int m = threadIdx.x; m <= out_order; m += blockDim.x) {
+        T v;
+        if (m == 0) {
+            v = o0;
+        } else {
+            const int n = m <= H ? m : nfft - m;   // the inverse transform of a real even spectrum is even
+            T y;                                   // Re of the length-n transform of C2 at index n
+            if (n == H) {
+                y = re[0] - im[0];
+            } else {
+                const int pa = fft_brev(n, lgh), pb = fft_brev(H - n, lgh);
+                const T ar = re[pa], ai = im[pa], br = re[pb], bi = -im[pb];
+                const T dr = T(0.5) * (ar - br), di = T(0.5) * (ai - bi);
+                y = T(0.5) * (ar + br) + tw[2 * n] * di + tw[2 * n + 1] * dr;
+            }
+            v = sc * y;
+        }
+        out[m] = v;
+    }
+}
+
+// Backward of gc2gc_fused_kernel (flags = 0) in ONE launch per row: gc1 from the row c1 and the cotangent g2 of c2.
+//   c2[0] = c1[0];  c2[m] = 2 c02[m],  c02 = Re ifft(C2),  C2[k] = f(X[k]) for the half spectrum k = 0 .. H of X = fft(c01).
+// Three half-length transforms in LDS: X is recomputed from c01; the cotangent of the even spectrum is a cosine transform of
+// g2, gcb[k] = (2 / n) w_k Re fft(g)[k] (w = 1 at k = 0, H, else 2: cb[k] is read for j = k and j = n - k); the element-wise
+// chain rule gives (gXr, gXi)[k]; and gc01[m] = sum_{k=0}^{H} gXr[k] cos(2 pi k m / n) - gXi[k] sin(2 pi k m / n) is the
+// unnormalised inverse real transform of the Hermitian spectrum Y (Y[0] = gXr[0], Y[H] = gXr[H], Y[k] = (gXr + i gXi)[k] / 2),
+// run as the conjugate of a forward half-length transform of Z[k] = E[k] + i O[k], E = (Y[k] + conj Y[H-k]) / 2,
+// O = conj(W)^k (Y[k] - conj Y[H-k]) / 2.  LDS: re[H] | im[H] | xr[H+1] | xi[H+1] | gcb[H+1].
+template <typename T>
+__global__ __launch_bounds__(256) void gc2gc_fused_bwd_kernel(const T* __restrict__ c1, const T* __restrict__ g2row, int n_in,
+                                                             int out_order, T g1, T g2, int nfft, const T* __restrict__ tw,
+                                                             T* __restrict__ gc1)
+{
+    extern __shared__ unsigned char smem_raw[];
+    const int H = nfft >> 1;
+    T* re = reinterpret_cast<T*>(smem_raw);
+    T* im = re + H;
+    T* xr = im + H;
+    T* xi = xr + (H + 1);
+    T* gcb = xi + (H + 1);
+    const long f = blockIdx.x;
+    const T* row = c1 + f * n_in;
+    const T* grow = g2row + f * (long)(out_order + 1);
+    const int lgh = 30 - __clz(nfft);
+    constexpr T kPi = T(3.14159265358979323846);
+    // half-length transform of a packed real sequence, then the split into the half spectrum (dr, di)[0 .. H]
+    auto split_to = [&](T* dr, T* di) {
+        for (int k = threadIdx.x; k <= (H >> 1); k += blockDim.x) {
+            if (k == 0) {
+                const T zr = re[0], zi = im[0];
+                dr[0] = zr + zi;
+                dr[H] = zr - zi;
+                if (di) {
+                    di[0] = T(0);
+                    di[H] = T(0);
+                }
+            } else {
+                const int pa = fft_brev(k, lgh), pb = fft_brev(H - k, lgh);
+                const T ar = re[pa], ai = im[pa], br = re[pb], bi = -im[pb];
+                const T sr = T(0.5) * (ar + br), si = T(0.5) * (ai + bi), dr_ = T(0.5) * (ar - br), di_ = T(0.5) * (ai - bi);
+                const T wr = tw[2 * k], wi = tw[2 * k + 1];
+                const T pr = wr * dr_ - wi * di_, pi_ = wr * di_ + wi * dr_;
+                dr[k] = sr + pi_;
+                dr[H - k] = sr - pi_;
+                if (di) {
+                    di[k] = si - pr;
+                    di[H - k] = -si - pr;
+                }
+            }
+        }
+    };
+    // ---- X = fft(c01) ----
+    for (int n = threadIdx.x; n < H; n += blockDim.x) {
+        const int i0 = 2 * n, i1 = 2 * n + 1;
+        re[n] = (i0 >= 1 && i0 < n_in) ? row[i0] : T(0);
+        im[n] = i1 < n_in ? row[i1] : T(0);
+    }
+    __syncthreads();
+    lds_fft_pow2(re, im, H, lgh, tw, 2);
+    split_to(xr, xi);
+    __syncthreads();
+    // ---- cosine transform of the cotangent: g[0] = 0, g[m] = g2[m] ----
+    for (int n = threadIdx.x; n < H; n += blockDim.x) {
+        const int i0 = 2 * n, i1 = 2 * n + 1;
+        re[n] = (i0 >= 1 && i0 <= out_order) ? grow[i0] : T(0);
+        im[n] = i1 <= out_order ? grow[i1] : T(0);
+    }
+    __syncthreads();
+    lds_fft_pow2(re, im, H, lgh, tw, 2);
+    split_to(gcb, static_cast<T*>(nullptr));
+    __syncthreads();
+    // ---- element-wise chain rule: (xr, xi)[k] <- (gXr, gXi)[k] ----
+    for (int k = threadIdx.x; k <= H; k += blockDim.x) {
+        const T cr = xr[k], ci = xi[k];
+        const T gc = gcb[k] * ((k == 0 || k == H) ? T(2) : T(4)) / T(nfft);
+        T lmag, ang, l_r, l_i, a_r, a_i;   // log |s|, angle(s) and their partial derivatives with respect to (cr, ci)
+        if (g1 == T(0)) {
+            lmag = cr; ang = ci;
+            l_r = T(1); l_i = T(0); a_r = T(0); a_i = T(1);
+        } else {
+            const T zr = T(1) + g1 * cr, zi = g1 * ci, r2 = zr * zr + zi * zi;
+            lmag = T(0.5) * dsa_log(r2) / g1;
+            ang = atan2(zi, zr) / g1;
+            l_r = zr / r2; l_i = zi / r2; a_r = -zi / r2; a_i = zr / r2;
+        }
+        T f_l, f_a;
+        if (g2 == T(0)) {
+            f_l = T(1); f_a = T(0);
+        } else {
+            ang -= T(2) * kPi * rint(ang / (T(2) * kPi));
+            const T e = dsa_exp(g2 * lmag);
+            f_l = e * cos(ang * g2);
+            f_a = -e * sin(ang * g2);
+        }
+        xr[k] = gc * (f_l * l_r + f_a * a_r);
+        xi[k] = gc * (f_l * l_i + f_a * a_i);
+    }
+    __syncthreads();
+    // ---- gc01 = 2 * conj(fft_H(conj Z)) unpacked ----
+    for (int k = threadIdx.x; k < H; k += blockDim.x) {
+        T yr, yi, br, bi;                      // Y[k], conj Y[H - k]
+        if (k == 0) {
+            yr = xr[0]; yi = T(0);
+            br = xr[H]; bi = T(0);
+        } else {
+            yr = T(0.5) * xr[k]; yi = T(0.5) * xi[k];
+            br = T(0.5) * xr[H - k]; bi = -T(0.5) * xi[H - k];
+        }
+        const T er = T(0.5) * (yr + br), ei = T(0.5) * (yi + bi), dr = T(0.5) * (yr - br), di = T(0.5) * (yi - bi);
+        const T wr = tw[2 * k], wi = -tw[2 * k + 1];            // conj(W)^k = (cos, +sin)(2 pi k / n)
+        const T or_ = wr * dr - wi * di, oi = wr * di + wi * dr;  // O[k]
+        // Z = E + i O = (er - oi) + i (ei + or); the transform runs on conj Z
+        re[k] = er - oi;
+        im[k] = -(ei + or_);
+    }
+    __syncthreads();
+    lds_fft_pow2(re, im, H, lgh, tw, 2);
+    T* out = gc1 + f * n_in;
+    for (int m = threadIdx.x; m < n_in; m += blockDim.x) {
+        T v;
+        if (m == 0) {
+            v = grow[0];
+        } else if (m >= nfft) {
+            v = T(0);                          // (rows longer than the transform are cropped by the forward)
+        } else {
+            const int pos = fft_brev(m >> 1, lgh);
+            v = T(2) * ((m & 1) ? -im[pos] : re[pos]);
+        }
+        out[m] = v;
+    }
+}
+
+template <typename T>
+static int gc2gc_launch(const void* c1, int64_t F, int n_in, int out_order, double g1, double g2, int nfft, const void* tw, int flags,
+                        void* c2, hipStream_t st)
+{
+    const size_t lds = sizeof(T) * (3 * (size_t)(nfft / 2) + 1);
+    static std::atomic<uint64_t> lds_set{0};
+    if (lds > 48 * 1024 && !ensure_dynamic_lds(reinterpret_cast<const void*>(&gc2gc_fused_kernel<T>), 150 * 1024, lds_set))
+        return fail(DSA_ERR_LAUNCH, "gc2gc: cannot raise the dynamic LDS limit%s");
+    // short transforms: one wave per row (two butterflies per lane and pass, the passes' barriers are single-wave barriers)
+    const int block = nfft <= 1024 ? 64 : 256;
+    hipLaunchKernelGGL((gc2gc_fused_kernel<T>), dim3((unsigned)F), dim3(block), lds, st, (const T*)c1, n_in, out_order, (T)g1, (T)g2, nfft,
+                       (const T*)tw, flags, (T*)c2);
+    return check_launch("gc2gc_fused");
+}
+
 }  // namespace dsa
 
 using namespace dsa;
-
-DSA_EXPORT int dsa_zerodf_fwd(const void* x, const void* b, int64_t B, int64_t T, int32_t M, int32_t P, int32_t zeroth_index,
-                              int32_t ignore_gain, int32_t dtype, void* y, void* stream)
-{
-    DSA_REQUIRE(M >= 0 && P > 0 && B >= 0 && T >= 0 && zeroth_index >= 0 && zeroth_index <= M, "zerodf: invalid sizes");
-    DSA_REQUIRE(T % P == 0, "zerodf: the sequence length must be frames x frame_period");
-    if (B * T == 0) return DSA_OK;
-    const int64_t N = T / P;
-    if (dtype == DSA_F32) return zerodf_launch_fwd<float>(x, b, B, T, N, M, P, zeroth_index, ignore_gain, y, (hipStream_t)stream);
-    if (dtype == DSA_F64) return zerodf_launch_fwd<double>(x, b, B, T, N, M, P, zeroth_index, ignore_gain, y, (hipStream_t)stream);
-    return fail(DSA_ERR_UNSUPPORTED, "zerodf: unsupported dtype%s");
-}
-
-DSA_EXPORT int dsa_zerodf_taylor_fwd(const void* x, const void* b, int64_t B, int64_t T, int32_t M, int32_t P, int32_t zeroth_index,
-                                     double scale, const void* acc, int32_t dtype, void* y, void* ysum, void* stream)
-{
-    DSA_REQUIRE(M >= 0 && P > 0 && B >= 0 && T >= 0 && zeroth_index >= 0 && zeroth_index <= M, "zerodf_taylor: invalid sizes");
-    DSA_REQUIRE(T % P == 0, "zerodf_taylor: the sequence length must be frames x frame_period");
-    if (B * T == 0) return DSA_OK;   // (an empty batch: its tensors have no storage)
-    DSA_REQUIRE((acc != nullptr) == (ysum != nullptr), "zerodf_taylor: acc and ysum come together");
-    DSA_REQUIRE(y != nullptr || ysum != nullptr, "zerodf_taylor: no output");
-    const int64_t N = T / P;
-    if (dtype == DSA_F32)
-        return zerodf_launch_fwd<float>(x, b, B, T, N, M, P, zeroth_index, 0, y, (hipStream_t)stream, scale, acc, ysum);
-    if (dtype == DSA_F64)
-        return zerodf_launch_fwd<double>(x, b, B, T, N, M, P, zeroth_index, 0, y, (hipStream_t)stream, scale, acc, ysum);
-    return fail(DSA_ERR_UNSUPPORTED, "zerodf_taylor: unsupported dtype%s");
-}
-
-DSA_EXPORT int dsa_zerodf_bwd(const void* gy, const void* x, const void* b, const void* y, int64_t B, int64_t T, int32_t M, int32_t P,
-                              int32_t zeroth_index, int32_t ignore_gain, int32_t dtype, void* gx, void* gb, void* stream)
-{
-    DSA_REQUIRE(M >= 0 && P > 0 && B >= 0 && T >= 0 && zeroth_index >= 0 && zeroth_index <= M && T % P == 0, "zerodf_bwd: invalid sizes");
-    if (B * T == 0) return DSA_OK;
-    const int64_t N = T / P;
-    if (dtype == DSA_F32)
-        return zerodf_launch_bwd<float>(gy, x, b, y, B, T, N, M, P, zeroth_index, ignore_gain, gx, gb, (hipStream_t)stream);
-    if (dtype == DSA_F64)
-        return zerodf_launch_bwd<double>(gy, x, b, y, B, T, N, M, P, zeroth_index, ignore_gain, gx, gb, (hipStream_t)stream);
-    return fail(DSA_ERR_UNSUPPORTED, "zerodf_bwd: unsupported dtype%s");
-}
-
-DSA_EXPORT int dsa_zerodf_taylor_bwd(const void* G, const void* x, const void* b, int64_t B, int64_t T, int32_t M, int32_t P,
-                                     int32_t zeroth_index, double scale, const void* gy, int32_t dtype, void* G_out, void* gb,
-                                     void* stream)
-{
-    DSA_REQUIRE(M >= 0 && P > 0 && B >= 0 && T >= 0 && zeroth_index >= 0 && zeroth_index <= M && T % P == 0, "zerodf_taylor_bwd: invalid sizes");
-    if (B * T == 0) return DSA_OK;
-    DSA_REQUIRE(G_out != nullptr && G_out != G, "zerodf_taylor_bwd: G_out must be a buffer of its own");
-    const int64_t N = T / P;
-    if (dtype == DSA_F32)
-        return zerodf_launch_bwd<float>(G, x, b, nullptr, B, T, N, M, P, zeroth_index, 0, G_out, gb, (hipStream_t)stream, scale, gy, true);
-    if (dtype == DSA_F64)
-        return zerodf_launch_bwd<double>(G, x, b, nullptr, B, T, N, M, P, zeroth_index, 0, G_out, gb, (hipStream_t)stream, scale, gy, true);
-    return fail(DSA_ERR_UNSUPPORTED, "zerodf_taylor_bwd: unsupported dtype%s");
-}
-
-DSA_EXPORT int dsa_thsolve_fwd(const void* p, const void* q, const void* r, int64_t F, int32_t n, int32_t dtype, void* g,
-                               void* stream)
-{
-    DSA_REQUIRE(n >= 1 && n <= kThMax && F >= 0, "thsolve: order must be in [1, 64]");
-    if (F == 0) return DSA_OK;
-    // cepstral order 24, float32: the unpivoted quad-layout solve of the mel-cepstral kernels (DSA_THSOLVE_QUAD=0: A/B)
-    static const bool quad = [] {
-        const char* e = getenv("DSA_THSOLVE_QUAD");
-        return !e || atoi(e) != 0;
-    }();
-    if (dtype == DSA_F32 && n == 24 && quad && F > 0) return thsolve_quad24_fwd(p, q, r, F, g, (hipStream_t)stream);
-    // other orders up to 55, float32: the same scheme as a template over the size -- chosen from (n, dtype) ALONE, like
-    // dsa_mcep_newton_update: a frame's rounding must not depend on how many frames travel with it (round 6: the F >= 64 test is gone)
-    if (dtype == DSA_F32 && n >= 2 && n <= 55 && quad && F > 0)
-        return thsolve_quadn_fwd(p, n, q, 2 * n - 1, r, n, nullptr, nullptr, F, n, g, (hipStream_t)stream);
-    if (dtype == DSA_F32) return th_launch<float>(false, nullptr, p, q, r, F, n, g, nullptr, nullptr, (hipStream_t)stream);
-    if (dtype == DSA_F64) return th_launch<double>(false, nullptr, p, q, r, F, n, g, nullptr, nullptr, (hipStream_t)stream);
-    return fail(DSA_ERR_UNSUPPORTED, "thsolve: unsupported dtype%s");
-}
-
-// mcep.py:216-222 for the geometries without a tuned kernel: mc_out = mc_in + solve(T(rt[:n]) + H(rt), rt[:n] - alpha_vec), rt:(F, 2n-1)
-DSA_EXPORT int dsa_mcep_newton_update(const void* rt, int64_t F, int32_t n, const void* alpha_vec, int32_t dtype, const void* mc_in,
-                                      void* mc_out, void* stream)
-{
-    DSA_REQUIRE(n >= 2 && n <= 55 && F >= 0, "mcep_newton_update: order must be in [2, 55]");
-    DSA_REQUIRE(F == 0 || (rt && alpha_vec && mc_out), "mcep_newton_update: null pointer");   // mc_in = NULL: the solution alone
-    if (dtype != DSA_F32) return fail(DSA_ERR_UNSUPPORTED, "mcep_newton_update: float32 only%s");
-    if (F == 0) return DSA_OK;
-    return thsolve_quadn_fwd(rt, 2 * n - 1, rt, 2 * n - 1, rt, 2 * n - 1, alpha_vec, mc_in, F, n, mc_out, (hipStream_t)stream);
-}
-
-// Cotangent of rt from the cotangent of the solution s = solve(T(rt[:n]) + H(rt), rt[:n] - alpha_vec):
-//   u = A^-1 gs (A is symmetric: the same batched solve), then per system
-//   grt[k] = -sum_{i + j = k} u_i s_j  -  [k < n] sum_{|i - j| = k} u_i s_j  +  [k < n] u_k      (Hankel, Toeplitz, right-hand side)
-namespace dsa {
-// Round 6: the sums with ONE FRAME PER LANE, everything in registers.  The round-5 kernel gave a wave to a frame and a lane one or two
-// of its 2 n - 1 sums, every multiply-add behind two LDS reads (143 us per 102 400 frames of order 49: a tenth of the 48 kHz analysis'
-// forward + backward).  Here a lane loads its frame's u and s rows (zero-padded to NMAX), runs the three sums fully unrolled at compile
-// time -- 2 NMAX^2 + NMAX multiply-adds, no memory access, no cross-lane operation -- and stores four results at a time.  The rows of a
-// wave's 64 consecutive frames are one contiguous block, so the per-lane 16-byte accesses use every byte of the lines they touch.
-// sums k = K4 .. K4 + 3 of a lane's frame, then the next group: a compile-time recursion (as a loop of 28 x 450 instructions the unroller
-// gives up and the arrays live in private memory)
-template <int NMAX, int K4>
-__device__ __forceinline__ void sums_lane_groups(const float (&uu)[NMAX], const float (&sv)[NMAX], float* orow, int nout)
-{
-    typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
-    if constexpr (K4 < 2 * NMAX - 1) {
-        if (K4 < nout) {   // (uniform)
-            float o[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int k = K4 + e;
-                float acc = 0.f;
-                if (k < 2 * NMAX - 1) {
-                    // Hankel: sum_{i + j = k} u_i s_j (zero padding makes the sum over the padded range the sum over the order's)
-#pragma unroll
-                    for (int i = (k - (NMAX - 1) > 0 ? k - (NMAX - 1) : 0); i <= (k < NMAX - 1 ? k : NMAX - 1); ++i) acc = __builtin_fmaf(-uu[i], sv[k - i], acc);
-                    if (k < NMAX) {
-                        // Toeplitz: sum_{|i - j| = k} u_i s_j, and the right-hand side's u_k (u_k = 0 from the order on)
-#pragma unroll
-                        for (int i = 0; i + k < NMAX; ++i) {
-                            acc = __builtin_fmaf(-uu[i], sv[i + k], acc);
-                            if (k > 0) acc = __builtin_fmaf(-uu[i + k], sv[i], acc);
-                        }
-                        acc += uu[k];
-                    }
-                }
-                o[e] = acc;
-            }
-            if (K4 + 3 < nout) {
-                *reinterpret_cast<f4u*>(orow + K4) = f4u{o[0], o[1], o[2], o[3]};
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (K4 + e < nout) orow[K4 + e] = o[e];
-            }
-            sums_lane_groups<NMAX, K4 + 4>(uu, sv, orow, nout);
-        }
-    }
-}
-
-template <int NMAX>
-__global__ __launch_bounds__(256) void newton_update_bwd_sums_lane_kernel(const float* __restrict__ u, const float* __restrict__ s, long F, int n,
-                                                                         float* __restrict__ grt)
-{
-    typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
-    const long f = (long)blockIdx.x * 256 + threadIdx.x;
-    if (f >= F) return;
-    const float* ur = u + f * n;
-    const float* sr = s + f * n;
-    float uu[NMAX], sv[NMAX];
-#pragma unroll
-    for (int i4 = 0; i4 < NMAX; i4 += 4) {
-        // (the group's values first, the array elements assigned unconditionally afterwards: element assignments on conditional paths keep
-        //  the arrays in private memory)
-        f4u a, b;
-        if (i4 + 3 < n) {   // (uniform)
-            a = *reinterpret_cast<const f4u*>(ur + i4);
-            b = *reinterpret_cast<const f4u*>(sr + i4);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                a[e] = i4 + e < n ? ur[i4 + e] : 0.f;
-                b[e] = i4 + e < n ? sr[i4 + e] : 0.f;
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { uu[i4 + e] = a[e]; sv[i4 + e] = b[e]; }
-    }
-    float* orow = grt + f * (2 * n - 1);
-    sums_lane_groups<NMAX, 0>(uu, sv, orow, 2 * n - 1);
-}
-}  // namespace dsa
-
-DSA_EXPORT int dsa_mcep_newton_update_bwd(const void* gs, const void* rt, const void* sol, int64_t F, int32_t n, int32_t dtype, void* u,
-                                          void* grt, void* stream)
-{
-    DSA_REQUIRE(n >= 2 && n <= 55 && F >= 0, "mcep_newton_update_bwd: order must be in [2, 55]");
-    DSA_REQUIRE(F == 0 || (gs && rt && sol && u && grt), "mcep_newton_update_bwd: null pointer");
-    if (dtype != DSA_F32) return fail(DSA_ERR_UNSUPPORTED, "mcep_newton_update_bwd: float32 only%s");
-    if (F == 0) return DSA_OK;
-    if (int rc = thsolve_quadn_fwd(rt, 2 * n - 1, rt, 2 * n - 1, gs, n, nullptr, nullptr, F, n, u, (hipStream_t)stream)) return rc;
-    // one frame per lane (round 6), whatever the batch: the two kernels sum in different orders, and a frame's bits must not depend on
-    // how many frames travel with it
-    const dim3 g((unsigned)((F + 255) / 256));
-    if (n <= 36)
-        hipLaunchKernelGGL((dsa::newton_update_bwd_sums_lane_kernel<36>), g, dim3(256), 0, (hipStream_t)stream, (const float*)u, (const float*)sol,
-                           (long)F, (int)n, (float*)grt);
-    else
-        hipLaunchKernelGGL((dsa::newton_update_bwd_sums_lane_kernel<56>), g, dim3(256), 0, (hipStream_t)stream, (const float*)u, (const float*)sol,
-                           (long)F, (int)n, (float*)grt);
-    return dsa::check_launch("mcep_newton_update_bwd");
-}
-
-DSA_EXPORT int dsa_thsolve_update_fwd(const void* p, const void* q, const void* r, int64_t r_stride, int64_t r_offset, int64_t F,
-                                      int32_t n, int32_t dtype, const void* b_in, void* b_out, void* stream)
-{
-    DSA_REQUIRE(n >= 1 && n <= kThMax && F >= 0, "thsolve_update: order must be in [1, 64]");
-    DSA_REQUIRE(r_offset >= 0 && r_stride >= r_offset + n, "thsolve_update: the right-hand side does not fit its row stride");
-    DSA_REQUIRE(F == 0 || (b_in != nullptr && b_out != nullptr && b_in != b_out), "thsolve_update: b_in and b_out must be distinct buffers");
-    if (F == 0) return DSA_OK;
-    if (dtype == DSA_F32 && n == 24)
-        return thsolve_quad24_fwd(p, q, r, F, b_out, (hipStream_t)stream, (int)r_stride, (int)r_offset, b_in);
-    return fail(DSA_ERR_UNSUPPORTED, "thsolve_update: order 24 in float32 only (dsa_thsolve_fwd + an addition otherwise)%s");
-}
-
-DSA_EXPORT int dsa_thsolve_bwd(const void* gg, const void* p, const void* q, const void* g, int64_t F, int32_t n,
-                               int32_t dtype, void* gp, void* gq, void* gr, void* stream)
-{
-    DSA_REQUIRE(n >= 1 && n <= kThMax && F >= 0, "thsolve_bwd: order must be in [1, 64]");
-    if (F == 0) return DSA_OK;
-    // order 24, float32: u = A^{-1} gbar on the quad-layout solve (A is symmetric; marked systems re-solved with pivoting as in
-    // the forward), then the diagonal sums (DSA_THSOLVE_QUAD=0: the one-wave-per-system kernel, A/B)
-    static const bool quad = [] {
-        const char* e = getenv("DSA_THSOLVE_QUAD");
-        return !e || atoi(e) != 0;
-    }();
-    if (dtype == DSA_F32 && n == 24 && quad && gp && gq && gr) {
-        if (int rc = thsolve_quad24_fwd(p, q, gg, F, gr, (hipStream_t)stream)) return rc;
-        hipLaunchKernelGGL(th_bwd_sums_kernel, dim3((unsigned)((F + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const float*)gr,
-                           (const float*)g, (long)F, (int)n, (float*)gp, (float*)gq);
-        return check_launch("th_solve_quad_bwd");
-    }
-    // the other orders the batched forward covers (csrc/thsolve_quad.hip: 2 .. 55, batches from 64 systems): the same two launches.
-    // (The one-wave-per-system backward -- a second pivoted elimination per system -- took 220 us per 12 800 systems of order 50,
-    // 37 % of a forward + backward of the 48 kHz analysis; this takes 39 + 7.)
-    if (dtype == DSA_F32 && n >= 2 && n <= 55 && n != 24 && F > 0 && quad && gp && gq && gr) {
-        if (int rc = thsolve_quadn_fwd(p, n, q, 2 * n - 1, gg, n, nullptr, nullptr, F, n, gr, (hipStream_t)stream)) return rc;
-        hipLaunchKernelGGL(th_bwd_sums_kernel, dim3((unsigned)((F + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const float*)gr,
-                           (const float*)g, (long)F, (int)n, (float*)gp, (float*)gq);
-        return check_launch("th_solve_quadn_bwd");
-    }
-    if (dtype == DSA_F32) return th_launch<float>(true, gg, p, q, g, F, n, gp, gq, gr, (hipStream_t)stream);
-    if (dtype == DSA_F64) return th_launch<double>(true, gg, p, q, g, F, n, gp, gq, gr, (hipStream_t)stream);
-    return fail(DSA_ERR_UNSUPPORTED, "thsolve_bwd: unsupported dtype%s");
-}
 
 // ---- gain normalisation of generalized cepstra and its inverse as ONE launch each (gnorm.py:102-112, ignorm.py:99-109), forward only ----
 //   forward:  (K, x1 / z),  z = 1 + gamma x0,  K = z^(1/gamma)      (gamma = 0: (exp x0, x1))
@@ -1745,4 +768,48 @@ DSA_EXPORT int dsa_mgcep_spectra(const void* x, const void* b1, int64_t F, int32
     if (dtype == DSA_F32) return mgcep_spectra_launch<float>(x, b1, F, K, M, Cr, Ci, gamma, out, st);
     if (dtype == DSA_F64) return mgcep_spectra_launch<double>(x, b1, F, K, M, Cr, Ci, gamma, out, st);
     return fail(DSA_ERR_UNSUPPORTED, "mgcep_spectra: unsupported dtype%s");
+}
+
+DSA_EXPORT int dsa_gc2gc_fwd(const void* c1, int64_t F, int32_t n_in, int32_t out_order, double in_gamma, double out_gamma,
+                             int32_t nfft, const void* twiddle, int32_t flags, int32_t dtype, void* c2, void* stream)
+{
+    DSA_REQUIRE(F >= 0 && n_in >= 1 && out_order >= 0, "gc2gc: sizes must be positive");
+    DSA_REQUIRE(nfft >= 4 && (nfft & (nfft - 1)) == 0, "gc2gc: n_fft must be a power of two");
+    DSA_REQUIRE(flags >= 0 && flags < 16, "gc2gc: unknown flags");
+    if (out_order + 1 > nfft || F > 0x7fffffffLL) return fail(DSA_ERR_UNSUPPORTED, "gc2gc: out_order + 1 must not exceed n_fft%s");
+    if (F == 0) return DSA_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == DSA_F32 && (size_t)nfft * 8 <= 150 * 1024) return gc2gc_launch<float>(c1, F, n_in, out_order, in_gamma, out_gamma, nfft, twiddle, flags, c2, st);
+    if (dtype == DSA_F64 && (size_t)nfft * 16 <= 150 * 1024) return gc2gc_launch<double>(c1, F, n_in, out_order, in_gamma, out_gamma, nfft, twiddle, flags, c2, st);
+    return fail(DSA_ERR_UNSUPPORTED, "gc2gc: unsupported dtype or n_fft too long for LDS%s");
+}
+
+DSA_EXPORT int dsa_gc2gc_bwd(const void* c1, const void* g2, int64_t F, int32_t n_in, int32_t out_order, double in_gamma,
+                             double out_gamma, int32_t nfft, const void* twiddle, int32_t dtype, void* gc1, void* stream)
+{
+    DSA_REQUIRE(F >= 0 && n_in >= 1 && out_order >= 0, "gc2gc_bwd: sizes must be positive");
+    DSA_REQUIRE(nfft >= 4 && (nfft & (nfft - 1)) == 0, "gc2gc_bwd: n_fft must be a power of two (>= 4)");
+    DSA_REQUIRE(out_order + 1 <= nfft, "gc2gc_bwd: out_order + 1 must not exceed n_fft");
+    if (F == 0) return DSA_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int block = nfft <= 1024 ? 64 : 256;
+    if (dtype == DSA_F32 && (size_t)nfft * 10 + 64 <= 150 * 1024) {
+        const size_t lds = sizeof(float) * (5 * (size_t)(nfft / 2) + 3);
+        static std::atomic<uint64_t> lds_set{0};
+        if (lds > 48 * 1024 && !ensure_dynamic_lds(reinterpret_cast<const void*>(&gc2gc_fused_bwd_kernel<float>), 150 * 1024, lds_set))
+            return fail(DSA_ERR_LAUNCH, "gc2gc_bwd: cannot raise the dynamic LDS limit%s");
+        hipLaunchKernelGGL((gc2gc_fused_bwd_kernel<float>), dim3((unsigned)F), dim3(block), lds, st, (const float*)c1, (const float*)g2,
+                           n_in, out_order, (float)in_gamma, (float)out_gamma, nfft, (const float*)twiddle, (float*)gc1);
+        return check_launch("gc2gc_fused_bwd");
+    }
+    if (dtype == DSA_F64 && (size_t)nfft * 20 + 64 <= 150 * 1024) {
+        const size_t lds = sizeof(double) * (5 * (size_t)(nfft / 2) + 3);
+        static std::atomic<uint64_t> lds_set{0};
+        if (lds > 48 * 1024 && !ensure_dynamic_lds(reinterpret_cast<const void*>(&gc2gc_fused_bwd_kernel<double>), 150 * 1024, lds_set))
+            return fail(DSA_ERR_LAUNCH, "gc2gc_bwd: cannot raise the dynamic LDS limit%s");
+        hipLaunchKernelGGL((gc2gc_fused_bwd_kernel<double>), dim3((unsigned)F), dim3(block), lds, st, (const double*)c1, (const double*)g2,
+                           n_in, out_order, in_gamma, out_gamma, nfft, (const double*)twiddle, (double*)gc1);
+        return check_launch("gc2gc_fused_bwd");
+    }
+    return fail(DSA_ERR_UNSUPPORTED, "gc2gc_bwd: unsupported dtype or n_fft too long for LDS%s");
 }

@@ -291,7 +291,7 @@ __global__ __launch_bounds__(64) void poledf_generic_bwd_kernel(const T* __restr
 }
 
 // ga[n][k] = sum over the samples of frames n - 1 and n of wt(t) dc_t[k], wt the weight with which a[n] enters c_t (1 - w in
-// frame n, w in frame n - 1, both in the last frame) -- the pattern of zerodf_bwd_b_kernel (csrc/mgc.hip).  One wave per
+// frame n, w in frame n - 1, both in the last frame) -- the pattern of zerodf_bwd_b_kernel (csrc/zerodf.hip).  One wave per
 // (utterance, frame), lane k per coefficient, the samples staged in LDS chunks; fixed summation order (deterministic).
 template <typename T>
 __global__ __launch_bounds__(64) void poledf_bwd_a_kernel(const T* __restrict__ uo, const T* __restrict__ x, const T* __restrict__ y,

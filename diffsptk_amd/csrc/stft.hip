@@ -1,10 +1,11 @@
-// STFT family for gfx950: Frame (a1), Window (a2), fftr (a3), Spectrum (a4), fused STFT (a5).
+// Fused STFT (a5) for gfx950: the tuned kernels and the entries dsa_stft_fwd / _bwd, dsa_istft_fwd, dsa_stft_fbank_fwd.
 //
 // Two kernel families:
 //  * generic  -- any frame length / period / even fft length, float32 and float64, every
 //                option of the reference.  One workgroup per frame, direct DFT against a
 //                host-built twiddle table.  Correctness path for odd configurations and for
-//                float64 (gradcheck); never the fast path.
+//                float64 (gradcheck); never the fast path.  Lives in spec.hip; reached
+//                through stft_generic_fwd / stft_generic_bwd (common.h).
 //  * tuned    -- nfft = 512, float32: the BASELINE configuration.  One workgroup handles 16
 //                consecutive frames of one utterance: the waveform stretch they share is read
 //                from HBM once into LDS (frames overlap there, not in HBM), each frame is
@@ -14,684 +15,10 @@
 //                coalesced write of the (frames x 257) tile.
 //                Algorithmic HBM traffic: P*4 B read + 257*4 B written per frame.
 //
-// Reference semantics: diffsptk/modules/{frame,window,fftr,spec,stft}.py (cited per kernel).
+// Reference semantics: diffsptk/modules/{stft,istft}.py (cited per kernel).
 #include "common.h"
 
 namespace dsa {
-
-// =========================================================================== generic kernels
-
-// Frame._forward frame.py:120-141.  grid = F frames, any block size.
-template <typename T>
-__global__ void frame_fwd_kernel(const T* __restrict__ x, long Tlen, long N, int L, int P, int left,
-                                 int zmean, int mode, T* __restrict__ y)
-{
-    __shared__ T scratch[16];
-    long f = blockIdx.x;
-    long b = f / N, n = f - b * N;
-    const T* xb = x + b * Tlen;
-    T* row = y + f * L;
-    T acc = 0;
-    for (int l = threadIdx.x; l < L; l += blockDim.x) {
-        T v = load_padded(xb, n * P + l - left, Tlen, mode);
-        row[l] = v;
-        acc += v;
-    }
-    if (zmean) {  // frame.py:139-140
-        T mean = block_sum(acc, scratch) / T(L);
-        for (int l = threadIdx.x; l < L; l += blockDim.x) row[l] -= mean;
-    }
-}
-
-// Frame without zmean, float32, L % 4 == 0: four samples per thread and a 16-byte store (the rows of y are 16-byte
-// aligned then); the four samples come as one 16-byte load when the source run is inside the waveform and aligned
-// (P, left multiples of 4), else one by one through the padding rule.  Persistent grid: the one-workgroup-per-frame
-// kernel above launches B * N tiny workgroups (0.17 ms per 204 800 frames against 0.07 ms here).
-__global__ __launch_bounds__(256) void frame_fwd_vec4_kernel(const float* __restrict__ x, long Tlen, long N, long F, int L, int P,
-                                                             int left, int mode, int src_aligned, float* __restrict__ y)
-{
-    const int L4 = L >> 2;
-    const long total = F * L4;
-    for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (long)gridDim.x * blockDim.x) {
-        const long f = q / L4;
-        const int l = (int)(q - f * L4) << 2;
-        const long b = f / N, n = f - b * N;
-        const float* xb = x + b * Tlen;
-        const long s0 = n * P + l - left;
-        float4 v;
-        if (src_aligned && s0 >= 0 && s0 + 4 <= Tlen) {
-            v = *reinterpret_cast<const float4*>(xb + s0);
-        } else {
-            v.x = load_padded(xb, s0, Tlen, mode);
-            v.y = load_padded(xb, s0 + 1, Tlen, mode);
-            v.z = load_padded(xb, s0 + 2, Tlen, mode);
-            v.w = load_padded(xb, s0 + 3, Tlen, mode);
-        }
-        *reinterpret_cast<float4*>(y + f * (long)L + l) = v;
-    }
-}
-
-// adjoint of Frame: gx[b,t] = sum over (n,l) whose source index is t of g'[b,n,l], where
-// g' = gy - mean_l(gy) if zmean.  Gather formulation (deterministic, no atomics) for constant
-// padding; the non-constant modes fold several padded positions onto one sample and use a
-// per-utterance serial-over-frames scatter within one block (deterministic as well).
-template <typename T>
-__global__ void frame_bwd_const_kernel(const T* __restrict__ gy, const T* __restrict__ gmean,
-                                       long Tlen, long N, int L, int P, int left,
-                                       T* __restrict__ gx)
-{
-    const long tb = (Tlen + blockDim.x - 1) / blockDim.x;   // blocks per utterance: (utterance, block) folded into grid.x
-    const long b = blockIdx.x / tb;
-    long t = ((long)blockIdx.x - b * tb) * blockDim.x + threadIdx.x;
-    if (t >= Tlen) return;
-    // frames n with 0 <= t + left - n*P < L
-    long p = t + left;
-    long n_hi = p / P;
-    if (n_hi > N - 1) n_hi = N - 1;
-    long n_lo = p - L + 1 <= 0 ? 0 : (p - L + P) / P;  // ceil((p-L+1)/P)
-    T acc = 0;
-    for (long n = n_lo; n <= n_hi; ++n) {
-        long l = p - n * P;
-        T g = gy[(b * N + n) * L + l];
-        if (gmean) g -= gmean[b * N + n];
-        acc += g;
-    }
-    gx[b * Tlen + t] = acc;
-}
-
-template <typename T>
-__global__ void row_mean_kernel(const T* __restrict__ g, int L, T* __restrict__ m)
-{
-    __shared__ T scratch[16];
-    long f = blockIdx.x;
-    T acc = 0;
-    for (int l = threadIdx.x; l < L; l += blockDim.x) acc += g[f * L + l];
-    T s = block_sum(acc, scratch);
-    if (threadIdx.x == 0) m[f] = s / T(L);
-}
-
-// general-mode adjoint: one block per utterance, frames visited in order, each frame's L
-// contributions added by distinct threads (a frame never maps two l onto the same t unless
-// the padding folds, in which case the fold is resolved by a second serial pass) -- simple and
-// deterministic; only used for reflect/replicate/circular padding.
-template <typename T>
-__global__ void frame_bwd_general_kernel(const T* __restrict__ gy, const T* __restrict__ gmean,
-                                         long Tlen, long N, int L, int P, int left, int mode,
-                                         T* __restrict__ gx)
-{
-    long b = blockIdx.x;
-    T* gxb = gx + b * Tlen;
-    for (long t = threadIdx.x; t < Tlen; t += blockDim.x) gxb[t] = 0;
-    __syncthreads();
-    // interior (un-folded) part: gather
-    for (long t = threadIdx.x; t < Tlen; t += blockDim.x) {
-        long p = t + left;
-        long n_hi = p / P;
-        if (n_hi > N - 1) n_hi = N - 1;
-        long n_lo = p - L + 1 <= 0 ? 0 : (p - L + P) / P;
-        T acc = 0;
-        for (long n = n_lo; n <= n_hi; ++n) {
-            T g = gy[(b * N + n) * L + (p - n * P)];
-            if (gmean) g -= gmean[b * N + n];
-            acc += g;
-        }
-        gxb[t] = acc;
-    }
-    __syncthreads();
-    // folded part: padded positions i < 0 or i >= T, visited serially by thread 0
-    if (threadIdx.x == 0) {
-        for (long n = 0; n < N; ++n)
-            for (int l = 0; l < L; ++l) {
-                long i = n * P + l - left;
-                if (i >= 0 && i < Tlen) continue;
-                long j = pad_src_index(i, Tlen, mode);
-                if (j < 0) continue;
-                T g = gy[(b * N + n) * L + l];
-                if (gmean) g -= gmean[b * N + n];
-                gxb[j] += g;
-            }
-    }
-}
-
-// Window._forward window.py:185-193
-template <typename T>
-__global__ void window_fwd_kernel(const T* __restrict__ x, long F, int L, const T* __restrict__ w,
-                                  int L2, T* __restrict__ y)
-{
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    long total = F * L2;
-    for (; i < total; i += (long)gridDim.x * blockDim.x) {
-        long f = i / L2;
-        int l = (int)(i - f * L2);
-        y[i] = l < L ? x[f * L + l] * w[l] : T(0);
-    }
-}
-
-// y = x * w row-wise for float32 rows whose length is a multiple of 4 and needs no padding / cropping (the forward and
-// the backward of Window are the same product then): 16-byte accesses and a 32-bit remainder per float4 instead of
-// a 64-bit division per element (0.16 -> 0.11 ms per 204 800 frames of 400 samples).
-__global__ __launch_bounds__(256) void window_vec4_kernel(const float4* __restrict__ x, unsigned n4, unsigned L4,
-                                                          const float4* __restrict__ w, float4* __restrict__ y)
-{
-    for (unsigned q = blockIdx.x * blockDim.x + threadIdx.x; q < n4; q += gridDim.x * blockDim.x) {
-        const float4 a = x[q], b = w[q % L4];
-        y[q] = make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w);
-    }
-}
-
-static bool window_vec4_ok(const void* a, const void* b, const void* w, int64_t F, int L, int L2)
-{
-    return L == L2 && (L & 3) == 0 && F * (int64_t)L >= 4096 && F * (int64_t)(L >> 2) < (1LL << 31) &&
-           ((((size_t)a) | ((size_t)b) | ((size_t)w)) & 15) == 0;
-}
-
-template <typename T>
-__global__ void window_bwd_kernel(const T* __restrict__ gy, long F, int L, const T* __restrict__ w,
-                                  int L2, T* __restrict__ gx)
-{
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    long total = F * L;
-    for (; i < total; i += (long)gridDim.x * blockDim.x) {
-        long f = i / L;
-        int l = (int)(i - f * L);
-        gx[i] = l < L2 ? gy[f * L2 + l] * w[l] : T(0);
-    }
-}
-
-// gw[l] = sum_f gy[f,l] * x[f,l]; one block per l, fixed summation order (deterministic)
-template <typename T>
-__global__ void window_gw_kernel(const T* __restrict__ gy, const T* __restrict__ x, long F, int L,
-                                 int L2, T* __restrict__ gw)
-{
-    __shared__ T scratch[16];
-    int l = blockIdx.x;
-    T acc = 0;
-    if (l < L2)
-        for (long f = threadIdx.x; f < F; f += blockDim.x) acc += gy[f * L2 + l] * x[f * L + l];
-    T s = block_sum(acc, scratch);
-    if (threadIdx.x == 0) gw[l] = s;
-}
-
-// Generic fused row transform: (optional framing) -> (optional zmean) -> (optional window) ->
-// direct DFT of length nfft -> formatter.  Covers fftr (fftr.py:136-151), the b-only branch of
-// Spectrum (spec.py:165-178) and STFT (stft.py:237-241) for any configuration.
-//   out_kind 0: fftr formats (DSA_FFTR_*), 1: spectrum formats (DSA_SPEC_*).
-// twiddle: (nfft, 2) = (cos, -sin)(2 pi m / nfft).
-// dynamic LDS: Lrow elements of T.
-// In-place radix-2 decimation-in-frequency FFT of n = 2^lg complex points held in LDS, run by the whole workgroup
-// (forward sign; tw = (cos, -sin)(2 pi m / n)).  Natural-order input, BIT-REVERSED output: X[k] sits at fft_brev(k, lg).
-// The generic row transforms use it whenever fft_length is a power of two (FFT = true): the direct sum they fall
-// back to costs n^2 / 2 multiply-adds per row -- 8.4 M at the 4096 points the MLSA filter's impulse responses use.
-template <typename T>
-__device__ __forceinline__ void lds_fft_pow2(T* re, T* im, int n, int lg, const T* __restrict__ tw, int tmul = 1)
-{   // tmul: the table is that of length n * tmul (a half-size transform reads every second entry of the full table)
-    // Two radix-2 stages at a time (s and s - 1): the four points i0, i0 + h/2, i0 + h, i0 + h + h/2 (bits s and s - 1 of
-    // i0 clear) are closed under both, so they pass through registers once -- half the LDS traffic and barriers of
-    // stage-by-stage radix 2, a sixth of its twiddle reads (from memory: one per group; the second pair's stage-s twiddle is
-    // -i times the first's -- a quarter turn further -- and stage s - 1's is its square), same bit-reversed output.
-    int s = lg - 1;
-    for (; s >= 1; s -= 2) {
-        const int h = 1 << s, h2 = h >> 1;
-        const int tstep = (n >> (s + 1)) * tmul;
-        for (int t = threadIdx.x; t < (n >> 2); t += blockDim.x) {
-            const int j = t & (h2 - 1);
-            const int i0 = ((t >> (s - 1)) << (s + 1)) | j;
-            const T a0r = re[i0], a0i = im[i0], a1r = re[i0 + h2], a1i = im[i0 + h2];
-            const T a2r = re[i0 + h], a2i = im[i0 + h], a3r = re[i0 + h + h2], a3i = im[i0 + h + h2];
-            const T c1 = tw[2 * (j * tstep)], s1 = tw[2 * (j * tstep) + 1];   // W^(j tstep): the group's one table read
-            const T c2 = s1, s2 = -c1;                                          // W^((j + h/2) tstep) = -i W^(j tstep)
-            const T c3 = c1 * c1 - s1 * s1, s3 = T(2) * c1 * s1;                // W^(2 j tstep), the twiddle of stage s - 1
-            // stage s
-            const T u0r = a0r + a2r, u0i = a0i + a2i, d0r = a0r - a2r, d0i = a0i - a2i;
-            const T u1r = a1r + a3r, u1i = a1i + a3i, d1r = a1r - a3r, d1i = a1i - a3i;
-            const T v0r = d0r * c1 - d0i * s1, v0i = d0r * s1 + d0i * c1;
-            const T v1r = d1r * c2 - d1i * s2, v1i = d1r * s2 + d1i * c2;
-            // stage s - 1
-            re[i0] = u0r + u1r;
-            im[i0] = u0i + u1i;
-            const T e0r = u0r - u1r, e0i = u0i - u1i;
-            re[i0 + h2] = e0r * c3 - e0i * s3;
-            im[i0 + h2] = e0r * s3 + e0i * c3;
-            re[i0 + h] = v0r + v1r;
-            im[i0 + h] = v0i + v1i;
-            const T e1r = v0r - v1r, e1i = v0i - v1i;
-            re[i0 + h + h2] = e1r * c3 - e1i * s3;
-            im[i0 + h + h2] = e1r * s3 + e1i * c3;
-        }
-        __syncthreads();
-    }
-    if (s == 0) {   // odd number of stages: the last one on its own (half = 1, twiddle 1)
-        for (int t = threadIdx.x; t < (n >> 1); t += blockDim.x) {
-            const int i = t << 1;
-            const T ar = re[i], ai = im[i], br = re[i + 1], bi = im[i + 1];
-            const T c = tw[0], sn = tw[1];
-            re[i] = ar + br;
-            im[i] = ai + bi;
-            const T dr = ar - br, di = ai - bi;
-            re[i + 1] = dr * c - di * sn;
-            im[i + 1] = dr * sn + di * c;
-        }
-        __syncthreads();
-    }
-}
-__device__ __forceinline__ int fft_brev(int k, int lg) { return (int)(__brev((unsigned)k) >> (32 - lg)); }
-
-// dynamic LDS: L elements of T (FFT: + 2 nfft).
-template <typename T, bool FFT = false>
-__global__ void row_dft_kernel(const T* __restrict__ x, long Tlen, long N, int L, int P, int left,
-                               int mode, int zmean, const T* __restrict__ w, int nfft,
-                               const T* __restrict__ twiddle, int out_kind, int fmt, T eps,
-                               int use_floor, T floor_lin, T* __restrict__ y)
-{
-    extern __shared__ unsigned char smem_raw[];
-    T* xs = reinterpret_cast<T*>(smem_raw);
-    T* fre = xs + L;        // FFT only
-    T* fim = fre + nfft;
-    __shared__ T scratch[16];
-    long f = blockIdx.x;
-    long b = f / N, n = f - b * N;
-    const T* xb = x + b * Tlen;
-    T acc = 0;
-    for (int l = threadIdx.x; l < L; l += blockDim.x) {
-        T v = load_padded(xb, n * P + l - left, Tlen, mode);
-        xs[l] = v;
-        acc += v;
-    }
-    T mean = 0;
-    if (zmean) mean = block_sum(acc, scratch) / T(L);
-    __syncthreads();
-    for (int l = threadIdx.x; l < L; l += blockDim.x) {
-        T v = xs[l] - mean;
-        xs[l] = w ? v * w[l] : v;
-    }
-    __syncthreads();
-    const int K = nfft / 2 + 1;
-    const int Lc = L < nfft ? L : nfft;  // rfft(x, n) crops when the row is longer than n
-    const bool inverse_adj = out_kind == 1 && fmt == DSA_SPEC_COMPLEX_INV;   // complex output times c_k / nfft
-    const bool complex_out = (out_kind == 0 && fmt == DSA_FFTR_COMPLEX) ||
-                             (out_kind == 1 && fmt == DSA_SPEC_COMPLEX) || inverse_adj;
-    const int lg = 31 - __clz(nfft);
-    if (FFT) {
-        for (int l = threadIdx.x; l < nfft; l += blockDim.x) {
-            fre[l] = l < Lc ? xs[l] : T(0);
-            fim[l] = T(0);
-        }
-        __syncthreads();
-        lds_fft_pow2(fre, fim, nfft, lg, twiddle);
-    }
-    T smax = 0;
-    for (int k = threadIdx.x; k < K; k += blockDim.x) {
-        T re = 0, im = 0;
-        if (FFT) {
-            const int q = fft_brev(k, lg);
-            re = fre[q], im = fim[q];
-        } else {
-            int idx = 0;
-            for (int l = 0; l < Lc; ++l) {
-                T c = twiddle[2 * idx], s = twiddle[2 * idx + 1];
-                re += xs[l] * c;
-                im += xs[l] * s;
-                idx += k;
-                if (idx >= nfft) idx -= nfft;
-            }
-        }
-        if (complex_out) {
-            const T sc = inverse_adj ? ((k == 0 || k == K - 1) ? T(1) : T(2)) / T(nfft) : T(1);
-            y[(f * K + k) * 2] = re * sc;
-            y[(f * K + k) * 2 + 1] = im * sc;
-        } else if (out_kind == 0) {
-            T v;
-            switch (fmt) {
-            case DSA_FFTR_REAL: v = re; break;
-            case DSA_FFTR_IMAG: v = im; break;
-            case DSA_FFTR_AMPLITUDE: v = dsa_sqrt(re * re + im * im); break;
-            default: {
-                T a = dsa_sqrt(re * re + im * im);  // abs() then square(), fftr.py:119
-                v = a * a;
-            }
-            }
-            y[f * K + k] = v;
-        } else {
-            T a = dsa_sqrt(re * re + im * im);  // fftr amplitude (spec.py:139), then spec.py:173
-            T s = a * a + eps;
-            if (use_floor) {
-                y[f * K + k] = s;  // formatted after the row maximum is known
-                smax = s > smax ? s : smax;
-            } else {
-                y[f * K + k] = spec_format(s, fmt);
-            }
-        }
-    }
-    if (out_kind == 1 && use_floor && !complex_out) {  // spec.py:174-176
-        T m = block_max(smax, scratch);
-        __syncthreads();
-        for (int k = threadIdx.x; k < K; k += blockDim.x) {
-            T s = y[f * K + k];
-            T fl = m * floor_lin;
-            y[f * K + k] = spec_format(s > fl ? s : fl, fmt);
-        }
-    }
-}
-
-// Backward of row_dft_kernel.  Recomputes X (nothing but x is saved by the forward), forms the
-// complex cotangent C[k] = dL/dRe X + i dL/dIm X for the requested format, applies the adjoint
-// of the half-spectrum DFT  gxw[l] = sum_k Re(C[k] exp(+i theta k l)), then the adjoints of the
-// window multiply and of zmean.  Output: gframe (F, L) = cotangent of the framed samples (the
-// overlap-add into the waveform is done by frame_bwd); gwpart (F, L) = per-frame contribution
-// to the window gradient (NULL unless the window is learnable).
-// dynamic LDS: (L + 3K) elements of T (FFT: + 2 nfft).
-template <typename T, bool FFT = false>
-__global__ void row_dft_bwd_kernel(const T* __restrict__ x, long Tlen, long N, int L, int P, int left,
-                                   int mode, int zmean, const T* __restrict__ w, int nfft,
-                                   const T* __restrict__ twiddle, int out_kind, int fmt, T eps,
-                                   int use_floor, T floor_lin, const T* __restrict__ gy,
-                                   T* __restrict__ gframe, T* __restrict__ gwpart)
-{
-    extern __shared__ unsigned char smem_raw[];
-    T* xc = reinterpret_cast<T*>(smem_raw);
-    __shared__ T scratch[16];
-    const int K = nfft / 2 + 1;
-    const int Lc = L < nfft ? L : nfft;
-    T* Cre = xc + L;
-    T* Cim = Cre + K;
-    T* fre = Cim + 2 * K;   // FFT only (behind the gs array)
-    T* fim = fre + nfft;
-    const int lg = 31 - __clz(nfft);
-    long f = blockIdx.x;
-    long b = f / N, n = f - b * N;
-    const T* xb = x + b * Tlen;
-    T acc = 0;
-    for (int l = threadIdx.x; l < L; l += blockDim.x) {
-        T v = load_padded(xb, n * P + l - left, Tlen, mode);
-        xc[l] = v;
-        acc += v;
-    }
-    T mean = 0;
-    if (zmean) mean = block_sum(acc, scratch) / T(L);
-    __syncthreads();
-    for (int l = threadIdx.x; l < L; l += blockDim.x) xc[l] -= mean;
-    __syncthreads();
-    const bool inverse_cot = out_kind == 1 && fmt == DSA_SPEC_COMPLEX_INV;
-    const bool complex_out = (out_kind == 0 && fmt == DSA_FFTR_COMPLEX) ||
-                             (out_kind == 1 && fmt == DSA_SPEC_COMPLEX) || inverse_cot;
-    // a complex cotangent (format "complex", the inverse transforms) does not depend on the spectrum: no forward transform
-    if (FFT && !complex_out) {
-        for (int l = threadIdx.x; l < nfft; l += blockDim.x) {
-            fre[l] = l < Lc ? (w ? xc[l] * w[l] : xc[l]) : T(0);
-            fim[l] = T(0);
-        }
-        __syncthreads();
-        lds_fft_pow2(fre, fim, nfft, lg, twiddle);
-    }
-    T smax = 0;
-    for (int k = threadIdx.x; k < K; k += blockDim.x) {
-        T re = 0, im = 0;
-        if (complex_out) {
-        } else if (FFT) {
-            const int q = fft_brev(k, lg);
-            re = fre[q], im = fim[q];
-        } else {
-            int idx = 0;
-            for (int l = 0; l < Lc; ++l) {
-                T xv = w ? xc[l] * w[l] : xc[l];
-                re += xv * twiddle[2 * idx];
-                im += xv * twiddle[2 * idx + 1];
-                idx += k;
-                if (idx >= nfft) idx -= nfft;
-            }
-        }
-        T cr, ci;
-        if (complex_out) {
-            cr = gy[(f * K + k) * 2];
-            ci = gy[(f * K + k) * 2 + 1];
-            if (inverse_cot) {   // irfft weights c_k / nfft
-                const T ck = ((k == 0 || k == K - 1) ? T(1) : T(2)) / T(nfft);
-                cr *= ck;
-                ci *= ck;
-            }
-        } else if (out_kind == 0) {
-            T g = gy[f * K + k];
-            switch (fmt) {
-            case DSA_FFTR_REAL: cr = g; ci = 0; break;
-            case DSA_FFTR_IMAG: cr = 0; ci = g; break;
-            case DSA_FFTR_AMPLITUDE: {
-                T a = dsa_sqrt(re * re + im * im);
-                T sc = a > T(0) ? g / a : T(0);
-                cr = sc * re; ci = sc * im;
-                break;
-            }
-            default: cr = T(2) * g * re; ci = T(2) * g * im;
-            }
-        } else {
-            // keep (re, im) for now; the cotangent of s needs the row maximum when floored
-            cr = re; ci = im;
-            T sv = re * re + im * im + eps;
-            smax = sv > smax ? sv : smax;
-        }
-        Cre[k] = cr;
-        Cim[k] = ci;
-    }
-    if (out_kind == 1 && !complex_out) {
-        // cotangent of s = |X|^2 + eps through the formatter and the relative floor
-        // s' = max(s, m * floor), m = amax(s) (spec.py:173-177): floored bins pass their
-        // cotangent (times floor) to the arg-max bin.
-        T* gsarr = Cim + K;
-        T m = use_floor ? block_max(smax, scratch) : T(0);
-        T fl = m * floor_lin;
-        __syncthreads();
-        T lost = 0;
-        for (int k = threadIdx.x; k < K; k += blockDim.x) {
-            T re = Cre[k], im = Cim[k];
-            T sv = re * re + im * im + eps;
-            bool floored = use_floor && sv < fl;
-            T se = floored ? fl : sv;
-            T g = gy[f * K + k];
-            T gs;
-            switch (fmt) {
-            case DSA_SPEC_DB: gs = g * T(4.342944819032518) / se; break;  // 10 / ln 10
-            case DSA_SPEC_LOGMAG: gs = g * T(0.5) / se; break;
-            case DSA_SPEC_MAG: gs = g * T(0.5) / dsa_sqrt(se); break;
-            default: gs = g;
-            }
-            if (floored) {
-                lost += gs;
-                gs = 0;
-            }
-            gsarr[k] = gs;
-        }
-        T tot = use_floor ? block_sum(lost, scratch) * floor_lin : T(0);
-        __syncthreads();
-        for (int k = threadIdx.x; k < K; k += blockDim.x) {
-            T re = Cre[k], im = Cim[k];
-            T gs = gsarr[k];
-            if (use_floor && (re * re + im * im + eps) == m) gs += tot;
-            Cre[k] = T(2) * gs * re;
-            Cim[k] = T(2) * gs * im;
-        }
-    }
-    __syncthreads();
-    if (FFT) {
-        // sum_k Re(C[k] e^{+i theta k l}) = Re FFT(conj(C), zero-extended to nfft points)[l]
-        for (int k = threadIdx.x; k < nfft; k += blockDim.x) {
-            fre[k] = k < K ? Cre[k] : T(0);
-            fim[k] = k < K ? -Cim[k] : T(0);
-        }
-        __syncthreads();
-        lds_fft_pow2(fre, fim, nfft, lg, twiddle);
-    }
-    T gsum = 0;
-    for (int l = threadIdx.x; l < L; l += blockDim.x) {
-        T g = 0;
-        if (FFT) {
-            if (l < Lc) g = fre[fft_brev(l, lg)];
-        } else if (l < Lc) {
-            int idx = 0;
-            for (int k = 0; k < K; ++k) {
-                g += Cre[k] * twiddle[2 * idx] + Cim[k] * twiddle[2 * idx + 1];
-                idx += l;
-                if (idx >= nfft) idx -= nfft;
-            }
-        }
-        if (gwpart) gwpart[f * L + l] = g * xc[l];
-        T gf = w ? g * w[l] : g;
-        gsum += gf;
-        gframe[f * L + l] = gf;
-    }
-    if (zmean) {
-        T gm = block_sum(gsum, scratch) / T(L);
-        for (int l = threadIdx.x; l < L; l += blockDim.x) gframe[f * L + l] -= gm;
-    }
-}
-
-// out[l] = sum_f part[f, l] in a fixed order (deterministic window gradient)
-template <typename T>
-__global__ void colsum_kernel(const T* __restrict__ part, long F, int L, T* __restrict__ out)
-{
-    __shared__ T scratch[16];
-    int l = blockIdx.x;
-    T acc = 0;
-    for (long f = threadIdx.x; f < F; f += blockDim.x) acc += part[f * L + l];
-    T s = block_sum(acc, scratch);
-    if (threadIdx.x == 0) out[l] = s;
-}
-
-// Spectrum with a denominator (spec.py:160-171): combines |B| and |A| amplitude rows.
-// ab:(F,K) or NULL, aa:(F,K) or NULL (at least aa here), gain:(F) = a[:,0].
-template <typename T>
-__global__ void spec_ratio_kernel(const T* __restrict__ ab, const T* __restrict__ aa,
-                                  const T* __restrict__ a, int la, int K, T eps, int use_floor,
-                                  T floor_lin, int fmt, T* __restrict__ y)
-{
-    __shared__ T scratch[16];
-    long f = blockIdx.x;
-    T gain = a[f * la];
-    T smax = 0;
-    for (int k = threadIdx.x; k < K; k += blockDim.x) {
-        T X = ab ? gain * (ab[f * K + k] / aa[f * K + k]) : gain / aa[f * K + k];
-        T s = X * X + eps;
-        smax = s > smax ? s : smax;
-        y[f * K + k] = use_floor ? s : spec_format(s, fmt);
-    }
-    if (use_floor) {
-        T m = block_max(smax, scratch);
-        __syncthreads();
-        for (int k = threadIdx.x; k < K; k += blockDim.x) {
-            T s = y[f * K + k];
-            T fl = m * floor_lin;
-            y[f * K + k] = spec_format(s > fl ? s : fl, fmt);
-        }
-    }
-}
-
-// Backward of Spectrum with a denominator (spec.py:160-177): X = K |B| / |A| (or K / |A| when b is
-// absent), s = X^2 + eps -> floor -> format.  One block per row; B(w), A(w) recomputed by direct DFT.
-//   Xbar = 2 X sbar;  |B|bar = Xbar K / |A|;  |A|bar = -Xbar X / |A|;  Kbar = sum_k Xbar X / K
-//   bbar[l] = Re sum_k (|B|bar B/|B|) e^{+i theta k l}   (same for a[1:], a[0] = K gets Kbar)
-// dynamic LDS: (lb + la + 5K) elements of T.
-template <typename T>
-__global__ void spec_ratio_bwd_kernel(const T* __restrict__ gy, const T* __restrict__ b, int lb,
-                                      const T* __restrict__ a, int la, int nfft, const T* __restrict__ twiddle,
-                                      T eps, int use_floor, T floor_lin, int fmt, T* __restrict__ gb,
-                                      T* __restrict__ ga)
-{
-    extern __shared__ unsigned char smem_raw[];
-    __shared__ T scratch[16];
-    const int K = nfft / 2 + 1;
-    T* bs = reinterpret_cast<T*>(smem_raw);
-    T* as = bs + lb;            // a1 = [1, a[1:]]
-    T* Bre = as + la;
-    T* Bim = Bre + K;
-    T* Are = Bim + K;
-    T* Aim = Are + K;
-    T* gsv = Aim + K;           // cotangent of s per bin, later Xbar
-    const long f = blockIdx.x;
-    const int Lb = lb < nfft ? lb : nfft, La = la < nfft ? la : nfft;
-    for (int l = threadIdx.x; l < lb; l += blockDim.x) bs[l] = b ? b[f * lb + l] : T(0);
-    for (int l = threadIdx.x; l < la; l += blockDim.x) as[l] = l == 0 ? T(1) : a[f * la + l];
-    __syncthreads();
-    const T gain = a[f * la];
-    T smax = 0;
-    for (int k = threadIdx.x; k < K; k += blockDim.x) {
-        T br = 0, bi = 0, ar = 0, ai = 0;
-        int idx = 0;
-        for (int l = 0; l < (Lb > La ? Lb : La); ++l) {
-            const T c = twiddle[2 * idx], sn = twiddle[2 * idx + 1];
-            if (b && l < Lb) { br += bs[l] * c; bi += bs[l] * sn; }
-            if (l < La) { ar += as[l] * c; ai += as[l] * sn; }
-            idx += k;
-            if (idx >= nfft) idx -= nfft;
-        }
-        Bre[k] = br; Bim[k] = bi; Are[k] = ar; Aim[k] = ai;
-        const T ab = b ? dsa_sqrt(br * br + bi * bi) : T(1), aa = dsa_sqrt(ar * ar + ai * ai);
-        const T X = gain * ab / aa;
-        const T sv = X * X + eps;
-        smax = sv > smax ? sv : smax;
-    }
-    const T m = use_floor ? block_max(smax, scratch) : T(0);
-    const T fl = m * floor_lin;
-    __syncthreads();
-    T lost = 0;
-    for (int k = threadIdx.x; k < K; k += blockDim.x) {
-        const T ab = b ? dsa_sqrt(Bre[k] * Bre[k] + Bim[k] * Bim[k]) : T(1);
-        const T aa = dsa_sqrt(Are[k] * Are[k] + Aim[k] * Aim[k]);
-        const T X = gain * ab / aa;
-        const T sv = X * X + eps;
-        const bool floored = use_floor && sv < fl;
-        const T se = floored ? fl : sv;
-        T g = gy[f * K + k];
-        switch (fmt) {
-        case DSA_SPEC_DB: g *= T(4.342944819032518) / se; break;
-        case DSA_SPEC_LOGMAG: g *= T(0.5) / se; break;
-        case DSA_SPEC_MAG: g *= T(0.5) / dsa_sqrt(se); break;
-        default: break;
-        }
-        if (floored) { lost += g; g = 0; }
-        gsv[k] = g;
-    }
-    const T tot = use_floor ? block_sum(lost, scratch) * floor_lin : T(0);
-    __syncthreads();
-    T kacc = 0;
-    for (int k = threadIdx.x; k < K; k += blockDim.x) {
-        const T ab = b ? dsa_sqrt(Bre[k] * Bre[k] + Bim[k] * Bim[k]) : T(1);
-        const T aa = dsa_sqrt(Are[k] * Are[k] + Aim[k] * Aim[k]);
-        const T X = gain * ab / aa;
-        T gs = gsv[k];
-        if (use_floor && (X * X + eps) == m) gs += tot;
-        const T Xbar = T(2) * X * gs;
-        kacc += Xbar * ab / aa;                       // dX/dK = |B|/|A|
-        const T abar_b = Xbar * gain / aa;            // d/d|B|
-        const T abar_a = -Xbar * X / aa;              // d/d|A|
-        // complex cotangents of B and A through the amplitude (0 at an exact zero, like torch.abs)
-        const T sb = (b && ab > T(0)) ? abar_b / ab : T(0), sa = aa > T(0) ? abar_a / aa : T(0);
-        Bre[k] *= sb; Bim[k] *= sb; Are[k] *= sa; Aim[k] *= sa;
-    }
-    const T kbar = block_sum(kacc, scratch);
-    __syncthreads();
-    for (int l = threadIdx.x; l < (lb > la ? lb : la); l += blockDim.x) {
-        T accb = 0, acca = 0;
-        if (l < nfft) {
-            int idx = 0;
-            for (int k = 0; k < K; ++k) {
-                const T c = twiddle[2 * idx], sn = twiddle[2 * idx + 1];
-                accb += Bre[k] * c + Bim[k] * sn;
-                acca += Are[k] * c + Aim[k] * sn;
-                idx += l;
-                if (idx >= nfft) idx -= nfft;
-            }
-        }
-        if (gb && l < lb) gb[f * lb + l] = accb;
-        if (l < la) ga[f * la + l] = l == 0 ? kbar : acca;
-    }
-}
-
-// remove_gain (utils/private.py:200-209): a1 = [1, a[1:]]
-template <typename T>
-__global__ void remove_gain_kernel(const T* __restrict__ a, long F, int la, T* __restrict__ a1)
-{
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= F * la) return;
-    a1[i] = (i % la == 0) ? T(1) : a[i];
-}
 
 // =========================================================================== tuned rFFT-512 path
 
@@ -1086,305 +413,6 @@ __global__ __launch_bounds__(128, 4) void stft512_fwd_kernel(
 #include "stft_bwd_pk_big.h"
 namespace dsa {
 
-// ------------------------------------------------------------------ host-side dispatch helpers
-template <typename T>
-static int launch_row_dft(const void* x, int64_t B, int64_t Tlen, int64_t N, int L, int P, int left,
-                          int mode, int zmean, const void* w, int nfft, const void* twiddle,
-                          int out_kind, int fmt, double eps, int use_floor, double floor_db,
-                          void* y, hipStream_t st)
-{
-    int64_t F = B * N;
-    if (F == 0) return DSA_OK;
-    T floor_lin = use_floor ? (T)pow(10.0, floor_db / 10.0) : T(0);
-    size_t lds = sizeof(T) * (size_t)L;
-    int threads = nfft / 2 + 1 >= 192 ? 256 : (nfft / 2 + 1 >= 96 ? 128 : 64);
-    // power-of-two lengths: radix-2 FFT in LDS (DSA_ROWDFT_DIRECT=1 keeps the direct sum, for A/B runs and tests)
-    static const bool direct_only = [] {
-        const char* e = getenv("DSA_ROWDFT_DIRECT");
-        return e && atoi(e) != 0;
-    }();
-    const size_t lds_fft = lds + sizeof(T) * 2 * (size_t)nfft;
-    if (!direct_only && nfft >= 32 && (nfft & (nfft - 1)) == 0 && lds_fft <= 150 * 1024) {
-        static std::atomic<uint64_t> lds_set{0};
-        if (lds_fft > 48 * 1024 &&
-            !ensure_dynamic_lds(reinterpret_cast<const void*>(&row_dft_kernel<T, true>), 150 * 1024, lds_set))
-            return fail(DSA_ERR_LAUNCH, "row_fft: cannot raise the dynamic LDS limit%s");
-        hipLaunchKernelGGL((row_dft_kernel<T, true>), dim3((unsigned)F), dim3(nfft >= 512 ? 256 : threads), lds_fft, st,
-                           (const T*)x, (long)Tlen, (long)N, L, P, left, mode, zmean, (const T*)w, nfft, (const T*)twiddle,
-                           out_kind, fmt, (T)eps, use_floor, floor_lin, (T*)y);
-        return check_launch("row_fft_generic");
-    }
-    if (lds > 60 * 1024) return fail(DSA_ERR_UNSUPPORTED, "row_dft: frame too long for LDS%s");
-    hipLaunchKernelGGL((row_dft_kernel<T>), dim3((unsigned)F), dim3(threads), lds, st, (const T*)x,
-                       (long)Tlen, (long)N, L, P, left, mode, zmean, (const T*)w, nfft,
-                       (const T*)twiddle, out_kind, fmt, (T)eps, use_floor, floor_lin, (T*)y);
-    return check_launch("row_dft_generic");
-}
-
-// ---------------------------------------------------------------------------------------------
-// Generalized cepstral transformation in ONE launch (GeneralizedCepstrumToGeneralizedCepstrum._forward, mgc2mgc.py:333-361):
-//   c01 = (0, c1[1:]) -> C1 = fft(c01, n) -> s = (1 + g1 C1)^(1/g1) (g1 = 0: exp C1) -> C2 = (|s|^g2 cos(g2 angle(s)) - 1) / g2
-//   (g2 = 0: log |s|) -> c02 = ifft(C2).real[: M2 + 1] -> c2 = (c1[0], 2 c02[1:]).
-// One workgroup per row, the n complex points in LDS; both transforms are the radix-2 LDS transform above: c01 is real, so C1 is
-// Hermitian and C2 is real and even -- its inverse transform IS its forward transform / n, and only the real parts leave.
-// As separate launches (row transform -> five element-wise operators -> adjoint row transform, modules/mgc2mgc.py) the
-// 4096-point spectra of the MLSA filter's impulse responses went through memory seven times (profiles/r02_mlsa_single_stage_trace.txt:
-// 7.2 of the 8.3 ms of the single-stage mode).  Forward only (the module composes the differentiable operators when a gradient is
-// wanted).
-// ---------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void gc2gc_fused_kernel(const T* __restrict__ c1, int n_in, int out_order, T g1, T g2, int nfft,
-                                                         const T* __restrict__ tw, int flags, T* __restrict__ c2)
-{
-    // Both transforms act on REAL data (c01, and the real even C2), so each runs as a complex transform of HALF the length on
-    // the packed sequence z[n] = x[2n] + i x[2n+1], followed by the split  X[k] = (Z[k] + conj Z[H-k]) / 2 - i W^k (Z[k] - conj Z[H-k]) / 2
-    // (H = n / 2): half the butterflies and half the LDS traffic of the full-length version (2.59 -> see DESIGN ms per 51 200 rows
-    // of 4096 points).  LDS: re[H] | im[H] | cb[H + 1] (the mapped half spectrum, natural order).
-    extern __shared__ unsigned char smem_raw[];
-    const int H = nfft >> 1;
-    T* re = reinterpret_cast<T*>(smem_raw);
-    T* im = re + H;
-    T* cb = im + H;
-    const long f = blockIdx.x;
-    const T* row = c1 + f * n_in;
-    const int lgh = 30 - __clz(nfft);   // log2(H)
-    // flags: the per-row scalar steps mgc2mgc.py:217-300 wraps around the transformation, folded in (each was a pass over the
-    // row in memory): 1 gnorm(in_gamma) before, 2 ignorm(out_gamma) after, 4 tail times out_gamma, 8 zeroth coefficient * out_gamma + 1
-    T k0 = row[0], tin = T(1);
-    if (flags & 1) {   // gnorm.py:99-109
-        if (g1 == T(0)) k0 = dsa_exp(row[0]);
-        else {
-            const T z = T(1) + g1 * row[0];
-            k0 = dsa_pow(z, T(1) / g1);
-            tin = T(1) / z;
-        }
-    }
-    for (int n = threadIdx.x; n < H; n += blockDim.x) {   // fft(c01, n): longer rows are cropped, c01[0] = 0
-        const int i0 = 2 * n, i1 = 2 * n + 1;
-        re[n] = (i0 >= 1 && i0 < n_in) ? row[i0] * tin : T(0);
-        im[n] = i1 < n_in ? row[i1] * tin : T(0);
-    }
-    __syncthreads();
-    lds_fft_pow2(re, im, H, lgh, tw, 2);   // Z[k] at position brev(k)
-    constexpr T kPi = T(3.14159265358979323846);
-    auto gmap = [&](T cr, T ci) -> T {
-        T lmag, ang;   // log |s|, angle(s) (wrapped to (-pi, pi] as .angle() of the reference's polar(r, theta) is)
-        if (g1 == T(0)) {
-            lmag = cr;
-            ang = ci;
-        } else {
-            const T zr = T(1) + g1 * cr, zi = g1 * ci;
-            lmag = T(0.5) * dsa_log(zr * zr + zi * zi) / g1;
-            ang = atan2(zi, zr) / g1;
-        }
-        if (g2 == T(0)) return lmag;
-        ang -= T(2) * kPi * rint(ang / (T(2) * kPi));
-        return (dsa_exp(g2 * lmag) * cos(ang * g2) - T(1)) / g2;
-    };
-    // split into X[k], X[H - k] and map both (C2 is real and even: cb[k], k = 0 .. H, carries it all)
-    for (int k = threadIdx.x; k <= (H >> 1); k += blockDim.x) {
-        if (k == 0) {
-            const T zr = re[0], zi = im[0];
-            cb[0] = gmap(zr + zi, T(0));
-            cb[H] = gmap(zr - zi, T(0));
-        } else {
-            const int pa = fft_brev(k, lgh), pb = fft_brev(H - k, lgh);
-            const T ar = re[pa], ai = im[pa], br = re[pb], bi = -im[pb];          // A = Z[k], B = conj Z[H - k]
-            const T sr = T(0.5) * (ar + br), si = T(0.5) * (ai + bi), dr = T(0.5) * (ar - br), di = T(0.5) * (ai - bi);
-            const T wr = tw[2 * k], wi = tw[2 * k + 1];                            // W_n^k = (cos, -sin)(2 pi k / n)
-            const T pr = wr * dr - wi * di, pi_ = wr * di + wi * dr;              // W D
-            cb[k] = gmap(sr + pi_, si - pr);                                       // X[k]     = S - i W D
-            cb[H - k] = gmap(sr - pi_, -si - pr);                                  // X[H - k] = conj(S + i W D)
-        }
-    }
-    __syncthreads();
-    for (int m = threadIdx.x; m < H; m += blockDim.x) {   // pack the even sequence C2[0 .. n - 1]: C2[j] = cb[j <= H ? j : n - j]
-        const int j0 = 2 * m, j1 = 2 * m + 1;
-        re[m] = cb[j0 <= H ? j0 : nfft - j0];
-        im[m] = cb[j1 <= H ? j1 : nfft - j1];
-    }
-    __syncthreads();
-    lds_fft_pow2(re, im, H, lgh, tw, 2);
-    T* out = c2 + f * (long)(out_order + 1);
-    T sc = T(2) / T(nfft), o0 = k0;
-    if (flags & 2) {   // ignorm.py:99-109
-        if (g2 == T(0)) o0 = dsa_log(k0);
-        else {
-            const T zz = dsa_pow(k0, g2);
-            o0 = (zz - T(1)) / g2;
-            sc *= zz;
-        }
-    }
-    if (flags & 4) sc *= g2;
-    if (flags & 8) o0 = o0 * g2 + T(1);
-    for (int m = threadIdx.x; m <= out_order; m += blockDim.x) {
-        T v;
-        if (m == 0) {
-            v = o0;
-        } else {
-            const int n = m <= H ? m : nfft - m;   // the inverse transform of a real even spectrum is even
-            T y;                                   // Re of the length-n transform of C2 at index n
-            if (n == H) {
-                y = re[0] - im[0];
-            } else {
-                const int pa = fft_brev(n, lgh), pb = fft_brev(H - n, lgh);
-                const T ar = re[pa], ai = im[pa], br = re[pb], bi = -im[pb];
-                const T dr = T(0.5) * (ar - br), di = T(0.5) * (ai - bi);
-                y = T(0.5) * (ar + br) + tw[2 * n] * di + tw[2 * n + 1] * dr;
-            }
-            v = sc * y;
-        }
-        out[m] = v;
-    }
-}
-
-// Backward of gc2gc_fused_kernel (flags = 0) in ONE launch per row: gc1 from the row c1 and the cotangent g2 of c2.
-//   c2[0] = c1[0];  c2[m] = 2 c02[m],  c02 = Re ifft(C2),  C2[k] = f(X[k]) for the half spectrum k = 0 .. H of X = fft(c01).
-// Three half-length transforms in LDS: X is recomputed from c01; the cotangent of the even spectrum is a cosine transform of
-// g2, gcb[k] = (2 / n) w_k Re fft(g)[k] (w = 1 at k = 0, H, else 2: cb[k] is read for j = k and j = n - k); the element-wise
-// chain rule gives (gXr, gXi)[k]; and gc01[m] = sum_{k=0}^{H} gXr[k] cos(2 pi k m / n) - gXi[k] sin(2 pi k m / n) is the
-// unnormalised inverse real transform of the Hermitian spectrum Y (Y[0] = gXr[0], Y[H] = gXr[H], Y[k] = (gXr + i gXi)[k] / 2),
-// run as the conjugate of a forward half-length transform of Z[k] = E[k] + i O[k], E = (Y[k] + conj Y[H-k]) / 2,
-// O = conj(W)^k (Y[k] - conj Y[H-k]) / 2.  LDS: re[H] | im[H] | xr[H+1] | xi[H+1] | gcb[H+1].
-template <typename T>
-__global__ __launch_bounds__(256) void gc2gc_fused_bwd_kernel(const T* __restrict__ c1, const T* __restrict__ g2row, int n_in,
-                                                             int out_order, T g1, T g2, int nfft, const T* __restrict__ tw,
-                                                             T* __restrict__ gc1)
-{
-    extern __shared__ unsigned char smem_raw[];
-    const int H = nfft >> 1;
-    T* re = reinterpret_cast<T*>(smem_raw);
-    T* im = re + H;
-    T* xr = im + H;
-    T* xi = xr + (H + 1);
-    T* gcb = xi + (H + 1);
-    const long f = blockIdx.x;
-    const T* row = c1 + f * n_in;
-    const T* grow = g2row + f * (long)(out_order + 1);
-    const int lgh = 30 - __clz(nfft);
-    constexpr T kPi = T(3.14159265358979323846);
-    // half-length transform of a packed real sequence, then the split into the half spectrum (dr, di)[0 .. H]
-    auto split_to = [&](T* dr, T* di) {
-        for (int k = threadIdx.x; k <= (H >> 1); k += blockDim.x) {
-            if (k == 0) {
-                const T zr = re[0], zi = im[0];
-                dr[0] = zr + zi;
-                dr[H] = zr - zi;
-                if (di) {
-                    di[0] = T(0);
-                    di[H] = T(0);
-                }
-            } else {
-                const int pa = fft_brev(k, lgh), pb = fft_brev(H - k, lgh);
-                const T ar = re[pa], ai = im[pa], br = re[pb], bi = -im[pb];
-                const T sr = T(0.5) * (ar + br), si = T(0.5) * (ai + bi), dr_ = T(0.5) * (ar - br), di_ = T(0.5) * (ai - bi);
-                const T wr = tw[2 * k], wi = tw[2 * k + 1];
-                const T pr = wr * dr_ - wi * di_, pi_ = wr * di_ + wi * dr_;
-                dr[k] = sr + pi_;
-                dr[H - k] = sr - pi_;
-                if (di) {
-                    di[k] = si - pr;
-                    di[H - k] = -si - pr;
-                }
-            }
-        }
-    };
-    // ---- X = fft(c01) ----
-    for (int n = threadIdx.x; n < H; n += blockDim.x) {
-        const int i0 = 2 * n, i1 = 2 * n + 1;
-        re[n] = (i0 >= 1 && i0 < n_in) ? row[i0] : T(0);
-        im[n] = i1 < n_in ? row[i1] : T(0);
-    }
-    __syncthreads();
-    lds_fft_pow2(re, im, H, lgh, tw, 2);
-    split_to(xr, xi);
-    __syncthreads();
-    // ---- cosine transform of the cotangent: g[0] = 0, g[m] = g2[m] ----
-    for (int n = threadIdx.x; n < H; n += blockDim.x) {
-        const int i0 = 2 * n, i1 = 2 * n + 1;
-        re[n] = (i0 >= 1 && i0 <= out_order) ? grow[i0] : T(0);
-        im[n] = i1 <= out_order ? grow[i1] : T(0);
-    }
-    __syncthreads();
-    lds_fft_pow2(re, im, H, lgh, tw, 2);
-    split_to(gcb, static_cast<T*>(nullptr));
-    __syncthreads();
-    // ---- element-wise chain rule: (xr, xi)[k] <- (gXr, gXi)[k] ----
-    for (int k = threadIdx.x; k <= H; k += blockDim.x) {
-        const T cr = xr[k], ci = xi[k];
-        const T gc = gcb[k] * ((k == 0 || k == H) ? T(2) : T(4)) / T(nfft);
-        T lmag, ang, l_r, l_i, a_r, a_i;   // log |s|, angle(s) and their partial derivatives with respect to (cr, ci)
-        if (g1 == T(0)) {
-            lmag = cr; ang = ci;
-            l_r = T(1); l_i = T(0); a_r = T(0); a_i = T(1);
-        } else {
-            const T zr = T(1) + g1 * cr, zi = g1 * ci, r2 = zr * zr + zi * zi;
-            lmag = T(0.5) * dsa_log(r2) / g1;
-            ang = atan2(zi, zr) / g1;
-            l_r = zr / r2; l_i = zi / r2; a_r = -zi / r2; a_i = zr / r2;
-        }
-        T f_l, f_a;
-        if (g2 == T(0)) {
-            f_l = T(1); f_a = T(0);
-        } else {
-            ang -= T(2) * kPi * rint(ang / (T(2) * kPi));
-            const T e = dsa_exp(g2 * lmag);
-            f_l = e * cos(ang * g2);
-            f_a = -e * sin(ang * g2);
-        }
-        xr[k] = gc * (f_l * l_r + f_a * a_r);
-        xi[k] = gc * (f_l * l_i + f_a * a_i);
-    }
-    __syncthreads();
-    // ---- gc01 = 2 * conj(fft_H(conj Z)) unpacked ----
-    for (int k = threadIdx.x; k < H; k += blockDim.x) {
-        T yr, yi, br, bi;                      // Y[k], conj Y[H - k]
-        if (k == 0) {
-            yr = xr[0]; yi = T(0);
-            br = xr[H]; bi = T(0);
-        } else {
-            yr = T(0.5) * xr[k]; yi = T(0.5) * xi[k];
-            br = T(0.5) * xr[H - k]; bi = -T(0.5) * xi[H - k];
-        }
-        const T er = T(0.5) * (yr + br), ei = T(0.5) * (yi + bi), dr = T(0.5) * (yr - br), di = T(0.5) * (yi - bi);
-        const T wr = tw[2 * k], wi = -tw[2 * k + 1];            // conj(W)^k = (cos, +sin)(2 pi k / n)
-        const T or_ = wr * dr - wi * di, oi = wr * di + wi * dr;  // O[k]
-        // Z = E + i O = (er - oi) + i (ei + or); the transform runs on conj Z
-        re[k] = er - oi;
-        im[k] = -(ei + or_);
-    }
-    __syncthreads();
-    lds_fft_pow2(re, im, H, lgh, tw, 2);
-    T* out = gc1 + f * n_in;
-    for (int m = threadIdx.x; m < n_in; m += blockDim.x) {
-        T v;
-        if (m == 0) {
-            v = grow[0];
-        } else if (m >= nfft) {
-            v = T(0);                          // (rows longer than the transform are cropped by the forward)
-        } else {
-            const int pos = fft_brev(m >> 1, lgh);
-            v = T(2) * ((m & 1) ? -im[pos] : re[pos]);
-        }
-        out[m] = v;
-    }
-}
-
-template <typename T>
-static int gc2gc_launch(const void* c1, int64_t F, int n_in, int out_order, double g1, double g2, int nfft, const void* tw, int flags,
-                        void* c2, hipStream_t st)
-{
-    const size_t lds = sizeof(T) * (3 * (size_t)(nfft / 2) + 1);
-    static std::atomic<uint64_t> lds_set{0};
-    if (lds > 48 * 1024 && !ensure_dynamic_lds(reinterpret_cast<const void*>(&gc2gc_fused_kernel<T>), 150 * 1024, lds_set))
-        return fail(DSA_ERR_LAUNCH, "gc2gc: cannot raise the dynamic LDS limit%s");
-    // short transforms: one wave per row (two butterflies per lane and pass, the passes' barriers are single-wave barriers)
-    const int block = nfft <= 1024 ? 64 : 256;
-    hipLaunchKernelGGL((gc2gc_fused_kernel<T>), dim3((unsigned)F), dim3(block), lds, st, (const T*)c1, n_in, out_order, (T)g1, (T)g2, nfft,
-                       (const T*)tw, flags, (T*)c2);
-    return check_launch("gc2gc_fused");
-}
-
 // Backward of stft512_fwd_kernel (autograd of stft.py:237-241), same
 // wave-per-pass structure and LDS tile.  Per pass of 4 frames:
 //   recompute Z (stage, window, FFT-256) -> split into X[k] -> cotangent S[k] of the half spectrum
@@ -1685,330 +713,11 @@ static int stft512_lds_bytes(int L, int P, int* io_floats)
 
 static int stft512_lds_bytes2() { return 2 * kFPW * kZS * 8 + 256 * 8 + 2 * kFPW * 4; }   // two waves + the shared table
 
-// ---- inverse path helpers ----
-// irfft(Y)[n] = sum_k c_k / N Re(Y_k e^{+2 pi i k n / N}), c = 1 at DC / Nyquist, 2 in between (ifftr.py:138):
-// that is the ADJOINT of rfft (the backward kernels of this file) applied to G_k = c_k / N Y_k.
-template <typename T>
-__global__ void irfft_scale_kernel(const T* __restrict__ y, long total, int K, int nfft, T* __restrict__ out)
-{
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;   // complex element index
-    if (i >= total) return;
-    const int k = (int)(i % K);
-    const T c = ((k == 0 || k == nfft / 2) ? T(1) : T(2)) / T(nfft);
-    out[2 * i] = y[2 * i] * c;
-    out[2 * i + 1] = y[2 * i + 1] * c;
-}
-// Unframe._forward unframe.py:203-205: x / (sum of squared windows + 1e-16), the divisor shared by all rows
-template <typename T>
-__global__ void div_rows_kernel(const T* __restrict__ x, long B, long Tlen, const T* __restrict__ d, T eps,
-                                T* __restrict__ out)
-{
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= Tlen) return;
-    const T r = T(1) / (d[t] + eps);
-    for (long b = blockIdx.y; b < B; b += gridDim.y) out[b * Tlen + t] = x[b * Tlen + t] * r;
-}
-
-// One Griffin-Lim phase update (griffin.py:263-282), element-wise over (B, N, K) complex bins:
-//   t' = t (first) or (1 - gamma) d_prev + gamma t;   diff = t' - t_prev;   c = t' + alpha diff;   d = t' + beta diff;
-//   z = sqrt(y + 1e-16) * c / (|c| + eps);   t_prev <- t',  d_prev <- d.
-// t:(B, Nt, K) is the STFT of the previous estimate (Nt >= N frames; the extra ones are dropped, griffin.py:270);
-// t == nullptr initialises: z = sqrt(y + 1e-16) * exp(i phase) (phase == nullptr: zeros).
-template <typename T>
-__global__ void griffin_update_kernel(const T* __restrict__ t, long B, long Nt, long N, int K, const T* __restrict__ y,
-                                      const T* __restrict__ phase, T* __restrict__ t_prev, T* __restrict__ d_prev, int first,
-                                      T alpha, T beta, T gamma, T eps, T* __restrict__ z)
-{
-    const long NK = N * K, total = B * NK;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const T s = dsa_sqrt(y[i] + T(1e-16));   // griffin.py:263-264
-        T cr, ci;
-        if (!t) {
-            const T ph = phase ? phase[i] : T(0);
-            z[2 * i] = s * dsa_cos(ph);
-            z[2 * i + 1] = s * dsa_sin(ph);
-            continue;
-        }
-        const long b = i / NK;
-        const long it = b * Nt * K + (i - b * NK);
-        T tr = t[2 * it], ti = t[2 * it + 1], dr, di;
-        if (first) {
-            cr = dr = tr;
-            ci = di = ti;
-        } else {
-            tr = (T(1) - gamma) * d_prev[2 * i] + gamma * tr;
-            ti = (T(1) - gamma) * d_prev[2 * i + 1] + gamma * ti;
-            const T fr = tr - t_prev[2 * i], fi = ti - t_prev[2 * i + 1];
-            cr = tr + alpha * fr;
-            ci = ti + alpha * fi;
-            dr = tr + beta * fr;
-            di = ti + beta * fi;
-        }
-        t_prev[2 * i] = tr;
-        t_prev[2 * i + 1] = ti;
-        d_prev[2 * i] = dr;
-        d_prev[2 * i + 1] = di;
-        const T r = s / (dsa_sqrt(cr * cr + ci * ci) + eps);   // griffin.py:281
-        z[2 * i] = cr * r;
-        z[2 * i + 1] = ci * r;
-    }
-}
-
 }  // namespace dsa
 
 using namespace dsa;
 
 // =========================================================================== C-ABI
-
-DSA_EXPORT int dsa_version(void) { return DSA_VERSION; }
-DSA_EXPORT const char* dsa_last_error(void) { return err_buf(); }
-DSA_EXPORT const char* dsa_last_kernel(void) { return kernel_name(); }
-DSA_EXPORT int dsa_device_count(void)
-{
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess) return fail(DSA_ERR_NO_DEVICE, "hipGetDeviceCount: %s", hipGetErrorString(e));
-    return n;
-}
-DSA_EXPORT int64_t dsa_num_frames(int64_t T, int32_t P) { return (T <= 0 || P <= 0) ? 0 : (T - 1) / P + 1; }
-
-DSA_EXPORT int dsa_frame_fwd(const void* x, int64_t B, int64_t T, int32_t L, int32_t P, int32_t center,
-                             int32_t zmean, int32_t pad_mode, int32_t dtype, void* y, void* stream)
-{
-    DSA_REQUIRE(L > 0 && P > 0 && T > 0 && B >= 0, "frame: sizes must be positive");
-    DSA_REQUIRE(pad_mode >= 0 && pad_mode <= 3, "frame: unknown pad mode");
-    // F.pad(mode="reflect") needs every pad amount -- (L//2, (L-1)//2) centred, (0, L-1) otherwise, frame.py:130-137 --
-    // below the signal length
-    DSA_REQUIRE(pad_mode != DSA_PAD_REFLECT || (center ? L / 2 : L - 1) < T || L == 1,
-                "frame: reflect padding needs pad < input length");
-    int64_t N = dsa_num_frames(T, P), F = B * N;
-    if (F == 0) return DSA_OK;
-    int left = center ? L / 2 : 0;
-    int threads = L >= 192 ? 256 : (L >= 96 ? 128 : 64);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == DSA_F32 && !zmean && (L & 3) == 0 && (((size_t)y) & 15) == 0 && F * (int64_t)L >= 4096) {
-        const int src_aligned = (P & 3) == 0 && (left & 3) == 0 && (T & 3) == 0 && (((size_t)x) & 15) == 0;
-        long blocks = (long)((F * (int64_t)(L >> 2) + 255) / 256);
-        if (blocks > 256 * 16) blocks = 256 * 16;
-        hipLaunchKernelGGL(frame_fwd_vec4_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)x, (long)T, (long)N,
-                           (long)F, L, P, left, pad_mode, src_aligned, (float*)y);
-        return check_launch("frame_fwd_vec4");
-    }
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((frame_fwd_kernel<float>), dim3((unsigned)F), dim3(threads), 0, st,
-                           (const float*)x, (long)T, (long)N, L, P, left, zmean, pad_mode, (float*)y);
-    else if (dtype == DSA_F64)
-        hipLaunchKernelGGL((frame_fwd_kernel<double>), dim3((unsigned)F), dim3(threads), 0, st,
-                           (const double*)x, (long)T, (long)N, L, P, left, zmean, pad_mode, (double*)y);
-    else
-        return fail(DSA_ERR_UNSUPPORTED, "frame: unsupported dtype%s");
-    return check_launch("frame_fwd");
-}
-
-template <typename T>
-static int frame_bwd_impl(const void* gy, int64_t B, int64_t Tlen, int L, int P, int center,
-                          int zmean, int pad_mode, void* gx, hipStream_t st)
-{
-    int64_t N = dsa_num_frames(Tlen, P), F = B * N;
-    int left = center ? L / 2 : 0;
-    T* gmean = nullptr;
-    if (zmean) {
-        // d/dx of (y - mean(y)) = g - mean(g): per-frame mean of the cotangent
-        if (hipMallocAsync((void**)&gmean, sizeof(T) * (size_t)F, st) != hipSuccess)
-            return fail(DSA_ERR_LAUNCH, "frame_bwd: workspace allocation failed%s");
-        hipLaunchKernelGGL((row_mean_kernel<T>), dim3((unsigned)F), dim3(64), 0, st, (const T*)gy, L, gmean);
-    }
-    if (pad_mode == DSA_PAD_CONSTANT) {
-        const int64_t nblk = ((Tlen + 255) / 256) * B;
-        if (nblk > 0x7fffffffLL) return fail(DSA_ERR_UNSUPPORTED, "frame_bwd: batch too large for one launch%s");
-        dim3 grid((unsigned)nblk);
-        hipLaunchKernelGGL((frame_bwd_const_kernel<T>), grid, dim3(256), 0, st, (const T*)gy, gmean,
-                           (long)Tlen, (long)N, L, P, left, (T*)gx);
-    } else {
-        hipLaunchKernelGGL((frame_bwd_general_kernel<T>), dim3((unsigned)B), dim3(256), 0, st,
-                           (const T*)gy, gmean, (long)Tlen, (long)N, L, P, left, pad_mode, (T*)gx);
-    }
-    int rc = check_launch("frame_bwd");
-    if (gmean) hipFreeAsync(gmean, st);
-    return rc;
-}
-
-DSA_EXPORT int dsa_frame_bwd(const void* gy, int64_t B, int64_t T, int32_t L, int32_t P, int32_t center,
-                             int32_t zmean, int32_t pad_mode, int32_t dtype, void* gx, void* stream)
-{
-    DSA_REQUIRE(L > 0 && P > 0 && T > 0 && B >= 0, "frame_bwd: sizes must be positive");
-    if (B == 0) return DSA_OK;
-    if (dtype == DSA_F32) return frame_bwd_impl<float>(gy, B, T, L, P, center, zmean, pad_mode, gx, (hipStream_t)stream);
-    if (dtype == DSA_F64) return frame_bwd_impl<double>(gy, B, T, L, P, center, zmean, pad_mode, gx, (hipStream_t)stream);
-    return fail(DSA_ERR_UNSUPPORTED, "frame_bwd: unsupported dtype%s");
-}
-
-DSA_EXPORT int dsa_window_fwd(const void* x, int64_t F, int32_t L, const void* w, int32_t L2, int32_t dtype,
-                              void* y, void* stream)
-{
-    DSA_REQUIRE(L > 0 && L2 > 0 && F >= 0, "window: sizes must be positive");
-    if (F == 0) return DSA_OK;
-    int64_t total = F * L2;
-    unsigned grid = (unsigned)((total + 255) / 256 > 65536 ? 65536 : (total + 255) / 256);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == DSA_F32) {
-        if (window_vec4_ok(x, y, w, F, L, L2)) {
-            const unsigned n4 = (unsigned)(F * (int64_t)(L >> 2));
-            hipLaunchKernelGGL(window_vec4_kernel, dim3((n4 + 255) / 256 > 16384 ? 16384 : (n4 + 255) / 256), dim3(256), 0, st,
-                               (const float4*)x, n4, (unsigned)(L >> 2), (const float4*)w, (float4*)y);
-            return check_launch("window_vec4");
-        }
-        hipLaunchKernelGGL((window_fwd_kernel<float>), dim3(grid), dim3(256), 0, st, (const float*)x,
-                           (long)F, L, (const float*)w, L2, (float*)y);
-    } else if (dtype == DSA_F64)
-        hipLaunchKernelGGL((window_fwd_kernel<double>), dim3(grid), dim3(256), 0, st, (const double*)x,
-                           (long)F, L, (const double*)w, L2, (double*)y);
-    else
-        return fail(DSA_ERR_UNSUPPORTED, "window: unsupported dtype%s");
-    return check_launch("window_fwd");
-}
-
-DSA_EXPORT int dsa_window_bwd(const void* gy, const void* x, int64_t F, int32_t L, const void* w, int32_t L2,
-                              int32_t dtype, void* gx, void* gw, void* stream)
-{
-    DSA_REQUIRE(L > 0 && L2 > 0 && F >= 0, "window_bwd: sizes must be positive");
-    if (F == 0) return DSA_OK;
-    int64_t total = F * L;
-    unsigned grid = (unsigned)((total + 255) / 256 > 65536 ? 65536 : (total + 255) / 256);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == DSA_F32) {
-        if (window_vec4_ok(gy, gx, w, F, L, L2)) {
-            const unsigned n4 = (unsigned)(F * (int64_t)(L >> 2));
-            hipLaunchKernelGGL(window_vec4_kernel, dim3((n4 + 255) / 256 > 16384 ? 16384 : (n4 + 255) / 256), dim3(256), 0, st,
-                               (const float4*)gy, n4, (unsigned)(L >> 2), (const float4*)w, (float4*)gx);
-        } else
-            hipLaunchKernelGGL((window_bwd_kernel<float>), dim3(grid), dim3(256), 0, st, (const float*)gy,
-                               (long)F, L, (const float*)w, L2, (float*)gx);
-        if (gw)
-            hipLaunchKernelGGL((window_gw_kernel<float>), dim3(L), dim3(256), 0, st, (const float*)gy,
-                               (const float*)x, (long)F, L, L2, (float*)gw);
-    } else if (dtype == DSA_F64) {
-        hipLaunchKernelGGL((window_bwd_kernel<double>), dim3(grid), dim3(256), 0, st, (const double*)gy,
-                           (long)F, L, (const double*)w, L2, (double*)gx);
-        if (gw)
-            hipLaunchKernelGGL((window_gw_kernel<double>), dim3(L), dim3(256), 0, st, (const double*)gy,
-                               (const double*)x, (long)F, L, L2, (double*)gw);
-    } else
-        return fail(DSA_ERR_UNSUPPORTED, "window_bwd: unsupported dtype%s");
-    return check_launch("window_bwd");
-}
-
-DSA_EXPORT int dsa_gc2gc_fwd(const void* c1, int64_t F, int32_t n_in, int32_t out_order, double in_gamma, double out_gamma,
-                             int32_t nfft, const void* twiddle, int32_t flags, int32_t dtype, void* c2, void* stream)
-{
-    DSA_REQUIRE(F >= 0 && n_in >= 1 && out_order >= 0, "gc2gc: sizes must be positive");
-    DSA_REQUIRE(nfft >= 4 && (nfft & (nfft - 1)) == 0, "gc2gc: n_fft must be a power of two");
-    DSA_REQUIRE(flags >= 0 && flags < 16, "gc2gc: unknown flags");
-    if (out_order + 1 > nfft || F > 0x7fffffffLL) return fail(DSA_ERR_UNSUPPORTED, "gc2gc: out_order + 1 must not exceed n_fft%s");
-    if (F == 0) return DSA_OK;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == DSA_F32 && (size_t)nfft * 8 <= 150 * 1024) return gc2gc_launch<float>(c1, F, n_in, out_order, in_gamma, out_gamma, nfft, twiddle, flags, c2, st);
-    if (dtype == DSA_F64 && (size_t)nfft * 16 <= 150 * 1024) return gc2gc_launch<double>(c1, F, n_in, out_order, in_gamma, out_gamma, nfft, twiddle, flags, c2, st);
-    return fail(DSA_ERR_UNSUPPORTED, "gc2gc: unsupported dtype or n_fft too long for LDS%s");
-}
-
-DSA_EXPORT int dsa_gc2gc_bwd(const void* c1, const void* g2, int64_t F, int32_t n_in, int32_t out_order, double in_gamma,
-                             double out_gamma, int32_t nfft, const void* twiddle, int32_t dtype, void* gc1, void* stream)
-{
-    DSA_REQUIRE(F >= 0 && n_in >= 1 && out_order >= 0, "gc2gc_bwd: sizes must be positive");
-    DSA_REQUIRE(nfft >= 4 && (nfft & (nfft - 1)) == 0, "gc2gc_bwd: n_fft must be a power of two (>= 4)");
-    DSA_REQUIRE(out_order + 1 <= nfft, "gc2gc_bwd: out_order + 1 must not exceed n_fft");
-    if (F == 0) return DSA_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int block = nfft <= 1024 ? 64 : 256;
-    if (dtype == DSA_F32 && (size_t)nfft * 10 + 64 <= 150 * 1024) {
-        const size_t lds = sizeof(float) * (5 * (size_t)(nfft / 2) + 3);
-        static std::atomic<uint64_t> lds_set{0};
-        if (lds > 48 * 1024 && !ensure_dynamic_lds(reinterpret_cast<const void*>(&gc2gc_fused_bwd_kernel<float>), 150 * 1024, lds_set))
-            return fail(DSA_ERR_LAUNCH, "gc2gc_bwd: cannot raise the dynamic LDS limit%s");
-        hipLaunchKernelGGL((gc2gc_fused_bwd_kernel<float>), dim3((unsigned)F), dim3(block), lds, st, (const float*)c1, (const float*)g2,
-                           n_in, out_order, (float)in_gamma, (float)out_gamma, nfft, (const float*)twiddle, (float*)gc1);
-        return check_launch("gc2gc_fused_bwd");
-    }
-    if (dtype == DSA_F64 && (size_t)nfft * 20 + 64 <= 150 * 1024) {
-        const size_t lds = sizeof(double) * (5 * (size_t)(nfft / 2) + 3);
-        static std::atomic<uint64_t> lds_set{0};
-        if (lds > 48 * 1024 && !ensure_dynamic_lds(reinterpret_cast<const void*>(&gc2gc_fused_bwd_kernel<double>), 150 * 1024, lds_set))
-            return fail(DSA_ERR_LAUNCH, "gc2gc_bwd: cannot raise the dynamic LDS limit%s");
-        hipLaunchKernelGGL((gc2gc_fused_bwd_kernel<double>), dim3((unsigned)F), dim3(block), lds, st, (const double*)c1, (const double*)g2,
-                           n_in, out_order, in_gamma, out_gamma, nfft, (const double*)twiddle, (double*)gc1);
-        return check_launch("gc2gc_fused_bwd");
-    }
-    return fail(DSA_ERR_UNSUPPORTED, "gc2gc_bwd: unsupported dtype or n_fft too long for LDS%s");
-}
-
-DSA_EXPORT int dsa_fftr_fwd(const void* x, int64_t F, int32_t len_in, int32_t nfft, int32_t out_format,
-                            const void* twiddle, int32_t dtype, void* y, void* stream)
-{
-    DSA_REQUIRE(len_in > 0 && nfft > 0 && nfft % 2 == 0, "fftr: fft_length must be positive even");
-    DSA_REQUIRE(out_format >= 0 && out_format <= 4, "fftr: unknown out_format");
-    hipStream_t st = (hipStream_t)stream;
-    // rows are "utterances" of len_in samples holding exactly one frame each
-    if (dtype == DSA_F32)
-        return launch_row_dft<float>(x, F, len_in, 1, len_in, len_in, 0, 0, 0, nullptr, nfft, twiddle, 0,
-                                     out_format, 0.0, 0, 0.0, y, st);
-    if (dtype == DSA_F64)
-        return launch_row_dft<double>(x, F, len_in, 1, len_in, len_in, 0, 0, 0, nullptr, nfft, twiddle, 0,
-                                      out_format, 0.0, 0, 0.0, y, st);
-    return fail(DSA_ERR_UNSUPPORTED, "fftr: unsupported dtype%s");
-}
-
-template <typename T>
-static int spec_fwd_impl(const void* b, int lb, const void* a, int la, int64_t F, int nfft, double eps,
-                         int use_floor, double floor_db, int fmt, const void* twiddle, void* y,
-                         hipStream_t st)
-{
-    if (!a)
-        return launch_row_dft<T>(b, F, lb, 1, lb, lb, 0, 0, 0, nullptr, nfft, twiddle, 1, fmt, eps,
-                                 use_floor, floor_db, y, st);
-    // denominator present: amplitude rows of b and of remove_gain(a), then the ratio kernel
-    const int K = nfft / 2 + 1;
-    T *amp_b = nullptr, *amp_a = nullptr, *a1 = nullptr;
-    size_t rows = sizeof(T) * (size_t)F * K;
-    if (hipMallocAsync((void**)&amp_a, rows, st) != hipSuccess ||
-        hipMallocAsync((void**)&a1, sizeof(T) * (size_t)F * la, st) != hipSuccess ||
-        (b && hipMallocAsync((void**)&amp_b, rows, st) != hipSuccess))
-        return fail(DSA_ERR_LAUNCH, "spec: workspace allocation failed%s");
-    int64_t tot = F * la;
-    hipLaunchKernelGGL((remove_gain_kernel<T>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st,
-                       (const T*)a, (long)F, la, a1);
-    int rc = launch_row_dft<T>(a1, F, la, 1, la, la, 0, 0, 0, nullptr, nfft, twiddle, 0, DSA_FFTR_AMPLITUDE,
-                               0.0, 0, 0.0, amp_a, st);
-    if (rc == DSA_OK && b)
-        rc = launch_row_dft<T>(b, F, lb, 1, lb, lb, 0, 0, 0, nullptr, nfft, twiddle, 0, DSA_FFTR_AMPLITUDE,
-                               0.0, 0, 0.0, amp_b, st);
-    if (rc == DSA_OK) {
-        T floor_lin = use_floor ? (T)pow(10.0, floor_db / 10.0) : T(0);
-        hipLaunchKernelGGL((spec_ratio_kernel<T>), dim3((unsigned)F), dim3(64), 0, st, (const T*)amp_b,
-                           (const T*)amp_a, (const T*)a, la, K, (T)eps, use_floor, floor_lin, fmt, (T*)y);
-        rc = check_launch("spec_ratio");
-    }
-    hipFreeAsync(amp_a, st);
-    hipFreeAsync(a1, st);
-    if (amp_b) hipFreeAsync(amp_b, st);
-    return rc;
-}
-
-DSA_EXPORT int dsa_spec_fwd(const void* b, int32_t lb, const void* a, int32_t la, int64_t F, int32_t nfft,
-                            double eps, int32_t use_floor, double relative_floor_db, int32_t out_format,
-                            const void* twiddle, int32_t dtype, void* y, void* stream)
-{
-    DSA_REQUIRE(F == 0 || b || a, "spec: either b or a must be specified");
-    DSA_REQUIRE(nfft > 1 && nfft % 2 == 0, "spec: fft_length must be positive even");
-    DSA_REQUIRE(out_format >= 0 && out_format <= 3, "spec: unknown out_format");
-    if (F == 0) return DSA_OK;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == DSA_F32)
-        return spec_fwd_impl<float>(b, lb, a, la, F, nfft, eps, use_floor, relative_floor_db, out_format, twiddle, y, st);
-    if (dtype == DSA_F64)
-        return spec_fwd_impl<double>(b, lb, a, la, F, nfft, eps, use_floor, relative_floor_db, out_format, twiddle, y, st);
-    return fail(DSA_ERR_UNSUPPORTED, "spec: unsupported dtype%s");
-}
 
 static void stft512_launch(bool zmean, dim3 grid, hipStream_t st, const float* x, long T, long N, int L, int P, int left, int mode,
                            const float* w, const float* tw, float eps, int use_floor, float floor_lin, int fmt, float* y,
@@ -2101,100 +810,12 @@ DSA_EXPORT int dsa_stft_fwd(const void* x, int64_t B, int64_t T, int32_t L, int3
 #undef DSA_BIG_LAUNCH
         return check_launch(S == 2 ? "stft1024_fwd" : "stft2048_fwd");
     }
-    if (dtype == DSA_F32)
-        return launch_row_dft<float>(x, B, T, N, L, P, left, pad_mode, zmean, w, nfft, twiddle, 1, out_format,
-                                     eps, use_floor, relative_floor_db, y, st);
-    if (dtype == DSA_F64)
-        return launch_row_dft<double>(x, B, T, N, L, P, left, pad_mode, zmean, w, nfft, twiddle, 1, out_format,
-                                      eps, use_floor, relative_floor_db, y, st);
-    return fail(DSA_ERR_UNSUPPORTED, "stft: unsupported dtype%s");
+    return stft_generic_fwd(dtype, x, B, T, N, L, P, left, pad_mode, zmean, w, nfft, twiddle, out_format, eps, use_floor,
+                            relative_floor_db, y, st);
 }
 
 // --------------------------------------------------------------------------- fused STFT -> mel filter bank
-// Host side of the filter-bank epilogue of stft512_fwd_pk_kernel<.., FBM = 1 / 2> (stft_pk.h).
-// dsa_fbank_scan_plan turns H (host, float64, 257 x C) into the (64, 32) float32 per-lane table; it is the C
-// statement of diffsptk_amd/utils/tables.py:fbank_scan_plan / fbank_scan_table (tests compare the two bit for bit).
-DSA_EXPORT int dsa_fbank_scan_plan(const double* H, int32_t K, int32_t C, float* table)
-{
-    DSA_REQUIRE(H && table, "fbank_scan_plan: null pointer");
-    if (K != 257 || C < 1 || C > 126) return fail(DSA_ERR_UNSUPPORTED, "fbank_scan_plan: needs 257 bins and at most 126 channels%s");
-    int jk[257] = {0};
-    double wd[257] = {0.0}, wu[257] = {0.0};
-    int prev = 0;
-    for (int k = 1; k < K - 1; ++k) {
-        int nz[3], n = 0;
-        for (int c = 0; c < C; ++c) {
-            const double h = H[(size_t)k * C + c];
-            if (!std::isfinite(h)) return fail(DSA_ERR_UNSUPPORTED, "fbank_scan_plan: non-finite weight%s");
-            if (h != 0.0) {
-                if (n < 3) nz[n] = c;
-                ++n;
-            }
-        }
-        int j;
-        if (n == 0) {
-            j = prev;
-        } else if (n == 1) {
-            const int c = nz[0];
-            if (c >= prev) j = c, wu[k] = H[(size_t)k * C + c];
-            else if (c + 1 >= prev) j = c + 1, wd[k] = H[(size_t)k * C + c];
-            else return fail(DSA_ERR_UNSUPPORTED, "fbank_scan_plan: channels are not ordered along the bins%s");
-        } else if (n == 2 && nz[1] == nz[0] + 1 && nz[1] >= prev) {
-            j = nz[1], wd[k] = H[(size_t)k * C + nz[0]], wu[k] = H[(size_t)k * C + nz[1]];
-        } else {
-            return fail(DSA_ERR_UNSUPPORTED, "fbank_scan_plan: a bin feeds more than two adjacent channels%s");
-        }
-        jk[k] = prev = j;
-    }
-    for (int c = 0; c < C; ++c)
-        if (!std::isfinite(H[c]) || !std::isfinite(H[(size_t)(K - 1) * C + c]))
-            return fail(DSA_ERR_UNSUPPORTED, "fbank_scan_plan: non-finite weight%s");
-    memset(table, 0, sizeof(float) * 64 * 32);
-    int32_t* ti = reinterpret_cast<int32_t*>(table);
-    bool valid[2][128] = {{false}};
-    for (int h = 0; h < 2; ++h) {
-        int j0[64], j1[64], run[64];
-        for (int l = 0; l < 64; ++l) {
-            const int b0 = h == 0 ? 2 * l + 1 : 255 - 2 * l, b1 = h == 0 ? 2 * l + 2 : 254 - 2 * l;
-            j0[l] = jk[b0], j1[l] = jk[b1];
-            float* t = table + l * 32;
-            t[0 + h] = (float)wd[b0], t[2 + h] = (float)wu[b0];
-            t[4 + h] = (float)wd[b1], t[6 + h] = (float)wu[b1];
-            if (h == 1 && l == 63) t[4 + h] = t[6 + h] = 0.f;   // bin 128 belongs to the lower half
-            t[8 + h] = j0[l] != j1[l] ? 0.f : 1.f;
-        }
-        run[0] = 0;
-        for (int l = 1; l < 64; ++l) run[l] = (j0[l] == j1[l] && j1[l - 1] == j0[l]) ? run[l - 1] + 1 : 0;
-        for (int l = 0; l < 64; ++l) {
-            float* t = table + l * 32;
-            float* m = t + 10 + 6 * h;
-            m[0] = run[l] >= 1, m[1] = run[l] >= 2, m[2] = run[l] >= 4, m[3] = run[l] >= 8;
-            m[4] = ((l / 16) % 2 == 1) && run[l] >= l % 16 + 1;
-            m[5] = l >= 32 && run[l] >= l - 31;
-            t[22 + h] = (l > 0 && j1[l - 1] == j0[l]) ? 1.f : 0.f;
-            const bool isE = l == 63 || j0[l + 1] != j1[l], isM = j0[l] != j1[l];
-            ti[l * 32 + 24] |= (j1[l] << (8 * h)) | (j0[l] << (16 + 8 * h));
-            ti[l * 32 + 25] |= ((int)isE << h) | ((int)isM << (2 + h));
-            if (isE) valid[h][j1[l]] = true;
-            if (isM) valid[h][j0[l]] = true;
-        }
-    }
-    for (int l = 0; l < 64; ++l)
-        for (int r = 0; r < 2; ++r) {
-            const int c = l + 64 * r;
-            if (c >= C) continue;
-            table[l * 32 + 26 + 2 * r] = (float)H[c];
-            table[l * 32 + 27 + 2 * r] = (float)H[(size_t)(K - 1) * C + c];
-            // channel c reads the up-slope sums of interval c and the down-slope sums of interval c + 1
-            ti[l * 32 + 30] |= ((int)valid[0][c] | ((int)valid[1][c] << 1) | ((int)valid[0][c + 1] << 2) | ((int)valid[1][c + 1] << 3)) << (4 * r);
-        }
-    bool has_ends = false;
-    for (int c = 0; c < C; ++c) has_ends = has_ends || H[c] != 0.0 || H[(size_t)(K - 1) * C + c] != 0.0;
-    if (has_ends)
-        for (int l = 0; l < 64; ++l) ti[l * 32 + 30] |= 256;   // bit 8 (every lane): bins 0 / 256 carry weight
-    return DSA_OK;
-}
-
+// (the per-lane table `plan` is the one dsa_fbank_scan_plan of fbank.hip makes)
 DSA_EXPORT int dsa_stft_fbank_fwd(const void* x, int64_t B, int64_t T, int32_t L, int32_t P, int32_t nfft, const void* w,
                                   const void* twiddle, int32_t center, double eps, const void* plan, int32_t C, double floor,
                                   double gamma, int32_t use_power, int32_t dtype, void* y, void* stream)
@@ -2223,122 +844,6 @@ DSA_EXPORT int dsa_stft_fbank_fwd(const void* x, int64_t B, int64_t T, int32_t L
     else DSA_FB_LAUNCH(2);
 #undef DSA_FB_LAUNCH
     return check_launch("stft512_fbank_fwd");
-}
-
-// --------------------------------------------------------------------------- backward entries
-namespace dsa {
-
-template <typename T>
-static int launch_row_dft_bwd(const void* x, int64_t B, int64_t Tlen, int64_t N, int L, int P, int left,
-                              int mode, int zmean, const void* w, int nfft, const void* twiddle,
-                              int out_kind, int fmt, double eps, int use_floor, double floor_db,
-                              const void* gy, void* gframe, void* gwpart, hipStream_t st)
-{
-    int64_t F = B * N;
-    if (F == 0) return DSA_OK;
-    T floor_lin = use_floor ? (T)pow(10.0, floor_db / 10.0) : T(0);
-    const int K = nfft / 2 + 1;
-    size_t lds = sizeof(T) * ((size_t)L + 3 * (size_t)K);
-    static const bool direct_only = [] {
-        const char* e = getenv("DSA_ROWDFT_DIRECT");
-        return e && atoi(e) != 0;
-    }();
-    const size_t lds_fft = lds + sizeof(T) * 2 * (size_t)nfft;
-    if (!direct_only && nfft >= 32 && (nfft & (nfft - 1)) == 0 && lds_fft <= 150 * 1024) {
-        static std::atomic<uint64_t> lds_set{0};
-        if (lds_fft > 48 * 1024 &&
-            !ensure_dynamic_lds(reinterpret_cast<const void*>(&row_dft_bwd_kernel<T, true>), 150 * 1024, lds_set))
-            return fail(DSA_ERR_LAUNCH, "row_fft_bwd: cannot raise the dynamic LDS limit%s");
-        hipLaunchKernelGGL((row_dft_bwd_kernel<T, true>), dim3((unsigned)F), dim3(256), lds_fft, st, (const T*)x, (long)Tlen,
-                           (long)N, L, P, left, mode, zmean, (const T*)w, nfft, (const T*)twiddle, out_kind, fmt,
-                           (T)eps, use_floor, floor_lin, (const T*)gy, (T*)gframe, (T*)gwpart);
-        return check_launch("row_fft_bwd_generic");
-    }
-    if (lds > 60 * 1024) return fail(DSA_ERR_UNSUPPORTED, "row_dft_bwd: frame too long for LDS%s");
-    hipLaunchKernelGGL((row_dft_bwd_kernel<T>), dim3((unsigned)F), dim3(256), lds, st, (const T*)x, (long)Tlen,
-                       (long)N, L, P, left, mode, zmean, (const T*)w, nfft, (const T*)twiddle, out_kind, fmt,
-                       (T)eps, use_floor, floor_lin, (const T*)gy, (T*)gframe, (T*)gwpart);
-    return check_launch("row_dft_bwd_generic");
-}
-
-template <typename T>
-static int stft_bwd_generic(const void* gy, const void* x, int64_t B, int64_t Tlen, int L, int P, int nfft,
-                            const void* w, const void* twiddle, int center, int zmean, int pad_mode,
-                            double eps, int use_floor, double floor_db, int fmt, void* gx, void* gw,
-                            hipStream_t st)
-{
-    int64_t N = dsa_num_frames(Tlen, P), F = B * N;
-    int left = center ? L / 2 : 0;
-    T *gframe = nullptr, *gwpart = nullptr;
-    size_t bytes = sizeof(T) * (size_t)F * L;
-    if (hipMallocAsync((void**)&gframe, bytes, st) != hipSuccess ||
-        (gw && hipMallocAsync((void**)&gwpart, bytes, st) != hipSuccess))
-        return fail(DSA_ERR_LAUNCH, "stft_bwd: workspace allocation failed%s");
-    int rc = launch_row_dft_bwd<T>(x, B, Tlen, N, L, P, left, pad_mode, zmean, w, nfft, twiddle, 1, fmt, eps,
-                                   use_floor, floor_db, gy, gframe, gwpart, st);
-    // overlap-add (zmean already folded into gframe)
-    if (rc == DSA_OK) rc = frame_bwd_impl<T>(gframe, B, Tlen, L, P, center, 0, pad_mode, gx, st);
-    if (rc == DSA_OK && gw) {
-        hipLaunchKernelGGL((colsum_kernel<T>), dim3(L), dim3(256), 0, st, (const T*)gwpart, (long)F, L, (T*)gw);
-        rc = check_launch("window_grad_colsum");
-    }
-    (void)hipFreeAsync(gframe, st);
-    if (gwpart) (void)hipFreeAsync(gwpart, st);
-    return rc;
-}
-
-}  // namespace dsa
-
-DSA_EXPORT int dsa_fftr_bwd(const void* gy, const void* x, int64_t F, int32_t len_in, int32_t nfft,
-                            int32_t out_format, const void* twiddle, int32_t dtype, void* gx, void* stream)
-{
-    DSA_REQUIRE(len_in > 0 && nfft > 0 && nfft % 2 == 0, "fftr_bwd: fft_length must be positive even");
-    DSA_REQUIRE(out_format >= 0 && out_format <= 4, "fftr_bwd: unknown out_format");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == DSA_F32)
-        return launch_row_dft_bwd<float>(x, F, len_in, 1, len_in, len_in, 0, 0, 0, nullptr, nfft, twiddle, 0,
-                                         out_format, 0.0, 0, 0.0, gy, gx, nullptr, st);
-    if (dtype == DSA_F64)
-        return launch_row_dft_bwd<double>(x, F, len_in, 1, len_in, len_in, 0, 0, 0, nullptr, nfft, twiddle, 0,
-                                          out_format, 0.0, 0, 0.0, gy, gx, nullptr, st);
-    return fail(DSA_ERR_UNSUPPORTED, "fftr_bwd: unsupported dtype%s");
-}
-
-DSA_EXPORT int dsa_spec_bwd(const void* gy, const void* b, int32_t lb, const void* a, int32_t la, int64_t F,
-                            int32_t nfft, double eps, int32_t use_floor, double relative_floor_db,
-                            int32_t out_format, const void* twiddle, int32_t dtype, void* gb, void* ga,
-                            void* stream)
-{
-    DSA_REQUIRE(F == 0 || b || a, "spec_bwd: either b or a must be specified");
-    DSA_REQUIRE(nfft > 1 && nfft % 2 == 0, "spec_bwd: fft_length must be positive even");
-    hipStream_t st = (hipStream_t)stream;
-    if (a) {
-        DSA_REQUIRE(F == 0 || ga != nullptr, "spec_bwd: ga is required when a is given");
-        if (F == 0) return DSA_OK;
-        const int K = nfft / 2 + 1;
-        const size_t esz = dtype == DSA_F32 ? 4 : 8;
-        const size_t lds = esz * ((size_t)lb + la + 5 * (size_t)K);
-        if (lds > 60 * 1024) return fail(DSA_ERR_UNSUPPORTED, "spec_bwd: rows too long for LDS%s");
-        const double fl = use_floor ? pow(10.0, relative_floor_db / 10.0) : 0.0;
-        if (dtype == DSA_F32)
-            hipLaunchKernelGGL((spec_ratio_bwd_kernel<float>), dim3((unsigned)F), dim3(128), lds, st, (const float*)gy,
-                               (const float*)b, b ? lb : 0, (const float*)a, la, nfft, (const float*)twiddle, (float)eps,
-                               use_floor, (float)fl, out_format, (float*)gb, (float*)ga);
-        else if (dtype == DSA_F64)
-            hipLaunchKernelGGL((spec_ratio_bwd_kernel<double>), dim3((unsigned)F), dim3(128), lds, st, (const double*)gy,
-                               (const double*)b, b ? lb : 0, (const double*)a, la, nfft, (const double*)twiddle, eps,
-                               use_floor, fl, out_format, (double*)gb, (double*)ga);
-        else
-            return fail(DSA_ERR_UNSUPPORTED, "spec_bwd: unsupported dtype%s");
-        return check_launch("spec_ratio_bwd");
-    }
-    if (dtype == DSA_F32)
-        return launch_row_dft_bwd<float>(b, F, lb, 1, lb, lb, 0, 0, 0, nullptr, nfft, twiddle, 1, out_format, eps,
-                                         use_floor, relative_floor_db, gy, gb, nullptr, st);
-    if (dtype == DSA_F64)
-        return launch_row_dft_bwd<double>(b, F, lb, 1, lb, lb, 0, 0, 0, nullptr, nfft, twiddle, 1, out_format, eps,
-                                          use_floor, relative_floor_db, gy, gb, nullptr, st);
-    return fail(DSA_ERR_UNSUPPORTED, "spec_bwd: unsupported dtype%s");
 }
 
 // dsa_stft_bwd and dsa_istft_fwd: div / div_eps only with out_format DSA_SPEC_COMPLEX_INV (the result is divided by
@@ -2505,11 +1010,8 @@ static int stft_bwd_impl(const void* gy, const void* x, int64_t B, int64_t T, in
             return fail(DSA_ERR_LAUNCH, "istft: workspace allocation failed%s");
         x = x0;
     }
-    int rc = dtype == DSA_F32
-                 ? stft_bwd_generic<float>(gy, x, B, T, L, P, nfft, w, twiddle, center, zmean, pad_mode, eps, use_floor,
-                                           relative_floor_db, out_format, gx, gw, st)
-                 : stft_bwd_generic<double>(gy, x, B, T, L, P, nfft, w, twiddle, center, zmean, pad_mode, eps, use_floor,
-                                            relative_floor_db, out_format, gx, gw, st);
+    int rc = stft_generic_bwd(dtype, gy, x, B, T, L, P, nfft, w, twiddle, center, zmean, pad_mode, eps, use_floor, relative_floor_db,
+                              out_format, gx, gw, st);
     if (x0) (void)hipFreeAsync(x0, st);
     if (rc == DSA_OK && div) rc = dsa_div_rows(gx, B, T, div, div_eps, dtype, gx, stream);
     return rc;
@@ -2534,62 +1036,4 @@ DSA_EXPORT int dsa_istft_fwd(const void* y, int64_t B, int64_t T, int32_t L, int
     DSA_REQUIRE(d != nullptr, "istft: the window-square sum is required");
     return stft_bwd_impl(y, nullptr, B, T, L, P, nfft, w, twiddle, center, 0, DSA_PAD_CONSTANT, 0.0, 0, 0.0,
                          DSA_SPEC_COMPLEX_INV, dtype, algo, out, nullptr, stream, d, d_eps);
-}
-
-// --------------------------------------------------------------------------- inverse path (8(f) row 2)
-DSA_EXPORT int dsa_irfft_scale(const void* y, int64_t F, int32_t nfft, int32_t dtype, void* out, void* stream)
-{
-    DSA_REQUIRE(nfft > 1 && nfft % 2 == 0, "irfft_scale: fft_length must be positive even");
-    const int K = nfft / 2 + 1;
-    const long total = (long)F * K;
-    if (total == 0) return DSA_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned blocks = (unsigned)((total + 255) / 256);
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((irfft_scale_kernel<float>), dim3(blocks), dim3(256), 0, st, (const float*)y, total, K, nfft, (float*)out);
-    else if (dtype == DSA_F64)
-        hipLaunchKernelGGL((irfft_scale_kernel<double>), dim3(blocks), dim3(256), 0, st, (const double*)y, total, K, nfft, (double*)out);
-    else
-        return fail(DSA_ERR_UNSUPPORTED, "irfft_scale: unsupported dtype%s");
-    return check_launch("irfft_scale");
-}
-
-DSA_EXPORT int dsa_div_rows(const void* x, int64_t B, int64_t T, const void* d, double eps, int32_t dtype, void* out,
-                            void* stream)
-{
-    DSA_REQUIRE(B >= 0 && T >= 0, "div_rows: sizes must be non-negative");
-    if (B * T == 0) return DSA_OK;
-    hipStream_t st = (hipStream_t)stream;
-    dim3 grid((unsigned)((T + 255) / 256), (unsigned)(B < 1024 ? B : 1024));
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((div_rows_kernel<float>), grid, dim3(256), 0, st, (const float*)x, (long)B, (long)T, (const float*)d, (float)eps, (float*)out);
-    else if (dtype == DSA_F64)
-        hipLaunchKernelGGL((div_rows_kernel<double>), grid, dim3(256), 0, st, (const double*)x, (long)B, (long)T, (const double*)d, eps, (double*)out);
-    else
-        return fail(DSA_ERR_UNSUPPORTED, "div_rows: unsupported dtype%s");
-    return check_launch("div_rows");
-}
-
-DSA_EXPORT int dsa_griffin_update(const void* t, int64_t B, int64_t Nt, int64_t N, int32_t K, const void* y, const void* phase,
-                                  void* t_prev, void* d_prev, int32_t first, double alpha, double beta, double gamma,
-                                  double eps, int32_t dtype, void* z, void* stream)
-{
-    DSA_REQUIRE(B >= 0 && N >= 0 && K > 0 && Nt >= N, "griffin_update: the transform must cover the spectrogram's frames");
-    DSA_REQUIRE(!t || (t_prev && d_prev), "griffin_update: the momentum buffers are required after the initial step");
-    const long total = (long)B * N * K;
-    if (total == 0) return DSA_OK;
-    hipStream_t st = (hipStream_t)stream;
-    long blocks = (total + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((griffin_update_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, st, (const float*)t, (long)B,
-                           (long)Nt, (long)N, K, (const float*)y, (const float*)phase, (float*)t_prev, (float*)d_prev, first,
-                           (float)alpha, (float)beta, (float)gamma, (float)eps, (float*)z);
-    else if (dtype == DSA_F64)
-        hipLaunchKernelGGL((griffin_update_kernel<double>), dim3((unsigned)blocks), dim3(256), 0, st, (const double*)t, (long)B,
-                           (long)Nt, (long)N, K, (const double*)y, (const double*)phase, (double*)t_prev, (double*)d_prev,
-                           first, alpha, beta, gamma, eps, (double*)z);
-    else
-        return fail(DSA_ERR_UNSUPPORTED, "griffin_update: unsupported dtype%s");
-    return check_launch("griffin_update");
 }

@@ -3,7 +3,7 @@
 //
 //   g:(F,n) = solve(T(p) + H(q), r - sub)  (+ add)          mcep.py:216-222, mgcep.py:226-229 (torch.linalg.solve there)
 //
-// What it replaces: th_solve_fwd_kernel (csrc/mgc.hip) -- one wave per system, one row per lane, row pivoting, the pivot row broadcast
+// What it replaces: th_solve_fwd_kernel (csrc/thsolve.hip) -- one wave per system, one row per lane, row pivoting, the pivot row broadcast
 // lane by lane through scalar registers -- took 174 us per 12 800 systems of order 50 (52 % of a Newton step of the mel-cepstral
 // analysis at the 48 kHz set-ups, profiles/r04_48k_kernel_trace_v1.txt).
 //

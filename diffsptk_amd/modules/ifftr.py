@@ -12,7 +12,7 @@ from .base import BaseFunctionalModule, Precomputed
 
 class RealValuedInverseFastFourierTransform(BaseFunctionalModule):
     """y:(..., L/2+1) complex -> x:(..., out_length) real = irfft(y)[..., :out_length] (ifftr.py:131-142).
-    Computed as the adjoint of the forward DFT kernel applied to c_k / L * y (csrc/stft.hip)."""
+    Computed as the adjoint of the forward DFT kernel applied to c_k / L * y (csrc/spec.hip)."""
 
     _takes_input_size = True
 

@@ -4,7 +4,7 @@ gamma = 0 is mel-cepstral analysis (the tuned kernel of modules/mcep.py, as in t
 For gamma in [-1, 0) every linear stage of a Newton step (mgcep.py:185-249: cfreqt + rfft; irfft + pfreqt / rfreqt
 + the P / Q transforms) is composed on the host into float64 matrices (utils/tables.py:mgcep_matrices), so a step is
 seven row products on the library's freqt kernel around the pointwise spectrum arithmetic, followed by the
-Toeplitz-plus-Hankel solve kernel (csrc/mgc.hip).  Gradients: the kernels' own backward entries chained by autograd.
+Toeplitz-plus-Hankel solve kernel (csrc/thsolve.hip).  Gradients: the kernels' own backward entries chained by autograd.
 """
 from __future__ import annotations
 
@@ -53,7 +53,7 @@ class MelGeneralizedCepstralAnalysis(nn.Module):
             return
         if cep_order < 1:
             raise ValueError("cep_order must be positive when gamma is not 0.")
-        if cep_order > 64:   # the Toeplitz-plus-Hankel solve keeps a system per wave (csrc/mgc.hip): say so here, not at the first call
+        if cep_order > 64:   # the Toeplitz-plus-Hankel solve keeps a system per wave (csrc/thsolve.hip): say so here, not at the first call
             raise ValueError("cep_order must be at most 64 when gamma is not 0 (limit of the device solver).")
         M = cep_order
         mats = dict(tables.mgcep_matrices(fft_length, cep_order, float(alpha)))   # (the table function caches its result)

@@ -3,7 +3,7 @@ section 8(f), row 4.
 
 The three modes that do not need torchlpc, for phase in {minimum, maximum, zero}:
   multi-stage   (mglsadf.py:254-386)  cepstrum of order `cep_order` (mgc2mgc), then `taylor_order` passes of the
-                                      time-variant FIR kernel (csrc/mgc.hip:zerodf) summed with Taylor weights of exp;
+                                      time-variant FIR kernel (csrc/zerodf.hip) summed with Taylor weights of exp;
   single-stage  (mglsadf.py:389-526)  impulse response of length `ir_length` (mgc2mgc to gamma = 1, or exp of the
                                       Hermitian transform for zero phase), then ONE pass of the FIR kernel;
   freq-domain   (mglsadf.py:529-644)  complex STFT of the excitation times the filter's complex spectrum (mgc2sp),

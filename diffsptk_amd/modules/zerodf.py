@@ -52,7 +52,7 @@ class LinearInterpolation(BaseFunctionalModule):
 
 class AllZeroDigitalFilter(BaseFunctionalModule):
     """x:(..., T), b:(..., T/P, M+1) -> y:(..., T): y[t] = sum_k h_t[k] x[t - k + zeroth_index] with the taps interpolated
-    linearly between frames (zerodf.py:184-243; both of the reference's modes compute this), one kernel (csrc/mgc.hip)."""
+    linearly between frames (zerodf.py:184-243; both of the reference's modes compute this), one kernel (csrc/zerodf.hip)."""
 
     _takes_input_size = True
 

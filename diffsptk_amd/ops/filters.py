@@ -1,4 +1,4 @@
-"""All-zero (csrc/mgc.hip) and all-pole (poledf.hip) time-variant filters, pseudo-QMF banks and interpolation (pqmf.hip)."""
+"""All-zero (csrc/zerodf.hip) and all-pole (poledf.hip) time-variant filters, pseudo-QMF banks and interpolation (pqmf.hip)."""
 from __future__ import annotations
 
 import math
@@ -226,7 +226,7 @@ class InterpolateFn(torch.autograd.Function):
 
 
 def zerodf_taylor_shapes_ok(x, b, P) -> bool:
-    """Shapes the fused Taylor-stage launches cover, forward and backward (csrc/mgc.hip:zerodf_rows_plan, zerodf_launch_bwd)."""
+    """Shapes the fused Taylor-stage launches cover, forward and backward (csrc/zerodf.hip:zerodf_rows_plan, zerodf_launch_bwd)."""
     return (P % 4 == 0 and 16 <= P <= 256 and b.size(-1) - 1 >= 16 and b.dim() >= 2 and tuple(b.shape[:-2]) == tuple(x.shape[:-1])
             and b.size(-2) * P == x.size(-1) and x.is_cuda and x.dtype == b.dtype and x.dtype in (torch.float32, torch.float64))
 

@@ -1,4 +1,4 @@
-"""Mel-generalized cepstra: gnorm, the mgcep Newton step and its solve (csrc/mgc.hip, thsolve_quad.hip), gc2gc (in stft.hip)."""
+"""Mel-generalized cepstra: gnorm, the mgcep Newton step and its solve (csrc/mgc.hip, thsolve.hip, thsolve_quad.hip), gc2gc (mgc.hip)."""
 from __future__ import annotations
 
 import torch

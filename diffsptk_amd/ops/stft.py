@@ -1,4 +1,4 @@
-"""Frame, Window, fftr, Spectrum, STFT and the inverse path (ifftr, Unframe, ISTFT, Griffin-Lim): csrc/stft.hip."""
+"""Frame, Window, fftr, Spectrum, STFT and the inverse path (ifftr, Unframe, ISTFT, Griffin-Lim): csrc/spec.hip, stft.hip, griffin.hip."""
 from __future__ import annotations
 
 import torch

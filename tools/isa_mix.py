@@ -5,6 +5,7 @@ DPP / conversions / packed 4, two-operand and move class 2, transcendentals 8, v
 binary16 matrix products run on the separate matrix pipe: 16 cycles each, listed beside).
 
     python tools/isa_mix.py [diffsptk_amd/lib/libdiffsptk_amd.so] [kernel-name-substring ...]      -> JSON per kernel
+    python tools/isa_mix.py --diff parent.so branch.so      -> per-kernel comparison of two builds (diff_libs), exit status 1 if it fails
 
 The loop taken is the LAST innermost loop of the kernel (for the mel-cepstral kernels: the Newton step; one pass = 16 frames)."""
 import collections
@@ -24,7 +25,8 @@ EIGHT = {"v_exp_f32", "v_log_f32", "v_rcp_f32", "v_rsq_f32", "v_sqrt_f32", "v_rc
 
 def disassemble(lib):
     """{kernel symbol: [(address, mnemonic, text)]} of the gfx950 code objects bundled in `lib` (the .hip_fatbin section holds
-    one clang offload bundle per translation unit: header magic, entry table (offset, size, triple), code objects)."""
+    one clang offload bundle per translation unit: header magic, entry table (offset, size, triple), code objects).
+    A symbol defined in two code objects of the library raises ValueError: the second would replace the first here."""
     import struct
 
     tmp = "/tmp/isa_mix_%d" % os.getpid()
@@ -65,6 +67,8 @@ def disassemble(lib):
                     m = re.match(r"^[0-9a-f]+ <(.+)>:", line)
                     if m:
                         cur = m.group(1)
+                        if cur in kernels:
+                            raise ValueError("%s: %s is defined in two code objects" % (lib, cur))
                         kernels[cur] = []
                         continue
                     m = re.match(r"^\s+(\S+)\s*(.*?)\s*//\s*([0-9A-Fa-f]+):", line)
@@ -89,6 +93,72 @@ def crossed_packed_f32(kernels):
                 if m and "1" in m.group(1):
                     bad.setdefault(name, []).append(op + " " + txt)
     return bad
+
+
+# scalar integer ALU: address and loop set-up, which the compiler derives anew from the set of callers a translation unit holds
+SALU_INT = re.compile(r"s_(add|addc|sub|subb|mul|mul_hi|lshl|lshr|ashr|lshl[1-4]_add|and|or|xor|andn2|orn2|not|mov|movk|cmov|cmp|cmpk|cselect|"
+                      r"bfe|bfm|min|max|sext|abs)_\w*[iub](16|32|64)$")
+TUNED = re.compile(r"stft512_|stft_big_|zerodf_\w*_rows")   # the kernels that must stay identical: classes (b) / (c)
+
+
+def _views(ins):
+    """The three views of a kernel that diff_libs compares: as is; with the literal of pc-relative address formation (the s_add_u32 /
+    s_addc_u32 pair behind s_getpc_b64) masked; and with, further, every scalar integer ALU instruction that touches neither exec nor
+    vcc dropped and every SGPR operand replaced by a placeholder that keeps its width.  The s_nop run behind a final s_endpgm is
+    left out of all three: it is the padding of the code object's text section, which falls to whichever kernel is linked last."""
+    end = len(ins)
+    while end and ins[end - 1][1] == "s_nop":
+        end -= 1
+    if end and ins[end - 1][1] == "s_endpgm":
+        ins = ins[:end]
+    plain = [op + " " + txt for _, op, txt in ins]
+    masked, since_getpc = [], 9
+    for _, op, txt in ins:
+        since_getpc = 0 if op == "s_getpc_b64" else since_getpc + 1
+        if since_getpc in (1, 2) and op in ("s_add_u32", "s_addc_u32"):
+            txt = re.sub(r"(0x[0-9a-f]+|\d+)$", "<pcrel>", txt)
+        masked.append((op, txt))
+    loose = []
+    for op, txt in masked:
+        if SALU_INT.match(op) and not re.search(r"\b(exec|vcc)", txt):
+            continue
+        loose.append(op + " " + re.sub(r"\bs\[(\d+):(\d+)\]", lambda m: "s[x%d]" % (int(m.group(2)) - int(m.group(1)) + 1),
+                                       re.sub(r"\bs\d+\b", "s", txt)))
+    return plain, [op + " " + txt for op, txt in masked], loose
+
+
+def diff_libs(parent, branch):
+    """(report text, passed) of two builds of the library, per kernel symbol: (a) both hold the same symbols, each once;
+    (b) identical; (c) identical but for the literal of pc-relative addresses; (d) identical, at an equal instruction count, but for
+    scalar integer ALU instructions and SGPR numbering; (e) anything else.  Passes when (a) holds, nothing is in (e) and every
+    tuned kernel (TUNED) is in (b) or (c)."""
+    import difflib
+
+    try:
+        kp, kb = disassemble(parent), disassemble(branch)
+    except ValueError as e:
+        return "(a) FAILS: %s\n" % e, False
+    out, cls = [], {}
+    only = sorted(set(kp) ^ set(kb))
+    for name in sorted(set(kp) & set(kb)):
+        vp, vb = _views(kp[name]), _views(kb[name])
+        cls[name] = "b" if vp[0] == vb[0] else "c" if vp[1] == vb[1] else "d" if vp[2] == vb[2] and len(vp[0]) == len(vb[0]) else "e"
+    bad_tuned = [n for n, c in cls.items() if c in "de" and TUNED.search(n)]
+    passed = not only and "e" not in cls.values() and not bad_tuned
+    out.append("parent %s: %d symbols, %d instructions; branch %s: %d symbols, %d instructions" % (
+        os.path.basename(parent), len(kp), sum(map(len, kp.values())), os.path.basename(branch), len(kb), sum(map(len, kb.values()))))
+    out.append("(a) same symbols, each in one code object: %s" % ("yes" if not only else "NO, in one build only: " + ", ".join(only)))
+    for c, what in (("b", "identical"), ("c", "identical but for pc-relative literals"),
+                    ("d", "identical but for scalar integer ALU and SGPR numbering"), ("e", "different")):
+        names = [n for n in cls if cls[n] == c]
+        out.append("(%s) %-56s %4d kernels, %d of them tuned (%s)" % (c, what, len(names), sum(1 for n in names if TUNED.search(n)), TUNED.pattern))
+    out.append("result: %s" % ("PASS" if passed else "FAIL"))
+    for c in "cde":
+        for n in (n for n in cls if cls[n] == c):
+            out.append("\n(%s) %s  [%d instructions]" % (c, n, len(kb[n])))
+            if c != "c":
+                out.extend(difflib.unified_diff(_views(kp[n])[1], _views(kb[n])[1], "parent", "branch", lineterm="", n=1))
+    return "\n".join(out) + "\n", passed
 
 
 def innermost_last_loop(ins):
@@ -159,7 +229,12 @@ def main():
     print(json.dumps(res, indent=1))
 
 
-if __name__ == "__main__" and "--audit" in sys.argv:
+if __name__ == "__main__" and "--diff" in sys.argv:
+    libs = [a for a in sys.argv[1:] if a != "--diff"]
+    report, ok = diff_libs(*libs)
+    sys.stdout.write(report)
+    sys.exit(0 if ok else 1)
+elif __name__ == "__main__" and "--audit" in sys.argv:
     args = [a for a in sys.argv[1:] if a != "--audit"]
     ks = disassemble(args[0] if args else os.path.join(ROOT, "diffsptk_amd", "lib", "libdiffsptk_amd.so"))
     bad = crossed_packed_f32(ks)
