@@ -230,6 +230,21 @@ def lpccheck(a: Tensor, margin: float = 1e-16, warn_type: str = "warn") -> Tenso
     return nn.LinearPredictiveCoefficientsStabilityCheck._func(a, margin=margin, warn_type=warn_type)
 
 
+def lpc2lsp(a: Tensor, log_gain: bool = False, sample_rate: int | None = None, out_format: str = "radian") -> Tensor:
+    """LPC coefficients -> line spectral pairs a:(..., M+1) -> (..., M+1) (functional.py: lpc2lsp)."""
+    return nn.LinearPredictiveCoefficientsToLineSpectralPairs._func(a, log_gain=log_gain, sample_rate=sample_rate, out_format=out_format)
+
+
+def lsp2lpc(w: Tensor, log_gain: bool = False, sample_rate: int | None = None, in_format: str = "radian") -> Tensor:
+    """Line spectral pairs -> LPC coefficients w:(..., M+1) -> (..., M+1) (functional.py: lsp2lpc)."""
+    return nn.LineSpectralPairsToLinearPredictiveCoefficients._func(w, log_gain=log_gain, sample_rate=sample_rate, in_format=in_format)
+
+
+def lspcheck(w: Tensor, rate: float = 0, n_iter: int = 1, warn_type: str = "warn") -> Tensor:
+    """Stability check of line spectral pairs w:(..., M+1) -> (..., M+1) (functional.py: lspcheck)."""
+    return nn.LineSpectralPairsStabilityCheck._func(w, rate=rate, n_iter=n_iter, warn_type=warn_type)
+
+
 def par2lar(k: Tensor) -> Tensor:
     """PARCOR coefficients -> log area ratio (functional.py: par2lar)."""
     return nn.ParcorCoefficientsToLogAreaRatio._func(k)

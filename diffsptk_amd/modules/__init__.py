@@ -35,6 +35,9 @@ from .par2lar import ParcorCoefficientsToLogAreaRatio
 from .lar2par import LogAreaRatioToParcorCoefficients
 from .par2is import ParcorCoefficientsToInverseSine
 from .is2par import InverseSineToParcorCoefficients
+from .lpc2lsp import LinearPredictiveCoefficientsToLineSpectralPairs
+from .lsp2lpc import LineSpectralPairsToLinearPredictiveCoefficients
+from .lspcheck import LineSpectralPairsStabilityCheck
 from .pqmf import PseudoQuadratureMirrorFilterBankAnalysis, PseudoQuadratureMirrorFilterBankSynthesis
 from .pqmf import PseudoQuadratureMirrorFilterBankAnalysis as PQMF
 from .pqmf import PseudoQuadratureMirrorFilterBankSynthesis as IPQMF
@@ -61,5 +64,6 @@ __all__ = [
     "LinearPredictiveCoefficientsToParcorCoefficients", "ParcorCoefficientsToLinearPredictiveCoefficients",
     "LinearPredictiveCoefficientsStabilityCheck", "ParcorCoefficientsToLogAreaRatio", "LogAreaRatioToParcorCoefficients",
     "ParcorCoefficientsToInverseSine", "InverseSineToParcorCoefficients",
+    "LinearPredictiveCoefficientsToLineSpectralPairs", "LineSpectralPairsToLinearPredictiveCoefficients", "LineSpectralPairsStabilityCheck",
     "RealValuedFastFourierTransform", "STFT", "ShortTimeFourierTransform", "Spectrum", "Window",
 ]

@@ -249,3 +249,110 @@ def lpccheck(a, bound, detect=False):
     caller reads back -- the only synchronisation, and only when asked for."""
     unstable = torch.zeros(1, dtype=torch.int32, device=a.device) if detect else None
     return LpcCheckFn.apply(a, bound, unstable), unstable
+
+
+def _lsp_rows(t):
+    """_rows for the line-spectral-pair entries, whose order is bounded (csrc/lsp.hip: one root per lane of a wave)."""
+    tc, F, M = _rows(t)
+    if M > _lib.LSP_MAX_ORDER:
+        raise ValueError(f"the order of the line spectral pairs is {M}: at most {_lib.LSP_MAX_ORDER} (DSA_LSP_MAX_ORDER) is supported.")
+    return tc, F, M
+
+
+class Lpc2LspFn(torch.autograd.Function):
+    """lpc2lsp.py:169-197 in one launch: a root search on two Chebyshev series, no eigen-solver.  `unit`: radians per unit of the
+    output format.  `failed`: a zeroed int32 tensor of one element that the kernel sets when a row's roots were not found (that row is
+    NaN), or None.  The backward works from the input a and the output w, without a root finder."""
+
+    @staticmethod
+    def forward(ctx, a, log_gain, unit, failed):
+        ac, F, M = _lsp_rows(a)   # (the order first: that error needs no device)
+        _require_device(a)
+        w = torch.empty_like(ac)
+        with torch.cuda.device(a.device):
+            _call("dsa_lpc2lsp_fwd", _p(ac), F, M, int(log_gain), float(unit), _dtype_code(ac), _p(w), _p(failed), _stream())
+        ctx.save_for_backward(ac, w)
+        ctx.cfg = (log_gain, unit)
+        return w
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gw):
+        ac, w = ctx.saved_tensors
+        log_gain, unit = ctx.cfg
+        gw, F, M = _rows(gw)
+        ga = torch.empty_like(ac)
+        with torch.cuda.device(gw.device):
+            _call("dsa_lpc2lsp_bwd", _p(gw), _p(ac), _p(w), F, M, int(log_gain), float(unit), _dtype_code(ac), _p(ga), _stream())
+        return ga, None, None, None
+
+
+class Lsp2LpcFn(torch.autograd.Function):
+    """lsp2lpc.py:171-195 in one launch: products of real second-order sections; the backward recomputes from the input w."""
+
+    @staticmethod
+    def forward(ctx, w, log_gain, unit):
+        wc, F, M = _lsp_rows(w)   # (the order first: that error needs no device)
+        _require_device(w)
+        a = torch.empty_like(wc)
+        with torch.cuda.device(w.device):
+            _call("dsa_lsp2lpc_fwd", _p(wc), F, M, int(log_gain), float(unit), _dtype_code(wc), _p(a), _stream())
+        ctx.save_for_backward(wc)
+        ctx.cfg = (log_gain, unit)
+        return a
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, ga):
+        (wc,) = ctx.saved_tensors
+        log_gain, unit = ctx.cfg
+        ga, F, M = _rows(ga)
+        gw = torch.empty_like(wc)
+        with torch.cuda.device(ga.device):
+            _call("dsa_lsp2lpc_bwd", _p(ga), _p(wc), F, M, int(log_gain), float(unit), _dtype_code(wc), _p(gw), _stream())
+        return gw, None, None
+
+
+class LspCheckFn(torch.autograd.Function):
+    """lspcheck.py:115-145 in one launch, each row stopping on its own distances.  `unstable`: a zeroed int32 tensor of one element
+    that the kernel sets by the test of lspcheck.py:121, or None.  The backward replays the forward from the input w."""
+
+    @staticmethod
+    def forward(ctx, w, min_distance, n_iter, unstable):
+        wc, F, M = _lsp_rows(w)   # (the order first: that error needs no device)
+        _require_device(w)
+        out = torch.empty_like(wc)
+        with torch.cuda.device(w.device):
+            _call("dsa_lspcheck_fwd", _p(wc), F, M, float(min_distance), int(n_iter), _dtype_code(wc), _p(out), _p(unstable), _stream())
+        ctx.save_for_backward(wc)
+        ctx.cfg = (min_distance, n_iter)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        (wc,) = ctx.saved_tensors
+        min_distance, n_iter = ctx.cfg
+        gout, F, M = _rows(gout)
+        gw = torch.empty_like(wc)
+        with torch.cuda.device(gout.device):
+            _call("dsa_lspcheck_bwd", _p(gout), _p(wc), F, M, float(min_distance), int(n_iter), _dtype_code(wc), _p(gw), _stream())
+        return gw, None, None, None
+
+
+def lpc2lsp(a, log_gain=False, unit=1.0, detect=False):
+    """(w, failed): failed is None unless detect, else a one-element int32 tensor (non-zero: some row's roots were not found and that
+    row is NaN) for the caller to read back."""
+    failed = torch.zeros(1, dtype=torch.int32, device=a.device) if detect else None
+    return Lpc2LspFn.apply(a, log_gain, unit, failed), failed
+
+
+def lsp2lpc(w, log_gain=False, unit=1.0):
+    return Lsp2LpcFn.apply(w, log_gain, unit)
+
+
+def lspcheck(w, min_distance, n_iter, detect=False):
+    """(out, unstable): unstable is None unless detect, else a one-element int32 tensor (non-zero: the test of lspcheck.py:121 fired)
+    that the caller reads back -- the only synchronisation, and only when asked for."""
+    unstable = torch.zeros(1, dtype=torch.int32, device=w.device) if detect else None
+    return LspCheckFn.apply(w, min_distance, n_iter, unstable), unstable

@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define DSA_VERSION 133 /* 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
+#define DSA_VERSION 134 /* 0.2.8: + dsa_lpc2lsp_fwd / _bwd, dsa_lsp2lpc_fwd / _bwd, dsa_lspcheck_fwd / _bwd (line spectral pairs by a Chebyshev-series root search, back by a product of real sections, and their stability check, forward and adjoint); 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
 
 typedef enum {
     DSA_OK = 0,
@@ -631,6 +631,49 @@ int dsa_par2lpc_bwd(const void* ga, const void* k, int64_t F, int32_t M, double 
 int dsa_lpccheck_fwd(const void* a, int64_t F, int32_t M, double bound, int32_t dtype, void* out, void* k, int32_t* unstable,
                      void* stream);
 int dsa_lpccheck_bwd(const void* gout, const void* k, int64_t F, int32_t M, double bound, int32_t dtype, void* ga, void* stream);
+
+/* ------------------------------------------------------------------ a15  line spectral pairs: lpc2lsp, lsp2lpc, lspcheck (0.2.8)
+ * Rows are (F, M+1) = [K, c_1 .. c_M]; one launch each, float32 and float64 with all arithmetic in float64 and one rounding at the
+ * store, int64 indexing, no allocation, no host synchronisation; F = 0 is a no-op before any pointer is looked at.  M < 0 or
+ * M > DSA_LSP_MAX_ORDER is DSA_ERR_INVALID_ARGUMENT.  A row's bits depend on (M, dtype, options) and the row alone, not on F or on its
+ * position.  `unit` is the angle in radians of one unit of the LSP format (radian 1, cycle 2 pi, khz 2000 pi / sample_rate,
+ * hz 2 pi / sample_rate): lpc2lsp divides by it, lsp2lpc multiplies.  log_gain is a flag.
+ *   dsa_lpc2lsp_fwd   LinearPredictiveCoefficientsToLineSpectralPairs._forward, lpc2lsp.py:169-197, which deflates the sum and
+ *                     difference polynomials (lpc2lsp.py:177-187) and takes the angles of the eigenvalues of their companion
+ *                     matrices (lpc2lsp.py:188-192).  Here: the two deflated polynomials as Chebyshev series in cos w, their roots
+ *                     bracketed by sign changes on a grid of pi / 64 (halved up to 6 times while fewer than M brackets are found)
+ *                     and refined by a fixed number of bisection and Newton steps; one wave per frame.  No eigen-solver.
+ *                     A row whose M roots cannot be found or do not interlace (a predictor that is not minimum phase, NaN input)
+ *                     gets NaN in w_1 .. w_M, K carried -- a departure: the reference returns the angles of off-circle roots.
+ *                     failed: one int32 or NULL, zeroed by the caller, set to 1 (an ordinary vector store) when there is such a row.
+ *   dsa_lpc2lsp_bwd   gw, the input a and the OUTPUT w -> ga, by the implicit function theorem on the root's own polynomial; no root
+ *                     finder.  A NaN row of w gives NaN in ga_1 .. ga_M.
+ *   dsa_lsp2lpc_fwd   LineSpectralPairsToLinearPredictiveCoefficients._forward, lsp2lpc.py:171-195, which multiplies the complex
+ *                     roots e^{+-jw} (lsp2lpc.py:180-188) and applies the trivial factors (lsp2lpc.py:148-153, 189-191).  Here: the
+ *                     product of the REAL sections 1 - 2 cos w_i z^-1 + z^-2 over the odd- and over the even-indexed LSPs, the same
+ *                     trivial factors, a = (p + q) / 2.  The kernel never produces a complex number and never refuses an order
+ *                     <= DSA_LSP_MAX_ORDER (the reference raises in float32 from M = 16 on, and in float64 at M = 63).
+ *   dsa_lsp2lpc_bwd   ga and the input w -> gw: each section divided out of its product again, O(M^2) per frame, no workspace.
+ *   dsa_lspcheck_fwd  LineSpectralPairsStabilityCheck._forward, lspcheck.py:115-145: n_iter Gauss-Seidel sweeps over the pairs
+ *                     (lspcheck.py:133-138), each followed by the clip to [min_distance, pi - min_distance] (lspcheck.py:139; the
+ *                     bounds rounded to the dtype, as torch.clip does with a Python scalar).  A row stops sweeping when ITS distances
+ *                     are all >= min_distance - 1e-16 -- a departure: the reference's break (lspcheck.py:140-142) is batch-wide.
+ *                     unstable: one int32 or NULL, zeroed by the caller, set to 1 (an ordinary vector store) by the test of
+ *                     lspcheck.py:121, which looks at the whole row, K included.
+ *   dsa_lspcheck_bwd  gout and the input w -> gw: the forward replayed to regenerate the masks of each sweep, the piecewise-linear
+ *                     adjoint applied in reverse (both clips pass the gradient on their bound); n_iter = 0 is the identity. */
+#define DSA_LSP_MAX_ORDER 64
+int dsa_lpc2lsp_fwd(const void* a, int64_t F, int32_t M, int32_t log_gain, double unit, int32_t dtype, void* w, int32_t* failed,
+                    void* stream);
+int dsa_lpc2lsp_bwd(const void* gw, const void* a, const void* w, int64_t F, int32_t M, int32_t log_gain, double unit, int32_t dtype,
+                    void* ga, void* stream);
+int dsa_lsp2lpc_fwd(const void* w, int64_t F, int32_t M, int32_t log_gain, double unit, int32_t dtype, void* a, void* stream);
+int dsa_lsp2lpc_bwd(const void* ga, const void* w, int64_t F, int32_t M, int32_t log_gain, double unit, int32_t dtype, void* gw,
+                    void* stream);
+int dsa_lspcheck_fwd(const void* w, int64_t F, int32_t M, double min_distance, int32_t n_iter, int32_t dtype, void* out,
+                     int32_t* unstable, void* stream);
+int dsa_lspcheck_bwd(const void* gout, const void* w, int64_t F, int32_t M, double min_distance, int32_t n_iter, int32_t dtype,
+                     void* gw, void* stream);
 
 #ifdef __cplusplus
 }
