@@ -13,6 +13,11 @@
  *  - every pointer is a DEVICE pointer (HIP, same process / same HIP runtime as the caller)
  *    unless the name ends in `_host`; the caller (PyTorch) allocates all buffers;
  *  - tensors are dense row-major ("contiguous"); leading batch dims are flattened by the caller;
+ *  - ALIGNMENT: a tensor pointer needs the natural alignment of its element and nothing more (4 bytes for DSA_F32, 8 for
+ *    DSA_F64 and for the float pairs of a complex64 tensor): a contiguous view that starts anywhere inside an allocation is a
+ *    valid argument, input or output.  The library chooses wider (8- / 16-byte) accesses itself, per call or per run inside a
+ *    kernel, where the address it is handed allows them, and computes the same values where it does not
+ *    (tests/test_gpu_alignment.py);
  *  - a ZERO count (B, F, n = 0: an empty batch, which the reference's ATen ops accept) is a successful no-op: the sizes are
  *    validated, the pointers are not looked at (an empty tensor has no storage; its data pointer is NULL);
  *  - `dtype`: DSA_F32 or DSA_F64 (the reference supports both; CI runs float64);
