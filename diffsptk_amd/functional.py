@@ -7,6 +7,7 @@ import functools
 from torch import Tensor
 
 from . import modules as nn
+from .modules.mlsacheck import MLSADigitalFilterStabilityCheck   # (not a name of modules.__all__ yet: modules/mlsacheck.py)
 
 
 def acorr(x: Tensor, acr_order: int, out_format: str | int = "naive") -> Tensor:
@@ -243,6 +244,13 @@ def lsp2lpc(w: Tensor, log_gain: bool = False, sample_rate: int | None = None, i
 def lspcheck(w: Tensor, rate: float = 0, n_iter: int = 1, warn_type: str = "warn") -> Tensor:
     """Stability check of line spectral pairs w:(..., M+1) -> (..., M+1) (functional.py: lspcheck)."""
     return nn.LineSpectralPairsStabilityCheck._func(w, rate=rate, n_iter=n_iter, warn_type=warn_type)
+
+
+def mlsacheck(c: Tensor, *, alpha: float = 0, pade_order: int = 4, strict: bool = True, threshold: float | None = None, fast: bool = True,
+              n_fft: int = 256, warn_type: str = "warn", mod_type: str = "scale") -> Tensor:
+    """Stability check of the MLSA digital filter c:(..., M+1) -> (..., M+1) (functional.py: mlsacheck)."""
+    return MLSADigitalFilterStabilityCheck._func(c, alpha=alpha, pade_order=pade_order, strict=strict, threshold=threshold, fast=fast,
+                                                 n_fft=n_fft, warn_type=warn_type, mod_type=mod_type)
 
 
 def par2lar(k: Tensor) -> Tensor:

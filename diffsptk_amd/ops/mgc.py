@@ -1,9 +1,11 @@
-"""Mel-generalized cepstra: gnorm, the mgcep Newton step and its solve (csrc/mgc.hip, thsolve.hip, thsolve_quad.hip), gc2gc (mgc.hip)."""
+"""Mel-generalized cepstra: gnorm, the mgcep Newton step and its solve (csrc/mgc.hip, thsolve.hip, thsolve_quad.hip), gc2gc (mgc.hip),
+the MLSA filter's stability check (mlsacheck.hip)."""
 from __future__ import annotations
 
 import torch
 from torch.autograd.function import once_differentiable
 
+from .. import _lib
 from ._core import _call, _dtype_code, _p, _require_device, _same_dtype, _stream
 
 
@@ -283,3 +285,44 @@ class ThSolveFn(torch.autograd.Function):
         with torch.cuda.device(gg.device):
             _call("dsa_thsolve_bwd", _p(ggc), _p(pc), _p(qc), _p(g), F, n, _dtype_code(pc), _p(gp), _p(gq), _p(gr), _stream())
         return gp, gq, gr
+
+
+MLSACHECK_MODES = {"fast": _lib.MLSACHECK_FAST, "scale": _lib.MLSACHECK_SCALE, "clip": _lib.MLSACHECK_CLIP}
+
+
+class MlsaCheckFn(torch.autograd.Function):
+    """mlsacheck.py:181-230 in one launch (dsa_mlsacheck).  `unstable`: a zeroed int32 tensor of one element that the kernel sets when
+    the threshold is below a frame's amplitude, or None.  The backward (dsa_mlsacheck_vjp) recomputes everything from the input mc:
+    nothing but mc is saved."""
+
+    @staticmethod
+    def forward(ctx, mc, alpha, threshold, mode, n_fft, unstable):
+        _require_device(mc)
+        mcc = mc.contiguous()
+        M1 = mcc.size(-1)
+        out = torch.empty_like(mcc)
+        with torch.cuda.device(mc.device):
+            _call("dsa_mlsacheck", _p(mcc), mcc.numel() // M1, M1 - 1, float(alpha), float(threshold), int(mode), int(n_fft), _dtype_code(mcc),
+                  _p(out), _p(unstable), _stream())
+        ctx.save_for_backward(mcc)
+        ctx.cfg = (float(alpha), float(threshold), int(mode), int(n_fft))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        (mcc,) = ctx.saved_tensors
+        gout = gout.contiguous()
+        M1 = mcc.size(-1)
+        gmc = torch.empty_like(mcc)
+        with torch.cuda.device(gout.device):
+            _call("dsa_mlsacheck_vjp", _p(gout), _p(mcc), mcc.numel() // M1, M1 - 1, *ctx.cfg, _dtype_code(mcc), _p(gmc), _stream())
+        return gmc, None, None, None, None, None
+
+
+def mlsacheck(mc, alpha, threshold, mode, n_fft, detect=False):
+    """(out, unstable) of the MLSA filter's stability check on mc:(..., M+1); mode: "fast", "scale" or "clip" (MLSACHECK_MODES).
+    unstable is None unless detect, else a one-element int32 tensor (non-zero: the threshold is below some frame's amplitude) that the
+    caller reads back -- the only synchronisation, and only when asked for."""
+    unstable = torch.zeros(1, dtype=torch.int32, device=mc.device) if detect else None
+    return MlsaCheckFn.apply(mc, alpha, threshold, MLSACHECK_MODES[mode], n_fft, unstable), unstable

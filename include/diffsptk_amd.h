@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define DSA_VERSION 134 /* 0.2.8: + dsa_lpc2lsp_fwd / _bwd, dsa_lsp2lpc_fwd / _bwd, dsa_lspcheck_fwd / _bwd (line spectral pairs by a Chebyshev-series root search, back by a product of real sections, and their stability check, forward and adjoint); 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
+#define DSA_VERSION 135 /* 0.2.9: + dsa_mlsacheck / dsa_mlsacheck_vjp (the stability check of the MLSA filter: the mel-cepstrum scaled or clipped where the amplitude of its gain-free part passes the threshold of the Pade approximation, forward and adjoint); 0.2.8: + dsa_lpc2lsp_fwd / _bwd, dsa_lsp2lpc_fwd / _bwd, dsa_lspcheck_fwd / _bwd (line spectral pairs by a Chebyshev-series root search, back by a product of real sections, and their stability check, forward and adjoint); 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
 
 typedef enum {
     DSA_OK = 0,
@@ -679,6 +679,40 @@ int dsa_lspcheck_fwd(const void* w, int64_t F, int32_t M, double min_distance, i
                      int32_t* unstable, void* stream);
 int dsa_lspcheck_bwd(const void* gout, const void* w, int64_t F, int32_t M, double min_distance, int32_t n_iter, int32_t dtype,
                      void* gw, void* stream);
+
+/* ------------------------------------------------------------------ a16  the MLSA filter's stability check: mlsacheck (0.2.9)
+ * MLSADigitalFilterStabilityCheck._forward, mlsacheck.py:181-230.  Rows are (F, M+1) mel-cepstra; one launch each, float32 and float64
+ * with all arithmetic in float64 and one rounding at the store, int64 indexing, no allocation, no workspace, no host synchronisation;
+ * F = 0 is a no-op before any pointer is looked at.  DSA_ERR_INVALID_ARGUMENT: F < 0 or M < 0, a mode that is none of
+ * DSA_MLSACHECK_*, a dtype that is none of DSA_F32 / DSA_F64, in the FFT modes n_fft <= 0 or 2 (n_fft / 2) < M + 1, frames without
+ * pointers.  A row's bits depend on (M, dtype, options) and the row alone, not on F or on its position.
+ * With gain = sum_m mc_m (-alpha)^m and c = mc except c_0 = mc_0 - gain (mlsacheck.py:191, 198):
+ *   DSA_MLSACHECK_FAST   a = max(sum_m c_m, 1e-16), s = min(1, threshold / a), out = s c, out_0 += gain (fast=True; n_fft is not looked at).
+ *   DSA_MLSACHECK_SCALE  C_k = sum_m c_m e^{-j 2 pi k m / n_fft}, k < K = n_fft / 2 + 1; a = max(max_k |C_k|, 1e-16), one s = min(1, threshold / a).
+ *   DSA_MLSACHECK_CLIP   s_k = min(1, threshold / |C_k|) per bin (|C_k| = 0: 1).
+ *   In both FFT modes out_m = (1 / N') sum_k w_k Re(s_k C_k e^{+j 2 pi k m / N'}), m <= M, with N' = 2 (K - 1) -- torch's default irfft
+ *   length, n_fft only when that is even -- and w = 2 except w_0 = w_{K-1} = 1, whose imaginary parts are ignored; out_0 += gain.  No FFT
+ *   is run: both transforms are (M + 1) x K sums.
+ * unstable: one int32 or NULL, zeroed by the caller, set to 1 (an ordinary vector store) when threshold < a in any frame.
+ * Two departures from the reference.  (1) Where the two transforms invert each other -- fast mode and every even n_fft -- a frame that
+ * nothing clips (a <= threshold) is returned with the INPUT'S BITS and its gradient is the cotangent's bits; the reference re-rounds
+ * c_0 through (c_0 - gain) * 1 + gain and the rest through its FFT pair.  (For odd n_fft the reference's irfft(rfft(c)) has another
+ * length than it was made with and is another vector than c; such a frame goes through both transforms here as it does there.)
+ * (2) The reference returns a tensor of the wrong width when 2 (n_fft / 2) < M + 1 (24 columns for M = 24, n_fft = 25); here that is
+ * an invalid argument, and the module raises ValueError at _precompute.
+ *   dsa_mlsacheck      mc -> out.
+ *   dsa_mlsacheck_vjp  gout and the INPUT mc -> gmc, the exact derivative of the piecewise-smooth forward, everything recomputed from
+ *                      mc: through s and the plain sum (fast), through s and the one bin that attains the maximum (scale; among equal
+ *                      bins the lowest), through every clipped bin's threshold / |C_k| and the adjoints of the two transforms (clip).  A
+ *                      clip that is exactly on its bound passes the gradient, as torch.clip does.
+ * float32 with M <= 63 and n_fft = 256 (or fast mode) runs the tuned kernels (one wave per frame, the bins over the lanes, the maximum a
+ * wave reduction, the complex exponentials by rotation); everything else the generic ones (one wave per frame, the row and the bins in
+ * LDS: DSA_ERR_UNSUPPORTED when 24 (M + 1) + 16 K bytes exceed 144 KiB). */
+enum { DSA_MLSACHECK_FAST = 0, DSA_MLSACHECK_SCALE = 1, DSA_MLSACHECK_CLIP = 2 };
+int dsa_mlsacheck(const void* mc, int64_t F, int32_t M, double alpha, double threshold, int32_t mode, int32_t n_fft, int32_t dtype,
+                  void* out, int32_t* unstable, void* stream);
+int dsa_mlsacheck_vjp(const void* gout, const void* mc, int64_t F, int32_t M, double alpha, double threshold, int32_t mode, int32_t n_fft,
+                      int32_t dtype, void* gmc, void* stream);
 
 #ifdef __cplusplus
 }
