@@ -21,8 +21,11 @@ from .modules import *  # noqa: F401,F403
 from .modules import __all__ as _module_names
 # exported from here and not from diffsptk_amd.modules: every name of modules.__all__ needs a row in the alignment sweep's table
 # (tests/alignment_rows.py); the change that adds that row moves the name into modules.__all__
+from .modules.excite import ExcitationGeneration
 from .modules.mlsacheck import MLSADigitalFilterStabilityCheck
+from .signals import mseq, mseq_like, nrand
 from .utils.public import get_alpha, read, write
 
 __version__ = "0.1.0"
-__all__ = [*_module_names, "functional", "get_alpha", "read", "write", "Graphed", "MLSADigitalFilterStabilityCheck"]
+__all__ = [*_module_names, "functional", "get_alpha", "read", "write", "Graphed", "MLSADigitalFilterStabilityCheck",
+           "ExcitationGeneration", "mseq", "mseq_like", "nrand"]

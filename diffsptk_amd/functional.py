@@ -7,6 +7,7 @@ import functools
 from torch import Tensor
 
 from . import modules as nn
+from .modules.excite import ExcitationGeneration   # (not a name of modules.__all__ yet, as the next one)
 from .modules.mlsacheck import MLSADigitalFilterStabilityCheck   # (not a name of modules.__all__ yet: modules/mlsacheck.py)
 
 
@@ -251,6 +252,13 @@ def mlsacheck(c: Tensor, *, alpha: float = 0, pade_order: int = 4, strict: bool 
     """Stability check of the MLSA digital filter c:(..., M+1) -> (..., M+1) (functional.py: mlsacheck)."""
     return MLSADigitalFilterStabilityCheck._func(c, alpha=alpha, pade_order=pade_order, strict=strict, threshold=threshold, fast=fast,
                                                  n_fft=n_fft, warn_type=warn_type, mod_type=mod_type)
+
+
+def excite(p: Tensor, frame_period: int = 80, *, voiced_region: str = "pulse", unvoiced_region: str = "gauss", polarity: str = "auto",
+           init_phase: str | float = "zeros") -> Tensor:
+    """Excitation from pitch p:(..., N) in samples, 0 = unvoiced -> (..., N P) (functional.py: excite)."""
+    return ExcitationGeneration._func(p, frame_period=frame_period, voiced_region=voiced_region, unvoiced_region=unvoiced_region,
+                                      polarity=polarity, init_phase=init_phase)
 
 
 def par2lar(k: Tensor) -> Tensor:

@@ -1,4 +1,5 @@
-"""All-zero (csrc/zerodf.hip) and all-pole (poledf.hip) time-variant filters, pseudo-QMF banks and interpolation (pqmf.hip)."""
+"""All-zero (csrc/zerodf.hip) and all-pole (poledf.hip) time-variant filters, pseudo-QMF banks and interpolation (pqmf.hip), and the
+excitation that drives the synthesis filters (excite.hip)."""
 from __future__ import annotations
 
 import math
@@ -6,6 +7,7 @@ import math
 import torch
 from torch.autograd.function import once_differentiable
 
+from .. import _lib
 from ._core import _call, _dtype_code, _p, _require_device, _same_dtype, _stream
 
 
@@ -295,3 +297,30 @@ def zerodf_taylor(x, b, P, zeroth_index, scale, acc, want_y=True):
         _call("dsa_zerodf_taylor_fwd", _p(xc), _p(bc), B, T, M, P, zeroth_index, float(scale), _p(acc), _dtype_code(xc),
               _p(y), _p(acc), _stream())
     return y, acc
+
+
+EXCITE_TYPES = {"pulse": _lib.EXCITE_PULSE, "harmonic-pulse": _lib.EXCITE_HARMONIC_PULSE, "sinusoidal": _lib.EXCITE_SINUSOIDAL,
+                "sawtooth": _lib.EXCITE_SAWTOOTH, "inverted-sawtooth": _lib.EXCITE_INVERTED_SAWTOOTH, "triangle": _lib.EXCITE_TRIANGLE,
+                "square": _lib.EXCITE_SQUARE}
+
+
+def excite(p, P, voiced_region, bipolar, shift=0.0):
+    """The voiced part of ExcitationGeneration._forward (excite.py:222-310) in one launch (dsa_excite): pitch p:(..., N) in samples,
+    0 = unvoiced -> (..., N P) with zeros in the unvoiced samples.  `shift`: the initial phase / 2 pi, a float or a tensor with one value
+    per utterance.  Forward only: the result carries no gradient, and p is not modified."""
+    _require_device(p)
+    pc = p.detach().contiguous()
+    N = pc.size(-1)
+    B = math.prod(pc.shape[:-1])
+    out = torch.empty(*pc.shape[:-1], N * P, device=pc.device, dtype=pc.dtype)
+    per_utterance = None
+    if isinstance(shift, torch.Tensor):
+        _require_device(shift)
+        _same_dtype(pc, shift)
+        per_utterance = shift.detach().contiguous()
+        if per_utterance.numel() != B:
+            raise ValueError(f"excite: {per_utterance.numel()} shifts for {B} utterances")
+    with torch.cuda.device(pc.device):
+        _call("dsa_excite", _p(pc), B, N, int(P), EXCITE_TYPES[voiced_region], int(bool(bipolar)),
+              0.0 if per_utterance is not None else float(shift), _p(per_utterance), _dtype_code(pc), _p(out), _stream())
+    return out

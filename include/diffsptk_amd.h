@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define DSA_VERSION 135 /* 0.2.9: + dsa_mlsacheck / dsa_mlsacheck_vjp (the stability check of the MLSA filter: the mel-cepstrum scaled or clipped where the amplitude of its gain-free part passes the threshold of the Pade approximation, forward and adjoint); 0.2.8: + dsa_lpc2lsp_fwd / _bwd, dsa_lsp2lpc_fwd / _bwd, dsa_lspcheck_fwd / _bwd (line spectral pairs by a Chebyshev-series root search, back by a product of real sections, and their stability check, forward and adjoint); 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
+#define DSA_VERSION 136 /* 0.3.0: + dsa_excite (pitch to excitation: the voiced shapes of ExcitationGeneration on a segmented float64 phase sum, one launch); 0.2.9: + dsa_mlsacheck / dsa_mlsacheck_vjp (the stability check of the MLSA filter: the mel-cepstrum scaled or clipped where the amplitude of its gain-free part passes the threshold of the Pade approximation, forward and adjoint); 0.2.8: + dsa_lpc2lsp_fwd / _bwd, dsa_lsp2lpc_fwd / _bwd, dsa_lspcheck_fwd / _bwd (line spectral pairs by a Chebyshev-series root search, back by a product of real sections, and their stability check, forward and adjoint); 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
 
 typedef enum {
     DSA_OK = 0,
@@ -713,6 +713,41 @@ int dsa_mlsacheck(const void* mc, int64_t F, int32_t M, double alpha, double thr
                   void* out, int32_t* unstable, void* stream);
 int dsa_mlsacheck_vjp(const void* gout, const void* mc, int64_t F, int32_t M, double alpha, double threshold, int32_t mode, int32_t n_fft,
                       int32_t dtype, void* gmc, void* stream);
+
+/* ------------------------------------------------------------------ a17  excitation generation: excite (0.3.0)
+ * ExcitationGeneration._forward, excite.py:222-310.  p:(B, N) pitch in samples, 0 = unvoiced -> out:(B, N P), the VOICED part of the
+ * excitation and zeros in every unvoiced sample (the host layer fills those: modules/excite.py); one launch, float32 and float64,
+ * int64 indexing, no allocation, no workspace, no host synchronisation; B = 0 or N = 0 is a no-op before any pointer is looked at.
+ * DSA_ERR_INVALID_ARGUMENT: B < 0, N < 0, P < 1 or P > 2^20, B N P beyond int64, a type that is none of DSA_EXCITE_*, a dtype that is
+ * none of DSA_F32 / DSA_F64, frames without pointers.
+ * Per voiced frame n (p_n != 0) and sample j < P, everything in the data's dtype except the sum:
+ *   target  b = p_{n+1}, or p_n when frame n + 1 is unvoiced or n is the last frame     (excite.py:236-239 and the replicate pad of
+ *           linear_intpl.py:99)
+ *   pitch   a + (j / P) (b - a), a = p_n                                                 (linear_intpl.py:100-105)
+ *   q       1 / pitch, correctly rounded                                                 (excite.py:262)
+ *   phase   the FLOAT64 sum of q from the first sample of the voiced run through this one, rounded to the dtype, plus the shift
+ *           (excite.py:263-265, 282, 294)
+ * and then the shape, bipolar != 0 selecting its bipolar form:
+ *   DSA_EXCITE_PULSE           sqrt(pitch) where ceil(phase) exceeds ceil of the phase of the sample before by >= 1 (the shift alone at
+ *                              the start of an utterance and after an unvoiced sample); bipolar: negated where ceil(phase / 2) does not
+ *                              rise as well                                              (excite.py:28-44)
+ *   DSA_EXCITE_HARMONIC_PULSE  the Dirichlet kernel of floor(pitch / 2) harmonics on the phase of the sample BEFORE, its singular branch
+ *                              at |2 sin(theta / 2)| < 1e-6, times sqrt(2 / max(harmonics, 1))   (excite.py:47-77)
+ *   DSA_EXCITE_SINUSOIDAL, _SAWTOOTH, _INVERTED_SAWTOOTH, _TRIANGLE, _SQUARE              (excite.py:80-114)
+ * shift: B values of the dtype (the initial phase / 2 pi per utterance: init_phase "random"), or NULL: then init_shift for every
+ * utterance.
+ * For float32 data the float64 sums are exact, so the result does not depend on how the sum is split over lanes, waves and chunks: an
+ * utterance's bits depend on (P, options, shift) and its own N values, not on B, its row or where a voiced run lies in it.
+ * Four departures from the reference.  (1) p is NOT modified (the reference overwrites the unvoiced frame behind every voiced run in
+ * place).  (2) The interpolated pitch is a + w (b - a) as in the library's filters, which differs from F.interpolate in the last place
+ * on some samples.  (3) Negative pitch values and values in (0, 1) are outside the contract (the reference's masks disagree with each
+ * other there).  (4) The host layer returns an ordinary tensor without a gradient, where the reference returns an inference tensor.
+ * One workgroup per utterance (a grid-stride loop beyond 65 536), 256 frames at a time: per-frame sums, a segmented scan over them, then
+ * lane = sample with a segmented wave scan inside the frame.  A single long utterance is correct and runs on one compute unit. */
+enum { DSA_EXCITE_PULSE = 0, DSA_EXCITE_HARMONIC_PULSE = 1, DSA_EXCITE_SINUSOIDAL = 2, DSA_EXCITE_SAWTOOTH = 3,
+       DSA_EXCITE_INVERTED_SAWTOOTH = 4, DSA_EXCITE_TRIANGLE = 5, DSA_EXCITE_SQUARE = 6 };
+int dsa_excite(const void* p, int64_t B, int64_t N, int32_t P, int32_t type, int32_t bipolar, double init_shift, const void* shift,
+               int32_t dtype, void* out, void* stream);
 
 #ifdef __cplusplus
 }
