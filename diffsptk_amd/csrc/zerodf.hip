@@ -357,9 +357,11 @@ __device__ __forceinline__ void zd_fma_hi(zd_v2d& acc, zd_v2d c, zd_v2d w) { acc
 
 template <typename T, int S>
 __global__ __launch_bounds__(256) DSA_PK_TARGET void zerodf_fwd_rows_kernel(const T* __restrict__ x, const T* __restrict__ b, long Tlen, long N,
-                                                              int M, int P, int z0, int ignore_gain, int nf, int G, T scale,
+                                                              int M, int P, int z0, int ignore_gain, int nf, int G, int ldb, T scale,
                                                               const T* acc, T* __restrict__ y, T* ysum)
 {
+    // (`b` may point at a run of M + 1 taps inside rows of ldb coefficients, with a zeroth index outside [0, M]: a filter too long
+    // for LDS is the sum of its tap pieces, zerodf_launch_fwd)
     using V2 = T __attribute__((ext_vector_type(2)));
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int NB = (M + 4) / 4;                 // 4-tap blocks
@@ -370,7 +372,7 @@ __global__ __launch_bounds__(256) DSA_PK_TARGET void zerodf_fwd_rows_kernel(cons
     const long chunks = (N + nf - 1) / nf;
     const long u = blockIdx.x / chunks, n0 = (blockIdx.x - u * chunks) * nf;
     const int frames = (int)((N - n0 < nf) ? N - n0 : nf);
-    const T* bu = b + u * N * (M + 1);
+    const T* bu = b + u * N * ldb;
     // (all loads of a batch first, then the stores: a load -> store loop waits out one trip to memory per element)
     for (int kk = threadIdx.x; kk < 4 * NB; kk += blockDim.x) {   // a thread walks down one tap: every row is read once
         const bool tap = kk <= M;
@@ -379,7 +381,7 @@ __global__ __launch_bounds__(256) DSA_PK_TARGET void zerodf_fwd_rows_kernel(cons
 #pragma unroll
         for (int p = 0; p <= 16; ++p) {
             const long row = n0 + p < N ? n0 + p : N - 1;
-            cv[p] = (tap && p <= frames) ? col[row * (M + 1)] : T(0);
+            cv[p] = (tap && p <= frames) ? col[row * ldb] : T(0);
         }
 #pragma unroll
         for (int p = 0; p < 16; ++p)
@@ -532,7 +534,7 @@ static int zerodf_launch_fwd(const void* x, const void* b, int64_t B, int64_t Tl
             const long chunks = (N + nf - 1) / nf;
             // (the kernel is written for S = 4 or 8 samples per thread; 8 measured the same at P = 80 and is not instantiated)
             hipLaunchKernelGGL((zerodf_fwd_rows_kernel<T, 4>), dim3((unsigned)(B * chunks)), dim3(256), lds_r, st, (const T*)x,
-                               (const T*)b, (long)Tlen, (long)N, M, P, z0, ig, nf, G, (T)scale, (const T*)acc, (T*)y, (T*)ysum);
+                               (const T*)b, (long)Tlen, (long)N, M, P, z0, ig, nf, G, M + 1, (T)scale, (const T*)acc, (T*)y, (T*)ysum);
             return check_launch("zerodf_rows_fwd");
         }
         if (ysum || scale != 1.0) return fail(DSA_ERR_UNSUPPORTED, "zerodf: the scaled / accumulating form needs P % 4 == 0 and M >= 16%s");
@@ -553,7 +555,31 @@ static int zerodf_launch_fwd(const void* x, const void* b, int64_t B, int64_t Tl
         return check_launch("zerodf_sliced_fwd");
     }
     const size_t lds = sizeof(T) * (2 * (size_t)(M + 1) + P + M);
-    if (lds > 64 * 1024) return fail(DSA_ERR_UNSUPPORTED, "zerodf: filter too long for LDS%s");
+    if (lds > 64 * 1024) {
+        // A filter whose rows fit none of the kernels above (float64 from about 2700 taps at P = 80: the 3999 taps of the zero- and
+        // mixed-phase single-stage MLSA filter at its defaults) as a sum of tap pieces, as the backward does: piece c = taps
+        // [c KC, c KC + Mc] with z0 - c KC as its (possibly negative) zeroth index, each on the rows kernel; the first piece writes
+        // y, the others add theirs to it (acc = ysum = y), in stream order.  The fewest pieces that all fit; everything is decided
+        // before anything is launched.  ignore_gain divides by a tap of the whole filter: not by pieces.
+        for (int np = 2; np <= 64 && !ig; ++np) {
+            const int KC = (((M + 1 + np - 1) / np) + 3) & ~3;
+            const int Ml = M - (np - 1) * KC;                  // order of the last piece
+            int S, nf[2], G[2];
+            size_t lds_p[2];
+            if (Ml < 16 || !zerodf_rows_plan(KC - 1, P, sizeof(T), S, nf[0], G[0], lds_p[0]) ||
+                !zerodf_rows_plan(Ml, P, sizeof(T), S, nf[1], G[1], lds_p[1]))
+                continue;
+            for (int c = 0; c < np; ++c) {
+                const int w = c == np - 1;
+                const long chunks = (N + nf[w] - 1) / nf[w];
+                hipLaunchKernelGGL((zerodf_fwd_rows_kernel<T, 4>), dim3((unsigned)(B * chunks)), dim3(256), lds_p[w], st, (const T*)x,
+                                   (const T*)b + c * KC, (long)Tlen, (long)N, w ? Ml : KC - 1, P, z0 - c * KC, 0, nf[w], G[w], M + 1, T(1),
+                                   (const T*)(c ? y : nullptr), (T*)(c ? nullptr : y), (T*)(c ? y : nullptr));
+            }
+            return check_launch("zerodf_rows_fwd");
+        }
+        return fail(DSA_ERR_UNSUPPORTED, "zerodf: filter too long for LDS%s");
+    }
     hipLaunchKernelGGL((zerodf_fwd_kernel<T>), dim3((unsigned)(B * N)), dim3(P >= 192 ? 256 : (P >= 96 ? 128 : 64)), lds, st,
                        (const T*)x, (const T*)b, (long)Tlen, (long)N, M, P, z0, ig, (T*)y);
     return check_launch("zerodf_fwd");
