@@ -9,6 +9,8 @@ from torch import Tensor
 from . import modules as nn
 from .modules.excite import ExcitationGeneration   # (not a name of modules.__all__ yet, as the next one)
 from .modules.mlsacheck import MLSADigitalFilterStabilityCheck   # (not a name of modules.__all__ yet: modules/mlsacheck.py)
+from .modules.imdct import InverseModifiedDiscreteCosineTransform, InverseModifiedDiscreteSineTransform   # (the same)
+from .modules.mdct import ModifiedDiscreteCosineTransform, ModifiedDiscreteSineTransform
 
 
 def acorr(x: Tensor, acr_order: int, out_format: str | int = "naive") -> Tensor:
@@ -279,3 +281,23 @@ def par2is(k: Tensor) -> Tensor:
 def is2par(s: Tensor) -> Tensor:
     """Inverse sine coefficients -> PARCOR coefficients (functional.py: is2par)."""
     return nn.InverseSineToParcorCoefficients._func(s)
+
+
+def mdct(x: Tensor, frame_length: int = 400, window: str = "sine") -> Tensor:
+    """Modified discrete cosine transform x:(..., T) -> (..., 2T/L, L/2) (functional.py: mdct)."""
+    return ModifiedDiscreteCosineTransform._func(x, frame_length=frame_length, window=window)
+
+
+def mdst(x: Tensor, frame_length: int = 400, window: str = "sine") -> Tensor:
+    """Modified discrete sine transform x:(..., T) -> (..., 2T/L, L/2) (functional.py: mdst)."""
+    return ModifiedDiscreteSineTransform._func(x, frame_length=frame_length, window=window)
+
+
+def imdct(y: Tensor, out_length: int | None = None, frame_length: int = 400, window: str = "sine") -> Tensor:
+    """Inverse modified discrete cosine transform y:(..., 2T/L, L/2) -> (..., T) (functional.py: imdct)."""
+    return InverseModifiedDiscreteCosineTransform._func(y, out_length=out_length, frame_length=frame_length, window=window)
+
+
+def imdst(y: Tensor, out_length: int | None = None, frame_length: int = 400, window: str = "sine") -> Tensor:
+    """Inverse modified discrete sine transform y:(..., 2T/L, L/2) -> (..., T) (functional.py: imdst)."""
+    return InverseModifiedDiscreteSineTransform._func(y, out_length=out_length, frame_length=frame_length, window=window)

@@ -839,3 +839,37 @@ def pqmf_filters(n_band: int, filter_order: int, mode: str = "analysis", alpha: 
         raise ValueError("analysis or synthesis is expected.")
     rows = [2 * p * np.cos(((2 * k + 1) * np.pi / (2 * K)) * n + (-1) ** k * phase) for k in range(K)]
     return np.asarray(rows), converged
+
+
+def mdct_scale(length: int, window) -> float:
+    """z of ModifiedDiscreteTransform._precompute (mdct.py:268-271): sqrt(4 / P), sqrt(2 / P) for the window named "rectangular"."""
+    z = 2 / (length // 2)
+    if window != "rectangular":
+        z *= 2
+    return z ** 0.5
+
+
+def mdct_basis(length: int, window, transform: str = "cosine") -> np.ndarray:
+    """(L, L/2) float64: z cos(pi/P (j + 1/2 + P/2)(k + 1/2)), or sin (mdct.py:262-280, the same operations in the same order)."""
+    if length < 2 or length % 2 == 1:
+        raise ValueError("length must be at least 2 and even.")
+    P = length // 2
+    n = np.arange(length, dtype=np.float64) + 0.5
+    k = (math.pi / P) * n[:P]
+    n = n + P / 2
+    if transform == "cosine":
+        return mdct_scale(length, window) * np.cos(k[None, :] * n[:, None])
+    if transform == "sine":
+        return mdct_scale(length, window) * np.sin(k[None, :] * n[:, None])
+    raise ValueError(f"transform must be either 'cosine' or 'sine'. Got '{transform}'.")
+
+
+@functools.lru_cache(maxsize=16)
+def mdct_twiddle(length: int) -> np.ndarray:
+    """The table of the fast lapped-transform kernels (csrc/mdct.hip), 3P/2 float64 values: P/2 pairs (cos, -sin)(pi (8n + 1) / (8P)), the
+    pre- and post-twiddle of the DCT-IV of length P through a P/2-point complex transform, then P/4 pairs (cos, -sin)(2 pi m / (P/2))."""
+    P = length // 2
+    M = P // 2
+    a = math.pi * (8.0 * np.arange(M, dtype=np.float64) + 1.0) / (8.0 * P)
+    b = 2.0 * math.pi * np.arange(M // 2, dtype=np.float64) / M
+    return np.concatenate([np.stack([np.cos(a), -np.sin(a)], 1).reshape(-1), np.stack([np.cos(b), -np.sin(b)], 1).reshape(-1)])

@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define DSA_VERSION 136 /* 0.3.0: + dsa_excite (pitch to excitation: the voiced shapes of ExcitationGeneration on a segmented float64 phase sum, one launch); 0.2.9: + dsa_mlsacheck / dsa_mlsacheck_vjp (the stability check of the MLSA filter: the mel-cepstrum scaled or clipped where the amplitude of its gain-free part passes the threshold of the Pade approximation, forward and adjoint); 0.2.8: + dsa_lpc2lsp_fwd / _bwd, dsa_lsp2lpc_fwd / _bwd, dsa_lspcheck_fwd / _bwd (line spectral pairs by a Chebyshev-series root search, back by a product of real sections, and their stability check, forward and adjoint); 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
+#define DSA_VERSION 137 /* 0.3.1: + dsa_mdct_analysis / dsa_mdct_synthesis (MDCT / MDST and their inverses: window, fold, DCT-IV through a quarter-length complex FFT and overlap-add in one launch each way; each is the other's adjoint); 0.3.0: + dsa_excite (pitch to excitation: the voiced shapes of ExcitationGeneration on a segmented float64 phase sum, one launch); 0.2.9: + dsa_mlsacheck / dsa_mlsacheck_vjp (the stability check of the MLSA filter: the mel-cepstrum scaled or clipped where the amplitude of its gain-free part passes the threshold of the Pade approximation, forward and adjoint); 0.2.8: + dsa_lpc2lsp_fwd / _bwd, dsa_lsp2lpc_fwd / _bwd, dsa_lspcheck_fwd / _bwd (line spectral pairs by a Chebyshev-series root search, back by a product of real sections, and their stability check, forward and adjoint); 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
 
 typedef enum {
     DSA_OK = 0,
@@ -748,6 +748,43 @@ enum { DSA_EXCITE_PULSE = 0, DSA_EXCITE_HARMONIC_PULSE = 1, DSA_EXCITE_SINUSOIDA
        DSA_EXCITE_INVERTED_SAWTOOTH = 4, DSA_EXCITE_TRIANGLE = 5, DSA_EXCITE_SQUARE = 6 };
 int dsa_excite(const void* p, int64_t B, int64_t N, int32_t P, int32_t type, int32_t bipolar, double init_shift, const void* shift,
                int32_t dtype, void* out, void* stream);
+
+/* ------------------------------------------------------------------ a18  lapped transforms: mdct, imdct, mdst, imdst (0.3.1)
+ * ModifiedDiscreteCosineTransform._forward, mdct.py:166-176, with the basis of ModifiedDiscreteTransform._precompute, mdct.py:253-285;
+ * InverseModifiedDiscreteCosineTransform._forward, imdct.py:169-181.  P = L/2, L >= 2 and even.
+ *   basis   C[j,k] = z cos(pi/P (j + 1/2 + P/2)(k + 1/2)), sin for DSA_MDCT_SINE; z = sqrt(4/P), sqrt(2/P) for the rectangular window
+ *   dsa_mdct_analysis   x:(B,T) -> y:(B,N,P),  y[n,k] = sum_{j<L} w[j] s[t] x[t] C[j,k] at t = (n-1)P + j, x = 0 outside [0, T);
+ *                       1 <= T <= N P (the host layer passes N = (T + P - 1) / P + 1, the frames of the reference's padded signal)
+ *   dsa_mdct_synthesis  y:(B,N,P) -> x:(B,T),  x[t] = s[t] sum_n w[j] sum_k y[n,k] C[j,k] at j = t + P - nP in [0, L): the two frames
+ *                       t / P and t / P + 1, the older one first; 0 <= T <= N P
+ *   scale   DSA_MDCT_SCALE_NONE: s = 1.  DSA_MDCT_SCALE_OVERLAP: s[t] = 1/2 for t < (N-1)P, else 1 -- Unframe's division by the number
+ *           of frames over a sample (imdct.py:178; its divisor c + 1e-16 rounds to exactly 2 or 1 in both dtypes), applied while the
+ *           synthesis stores and while the analysis loads.
+ * Each entry is the other's adjoint: d/dx of analysis(SCALE_NONE) is synthesis(SCALE_NONE) at the same T and N, d/dy of
+ * synthesis(scale) is analysis(scale) of the cotangent -- two kernel families serve all eight directions of the four operators.
+ * Tables, built by the host layer in float64 and cast to the dtype (device pointers, read-only):
+ *   w        (L)  Window(L, norm="none", symmetric=True)
+ *   basis    (L, P) for the analysis, basis_t (P, L), its transpose, for the synthesis: C above with z folded in.  The generic kernels
+ *            read it; NULL when the fast kernels are to run.
+ *   twiddle  3P/2 values of the dtype: P/2 pairs (cos, -sin)(pi (8n + 1) / (8P)) and P/4 pairs (cos, -sin)(2 pi m / (P/2)).  The fast
+ *            kernels read it, with z as a scalar; NULL selects the generic kernels.
+ * algo: DSA_ALGO_AUTO runs the fast kernels when dtype is DSA_F32, L is a power of two in DSA_MDCT_FAST_MIN_LENGTH ..
+ * DSA_MDCT_FAST_MAX_LENGTH and `twiddle` is given (or `basis` is not); DSA_ALGO_GENERIC never does; DSA_ALGO_TUNED returns
+ * DSA_ERR_UNSUPPORTED where they cannot.  dsa_last_kernel(): "mdct_analysis_fast", "mdct_analysis_generic", "mdct_synthesis_fast",
+ * "mdct_synthesis_generic".
+ * One launch, no allocation, no workspace, no atomics (every output element is written once, by one thread: deterministic), int64
+ * indexing; B = 0 or N = 0 (and T = 0 in the synthesis) is a no-op before any pointer is looked at.  DSA_ERR_INVALID_ARGUMENT with
+ * a message that names "mdct": L odd or < 2, a negative size, T > N P, T < 1 in the analysis, a transform / scale / dtype / algo that
+ * is none of the enumerators, more than 2^31 - 1 tiles, a missing pointer.
+ * A frame's bits depend on (L, tables, options) and its own 2P samples (P coefficients), not on B, N, T or its place in them. */
+enum { DSA_MDCT_COSINE = 0, DSA_MDCT_SINE = 1 };
+enum { DSA_MDCT_SCALE_NONE = 0, DSA_MDCT_SCALE_OVERLAP = 1 };
+#define DSA_MDCT_FAST_MIN_LENGTH 16
+#define DSA_MDCT_FAST_MAX_LENGTH 4096
+int dsa_mdct_analysis(const void* x, int64_t B, int64_t T, int64_t N, int32_t L, const void* w, const void* basis, const void* twiddle,
+                      double z, int32_t transform, int32_t scale, int32_t dtype, int32_t algo, void* y, void* stream);
+int dsa_mdct_synthesis(const void* y, int64_t B, int64_t N, int32_t L, const void* w, const void* basis_t, const void* twiddle, double z,
+                       int32_t transform, int32_t scale, int64_t T, int32_t dtype, int32_t algo, void* x, void* stream);
 
 #ifdef __cplusplus
 }
