@@ -21,6 +21,7 @@ from .modules import *  # noqa: F401,F403
 from .modules import __all__ as _module_names
 # exported from here and not from diffsptk_amd.modules: every name of modules.__all__ needs a row in the alignment sweep's table
 # (tests/alignment_rows.py); the change that adds that row moves the name into modules.__all__
+from .modules.delta import Delta
 from .modules.excite import ExcitationGeneration
 from .modules.imdct import InverseModifiedDiscreteCosineTransform, InverseModifiedDiscreteSineTransform, InverseModifiedDiscreteTransform
 from .modules.imdct import InverseModifiedDiscreteCosineTransform as IMDCT
@@ -28,6 +29,9 @@ from .modules.imdct import InverseModifiedDiscreteSineTransform as IMDST
 from .modules.mdct import ModifiedDiscreteCosineTransform, ModifiedDiscreteSineTransform, ModifiedDiscreteTransform
 from .modules.mdct import ModifiedDiscreteCosineTransform as MDCT
 from .modules.mdct import ModifiedDiscreteSineTransform as MDST
+from .modules.mcpf import MelCepstrumPostfiltering
+from .modules.mlpg import MaximumLikelihoodParameterGeneration
+from .modules.mlpg import MaximumLikelihoodParameterGeneration as MLPG
 from .modules.mlsacheck import MLSADigitalFilterStabilityCheck
 from .signals import mseq, mseq_like, nrand
 from .utils.public import get_alpha, read, write
@@ -35,4 +39,5 @@ from .utils.public import get_alpha, read, write
 __version__ = "0.1.0"
 __all__ = [*_module_names, "functional", "get_alpha", "read", "write", "Graphed", "MLSADigitalFilterStabilityCheck",
            "ExcitationGeneration", "mseq", "mseq_like", "nrand", "MDCT", "IMDCT", "MDST", "IMDST", "ModifiedDiscreteCosineTransform",
-           "InverseModifiedDiscreteCosineTransform", "ModifiedDiscreteSineTransform", "InverseModifiedDiscreteSineTransform"]
+           "InverseModifiedDiscreteCosineTransform", "ModifiedDiscreteSineTransform", "InverseModifiedDiscreteSineTransform", "Delta", "MLPG",
+           "MaximumLikelihoodParameterGeneration", "MelCepstrumPostfiltering"]

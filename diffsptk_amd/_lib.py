@@ -18,7 +18,8 @@ CSRC = os.path.join(_PKG, "csrc")
 LIB_DIR = os.path.join(_PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libdiffsptk_amd.so")
 SOURCES = ("core.hip", "stft.hip", "spec.hip", "griffin.hip", "mcep.hip", "mcep_mfma.hip", "lpc.hip", "fbank.hip", "fftcep.hip", "mgc.hip", "thsolve.hip",
-           "zerodf.hip", "rows_gemm.hip", "thsolve_quad.hip", "poledf.hip", "plp.hip", "pqmf.hip", "parcor.hip", "lsp.hip", "mlsacheck.hip", "excite.hip", "mdct.hip")
+           "zerodf.hip", "rows_gemm.hip", "thsolve_quad.hip", "poledf.hip", "plp.hip", "pqmf.hip", "parcor.hip", "lsp.hip", "mlsacheck.hip", "excite.hip", "mdct.hip",
+           "paramgen.hip")
 HIPCC_FLAGS = (
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
     "-mcode-object-version=5", "-Wno-unused-value", "-ffp-contract=on",
@@ -48,6 +49,7 @@ SOURCE_FLAGS = {
     "mlsacheck.hip": _NO_PK,
     "excite.hip": _NO_PK,
     "mdct.hip": _NO_PK,
+    "paramgen.hip": _NO_PK,
     "mcep_mfma.hip": _NO_PK,   # (its kernels carry DSA_PK_TARGET -- measured faster with the compiler's pairing -- except mgcep_step_h)
 }
 

@@ -11,6 +11,9 @@ from .modules.excite import ExcitationGeneration   # (not a name of modules.__al
 from .modules.mlsacheck import MLSADigitalFilterStabilityCheck   # (not a name of modules.__all__ yet: modules/mlsacheck.py)
 from .modules.imdct import InverseModifiedDiscreteCosineTransform, InverseModifiedDiscreteSineTransform   # (the same)
 from .modules.mdct import ModifiedDiscreteCosineTransform, ModifiedDiscreteSineTransform
+from .modules.delta import Delta
+from .modules.mcpf import MelCepstrumPostfiltering
+from .modules.mlpg import MaximumLikelihoodParameterGeneration
 
 
 def acorr(x: Tensor, acr_order: int, out_format: str | int = "naive") -> Tensor:
@@ -301,3 +304,19 @@ def imdct(y: Tensor, out_length: int | None = None, frame_length: int = 400, win
 def imdst(y: Tensor, out_length: int | None = None, frame_length: int = 400, window: str = "sine") -> Tensor:
     """Inverse modified discrete sine transform y:(..., 2T/L, L/2) -> (..., T) (functional.py: imdst)."""
     return InverseModifiedDiscreteSineTransform._func(y, out_length=out_length, frame_length=frame_length, window=window)
+
+
+def delta(x: Tensor, seed=[[-0.5, 0, 0.5]], static_out: bool = True) -> Tensor:
+    """Delta components x:(B, T, D) or (T, D) -> (B, T, DxH) or (T, DxH) (functional.py: delta)."""
+    return Delta._func(x, seed=seed, static_out=static_out)
+
+
+def mlpg(u: Tensor, seed=[[-0.5, 0, 0.5], [1, -2, 1]]) -> Tensor:
+    """Maximum likelihood parameter generation u:(..., T, DxH) -> (..., T, D) (functional.py: mlpg); the banded factor is cached
+    per (T, seed, device, dtype)."""
+    return MaximumLikelihoodParameterGeneration._func(u, seed=seed)
+
+
+def mcpf(mc: Tensor, alpha: float = 0, beta: float = 0, onset: int = 2, ir_length: int = 128) -> Tensor:
+    """Mel-cepstrum postfiltering mc:(..., M+1) -> (..., M+1) (functional.py: mcpf)."""
+    return MelCepstrumPostfiltering._func(mc, alpha=alpha, beta=beta, onset=onset, ir_length=ir_length)

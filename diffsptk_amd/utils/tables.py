@@ -873,3 +873,105 @@ def mdct_twiddle(length: int) -> np.ndarray:
     a = math.pi * (8.0 * np.arange(M, dtype=np.float64) + 1.0) / (8.0 * P)
     b = 2.0 * math.pi * np.arange(M // 2, dtype=np.float64) / M
     return np.concatenate([np.stack([np.cos(a), -np.sin(a)], 1).reshape(-1), np.stack([np.cos(b), -np.sin(b)], 1).reshape(-1)])
+
+
+def delta_window(seed, static_out: bool = True) -> np.ndarray:
+    """(H, L) float64, L odd: the window of Delta._precompute (delta.py:105-178) from either seed form -- lists of coefficients (an
+    even-length list gets the longer padding on the right), or the widths of the first (and second) order regression coefficients."""
+    if not isinstance(seed, (tuple, list)):
+        raise ValueError("seed must be tuple or list.")
+    rows = []
+    if isinstance(seed[0], (tuple, list)):
+        lists = ([[1.0]] if static_out else []) + [list(c) for c in seed]
+        max_len = max(len(c) for c in lists)
+        max_len += max_len % 2 == 0
+        for c in lists:
+            left = (max_len - len(c)) // 2
+            rows.append([0.0] * left + [float(v) for v in c] + [0.0] * (max_len - len(c) - left))
+    else:
+        if min(seed) <= 0:
+            raise ValueError("The width of regression coefficients must be positive.")
+        max_len = max(seed) * 2 + 1
+        if static_out:
+            w = np.zeros(max_len)
+            w[(max_len - 1) // 2] = 1
+            rows.append(w)
+        n = seed[0]
+        z = 1 / (n * (n + 1) * (2 * n + 1) / 3)
+        j = np.arange(-n, n + 1, dtype=np.float64)
+        rows.append(np.pad(j * z, (max_len - (n * 2 + 1)) // 2))
+        if 2 <= len(seed):
+            n = seed[1]
+            a0 = 2 * n + 1
+            a1 = a0 * n * (n + 1) / 3
+            a2 = a1 * (3 * n * n + 3 * n - 1) / 5
+            z = 1 / (2 * (a2 * a0 - a1 * a1))
+            j = np.arange(-n, n + 1, dtype=np.float64)
+            rows.append(np.pad((a0 * j * j - a1) * z, (max_len - (n * 2 + 1)) // 2))
+        if 3 <= len(seed):
+            raise ValueError("3rd order regression is not supported.")
+    return np.asarray(rows, dtype=np.float64)
+
+
+def mlpg_threshold(seed) -> np.ndarray:
+    """(H) int32: the half-width below which a row of W near either end drops its window (mlpg.py:131-137); 0 for the static one."""
+    th = [len(c) // 2 for c in seed] if isinstance(seed[0], (tuple, list)) else list(seed)
+    return np.asarray([0] + th, dtype=np.int32)
+
+
+def mlpg_keep(size: int, th: np.ndarray, N: int) -> np.ndarray:
+    """(T, H) bool: whether row (t, h) of W keeps its window (mlpg.py:151-154)."""
+    t = np.arange(size)[:, None]
+    return np.where(t < N, th[None, :] <= t, np.where(t > size - N - 1, th[None, :] < size - t, True))
+
+
+def mlpg_band(size: int, window: np.ndarray, th: np.ndarray) -> np.ndarray:
+    """The lower band of A = W^T W, (T, K + 1) float64 with K = 2N = L - 1: band[s, i] = A[s, s - K + i] (0 left of column 0), W the
+    (T H, T) window matrix of mlpg.py:139-156 -- which is never formed: row (t, h) adds window[h, a] window[h, b] at (t - N + a, t - N + b)."""
+    H, L = window.shape
+    N = (L - 1) // 2
+    K = 2 * N
+    if size < K:
+        raise ValueError(f"The sequence length {size} must be at least {K} for windows of length {L}.")
+    keep = mlpg_keep(size, th, N).astype(np.float64)
+    band = np.zeros((size, K + 1), dtype=np.float64)
+    t = np.arange(size)
+    for a in range(L):
+        for b in range(a + 1):
+            c = keep @ (window[:, a] * window[:, b])
+            ok = (t - N + b >= 0) & (t - N + a <= size - 1)
+            band[t[ok] - N + a, K - (a - b)] += c[ok]
+    return band
+
+
+def mlpg_factor(size: int, window: np.ndarray, th: np.ndarray) -> np.ndarray:
+    """The banded Cholesky factor of A = W^T W as the kernels of csrc/paramgen.hip read it, (T, K + 1) float64: row s holds
+    G[s, s-K .. s-1] and, last, 1 / G[s, s], where A = G G^T.  O(T N^2) work on the host."""
+    band = mlpg_band(size, window, th)
+    K = band.shape[1] - 1
+    G = np.zeros_like(band)
+    for s in range(size):
+        for i in range(max(0, K - s), K + 1):   # column j = s - K + i
+            j = s - K + i
+            # sum_m G[s, m] G[j, m] over the columns m < j both rows hold: m = s - K .. j - 1
+            n = i - max(0, K - s)
+            v = band[s, i] - (G[s, i - n:i] @ G[j, K - n:K] if n else 0.0)
+            if i < K:
+                G[s, i] = v / G[j, K]
+            else:
+                if not v > 0:
+                    raise ValueError("The window matrix does not have full column rank.")
+                G[s, K] = math.sqrt(v)
+    G[:, K] = 1.0 / G[:, K]
+    return G
+
+
+def mcpf_table(cep_order: int, alpha: float, ir_length: int) -> np.ndarray:
+    """(ir_length // 2 + 1, M + 1) float64: the real part of the ir_length-point spectrum of freqt(mc, -alpha) truncated to order
+    ir_length - 1, as a matrix applied to mc (mcpf.py:142-160, c2acr.py:98)."""
+    if ir_length < 2:
+        raise ValueError("ir_length must be at least 2.")
+    A = freqt_matrix(cep_order, ir_length - 1, -alpha)   # (M + 1, ir_length)
+    k = np.arange(ir_length // 2 + 1, dtype=np.float64)[:, None]
+    m = np.arange(ir_length, dtype=np.float64)[None, :]
+    return np.cos((2.0 * math.pi / ir_length) * k * m) @ A.T

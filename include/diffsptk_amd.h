@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define DSA_VERSION 137 /* 0.3.1: + dsa_mdct_analysis / dsa_mdct_synthesis (MDCT / MDST and their inverses: window, fold, DCT-IV through a quarter-length complex FFT and overlap-add in one launch each way; each is the other's adjoint); 0.3.0: + dsa_excite (pitch to excitation: the voiced shapes of ExcitationGeneration on a segmented float64 phase sum, one launch); 0.2.9: + dsa_mlsacheck / dsa_mlsacheck_vjp (the stability check of the MLSA filter: the mel-cepstrum scaled or clipped where the amplitude of its gain-free part passes the threshold of the Pade approximation, forward and adjoint); 0.2.8: + dsa_lpc2lsp_fwd / _bwd, dsa_lsp2lpc_fwd / _bwd, dsa_lspcheck_fwd / _bwd (line spectral pairs by a Chebyshev-series root search, back by a product of real sections, and their stability check, forward and adjoint); 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
+#define DSA_VERSION 138 /* 0.3.2: + dsa_delta / dsa_delta_vjp, dsa_mlpg, dsa_mcpf / dsa_mcpf_vjp (parameter generation: delta features, maximum likelihood parameter generation by a banded Cholesky solve, mel-cepstrum postfiltering in closed form); 0.3.1: + dsa_mdct_analysis / dsa_mdct_synthesis (MDCT / MDST and their inverses: window, fold, DCT-IV through a quarter-length complex FFT and overlap-add in one launch each way; each is the other's adjoint); 0.3.0: + dsa_excite (pitch to excitation: the voiced shapes of ExcitationGeneration on a segmented float64 phase sum, one launch); 0.2.9: + dsa_mlsacheck / dsa_mlsacheck_vjp (the stability check of the MLSA filter: the mel-cepstrum scaled or clipped where the amplitude of its gain-free part passes the threshold of the Pade approximation, forward and adjoint); 0.2.8: + dsa_lpc2lsp_fwd / _bwd, dsa_lsp2lpc_fwd / _bwd, dsa_lspcheck_fwd / _bwd (line spectral pairs by a Chebyshev-series root search, back by a product of real sections, and their stability check, forward and adjoint); 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
 
 typedef enum {
     DSA_OK = 0,
@@ -785,6 +785,55 @@ int dsa_mdct_analysis(const void* x, int64_t B, int64_t T, int64_t N, int32_t L,
                       double z, int32_t transform, int32_t scale, int32_t dtype, int32_t algo, void* y, void* stream);
 int dsa_mdct_synthesis(const void* y, int64_t B, int64_t N, int32_t L, const void* w, const void* basis_t, const void* twiddle, double z,
                        int32_t transform, int32_t scale, int64_t T, int32_t dtype, int32_t algo, void* x, void* stream);
+
+/* ------------------------------------------------------------------ a19  parameter generation: delta, mlpg, mcpf (0.3.2)
+ * The stage between an acoustic model's output and mlsacheck -> excite -> MLSA.  float32 and float64; every sum is taken in float64.
+ * No allocation, no atomics, int64 indexing, one launch per entry (dsa_mlpg: two); a result's bits depend on its own column (delta, mlpg) or frame
+ * (mcpf), not on the batch around it.  B = 0, T = 0 or D = 0 (mcpf: F = 0) is a no-op before any pointer is looked at.
+ * DSA_ERR_INVALID_ARGUMENT with a message that names the operator: a negative size, H or L outside 1 .. 1024, an even L, a dtype or
+ * direction that is none of the enumerators, a missing pointer, and what each entry lists below.
+ *
+ * Delta._forward, delta.py:181-201 (the window of Delta._precompute, delta.py:105-178, from the host: (H, L) of the dtype, L odd,
+ * N = (L - 1) / 2):
+ *   dsa_delta  x:(B,T,D) -> y:(B,T,H,D)   y[b,t,h,d] = sum_j window[h,j] x[b, clamp(t + j - N, 0, T - 1), d]
+ *   dsa_delta_vjp  gy:(B,T,H,D) -> gx:(B,T,D) the adjoint as a gather: row s sums window[h,j] gy[t,h] over the t with
+ *                  clamp(t + j - N) = s -- one t inside, up to N + 1 at rows 0 and T - 1, where the replicate padding folds
+ *
+ * MaximumLikelihoodParameterGeneration._forward, mlpg.py:165-171, with the matrix of _precompute, mlpg.py:126-163, never formed:
+ *   W:(T H, T)   W[(t,h), s] = window[h, s - t + N] for 0 <= s - t + N < L, kept where t < N ? th[h] <= t : (t > T - N - 1 ? th[h] < T - t : 1)
+ *                (mlpg.py:146-156: the first and last N rows drop a dynamic window whose half-width th[h] does not fit; th[0] = 0)
+ *   A = W^T W    symmetric positive definite, banded with half-bandwidth K = 2N = L - 1; A = G G^T, G lower banded
+ *   factor:(T, K + 1) of the dtype, from the host in float64: factor[s, i] = G[s, s - K + i] for i < K (0 left of column 0),
+ *                factor[s, K] = 1 / G[s, s]
+ *   dsa_mlpg, DSA_MLPG_FORWARD   u:(B,T,H,D) -> out:(B,T,D) = A^-1 W^T u: the right-hand side as a gather into out, then forward and
+ *                back substitution per column (b, d) in place; `work` is not read (NULL)
+ *   dsa_mlpg, DSA_MLPG_ADJOINT   u:(B,T,D), the cotangent -> out:(B,T,H,D) = W A^-1 u: the sweeps into work:(B,T,D) of the dtype,
+ *                then W applied to it
+ *   th:(H) int32 on the device.  One lane per column; the last K values of the recurrence stay in registers for K <=
+ *   DSA_MLPG_MAX_REGISTER_BAND and are read back from the column otherwise.  dsa_last_kernel(): "mlpg_forward_reg", "mlpg_adjoint_reg",
+ *   "mlpg_forward_any", "mlpg_adjoint_any".  T < L - 1 is an invalid argument: the reference cannot build its matrix there either
+ *   (a shape mismatch at mlpg.py:152).
+ *
+ * MelCepstrumPostfiltering._forward, mcpf.py:191-209 (freqt.py, c2acr.py:97-101, mc2b.py, b2mc.py), in closed form:
+ *   out[j] = w[j] mc[j], w[j] = 1 for j < onset, else scale = 1 + beta;   out[0] += log(e1 / e2) / 2
+ *   e = sum_{k < bins} u_k exp(2 s_k), u_k = 1 at k = 0 and k = bins - 1, else 2 (the reference's hfft over bins = ir_length / 2 + 1
+ *   values has 2 (bins - 1) points: ir_length - 1 of them for an odd ir_length; the factor 1 / n cancels in the ratio);
+ *   s = R mc for e1, s = R (w mc) for e2;   R[k,j] = sum_{m < ir_length} cos(2 pi k m / ir_length) A[m,j], A the freqt matrix of -alpha
+ *   table:(bins, M1) = R and table_t:(M1, bins) = R^T, FLOAT64 for either dtype, from the host
+ *   dsa_mcpf  mc:(F,M1) -> out:(F,M1)
+ *   dsa_mcpf_vjp  mc, g:(F,M1) -> gmc:(F,M1): the adjoint of the Jacobian at mc; nothing is saved by the forward
+ *   One wave per frame, the bins over the lanes.  2 <= bins <= DSA_MCPF_MAX_BINS, onset >= 0 (it may exceed M1), scale finite. */
+enum { DSA_MLPG_FORWARD = 0, DSA_MLPG_ADJOINT = 1 };
+#define DSA_MLPG_MAX_REGISTER_BAND 8
+#define DSA_MCPF_MAX_BINS 2049
+int dsa_delta(const void* x, int64_t B, int64_t T, int64_t D, const void* window, int32_t H, int32_t L, int32_t dtype, void* y, void* stream);
+int dsa_delta_vjp(const void* gy, int64_t B, int64_t T, int64_t D, const void* window, int32_t H, int32_t L, int32_t dtype, void* gx, void* stream);
+int dsa_mlpg(const void* u, int64_t B, int64_t T, int64_t D, const void* window, const void* th, int32_t H, int32_t L, const void* factor,
+             int32_t direction, int32_t dtype, void* work, void* out, void* stream);
+int dsa_mcpf(const void* mc, int64_t F, int32_t M1, const void* table_t, int32_t bins, double scale, int32_t onset, int32_t dtype, void* out,
+                 void* stream);
+int dsa_mcpf_vjp(const void* mc, const void* g, int64_t F, int32_t M1, const void* table, const void* table_t, int32_t bins, double scale,
+                 int32_t onset, int32_t dtype, void* gmc, void* stream);
 
 #ifdef __cplusplus
 }
