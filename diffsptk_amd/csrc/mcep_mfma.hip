@@ -683,7 +683,8 @@ static unsigned int* reset_queue(void* scratch, hipStream_t st, int words = 2)
 // `sti`: NULL (spectra in X) or the waveform side of the fused STFT -> mel-cepstrum launch (X is then unused)
 int mcep_mfma_fwd(const void* X, int64_t F, int n_iter, const void* G, const void* D, const void* E, const void* av,
                   const void* images, void* scratch, void* mc, void* hist, hipStream_t st, bool scratch_clean = false,
-                  const StftIn* sti = nullptr, bool hist_has_rt = false, bool overlapped = false, int reserve_cus = 0)
+                  const StftIn* sti = nullptr, bool hist_has_rt = false, bool overlapped = false, int reserve_cus = 0,
+                  bool fixed_steps = false)
 {
     // DSA_ALGO_HIST_HAS_RT: the caller's history buffer continues behind the (n_iter + 1, F, 25) iterates with (n_iter, F, 49) rows of rt
     float* hist_rt = (hist && hist_has_rt) ? (float*)hist + (size_t)(n_iter + 1) * (size_t)F * mm::M1 : nullptr;
@@ -724,6 +725,9 @@ int mcep_mfma_fwd(const void* X, int64_t F, int n_iter, const void* G, const voi
     if (!queue) return fail(DSA_ERR_LAUNCH, "mcep_mfma: cannot reset the tile queue%s");
     // see the ticket comment in the kernel: a short last round goes to one wave per SIMD pair
     const long slots = grid * WAVES, full = ntiles16 / slots * slots, rest = ntiles16 - full;
+    // (sized for tiles that all take the same time.  With the stopping rule of round 8 a tile takes 5 to 8 steps, and the plan still
+    //  wins: the bench step at 0.3898 - 0.3905 ms against 0.4053 - 0.4055 with every tile in the shared queue, three alternating runs
+    //  each, profiles/r08_early_stop_ab.txt)
     long tiles_shared = (full > 0 && rest > 0 && rest <= slots / 2) ? full : ntiles16;
     // DSA_ALGO_OVERLAPPED_LAUNCHES: the short round packed onto the first tail_wgs workgroups at two waves per SIMD; everyone else
     // exits and leaves its CU to the next launch on the caller's other stream (include/diffsptk_amd.h)
@@ -732,17 +736,19 @@ int mcep_mfma_fwd(const void* X, int64_t F, int n_iter, const void* G, const voi
         tiles_shared = full;
         tail_wgs = (int)((rest + WAVES - 1) / WAVES);
     }
+    // DSA_ALGO_FIXED_STEPS: a threshold no update compares below -- every step runs and every update is applied
+    const float tau = fixed_steps ? -1.f : mh::STOP_TAU;
 #define DSA_MCEP_FWD_LAUNCH(FU, RT, XPTR, STI)                                                                                       \
     hipLaunchKernelGGL((mcep_mfma_fwd_kernel_h<WAVES, FU, RT>), dim3((unsigned)grid), dim3(WAVES * 64), lds_bytes, st, (const float*)(XPTR), \
                        (long)F, n_iter, (const float*)G, (const float*)D, (const float*)E, (const float*)av, (float*)mc, (float*)hist,  \
-                       ntiles16, tiles_shared, queue, (const _Float16*)images, STI, hist_rt, tail_wgs)
+                       ntiles16, tiles_shared, queue, (const _Float16*)images, STI, hist_rt, tail_wgs, tau)
     if (padm) {
         if (rt) hipLaunchKernelGGL((mcep_mfma_fwd_kernel_h<WAVES, true, true, true>), dim3((unsigned)grid), dim3(WAVES * 64), lds_bytes, st, (const float*)nullptr,
                                    (long)F, n_iter, (const float*)G, (const float*)D, (const float*)E, (const float*)av, (float*)mc, (float*)hist,
-                                   ntiles16, tiles_shared, queue, (const _Float16*)images, *sti, hist_rt, tail_wgs);
+                                   ntiles16, tiles_shared, queue, (const _Float16*)images, *sti, hist_rt, tail_wgs, tau);
         else hipLaunchKernelGGL((mcep_mfma_fwd_kernel_h<WAVES, true, false, true>), dim3((unsigned)grid), dim3(WAVES * 64), lds_bytes, st, (const float*)nullptr,
                                 (long)F, n_iter, (const float*)G, (const float*)D, (const float*)E, (const float*)av, (float*)mc, (float*)hist,
-                                ntiles16, tiles_shared, queue, (const _Float16*)images, *sti, hist_rt, tail_wgs);
+                                ntiles16, tiles_shared, queue, (const _Float16*)images, *sti, hist_rt, tail_wgs, tau);
         return check_launch("stft512_mcep_fused_fwd");
     }
     if (sti) {
@@ -760,7 +766,7 @@ int mcep_mfma_fwd(const void* X, int64_t F, int n_iter, const void* G, const voi
 int stft_mcep_fused_fwd(const void* x, int64_t B, int64_t T, int P, int center, const void* window, const void* twiddle, double eps,
                         int n_iter, const void* G, const void* D, const void* E, const void* av, const void* images, void* scratch,
                         void* mc, void* hist, void* X_out, hipStream_t st, bool scratch_clean, bool hist_has_rt, bool overlapped, int pad_mode,
-                        int zmean, float floor_lin, int reserve_cus)
+                        int zmean, float floor_lin, int reserve_cus, bool fixed_steps)
 {
     const int64_t N = T <= 0 ? 0 : (T - 1) / P + 1;
     StftIn sti;
@@ -776,7 +782,7 @@ int stft_mcep_fused_fwd(const void* x, int64_t B, int64_t T, int P, int center, 
     sti.pad_mode = pad_mode;
     sti.zmean = zmean;
     sti.floor_lin = floor_lin;
-    return mcep_mfma_fwd(nullptr, B * N, n_iter, G, D, E, av, images, scratch, mc, hist, st, scratch_clean, &sti, hist_has_rt, overlapped, reserve_cus);
+    return mcep_mfma_fwd(nullptr, B * N, n_iter, G, D, E, av, images, scratch, mc, hist, st, scratch_clean, &sti, hist_has_rt, overlapped, reserve_cus, fixed_steps);
 }
 
 // mcep.py:208-222, all n_iter steps in one persistent launch, for orders 32 .. 54 (the 48 kHz set-ups fft_length 2048 / order 49 and

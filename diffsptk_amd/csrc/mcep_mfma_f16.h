@@ -74,6 +74,10 @@ constexpr int IMG_DH = 0, IMG_DL = IMG_DH + IMG_D, IMG_EH = IMG_DL + IMG_D, IMG_
 constexpr int IMG_GH = IMG_EL + IMG_E, IMG_GL = IMG_GH + IMG_G, IMG_HALVES = IMG_GL + IMG_G;
 constexpr int IMG_BYTES = IMG_HALVES * 2 + 32 * 4;  // + the Nyquist row G[256][0..24] as float32
 constexpr int EMAX_LOG2 = 15;   // largest scaled e is <= 2^15
+// Stopping rule of the forward kernel (see the end of its Newton step): a frame's iteration ends with the first step whose update is
+// at most STOP_TAU max(1, |mc|_inf).  Above the kernel's own update floor on converged frames, far below the suite's tolerance
+// (DESIGN.md 3.1).
+constexpr float STOP_TAU = 0x1p-20f;
 // LDS carve-up (float units; same region sizes as namespace mm: the binary16 hi + lo images take
 // exactly the room of one float32 image)
 constexpr int DH_OFF = 0;                    // [16 mt][64 lane] f16x8
@@ -81,7 +85,7 @@ constexpr int DL_OFF = DH_OFF + 16 * 64 * 4;
 constexpr int EH_OFF = DL_OFF + 16 * 64 * 4;  // [3 it][8 j][64 lane] f16x8
 constexpr int EL_OFF = EH_OFF + 24 * 64 * 4;
 constexpr int H_E48 = EL_OFF + 24 * 64 * 4;  // [16 mt][4 g][4 r] float
-constexpr int H_E256 = H_E48 + 256;      // [48] scaled by SE, [48] = unscaled E[256][48]
+constexpr int H_E256 = H_E48 + 256;      // [48] scaled by SE, [48] = unscaled E[256][48], [50] = the stopping rule's tau
 constexpr int H_D256 = H_E256 + 52;      // [32]
 constexpr int H_AV = H_D256 + 32;        // [28]
 constexpr int H_NAV = H_AV + 28;         // [28] -alpha_vec, zero-padded
@@ -232,7 +236,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) DSA_PK_TARGET void mcep_mfma
     const float* __restrict__ X, long F, int n_iter, const float* __restrict__ G,
     const float* __restrict__ D, const float* __restrict__ E, const float* __restrict__ av,
     float* __restrict__ mc_out, float* __restrict__ hist, long ntiles16, long tiles_shared,
-    unsigned int* __restrict__ queue, const _Float16* __restrict__ img, StftIn sti, float* __restrict__ hist_rt, int tail_wgs)
+    unsigned int* __restrict__ queue, const _Float16* __restrict__ img, StftIn sti, float* __restrict__ hist_rt, int tail_wgs, float tau)
 {
     // hist_rt (round 5; NULL or (n_iter, F, 49)): every step's rt = e E row, kept for the backward, which then skips its own second
     // forward chain (DSA_ALGO_HIST_HAS_RT; 196 more bytes per frame and step)
@@ -257,6 +261,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) DSA_PK_TARGET void mcep_mfma
     }
     if (tid < 48) lds[H_E256 + tid] = SE * E[H * M2 + tid];
     if (tid == 48) lds[H_E256 + 48] = E[H * M2 + 48];
+    if (tid == 50) lds[H_E256 + 50] = tau;   // (a free slot of the region) the stopping rule's threshold, read where it is used
     if (tid < 32) lds[H_D256 + tid] = tid < M1 ? kNeg2Log2e * D[tid * K + H] : 0.f;
     if (tid < 28) {
         const float a_ = tid < M1 ? av[tid] : 0.f;
@@ -670,6 +675,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) DSA_PK_TARGET void mcep_mfma
                 }
             }
         }
+        unsigned frozen = 0u;   // frames whose iteration has stopped, frame n at bits n and n + 16 (see the end of the step)
         for (int iter = 0; iter < n_iter; ++iter) {
             DSA_STAMPS_DECL;
             DSA_STAMP(0);
@@ -978,13 +984,47 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) DSA_PK_TARGET void mcep_mfma
             for (int ks = 0; ks < KS; ++ks) rt_q[4 * ks + gs] = xq[ks];
             __builtin_amdgcn_wave_barrier();
             // mc += x  (mcep.py:222); window entries 28.. still hold rt, and 25..27 are zero
-            mcv[0] += rt_lds[8 * g];
+            float xv[8];
+            xv[0] = rt_lds[8 * g];
 #pragma unroll
-            for (int i = 1; i < 8; ++i) mcv[i] += keep_if(g_lt3, rt_lds[8 * g + i]);
+            for (int i = 1; i < 8; ++i) xv[i] = keep_if(g_lt3, rt_lds[8 * g + i]);
             __builtin_amdgcn_wave_barrier();
+            // Stopping rule (round 8), per frame: once |x|_inf <= tau max(1, |mc|_inf) -- mc the iterate this step started from -- the
+            // step's update is rounding noise of the solve on a finished answer.  It is still applied; every later update of the frame
+            // is discarded.  The rule reads nothing but the frame's own values, so a frame's bits depend neither on its tile
+            // neighbours nor on the kernel path.  A NaN in x compares false: such a frame runs every step.  tau < 0
+            // (DSA_ALGO_FIXED_STEPS) never compares true either: every update is applied, as before round 8.
+            // `frozen` is wave-uniform (a ballot) and lives in ONE scalar register across the step -- the fused instantiations have none to
+            // spare, and tau comes from LDS for the same reason; doubled it is the lane mask of the stopped frames' four lane groups.
+            {
+                const float tau = lds[H_E256 + 50];
+                float mabs = __builtin_fmaxf(__builtin_fabsf(mcv[0]), __builtin_fabsf(mcv[1]));
+#pragma unroll
+                for (int i = 2; i < 8; ++i) mabs = __builtin_fmaxf(mabs, __builtin_fabsf(mcv[i]));
+                const float thr = tau * __builtin_fmaxf(1.f, rows_max4(mabs));
+                bool small = __builtin_fabsf(xv[0]) <= thr;
+#pragma unroll
+                for (int i = 1; i < 8; ++i) small = small && (__builtin_fabsf(xv[i]) <= thr);
+                const unsigned long long sb = __builtin_amdgcn_ballot_w64(small);
+                unsigned conv = (unsigned)sb & (unsigned)(sb >> 32);   // lane groups 0 & 2, 1 & 3 of frame n at bits n, n + 16
+                conv &= (conv >> 16) | (conv << 16);                   // all four, at both bits
+                const unsigned long long fmask = ((unsigned long long)frozen << 32) | frozen;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    // the sum for the live lanes, the old value for the stopped ones: one select on the scalar mask, no vector temporaries
+                    const float s = mcv[i] + xv[i];
+                    float r;
+                    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(s), "v"(mcv[i]), "s"(fmask));
+                    mcv[i] = r;
+                }
+                frozen |= conv;
+            }
             DSA_STAMP(5);
             DSA_STAMPS_FLUSH;
             if (!(DSA_FUSED_DBG & 8) && hist && f_ok) store_mc_row(hist + ((long)(iter + 1) * F + f) * M1, g, mcv);
+            // all 16 frames of the tile converged (padding lanes repeat frame F - 1): the remaining steps would change nothing.  With a
+            // history every step still runs, updates masked, so that the iterates and the rt rows the backward reads are complete.
+            if (!hist && frozen == 0xffffffffu) break;
         }
         DSA_STAMP_T(19);
         if (f_ok) store_mc_row(mc_out + f * M1, g, mcv);

@@ -402,6 +402,30 @@ class overlapped_launches:
         return False
 
 
+_fixed_steps = [False]
+
+
+class fixed_newton_steps:
+    """``with ops.fixed_newton_steps():`` -- the tuned mel-cepstral forward launches (STFT -> mel-cepstrum in one launch, mcep alone;
+    float32, fft_length 512, cep_order 24) run every one of their ``n_iter`` Newton steps (DSA_ALGO_FIXED_STEPS,
+    include/diffsptk_amd.h).  By default ``n_iter`` is the LARGEST number of steps: a frame stops at the first step whose update is at
+    most 2^-20 max(1, |mc|_inf), which is where float32 steps stop improving it.  The difference between the two is a small
+    fraction of the tolerance the results are tested to; inside the context the results are those of the fixed-step kernels bit for
+    bit.  Every other kernel family runs exactly ``n_iter`` steps either way."""
+
+    def __init__(self, on: bool = True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.prev = _fixed_steps[0]
+        _fixed_steps[0] = self.on
+        return self
+
+    def __exit__(self, *exc):
+        _fixed_steps[0] = self.prev
+        return False
+
+
 _reserved_cus = [0]
 
 
@@ -427,8 +451,9 @@ class reserve_cus:
 
 def _mcep_algo(clean: bool) -> int:
     """The algo bits of a tuned mel-cepstral forward launch: DSA_ALGO_SCRATCH_IS_CLEAN with DSA_ALGO_OVERLAPPED_LAUNCHES
-    (overlapped_launches()) on the kept-zero scratch, and DSA_ALGO_RESERVE_CUS (reserve_cus())."""
-    flag = _lib.algo_reserve_cus(_reserved_cus[0])
+    (overlapped_launches()) on the kept-zero scratch, DSA_ALGO_RESERVE_CUS (reserve_cus()) and DSA_ALGO_FIXED_STEPS
+    (fixed_newton_steps())."""
+    flag = _lib.algo_reserve_cus(_reserved_cus[0]) | (_lib.ALGO_FIXED_STEPS if _fixed_steps[0] else 0)
     if clean:
         flag |= _lib.ALGO_SCRATCH_IS_CLEAN | (_lib.ALGO_OVERLAPPED_LAUNCHES if _overlapped[0] else 0)
     return flag
