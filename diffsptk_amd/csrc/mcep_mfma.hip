@@ -123,6 +123,14 @@ __device__ __forceinline__ float rows_max4(float x)
     auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
     return __builtin_fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
 }
+// the same on unsigned values (the bit patterns of non-negative floats order like the floats, with every NaN above them)
+__device__ __forceinline__ unsigned rows_maxu4(unsigned x)
+{
+    auto a = __builtin_amdgcn_permlane16_swap(x, x, false, false);
+    x = a[0] > a[1] ? a[0] : a[1];
+    auto b = __builtin_amdgcn_permlane32_swap(x, x, false, false);
+    return b[0] > b[1] ? b[0] : b[1];
+}
 
 // value of lane Q of this lane's quad (DPP quad_perm broadcast: a plain VALU move, no LDS)
 template <int Q>
@@ -725,9 +733,10 @@ int mcep_mfma_fwd(const void* X, int64_t F, int n_iter, const void* G, const voi
     if (!queue) return fail(DSA_ERR_LAUNCH, "mcep_mfma: cannot reset the tile queue%s");
     // see the ticket comment in the kernel: a short last round goes to one wave per SIMD pair
     const long slots = grid * WAVES, full = ntiles16 / slots * slots, rest = ntiles16 - full;
-    // (sized for tiles that all take the same time.  With the stopping rule of round 8 a tile takes 5 to 8 steps, and the plan still
-    //  wins: the bench step at 0.3898 - 0.3905 ms against 0.4053 - 0.4055 with every tile in the shared queue, three alternating runs
-    //  each, profiles/r08_early_stop_ab.txt)
+    // (sized for tiles that all take the same time.  With the stopping rule a tile takes mostly 5, sometimes 6 to 8 steps (round 9;
+    //  5 to 8 in round 8), and the plan still wins: the bench step at 0.3769 - 0.3774 ms against 0.3925 - 0.3929 with every tile in
+    //  the shared queue, three alternating runs each, profiles/r09_quadratic_stop_ab.txt; round 8: 0.390 against 0.405,
+    //  profiles/r08_early_stop_ab.txt)
     long tiles_shared = (full > 0 && rest > 0 && rest <= slots / 2) ? full : ntiles16;
     // DSA_ALGO_OVERLAPPED_LAUNCHES: the short round packed onto the first tail_wgs workgroups at two waves per SIMD; everyone else
     // exits and leaves its CU to the next launch on the caller's other stream (include/diffsptk_amd.h)

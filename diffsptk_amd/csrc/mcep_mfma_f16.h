@@ -74,10 +74,20 @@ constexpr int IMG_DH = 0, IMG_DL = IMG_DH + IMG_D, IMG_EH = IMG_DL + IMG_D, IMG_
 constexpr int IMG_GH = IMG_EL + IMG_E, IMG_GL = IMG_GH + IMG_G, IMG_HALVES = IMG_GL + IMG_G;
 constexpr int IMG_BYTES = IMG_HALVES * 2 + 32 * 4;  // + the Nyquist row G[256][0..24] as float32
 constexpr int EMAX_LOG2 = 15;   // largest scaled e is <= 2^15
-// Stopping rule of the forward kernel (see the end of its Newton step): a frame's iteration ends with the first step whose update is
-// at most STOP_TAU max(1, |mc|_inf).  Above the kernel's own update floor on converged frames, far below the suite's tolerance
-// (DESIGN.md 3.1).
+// Stopping rule of the forward kernel (see the end of its Newton step), on u_k = |x|_inf / max(1, |mc|_inf) of step k's update x: a
+// frame's iteration ends with the first step for which
+//   u_k <= STOP_TAU  (round 8: the update is rounding noise; above the kernel's own update floor on converged frames, far below the
+//                     suite's tolerance), or
+//   u_k <= STOP_FACTOR STOP_TAU and u_k <= u_(k-1) / STOP_FACTOR  (round 9: quadratic phase, u_(k+1) ~ C u_k^2 with C <= ~164
+//                     measured, so the next update would be below the floor: C (2^-16)^2 = 3.8e-8, a tenth of it.  The guard on
+//                     the contraction leaves linearly converging frames, whose small update does not mean a small error, to the first
+//                     clause.  False at step 1.)
+// The update of the stopping step is applied, later ones are discarded.  The kernel gets STOP_TAU as an argument
+// (negative: DSA_ALGO_FIXED_STEPS, both clauses false) and derives the second threshold from it.
 constexpr float STOP_TAU = 0x1p-20f;
+constexpr float STOP_FACTOR = 16.f;
+constexpr int H_UPREV = 56;   // slot of u_(k-1) in a frame's rt window (the step uses entries 0..48 of its RS = 68)
+static_assert(H_UPREV > 48 && H_UPREV < RS, "u_prev sits in the unused tail of the frame's rt window");
 // LDS carve-up (float units; same region sizes as namespace mm: the binary16 hi + lo images take
 // exactly the room of one float32 image)
 constexpr int DH_OFF = 0;                    // [16 mt][64 lane] f16x8
@@ -676,6 +686,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) DSA_PK_TARGET void mcep_mfma
             }
         }
         unsigned frozen = 0u;   // frames whose iteration has stopped, frame n at bits n and n + 16 (see the end of the step)
+        rt_lds[H_UPREV] = 0.f;  // no update before the first step (the fused prologue's tile in this region has been consumed)
         for (int iter = 0; iter < n_iter; ++iter) {
             DSA_STAMPS_DECL;
             DSA_STAMP(0);
@@ -996,18 +1007,35 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) DSA_PK_TARGET void mcep_mfma
             // (DSA_ALGO_FIXED_STEPS) never compares true either: every update is applied, as before round 8.
             // `frozen` is wave-uniform (a ballot) and lives in ONE scalar register across the step -- the fused instantiations have none to
             // spare, and tau comes from LDS for the same reason; doubled it is the lane mask of the stopped frames' four lane groups.
+            // Round 9, the second clause: the frame also stops once u = |x|_inf / max(1, |mc|_inf) <= STOP_FACTOR tau AND u <= u_prev /
+            // STOP_FACTOR, u_prev the same quotient one step earlier -- Newton in its quadratic phase, whose NEXT update would be below
+            // tau: the step that only confirms convergence is not run.  The contraction guard keeps slowly (linearly) converging frames
+            // on the first clause alone.  u_prev is the one value a frame carries from step to step: it lives in the free slot
+            // H_UPREV of the frame's rt window in LDS (one read and one write per step, the same value from the frame's four lanes),
+            // not in a register, and starts at 0, which no positive u compares below: step 1 never stops through this clause.
+            // |x|_inf is formed on the bit patterns (unsigned maximum of |x|): a NaN is larger than every number there, stays a NaN as a
+            // float and compares false in both clauses, where a float maximum would drop it.  It is reduced over the frame's four
+            // lane groups, so the four lanes decide alike and the ballot needs no combining.
             {
                 const float tau = lds[H_E256 + 50];
                 float mabs = __builtin_fmaxf(__builtin_fabsf(mcv[0]), __builtin_fabsf(mcv[1]));
 #pragma unroll
                 for (int i = 2; i < 8; ++i) mabs = __builtin_fmaxf(mabs, __builtin_fabsf(mcv[i]));
-                const float thr = tau * __builtin_fmaxf(1.f, rows_max4(mabs));
-                bool small = __builtin_fabsf(xv[0]) <= thr;
+                const float mnorm = __builtin_fmaxf(1.f, rows_max4(mabs));
+                const float thr = tau * mnorm;
+                unsigned xb = __float_as_uint(xv[0]) & 0x7fffffffu;
 #pragma unroll
-                for (int i = 1; i < 8; ++i) small = small && (__builtin_fabsf(xv[i]) <= thr);
-                const unsigned long long sb = __builtin_amdgcn_ballot_w64(small);
-                unsigned conv = (unsigned)sb & (unsigned)(sb >> 32);   // lane groups 0 & 2, 1 & 3 of frame n at bits n, n + 16
-                conv &= (conv >> 16) | (conv << 16);                   // all four, at both bits
+                for (int i = 1; i < 8; ++i) {
+                    const unsigned b = __float_as_uint(xv[i]) & 0x7fffffffu;
+                    xb = b > xb ? b : xb;
+                }
+                const float xinf = __uint_as_float(rows_maxu4(xb));
+                const float u = xinf * __builtin_amdgcn_rcpf(mnorm);
+                const float u_prev = rt_lds[H_UPREV];
+                rt_lds[H_UPREV] = u;
+                // (bitwise on purpose: && / || on lane-dependent conditions become exec-mask branches)
+                const bool small = (xinf <= thr) | ((xinf <= STOP_FACTOR * thr) & (STOP_FACTOR * u <= u_prev));
+                const unsigned conv = (unsigned)__builtin_amdgcn_ballot_w64(small);   // frame n at bits n and n + 16 (and n + 32, n + 48)
                 const unsigned long long fmask = ((unsigned long long)frozen << 32) | frozen;
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {

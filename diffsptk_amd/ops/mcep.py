@@ -409,7 +409,8 @@ class fixed_newton_steps:
     """``with ops.fixed_newton_steps():`` -- the tuned mel-cepstral forward launches (STFT -> mel-cepstrum in one launch, mcep alone;
     float32, fft_length 512, cep_order 24) run every one of their ``n_iter`` Newton steps (DSA_ALGO_FIXED_STEPS,
     include/diffsptk_amd.h).  By default ``n_iter`` is the LARGEST number of steps: a frame stops at the first step whose update is at
-    most 2^-20 max(1, |mc|_inf), which is where float32 steps stop improving it.  The difference between the two is a small
+    most 2^-20 max(1, |mc|_inf), which is where float32 steps stop improving it, or at most 2^-16 max(1, |mc|_inf) and a sixteenth of
+    the update before it -- the quadratic phase, in which the next update would be below 2^-20 (never at step 1).  The difference between the two is a small
     fraction of the tolerance the results are tested to; inside the context the results are those of the fixed-step kernels bit for
     bit.  Every other kernel family runs exactly ``n_iter`` steps either way."""
 

@@ -114,9 +114,10 @@ enum { DSA_ALGO_AUTO = 0, DSA_ALGO_GENERIC = 1, DSA_ALGO_TUNED = 2 };
 #define DSA_ALGO_RESERVED_CUS(algo) (((algo) >> 16) & 63)
 /* OR-ed into `algo` of dsa_mcep_fwd / dsa_stft_mcep_fwd / dsa_stft_mcep_opts_fwd (0.3.3): run every one of the n_iter Newton steps.
  * Without the flag the tuned forward (float32, fft_length 512, cep_order 24) treats n_iter as the LARGEST number of steps: a frame's
- * iteration ends with the first step whose update x satisfies |x|_inf <= 2^-20 max(1, |mc|_inf) -- mc the iterate the step started
- * from.  That update is still applied, every later one of the frame is discarded: from there on float32 Newton steps only add the
- * solve's rounding error to a finished answer.  The rule reads the frame's own values only, so a frame's result does
+ * iteration ends with the first step k whose update x satisfies, with u_k = |x|_inf / max(1, |mc|_inf) -- mc the iterate the step started
+ * from --, either u_k <= 2^-20, or u_k <= 2^-16 and u_k <= u_(k-1) / 16: Newton's quadratic phase, in which the NEXT update would
+ * be below 2^-20; never at step 1.  That update is still applied, every later one of the frame is discarded: from there on float32
+ * Newton steps only add the solve's rounding error to a finished answer (DESIGN.md 3.1).  The rule reads the frame's own values only, so a frame's result does
  * not depend on its batch, its neighbours or the kernel path; a frame with a NaN never stops early.  Without a history (mc_hist = NULL)
  * a 16-frame tile leaves the step loop once all its frames have stopped; with one, all n_iter steps run with the stopped frames'
  * updates masked, so the iterates repeat from the stopping step on and the rt rows are complete.  With the flag the results are those
