@@ -17,7 +17,7 @@ _ROOT = os.path.dirname(_PKG)
 CSRC = os.path.join(_PKG, "csrc")
 LIB_DIR = os.path.join(_PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libdiffsptk_amd.so")
-SOURCES = ("core.hip", "stft.hip", "spec.hip", "griffin.hip", "mcep.hip", "mcep_mfma.hip", "lpc.hip", "fbank.hip", "fftcep.hip", "mgc.hip", "thsolve.hip",
+SOURCES = ("core.hip", "stft.hip", "spec.hip", "griffin.hip", "mcep.hip", "mcep_mfma.hip", "mcep_mfma_bwd.hip", "mgcep_step.hip", "mcep_resid.hip", "mcep_big.hip", "lpc.hip", "fbank.hip", "fftcep.hip", "mgc.hip", "thsolve.hip",
            "zerodf.hip", "rows_gemm.hip", "thsolve_quad.hip", "poledf.hip", "plp.hip", "pqmf.hip", "parcor.hip", "lsp.hip", "mlsacheck.hip", "excite.hip", "mdct.hip",
            "paramgen.hip")
 HIPCC_FLAGS = (
@@ -50,7 +50,12 @@ SOURCE_FLAGS = {
     "excite.hip": _NO_PK,
     "mdct.hip": _NO_PK,
     "paramgen.hip": _NO_PK,
-    "mcep_mfma.hip": _NO_PK,   # (its kernels carry DSA_PK_TARGET -- measured faster with the compiler's pairing -- except mgcep_step_h)
+    # the mel-cepstral units: their kernels carry DSA_PK_TARGET -- measured faster with the compiler's pairing -- except mgcep_step_h
+    "mcep_mfma.hip": _NO_PK,
+    "mcep_mfma_bwd.hip": _NO_PK,
+    "mgcep_step.hip": _NO_PK,
+    "mcep_resid.hip": _NO_PK,
+    "mcep_big.hip": _NO_PK,
 }
 
 _lib = None

@@ -20,6 +20,7 @@
 #include <atomic>
 
 #include "../../include/diffsptk_amd.h"
+#include "mcep_units.h"   // internal declarations of the mel-cepstral families, for the units that define and the units that call them
 
 #define DSA_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -65,9 +66,7 @@ inline bool ensure_dynamic_lds(const void* kernel, int bytes, std::atomic<uint64
     return true;
 }
 
-// matrix-core "transform of the spectrum x (K x C) matrix" launcher of fbank.hip, shared with fftcep.hip
-// (use_power: 0 sqrt x | 1 x | 2 log x;  post_mode 0: floor + glog, 1: scale with the first column halved,
-//  3: first and last column halved;  needs float32, C <= 48, C < K <= 320)
+// ---- functions one unit defines and another calls (those of the mel-cepstral families: mcep_units.h, included above) ----
 // the generic route of the STFT (csrc/spec.hip), the fallback of dsa_stft_fwd / dsa_stft_bwd (csrc/stft.hip): float32 and float64
 int stft_generic_fwd(int dtype, const void* x, int64_t B, int64_t Tlen, int64_t N, int L, int P, int left, int mode, int zmean,
                      const void* w, int nfft, const void* twiddle, int fmt, double eps, int use_floor, double floor_db, void* y,
@@ -75,29 +74,9 @@ int stft_generic_fwd(int dtype, const void* x, int64_t B, int64_t Tlen, int64_t 
 int stft_generic_bwd(int dtype, const void* gy, const void* x, int64_t B, int64_t Tlen, int L, int P, int nfft, const void* w,
                      const void* twiddle, int center, int zmean, int pad_mode, double eps, int use_floor, double floor_db, int fmt,
                      void* gx, void* gw, hipStream_t st);
-// 24 x 24 Toeplitz-plus-Hankel systems, float32, 16 per wave in the quad layout (csrc/mcep_mfma.hip)
-int thsolve_quad24_fwd(const void* p, const void* q, const void* r, int64_t F, void* g, hipStream_t st, int r_stride = 24,
-                       int r_off = 0, const void* add = nullptr);
-// the whole Newton step of mgcep (gamma != 0, fft_length 512, cep_order 24, float32) in one launch: csrc/mgcep_step_f16.h
-int mgcep_step_solve_fwd(const void* x, const void* b1, int64_t F, double gamma, const void* images, void* b1_out, void* r_out, hipStream_t st,
-                         void* pt_out = nullptr, void* qt_out = nullptr, int n_steps = 1, void* b1_prev_out = nullptr);
-int mgcep_step_bwd_h(const void* x, const void* b1, const void* gpt, const void* gqt, const void* gr, int64_t F, double gamma,
-                     const void* images, const void* gx_in, void* gx, void* gb1, hipStream_t st);
-// the spectral half of a Newton step of the untuned mel-cepstral analysis on binary16-split chains: csrc/mcep_resid_f16.h
-int64_t mcep_resid_h_images_bytes(int K, int M1);
-int mcep_resid_h_prepare(const void* D, int ldd, const void* E, int lde, int K, int M1, void* images, hipStream_t st);
-int mcep_resid_h_fwd(const void* logx, int64_t F, int K, const void* mc, int M1, const void* images, void* out, int ldo, hipStream_t st);
-int64_t mcep_resid_bwd_images_bytes(int K, int M1);
-int mcep_resid_bwd_prepare(const void* D, int ldd, const void* E, int lde, int K, int M1, void* images, hipStream_t st);
-int mcep_glogx_h(const void* logx, int64_t F, int K, const void* mcs, int M1, const void* grts, int n_iter, const void* images, void* glogx,
-                 hipStream_t st);
-int mcep_resid_bwd_h(const void* logx, int64_t F, int K, const void* mc, int M1, const void* grt, const void* images, void* glogx, void* gmc,
-                     hipStream_t st);
-int mcep_big_newton(const void* logx, int64_t F, int K, const void* mc_in, int M1, const void* images, const void* av, int n_iter,
-                    void* mc_out, hipStream_t st);   // csrc/mcep_mfma.hip (mcep_big_f16.h)
-// orders 2 .. 55, float32, strided operands (csrc/thsolve_quad.hip)
-int thsolve_quadn_fwd(const void* p, int ldp, const void* q, int ldq, const void* r, int ldr, const void* sub, const void* add, int64_t F,
-                      int n, void* g, hipStream_t st);
+// matrix-core "transform of the spectrum x (K x C) matrix" launcher of fbank.hip, shared with fftcep.hip
+// (use_power: 0 sqrt x | 1 x | 2 log x;  post_mode 0: floor + glog, 1: scale with the first column halved,
+//  3: first and last column halved;  needs float32, C <= 48, C < K <= 320)
 int fbank_mfma_launch_ex(const void* x, int64_t F, int K, const void* H, int C, int ldh, double floor, double gamma,
                          int use_power, int post_mode, double post_scale, void* y, void* E, hipStream_t st, const char* name,
                          const void* W2 = nullptr, int Mo = 0, void* z = nullptr,   // optional second product z = y W2

@@ -18,7 +18,8 @@
 //
 // Kernel families:
 //  * generic : one workgroup per frame, any (nfft, M), float32/float64, forward and backward.
-//  * tuned   : see mcep_mfma.hip (float32, f32 MFMA, 16 frames per wave).
+//  * tuned   : see mcep_mfma.hip (forward) and mcep_mfma_bwd.hip (float32, binary16-split MFMA, 16 frames per wave); declared in
+//              mcep_units.h.
 #include "common.h"
 
 namespace dsa {
@@ -332,22 +333,6 @@ static int mcep_generic_bwd(const void* gmc, const void* X, const void* hist, in
                        (const T*)E, (const T*)av, (T*)gX);
     return check_launch("mcep_generic_bwd");
 }
-
-// tuned kernels (mcep_mfma.hip)
-int mcep_mfma_supported(int nfft, int M, int dtype);
-int64_t mcep_mfma_images_bytes();
-int mcep_mfma_prepare(const void* G, const void* D, const void* E, void* images, hipStream_t st);
-struct StftIn;
-int mcep_mfma_fwd(const void* X, int64_t F, int n_iter, const void* G, const void* D, const void* E, const void* av,
-                  const void* images, void* scratch, void* mc, void* hist, hipStream_t st, bool scratch_clean = false,
-                  const StftIn* sti = nullptr, bool hist_has_rt = false, bool overlapped = false, int reserve_cus = 0,
-                  bool fixed_steps = false);
-int stft_mcep_fused_fwd(const void* x, int64_t B, int64_t T, int P, int center, const void* window, const void* twiddle, double eps,
-                        int n_iter, const void* G, const void* D, const void* E, const void* av, const void* images, void* scratch,
-                        void* mc, void* hist, void* X_out, hipStream_t st, bool scratch_clean, bool hist_has_rt, bool overlapped, int pad_mode,
-                        int zmean, float floor_lin, int reserve_cus, bool fixed_steps);
-int mcep_mfma_bwd(const void* gmc, const void* X, const void* hist, int64_t F, int n_iter, const void* av,
-                  const void* images, void* scratch, void* gX, hipStream_t st, bool has_workspace = false, bool hist_has_rt = false);
 
 }  // namespace dsa
 

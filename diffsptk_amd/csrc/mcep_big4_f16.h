@@ -1,4 +1,4 @@
-// Round 6, third cut of the one-launch Newton kernel for the 48 kHz set-ups (mcep.py:208-222; included by mcep_mfma.hip after
+// Round 6, third cut of the one-launch Newton kernel for the 48 kHz set-ups (mcep.py:208-222; device code of the unit mcep_big.hip, on
 // mcep_big_f16.h, whose solver wrappers, record geometry and images it shares): TWIN workgroups.
 //
 // The eight-wave kernels of mcep_big_f16.h run a step in lock step: every wave of the CU is in the products (binary16 matrix pipe +

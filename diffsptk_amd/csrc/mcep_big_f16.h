@@ -1,5 +1,5 @@
 // Round 6: ALL Newton steps of MelCepstralAnalysis (mcep.py:208-222) at the 48 kHz set-ups (fft_length 2048 / order 49 and every
-// order 36 .. 55 the octet-layout solver covers) in ONE persistent launch (included by mcep_mfma.hip).
+// order 36 .. 55 the octet-layout solver covers) in ONE persistent launch (device code of the unit mcep_big.hip).
 //
 // Rounds 4-5 ran a step as two launches -- dsa_mcep_newton_resid_h (rt = exp(logx - 2 mc D) E on binary16 splits, mcep_resid_f16.h)
 // and dsa_mcep_newton_update (the batched Toeplitz-plus-Hankel solve, thsolve_tq.h) -- with rt:(F, 2 M + 1) and mc:(F, M + 1)
@@ -22,6 +22,8 @@
 // but 1.68 ms per 12 800 frames against 0.93 -- a lone wave per SIMD ran the two eliminations one after the other.
 #pragma once
 
+#include "common.h"
+#include "f16_split.h"   // the splits; namespace mrh: the stage geometry of mcep_resid_f16.h, whose images this kernel reads
 #include "thsolve_tq.h"
 
 #ifndef DSA_BIG_ABL

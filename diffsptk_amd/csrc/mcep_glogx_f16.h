@@ -1,4 +1,4 @@
-// Round 6 (0.2.2): glogx of the 48 kHz mel-cepstral analysis in ONE pass over the bins (included by mcep_mfma.hip after
+// Round 6 (0.2.2): glogx of the 48 kHz mel-cepstral analysis in ONE pass over the bins (device code of the unit mcep_resid.hip, on
 // mcep_resid_bwd_f16.h, whose images, scales and arithmetic it shares; autograd of mcep.py:210-215 summed over the Newton steps).
 //
 // The reverse sweep's step (mcep_resid_bwd_h_kernel) forms z_s = (grt_s E^T) * exp(logx - 2 mc_s D) over all bins and needs it twice:
@@ -19,6 +19,8 @@
 // (First cut: four waves, a whole stage per wave -- one wave per SIMD with nothing to hide its dependent chains behind, and 33 stages
 // over 4 waves is 9 against 8.25: 1.45 ms per 102 400 frames at 1 025 bins; see profiles/r06_48khz_gradient_one_node.txt.)
 #pragma once
+
+#include "mcep_resid_bwd_f16.h"
 
 namespace dsa {
 
@@ -192,32 +194,6 @@ __global__ __launch_bounds__(512, 1) DSA_PK_TARGET void mcep_glogx_h_kernel(cons
             body(u + GW, ib, xb);
         }
     }
-}
-
-// glogx = sum over the steps of (grt_s E^T) * exp(logx - 2 mc_s D): mcs (n_iter, F, M1) the iterates the steps started from, grts
-// (n_iter, F, 2 M1 - 1) the cotangents dsa_mcep_newton_update_bwd produced for them; `images` of mcep_resid_bwd_prepare.
-// DSA_ERR_UNSUPPORTED (no error text): orders outside 32 .. 54 or more steps than one workgroup's LDS holds -- the caller keeps the
-// in-place accumulation of dsa_mcep_newton_resid_h_bwd.
-int mcep_glogx_h(const void* logx, int64_t F, int K, const void* mcs, int M1, const void* grts, int n_iter, const void* images, void* glogx,
-                 hipStream_t st)
-{
-    const int ks1 = (M1 + 31) / 32, kse = mrb::kse_of(M1), N = 2 * M1 - 1;
-    if (!(ks1 == 2 && M1 >= 33 && M1 <= 55 && K >= 4 && n_iter >= 1)) return DSA_ERR_UNSUPPORTED;
-    if ((long)n_iter * mgx::step_bytes(2, kse) > mgx::kMaxLds) return DSA_ERR_UNSUPPORTED;
-    const dim3 grid((unsigned)((F + 15) / 16));
-    const int lds_b = n_iter * mgx::step_bytes(2, kse);
-#define DSA_GLOGX(KSEV, NT3V)                                                                                                             \
-    do {                                                                                                                                  \
-        static std::atomic<uint64_t> attr{0};                                                                                             \
-        if (!ensure_dynamic_lds((const void*)mcep_glogx_h_kernel<2, KSEV, NT3V>, mgx::kMaxLds, attr))                                     \
-            return fail(DSA_ERR_LAUNCH, "mcep_glogx_h: cannot reserve LDS%s");                                                            \
-        hipLaunchKernelGGL((mcep_glogx_h_kernel<2, KSEV, NT3V>), grid, dim3(512), lds_b, st, (const float*)logx, (long)F, K,              \
-                           (const float*)mcs, M1, (const float*)grts, N, n_iter, (const _Float16*)images, (float*)glogx);                 \
-    } while (0)
-    if (kse == 3) DSA_GLOGX(3, 3);
-    else DSA_GLOGX(4, 4);
-#undef DSA_GLOGX
-    return check_launch("mcep_glogx_h");
 }
 
 }  // namespace dsa

@@ -1,4 +1,4 @@
-// Round 5: the mel-cepstral backward at TWO waves per SIMD (included by mcep_mfma.hip after mcep_mfma_bwd_f16.h, whose operand
+// Round 5: the mel-cepstral backward at TWO waves per SIMD (device code of the unit mcep_mfma_bwd.hip, beside mcep_mfma_bwd_f16.h, whose operand
 // images, scales and mathematics it shares: the reverse sweep over the unrolled Newton iteration, mcep.py:189-224 under autograd).
 //
 // mcep_mfma_bwd_kernel_h keeps four 257-bin arrays of its 16 frames in registers (log2 X, lbar, e, zbar: 256 registers before the
@@ -15,6 +15,8 @@
 // invariant).  The split tail of mcep_mfma_bwd_kernel_h (pieces of Newton steps handed over through memory) is NOT taken over: it assumes
 // slots that run at one speed, and measured here it never helps (batch 160 .. 1024: equal or up to 5 % slower).
 #pragma once
+
+#include "mcep_mfma_bwd_f16.h"
 
 namespace dsa {
 

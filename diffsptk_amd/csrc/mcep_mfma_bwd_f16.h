@@ -1,5 +1,5 @@
-// Split-precision backward of the tuned mel-cepstral analysis (included by mcep_mfma.hip after
-// mcep_mfma_f16.h).  Same mathematics as mcep_mfma_bwd_kernel (reverse sweep over the unrolled Newton
+// Split-precision backward of the tuned mel-cepstral analysis (device code of the unit mcep_mfma_bwd.hip; the forward's
+// scales and images it reads are in f16_split.h).  Same mathematics as mcep_mfma_bwd_kernel (reverse sweep over the unrolled Newton
 // iteration from the saved iterates, mcep.py:189-224 under autograd), with every matrix chain on
 // v_mfma_f32_16x16x32_f16 as three binary16 products per float32 operand pair:
 //   forward re-computation   d^T = D^T mc_k^T,  rt^T = E^T e^T          (images DH/DL, EH/EL in LDS)
@@ -13,10 +13,14 @@
 // tiles drawn from a device counter.
 #pragma once
 
+#include "common.h"
+#include "f16_split.h"
+#include "mcep_solve.h"
+
 namespace dsa {
 
+// (namespace mhb begins in f16_split.h: the backward's operand images)
 namespace mhb {
-using namespace mh;
 constexpr int WAVES_B = 4;
 constexpr float SEB = 65536.f;   // scale of the E image with bins as rows (|E| <= ~0.0044)
 constexpr int SEB_LOG2 = 16;
@@ -25,15 +29,6 @@ constexpr int SDB_LOG2 = 8;
 constexpr float SGB = 4096.f;    // scale of the G image with bins as rows (|G| <= 0.13)
 constexpr int SGB_LOG2 = 12;
 constexpr int VMAX_LOG2 = 13;    // per-frame scaled cotangents are below 2^13
-// backward images (binary16 elements) behind the forward ones in the per-launch workspace
-constexpr int IMG_EB = 16 * 2 * 64 * 8, IMG_DB = 2 * 8 * 64 * 8, IMG_GB = 16 * 64 * 8;
-constexpr int B_BASE = IMG_BYTES / 2;                 // halves: forward images + the Nyquist row of G
-constexpr int IMG_EBH = B_BASE, IMG_EBL = IMG_EBH + IMG_EB;
-constexpr int IMG_DBH = IMG_EBL + IMG_EB, IMG_DBL = IMG_DBH + IMG_DB;
-constexpr int IMG_GBH = IMG_DBL + IMG_DB, IMG_GBL = IMG_GBH + IMG_GB;
-constexpr int IMG_B_HALVES = IMG_GBL + IMG_GB;
-constexpr int TAIL_B = 32 + 64 + 256;                 // float32: -2 D[c][256] | E[256][m] | E[bin][48]
-constexpr int IMG_B_BYTES = IMG_B_HALVES * 2 + TAIL_B * 4;
 // LDS carve-up (float units)
 constexpr int B_DB = EL_OFF + 24 * 64 * 4;            // DB hi | lo: 2 x 4096 floats
 constexpr int B_E48 = B_DB + 2 * IMG_DB / 2;          // [16 mt][4 g][4 r]
@@ -82,18 +77,6 @@ __global__ __launch_bounds__(256) void mcep_hb_prep_kernel(const float* __restri
     if (idx < 32) tail[idx] = idx < M1 ? -2.f * D[idx * K + H] : 0.f;
     if (idx >= 32 && idx < 96) tail[idx] = idx - 32 < M2 ? E[H * M2 + idx - 32] : 0.f;
     if (idx >= 96 && idx < 96 + 256) tail[idx] = E[(idx - 96) * M2 + 48];
-}
-
-// v = hi + lo (binary16), eight values of one MFMA operand
-__device__ __forceinline__ void split8(const float (&v)[8], f16x8& hi, f16x8& lo)
-{
-#pragma unroll
-    for (int i = 0; i < 8; i += 2) {
-        f16x2 h, l;
-        split2(v[i], v[i + 1], h, l);
-        hi[i] = h[0]; hi[i + 1] = h[1];
-        lo[i] = l[0]; lo[i + 1] = l[1];
-    }
 }
 
 // SAVED_RT (round 5): the forward kept every step's rt row (DSA_ALGO_HIST_HAS_RT, `hist_rt`: (n_iter, F, 49)); the step then loads it

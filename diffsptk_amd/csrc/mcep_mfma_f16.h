@@ -1,4 +1,4 @@
-// Split-precision variant of the tuned mel-cepstral forward (included by mcep_mfma.hip).
+// Split-precision variant of the tuned mel-cepstral forward (device code of the unit mcep_mfma.hip).
 //
 // fp32 MFMA runs at the fp32 VECTOR rate and shares the vector datapath, so in
 // mcep_mfma_fwd_kernel_v2 the two matrix chains of a Newton step (d = mc D, rt = e E) cost as much
@@ -19,6 +19,9 @@
 // elimination) is the code of mcep_mfma_fwd_kernel_v2.
 #pragma once
 
+#include "common.h"
+#include "f16_split.h"
+#include "mcep_solve.h"
 #include "pk_math.h"
 
 namespace dsa {
@@ -38,42 +41,8 @@ struct StftIn {
     float floor_lin;       // spec.py:174-176: < 0 none, else every bin at least (the frame's largest value) x this (10^(dB / 10))
 };
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-// explicit global address space: a pointer that went through an opaque asm statement is otherwise loaded from
-// with FLAT instructions, which count on the LDS counter too and stall every LDS wait behind an L2 round trip
-typedef const __attribute__((address_space(1))) f16x8* gf16x8_ptr;
-// Streaming the operand images from L2: a buffer descriptor over the image block (wave-uniform) + a 32-bit lane offset +
-// a constant -- buffer_load_dwordx4 takes all three without a vector instruction (as 64-bit per-lane pointers the steps
-// beyond the 4 KB immediate cost two carry-chained vector additions per window: 94 vector instructions per tile and step)
-typedef int i32x4v __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t image_rsrc(const _Float16* base, int bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(base), 0, bytes, 0x00020000);
-}
-__device__ __forceinline__ f16x8 gload8(__amdgpu_buffer_rsrc_t rsrc, unsigned lane_bytes, int const_bytes)
-{
-    const i32x4v r = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)lane_bytes, const_bytes, 0);
-    return __builtin_bit_cast(f16x8, r);
-}
-typedef const __attribute__((address_space(1))) float* gf32_ptr;
-
+// (namespace mh begins in f16_split.h: scales, operand images, the LDS regions of the images)
 namespace mh {
-using namespace mm;
-constexpr float SD = 16.f;      // scale of the D^T image (|-2 log2(e) D| <= ~7)
-constexpr float SM = 1024.f;    // scale of mc
-constexpr float SE = 65536.f;   // scale of the E^T image (|E| <= ~0.01)
-constexpr int SE_LOG2 = 16;
-constexpr float SG = 4096.f;    // scale of the (ln 2) G^T image (|G| <= 0.13 for |alpha| <= 0.95)
-constexpr float SL = 128.f;     // scale of log2 X (|log2 X| < 150 for any float32 input)
-// operand images in global memory (binary16 elements), written by mcep_h_prep_kernel once per launch
-constexpr int IMG_D = 16 * 64 * 8, IMG_E = 24 * 64 * 8, IMG_G = 16 * 64 * 8;
-constexpr int IMG_DH = 0, IMG_DL = IMG_DH + IMG_D, IMG_EH = IMG_DL + IMG_D, IMG_EL = IMG_EH + IMG_E;
-constexpr int IMG_GH = IMG_EL + IMG_E, IMG_GL = IMG_GH + IMG_G, IMG_HALVES = IMG_GL + IMG_G;
-constexpr int IMG_BYTES = IMG_HALVES * 2 + 32 * 4;  // + the Nyquist row G[256][0..24] as float32
-constexpr int EMAX_LOG2 = 15;   // largest scaled e is <= 2^15
 // Stopping rule of the forward kernel (see the end of its Newton step), on u_k = |x|_inf / max(1, |mc|_inf) of step k's update x: a
 // frame's iteration ends with the first step for which
 //   u_k <= STOP_TAU  (round 8: the update is rounding noise; above the kernel's own update floor on converged frames, far below the
@@ -88,12 +57,7 @@ constexpr float STOP_TAU = 0x1p-20f;
 constexpr float STOP_FACTOR = 16.f;
 constexpr int H_UPREV = 56;   // slot of u_(k-1) in a frame's rt window (the step uses entries 0..48 of its RS = 68)
 static_assert(H_UPREV > 48 && H_UPREV < RS, "u_prev sits in the unused tail of the frame's rt window");
-// LDS carve-up (float units; same region sizes as namespace mm: the binary16 hi + lo images take
-// exactly the room of one float32 image)
-constexpr int DH_OFF = 0;                    // [16 mt][64 lane] f16x8
-constexpr int DL_OFF = DH_OFF + 16 * 64 * 4;
-constexpr int EH_OFF = DL_OFF + 16 * 64 * 4;  // [3 it][8 j][64 lane] f16x8
-constexpr int EL_OFF = EH_OFF + 24 * 64 * 4;
+// LDS carve-up behind the images (float units)
 constexpr int H_E48 = EL_OFF + 24 * 64 * 4;  // [16 mt][4 g][4 r] float
 constexpr int H_E256 = H_E48 + 256;      // [48] scaled by SE, [48] = unscaled E[256][48], [50] = the stopping rule's tau
 constexpr int H_D256 = H_E256 + 52;      // [32]
@@ -133,63 +97,6 @@ constexpr int h_lds_floats_fused(int waves) { return h_lds_floats(waves) + FU_FL
 template <bool PK> __device__ __forceinline__ v2f fu_mul(v2f a, v2f b) { if constexpr (PK) return pk_mul(a, b); else return sc_mul(a, b); }
 template <bool PK> __device__ __forceinline__ v2f fu_cmul(v2f a, v2f t) { if constexpr (PK) return pk_cmul(a, t); else return sc_cmul(a, t); }
 template <bool PK, bool ZT> __device__ __forceinline__ void fu_fft16(v2f (&v)[16]) { if constexpr (PK) pk_fft16<ZT>(v); else sc_fft16<ZT>(v); }
-
-__device__ __forceinline__ f32x4 mfma_h(f16x8 a, f16x8 b, f32x4 c)
-{
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-
-// x = hi + lo in binary16 (round to nearest): two values at a time
-__device__ __forceinline__ void split2(float x0, float x1, f16x2& hi, f16x2& lo)
-{
-    hi = __builtin_convertvector(f32x2v{x0, x1}, f16x2);
-    // lo = binary16(x - float(hi)), the difference exact in float32: ONE v_fma_mixlo_f16 / v_fma_mixhi_f16 per value (binary16
-    // operand taken from its half register, float32 multiply-add, result rounded into the low / high half of the destination).
-    // Round 2 used v_fma_mix_f32 + a packed conversion (three instructions per pair), the compiler's own form is five.
-    const unsigned hb = __builtin_bit_cast(unsigned, hi);
-    // (one statement: the compiler does not see a half-register write inside inline assembly, and gfx950 wants a wait state
-    // between such a write and the next vector instruction touching the register -- the second half's read-modify-write)
-    unsigned lb;
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]\n\ts_nop 0\n\t"
-        "v_fma_mixhi_f16 %0, %1, -1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\ts_nop 0"
-        : "=&v"(lb) : "v"(hb), "v"(x0), "v"(x1));
-    lo = __builtin_bit_cast(f16x2, lb);
-}
-// four values at a time: the two pairs' half-register writes interleaved, so that the wait state between the low-half write and
-// the high half's read-modify-write of one destination is the other pair's instruction (3 of 4 s_nop fewer per four values)
-__device__ __forceinline__ void split4(float x0, float x1, float x2, float x3, f16x2& hiA, f16x2& hiB, f16x2& loA, f16x2& loB)
-{
-    hiA = __builtin_convertvector(f32x2v{x0, x1}, f16x2);
-    hiB = __builtin_convertvector(f32x2v{x2, x3}, f16x2);
-    const unsigned ha = __builtin_bit_cast(unsigned, hiA), hb = __builtin_bit_cast(unsigned, hiB);
-    unsigned la, lb;
-    asm("v_fma_mixlo_f16 %0, %2, -1.0, %4 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixlo_f16 %1, %3, -1.0, %6 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixhi_f16 %0, %2, -1.0, %5 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mixhi_f16 %1, %3, -1.0, %7 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\ts_nop 0"
-        : "=&v"(la), "=&v"(lb) : "v"(ha), "v"(hb), "v"(x0), "v"(x1), "v"(x2), "v"(x3));
-    loA = __builtin_bit_cast(f16x2, la);
-    loB = __builtin_bit_cast(f16x2, lb);
-}
-// c * s + b on both halves of a register pair: v_pk_fma_f32 (two flops per lane and issue slot)
-#ifdef DSA_MCEP_NOPK
-__device__ __forceinline__ f32x2v fma2(f32x2v c, float s, f32x2v b)
-{
-    float r0 = __builtin_fmaf(c[0], s, b[0]), r1 = __builtin_fmaf(c[1], s, b[1]);
-    asm volatile("" : "+v"(r0));
-    return f32x2v{r0, r1};
-}
-#else
-__device__ __forceinline__ f32x2v fma2(f32x2v c, float s, f32x2v b) { return c * f32x2v{s, s} + b; }
-#endif
-__device__ __forceinline__ f32x2v lo2(f32x4 v) { return __builtin_shufflevector(v, v, 0, 1); }
-__device__ __forceinline__ f32x2v hi2(f32x4 v) { return __builtin_shufflevector(v, v, 2, 3); }
-
-__device__ __forceinline__ void split1(float x, _Float16& hi, _Float16& lo)
-{
-    hi = (_Float16)x;
-    lo = (_Float16)(x - (float)hi);
-}
 
 // Operand images of the three constant matrices, split into binary16 hi / lo, in the exact
 // per-lane order the MFMAs consume them (one 16-byte element per lane and k-step).  One tiny launch

@@ -1,5 +1,5 @@
 // Round 6: the ADJOINT of the spectral half of a Newton step of MelCepstralAnalysis at the geometries the tile kernels do not cover
-// (the 48 kHz set-ups: fft_length 1024 / 2048, orders 32 .. 54), on the binary16 matrix pipe (included by mcep_mfma.hip).
+// (the 48 kHz set-ups: fft_length 1024 / 2048, orders 32 .. 54), on the binary16 matrix pipe (device code of the unit mcep_resid.hip).
 //
 //   forward (mcep_resid_f16.h):   tau = logx - 2 mc D,  e = exp(tau),  rt = e E                                  (mcep.py:210-215)
 //   this launch, given grt:(F, N): ebar = grt E^T,  z = ebar * e,  glogx += z,  gmc = -2 z D^T                    (their autograd)
@@ -17,6 +17,9 @@
 //   third chain   (-2 D)[coef, bins] z                             NT3 tiles x 3 terms, z scaled per stage by a power of two
 // The first chain's C/D tiles are the k-slots of the third chain's B operand (as e is of the forward's second chain).
 #pragma once
+
+#include "common.h"
+#include "f16_split.h"
 
 namespace dsa {
 
@@ -298,51 +301,6 @@ __global__ __launch_bounds__(256, 2) DSA_PK_TARGET void mcep_resid_bwd_h_kernel(
             const int c = 16 * tc + 4 * g + r;
             if (c < M1) orow[c] = acc[tc][r];
         }
-}
-
-int64_t mcep_resid_bwd_images_bytes(int K, int M1)
-{
-    const int ks1 = (M1 + 31) / 32;
-    return (int64_t)((K + 31) / 32) * mrb::stage_halves_b(ks1, mrb::kse_of(M1), mrb::nt3_of(M1)) * 2;
-}
-
-int mcep_resid_bwd_prepare(const void* D, int ldd, const void* E, int lde, int K, int M1, void* images, hipStream_t st)
-{
-    const int ks1 = (M1 + 31) / 32, kse = mrb::kse_of(M1), nt3 = mrb::nt3_of(M1);
-    const long pairs = (long)((K + 31) / 32) * mrb::stage_halves_b(ks1, kse, nt3) / 2;
-    hipLaunchKernelGGL(mcep_resid_bwd_prep_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st, (const float*)D, ldd, (const float*)E,
-                       lde, K, M1, 2 * M1 - 1, ks1, kse, nt3, (_Float16*)images);
-    return check_launch("mcep_resid_bwd_prepare");
-}
-
-// orders 32 .. 54 (M1 33 .. 55: two k-steps of coefficients); DSA_ERR_UNSUPPORTED otherwise -- the caller keeps the composed gradient
-int mcep_resid_bwd_h(const void* logx, int64_t F, int K, const void* mc, int M1, const void* grt, const void* images, void* glogx, void* gmc,
-                     hipStream_t st)
-{
-    const int ks1 = (M1 + 31) / 32, kse = mrb::kse_of(M1), nt3 = mrb::nt3_of(M1), N = 2 * M1 - 1;
-    if (!(ks1 == 2 && M1 >= 33 && M1 <= 55 && K >= 4)) return DSA_ERR_UNSUPPORTED;
-    const dim3 grid((unsigned)((F + 63) / 64));
-#define DSA_RESID_BWD(KSEV, NT3V)                                                                                                         \
-    do {                                                                                                                                  \
-        constexpr int lds_b = 2 * mrb::stage_halves_b(2, KSEV, NT3V) * 2;                                                                 \
-        static std::atomic<uint64_t> attr{0}, attr0{0};                                                                                   \
-        if (glogx) {                                                                                                                      \
-            if (!ensure_dynamic_lds((const void*)mcep_resid_bwd_h_kernel<2, KSEV, NT3V, true>, lds_b, attr))                              \
-                return fail(DSA_ERR_LAUNCH, "mcep_resid_bwd_h: cannot reserve LDS%s");                                                    \
-            hipLaunchKernelGGL((mcep_resid_bwd_h_kernel<2, KSEV, NT3V, true>), grid, dim3(256), lds_b, st, (const float*)logx, (long)F, K, \
-                               (const float*)mc, M1, (const float*)grt, N, (const _Float16*)images, (float*)glogx, (float*)gmc);          \
-        } else {                                                                                                                          \
-            if (!ensure_dynamic_lds((const void*)mcep_resid_bwd_h_kernel<2, KSEV, NT3V, false>, lds_b, attr0))                            \
-                return fail(DSA_ERR_LAUNCH, "mcep_resid_bwd_h: cannot reserve LDS%s");                                                    \
-            hipLaunchKernelGGL((mcep_resid_bwd_h_kernel<2, KSEV, NT3V, false>), grid, dim3(256), lds_b, st, (const float*)logx, (long)F, K, \
-                               (const float*)mc, M1, (const float*)grt, N, (const _Float16*)images, (float*)nullptr, (float*)gmc);        \
-        }                                                                                                                                 \
-    } while (0)
-    (void)nt3;
-    if (kse == 3) DSA_RESID_BWD(3, 3);   // M1 33 .. 48: N = 2 M1 - 1 <= 95 columns of rt, three tiles of coefficients
-    else DSA_RESID_BWD(4, 4);            // M1 49 .. 55
-#undef DSA_RESID_BWD
-    return check_launch("mcep_resid_bwd_h");
 }
 
 }  // namespace dsa

@@ -1,5 +1,5 @@
 // Round 5: the spectral half of a Newton step of MelCepstralAnalysis for the geometries the tile kernel does not cover (the 48 kHz
-// set-ups: fft_length 1024 / 2048, orders 34 / 49), matrix chains as 3-term binary16 splits (included by mcep_mfma.hip):
+// set-ups: fft_length 1024 / 2048, orders 34 / 49), matrix chains as 3-term binary16 splits (device code of the unit mcep_resid.hip):
 //   rt:(F, N) = exp(logx - 2 mc D) E,   logx:(F, K) natural logarithms, mc:(F, M1), D:(M1 x K), E:(K x N), N = 2 M1 - 1   (mcep.py:210-215)
 // mcep_resid_mfma_kernel (rows_gemm.hip, round 4) runs both products on v_mfma_f32_16x16x4_f32, i.e. on the float32 datapath: 82
 // matrix instructions of 32 cycles per 32 bins and 16 frames at order 49 (76 us per step and 12 800 frames at 2048 / 49, two thirds
@@ -13,15 +13,10 @@
 // 12 KS1 / 2 + 3 NT binary16 products per stage instead of 82 float32 ones.
 #pragma once
 
-namespace dsa {
+#include "common.h"
+#include "f16_split.h"   // the splits; namespace mrh: the stage geometry, shared with mcep_big_f16.h
 
-namespace mrh {
-constexpr int WAVES = 4;
-constexpr int LOG2_SD = 9;     // scale of the -2 log2(e) D image (|D| <= ~20 for |alpha| <= 0.9)
-constexpr int LOG2_SE = 16;    // scale of the E image (|E| <= ~0.03)
-constexpr int EMAX_LOG2 = 13;  // scaled e is at most 2^13
-constexpr int stage_halves(int ks1, int nt) { return (4 * ks1 + 2 * nt) * 512; }
-}  // namespace mrh
+namespace dsa {
 
 // images: per stage j (bins 32 j ..): [2 t][KS1 ks][2 (hi, lo)][64 lane][8 i] first chain (row = bin 32 j + 16 t + (lane & 15), k-slot
 // (g, i) <-> coefficient 32 ks + 8 g + i) | [NT tc][2 (hi, lo)][64 lane][8 i] second chain (row = column 16 tc + (lane & 15),
@@ -233,46 +228,6 @@ __global__ __launch_bounds__(256, 2) DSA_PK_TARGET void mcep_resid_h_kernel(cons
             const int col = 16 * tc + 4 * g + r;
             if (col < N) orow[col] = acc[tc][r];
         }
-}
-
-int64_t mcep_resid_h_images_bytes(int K, int M1)
-{
-    const int ks1 = (M1 + 31) / 32, nt = (2 * M1 - 1 + 15) / 16;
-    return (int64_t)((K + 31) / 32) * mrh::stage_halves(ks1, nt) * 2;
-}
-
-int mcep_resid_h_prepare(const void* D, int ldd, const void* E, int lde, int K, int M1, void* images, hipStream_t st)
-{
-    const int ks1 = (M1 + 31) / 32, nt = (2 * M1 - 1 + 15) / 16;
-    const long pairs = (long)((K + 31) / 32) * mrh::stage_halves(ks1, nt) / 2;
-    hipLaunchKernelGGL(mcep_resid_h_prep_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st, (const float*)D, ldd, (const float*)E, lde,
-                       K, M1, 2 * M1 - 1, ks1, nt, (_Float16*)images);
-    return check_launch("mcep_resid_prepare");
-}
-
-int mcep_resid_h_fwd(const void* logx, int64_t F, int K, const void* mc, int M1, const void* images, void* out, int ldo, hipStream_t st)
-{
-    const int ks1 = (M1 + 31) / 32, nt = (2 * M1 - 1 + 15) / 16, N = 2 * M1 - 1;
-    const dim3 grid((unsigned)((F + 63) / 64));
-#define DSA_RESID_H(KS, NTV)                                                                                                           \
-    hipLaunchKernelGGL((mcep_resid_h_kernel<KS, NTV>), grid, dim3(256), 0, st, (const float*)logx, (long)F, K, (const float*)mc, M1, \
-                       (const _Float16*)images, N, (float*)out, ldo)
-    if (ks1 == 1) {
-        switch (nt) {
-            case 1: DSA_RESID_H(1, 1); break;
-            case 2: DSA_RESID_H(1, 2); break;
-            case 3: DSA_RESID_H(1, 3); break;
-            default: DSA_RESID_H(1, 4); break;
-        }
-    } else {
-        switch (nt) {
-            case 5: DSA_RESID_H(2, 5); break;
-            case 6: DSA_RESID_H(2, 6); break;
-            default: DSA_RESID_H(2, 7); break;
-        }
-    }
-#undef DSA_RESID_H
-    return check_launch("mcep_resid_h");
 }
 
 }  // namespace dsa

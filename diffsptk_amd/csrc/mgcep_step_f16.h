@@ -1,6 +1,6 @@
 // Round 5: one Newton step of the mel-generalized cepstral analysis (gamma != 0) in ONE launch, matrix chains as 3-term binary16
-// splits (included by mcep_mfma.hip: the block elimination, the split helpers and the quad-layout Toeplitz-plus-Hankel solve live
-// there).  mgcep.py:199-230 for fft_length 512, cep_order 24, float32:
+// splits (device code of the unit mgcep_step.hip; the block elimination is in mcep_solve.h, the split helpers in f16_split.h, the
+// stand-alone quad-layout Toeplitz-plus-Hankel solve in thsolve_quad.hip).  mgcep.py:199-230 for fft_length 512, cep_order 24, float32:
 //   (re, im) = b1 (Cr, Ci);  X = 1 + g re, Y = g im, D = X^2 + Y^2, pp = x D^(-1/g - 1), qq = pp / D                 (:199-209)
 //   pt = pp Pr,  qt = (1 + g)(qq (X^2 - Y^2) Qr + qq 2XY Qi),  r = pp X Rr + pp Y Ri                                   (:212-220)
 //   b1 <- b1 + solve(toeplitz(pt) + hankel(qt), r[1:])                                                                 (:226-230)
@@ -18,7 +18,16 @@
 // of the last step, mgcep.py:221, reads it).
 #pragma once
 
+#include "common.h"
+#include "f16_split.h"
+#include "mcep_solve.h"
+#include "th_solve_reg.h"
+
 namespace dsa {
+
+// the solve's LDS record (this kernel's and thsolve_quad24_kernel's, mgcep_step.hip)
+constexpr int kTq = 132;   // floats per system in LDS: q window [0, 52) | mirrored p window [52, 104) | r [104, 132); 132 % 32 = 4: the four lanes of a
+                           // system read four consecutive banks and the eight systems of a 32-lane half cover the 32 banks once (136: two systems per bank range)
 
 namespace mgh {
 using namespace mm;
@@ -557,37 +566,6 @@ __global__ __launch_bounds__(512, 2) DSA_PK_TARGET void mgcep_step_bwd_h_kernel(
                 }
         }
     }
-}
-
-int mgcep_step_bwd_h(const void* x, const void* b1, const void* gpt, const void* gqt, const void* gr, int64_t F, double gamma,
-                     const void* images, const void* gx_in, void* gx, void* gb1, hipStream_t st)
-{
-    const int lds_bytes = 2 * mgh::BW_STAGE_HALVES * 2;
-    static std::atomic<uint64_t> attr{0};
-    if (!ensure_dynamic_lds((const void*)mgcep_step_bwd_h_kernel, lds_bytes, attr))
-        return fail(DSA_ERR_LAUNCH, "mgcep_step_bwd_h: cannot reserve the LDS stage buffers%s");
-    const long ntiles = (long)((F + 15) / 16);
-    long blocks = (ntiles + mgh::WAVES - 1) / mgh::WAVES;
-    if (blocks > 256) blocks = 256;
-    hipLaunchKernelGGL(mgcep_step_bwd_h_kernel, dim3((unsigned)blocks), dim3(mgh::WAVES * 64), lds_bytes, st, (const float*)x, (const float*)b1,
-                       (const float*)gpt, (const float*)gqt, (const float*)gr, (long)F, (float)gamma, (const _Float16*)images,
-                       (const float*)gx_in, (float*)gx, (float*)gb1);
-    return check_launch("mgcep_step_bwd_h");
-}
-
-int mgcep_step_solve_fwd(const void* x, const void* b1, int64_t F, double gamma, const void* images, void* b1_out, void* r_out, hipStream_t st,
-                         void* pt_out, void* qt_out, int n_steps, void* b1_prev_out)
-{
-    const int lds_bytes = mgh::LDS_FLOATS * 4;
-    static std::atomic<uint64_t> attr{0};
-    if (!ensure_dynamic_lds((const void*)mgcep_step_h_kernel, lds_bytes, attr))
-        return fail(DSA_ERR_LAUNCH, "mgcep_step_solve: cannot reserve the LDS stage buffers%s");
-    const long ntiles = (long)((F + 15) / 16);
-    long blocks = (ntiles + mgh::WAVES - 1) / mgh::WAVES;
-    if (blocks > 256) blocks = 256;
-    hipLaunchKernelGGL(mgcep_step_h_kernel, dim3((unsigned)blocks), dim3(mgh::WAVES * 64), lds_bytes, st, (const float*)x, (const float*)b1,
-                       (long)F, (float)gamma, (const _Float16*)images, (float*)b1_out, (float*)r_out, (float*)pt_out, (float*)qt_out, n_steps, (float*)b1_prev_out);
-    return check_launch("mgcep_step_solve");
 }
 
 }  // namespace dsa

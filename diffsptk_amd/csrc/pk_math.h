@@ -3,6 +3,8 @@
 // STFT -> mel-cepstrum kernel (mcep_mfma_f16.h).  Modifier semantics are checked by tools/test_pk_asm.cpp.
 #pragma once
 
+#include "common.h"
+
 #ifndef FFT16_OUT
 #define FFT16_OUT(k) (4 * ((k)&3) + ((k) >> 2))   // register that holds X[k] after fft16 / pk_fft16
 #endif

@@ -17,6 +17,7 @@
 //
 // Reference semantics: diffsptk/modules/{stft,istft}.py (cited per kernel).
 #include "common.h"
+#include "stft_tile.h"
 
 namespace dsa {
 
@@ -71,13 +72,6 @@ __device__ __forceinline__ void fft16(cf (&v)[16])
 }
 #define FFT16_OUT(k) (4 * ((k)&3) + ((k) >> 2))
 
-constexpr int kFPW = 4;         // frames per wave (16 lanes each)
-constexpr int kTile = kFPW * 257;  // floats in one output tile (4 rows)
-// Per-frame stride of the forward kernel's complex tile: ODD, so that the 8-byte transposed reads of the two
-// frames a 32-lane LDS service group covers land on opposite bank parities (stride 256: 2-way conflict on
-// every one of the 16 reads; PMC: 39 % of the kernel's LDS cycles were conflict cycles).
-constexpr int kZS = 272;   // = 16 x 17: the padded transpose tile of a frame (see the forward kernel)
-
 #ifdef DSA_STFT_TIMING
 __device__ unsigned long long g_stft_stamps[16];
 #define STFT_STAMP(i)                                                                 \
@@ -100,10 +94,7 @@ __device__ unsigned long long g_stft_stamps[16];
 //                        (c) then the spectra Z in natural order, (d) finally the staged 4 x 257
 //                        output tile -- each use is dead before the next begins;
 //   t256[16][16] cf    : W256^(j k1), shared by the 4 frames;   fmax[kFPW].
-// The workgroup IS one wave: LDS operations of a wave execute in order, so the phases only need a compiler
-// fence.  (__syncthreads() = s_waitcnt vmcnt(0) lgkmcnt(0) + s_barrier: its vmcnt(0) made every pass wait for the
-// previous pass's output stores before touching LDS.)
-#define DSA_WAVE_SYNC() __builtin_amdgcn_wave_barrier()
+// (kFPW, the tile stride kZS and DSA_WAVE_SYNC, the fence between the phases: stft_tile.h)
 // PLAIN: power format, no relative floor, constant padding, fixed at compile time (the bench path): the format
 // branches and the per-frame maxima leave the register allocation.
 // LC: frame length fixed at compile time (0 = runtime).  With LC = 400 the selects that cut a lane's 32 samples at

@@ -17,6 +17,10 @@
 //    first): deterministic, last-bit different from before.
 #pragma once
 
+#include "common.h"
+#include "pk_math.h"
+#include "stft_tile.h"
+
 // DSA_SBWD_ABL (ablation bit mask for tools/gpu_ab_lib.sh builds only; 0 in the product): 1 no cotangent loads | 2 no
 // waveform fetch | 4 no stores | 8 no forward transform | 16 no inverse transform | 32 no overlap-add gather
 #ifndef DSA_SBWD_ABL

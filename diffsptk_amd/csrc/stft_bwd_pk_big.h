@@ -19,6 +19,10 @@
 // two waves ever add into one sample and the result does not depend on how the utterance is cut into runs.
 #pragma once
 
+#include "common.h"
+#include "stft_bwd_pk.h"   // the conjugated packed helpers and pk_ifft16
+#include "stft_tile.h"
+
 namespace dsa {
 
 template <int S>

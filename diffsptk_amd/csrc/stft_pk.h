@@ -17,7 +17,9 @@
 // keep the all-options kernel).
 #pragma once
 
+#include "common.h"
 #include "pk_math.h"
+#include "stft_tile.h"
 
 namespace dsa {
 

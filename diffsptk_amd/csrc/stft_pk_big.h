@@ -18,7 +18,9 @@
 // per instruction, exactly like the 512 kernel.  Per pass the same FFT work and the same bytes as the 512 kernel's pass.
 #pragma once
 
+#include "common.h"
 #include "pk_math.h"
+#include "stft_tile.h"
 
 namespace dsa {
 

@@ -1,7 +1,9 @@
 // The row-pivoted Toeplitz-plus-Hankel solve of ONE system by ONE wave, rows in registers (shared by csrc/thsolve.hip -- the general
-// kernel -- and the quad-layout kernels of csrc/mcep_mfma.hip / csrc/thsolve_quad.hip, which fall back to it for the systems
-// their unpivoted elimination gives up on).
+// kernel -- and the quad-layout kernels of csrc/mgcep_step_f16.h / csrc/mcep_big_f16.h / csrc/thsolve_quad.hip, which fall back to it
+// for the systems their unpivoted elimination gives up on).
 #pragma once
+
+#include "common.h"
 
 namespace dsa {
 

@@ -1,5 +1,5 @@
 // Batched Toeplitz-plus-Hankel solve for orders up to 55 on the float32 matrix instruction -- the order-24 scheme of
-// csrc/mcep_mfma.hip (thsolve_quad24_kernel / the elimination inside the tuned mel-cepstral kernels) as a template over the size.
+// csrc/mcep_solve.h (thsolve_quad24_kernel, csrc/mgcep_step.hip / the elimination inside the tuned mel-cepstral kernels) as a template over the size.
 //
 //   g:(F,n) = solve(T(p) + H(q), r - sub)  (+ add)          mcep.py:216-222, mgcep.py:226-229 (torch.linalg.solve there)
 //

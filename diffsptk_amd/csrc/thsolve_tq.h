@@ -1,6 +1,6 @@
 // Device side of the batched Toeplitz-plus-Hankel solve (csrc/thsolve_quad.hip: the scheme, the launchers): the quad- and octet-layout
 // elimination / back-substitution templates and the two kernels.  A header since round 6: the persistent Newton kernel of the 48 kHz
-// set-ups (csrc/mcep_big_f16.h, included by mcep_mfma.hip) runs the octet-layout solve inside its own step loop.
+// set-ups (csrc/mcep_big_f16.h, unit mcep_big.hip) runs the octet-layout solve inside its own step loop.
 #pragma once
 
 #include <utility>

@@ -1,4 +1,4 @@
-"""Mel-cepstral analysis: the tuned kernels (csrc/mcep.hip, mcep_mfma.hip), the composed Newton paths (rows_gemm.hip, thsolve.hip)."""
+"""Mel-cepstral analysis: the tuned kernels (csrc/mcep.hip, mcep_mfma.hip, mcep_mfma_bwd.hip), the composed Newton paths (rows_gemm.hip, thsolve.hip)."""
 from __future__ import annotations
 
 import os

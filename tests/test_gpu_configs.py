@@ -1031,7 +1031,7 @@ def test_48khz_newton_steps_in_one_launch_equal_the_two_launch_step_bit_for_bit(
 @pytest.mark.parametrize("M,nfft", [(34, 1024), (32, 2048), (42, 2048), (49, 2048), (54, 2048)])
 def test_48khz_newton_steps_wide_tiles_and_plan_give_the_narrow_tiles_bits(M, nfft, monkeypatch):
     """The wide tile shape of dsa_mcep_newton_steps (128 frames per workgroup, a wave per 16-frame group running both stages of a staged
-    pair and solving its 16 systems itself) and the plan that mixes rounds of wide tiles with narrow ones (csrc/mcep_mfma.hip:
+    pair and solving its 16 systems itself) and the plan that mixes rounds of wide tiles with narrow ones (csrc/mcep_big.hip:
     mcep_big_newton) against the narrow tiles: the same bits per frame at ragged sizes, in every round of a multi-round launch and
     across the plan's two launches; non-finite frames contained."""
     K = nfft // 2 + 1

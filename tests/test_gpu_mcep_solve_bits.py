@@ -1,4 +1,4 @@
-"""The forward Newton solve of the tuned mel-cepstral kernels (blk_elim_all_r24 in csrc/mcep_mfma.hip) on shapes and inputs the
+"""The forward Newton solve of the tuned mel-cepstral kernels (blk_elim_all_r24 in csrc/mcep_solve.h) on shapes and inputs the
 other tests leave out.  The fused launch (stft512_mcep_fused_fwd) and the two-kernel path (stft512_fwd + mcep_mfma_fwd) run the same
 solve code, so their mel-cepstra must agree bit for bit: on a ragged last tile of 16 frames, on a single frame and around frames
 made non-finite by their samples.  On badly conditioned inputs -- near-silent utterances, a quiet stretch inside an utterance -- the

@@ -348,18 +348,47 @@ def test_fftcep_module_contract():
 
 
 def test_build_recipe_is_consistent():
-    """Every per-source flag set names a source of the build, every source exists, and the library on disk
-    exports the entry points the header declares (the loader checks each signature on load)."""
+    """Every per-source flag set names a source of the build, every source exists, every csrc/*.hip file is a source of the
+    build (no orphaned unit), and the library on disk exports the entry points the header declares (the loader checks each
+    signature on load)."""
     import os
 
     from diffsptk_amd import _lib
 
     assert set(_lib.SOURCE_FLAGS) <= set(_lib.SOURCES)
+    assert len(set(_lib.SOURCES)) == len(_lib.SOURCES)
     files, deps = _lib._sources()
     assert all(os.path.exists(f) for f in files + deps)
+    on_disk = {f for f in os.listdir(_lib.CSRC) if f.endswith(".hip")}
+    assert on_disk == set(_lib.SOURCES), sorted(on_disk ^ set(_lib.SOURCES))
     lib = _lib.load()
     for name in _lib.SIGNATURES:
         assert hasattr(lib, name), name
+
+
+def test_every_csrc_header_compiles_alone():
+    """Every csrc/*.h is a header, not a fragment: it includes what it uses, so it passes the compiler's syntax check as a
+    translation unit of its own (host and gfx950 device pass; nothing is written)."""
+    import shutil
+    import subprocess
+    from concurrent.futures import ThreadPoolExecutor
+
+    from diffsptk_amd import _lib
+
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not found")
+    headers = sorted(h for h in os.listdir(_lib.CSRC) if h.endswith(".h"))
+    assert len(headers) >= 20
+
+    def check(h):
+        return subprocess.run([hipcc, "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-Wno-pragma-once-outside-header",
+                               "-x", "hip", os.path.join(_lib.CSRC, h)], capture_output=True, text=True)
+
+    with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as pool:
+        results = list(pool.map(check, headers))
+    failed = {h: (r.stdout + r.stderr)[-600:] for h, r in zip(headers, results) if r.returncode != 0}
+    assert not failed, failed
 
 
 def test_no_crossed_packed_float32():

@@ -1,7 +1,8 @@
 // Kernel-only timing of the tuned mcep forward for compile-time A/B experiments (dev tool):
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -mcode-object-version=5 -Wno-unused-value [-DDSA_...] \
 //         tools/ab_kernel.cpp -o build/ab_<tag> && build/ab_<tag> [frames] [reps]
-#include "../diffsptk_amd/csrc/mcep_mfma.hip"
+#include "../diffsptk_amd/csrc/mcep_mfma.hip"       // the unit under measurement: the forward
+#include "../diffsptk_amd/csrc/mcep_mfma_bwd.hip"   // mcep_mfma_prepare writes the backward's images through this unit
 
 #include <algorithm>
 #include <cmath>
@@ -32,13 +33,16 @@ int main(int argc, char** argv)
     hipMemcpy(D, hD.data(), hD.size() * 4, hipMemcpyHostToDevice);
     hipMemcpy(E, hE.data(), hE.size() * 4, hipMemcpyHostToDevice);
     hipMemcpy(av, hav.data(), 100, hipMemcpyHostToDevice);
+    void *img, *scratch;
+    hipMalloc(&img, dsa::mcep_mfma_images_bytes()); hipMalloc(&scratch, 256);
+    dsa::mcep_mfma_prepare(G, D, E, img, 0);
     hipEvent_t e0, e1;
     hipEventCreate(&e0); hipEventCreate(&e1);
     std::vector<float> ts;
     for (int rep = 0; rep < reps + 3; ++rep) {
         float ms = 0;
         hipEventRecord(e0);
-        dsa::launch_h<8>(X, F, 10, G, D, E, av, mc, nullptr, 0, "h8");
+        if (dsa::mcep_mfma_fwd(X, F, 10, G, D, E, av, img, scratch, mc, nullptr, 0)) { printf("launch failed\n"); return 1; }
         hipEventRecord(e1);
         hipEventSynchronize(e1);
         hipEventElapsedTime(&ms, e0, e1);

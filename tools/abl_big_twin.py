@@ -1,4 +1,4 @@
-"""Ablation timings of the twin-workgroup Newton kernel.  The ablations are COMPILE-TIME since the round's end (tools/build_variant.sh <out.so> mcep_mfma.hip
+"""Ablation timings of the twin-workgroup Newton kernel.  The ablations are COMPILE-TIME since the round's end (tools/build_variant.sh <out.so> mcep_big.hip
 -DDSA_BIG_ABL=1|2|3: 1 no solve, 2 no products; results are garbage, times are not): run this script under tools/ab_libs.sh with those builds -- the
 DSA_MCEP_BIG_ABL variable it sets is no longer read by the library (the numbers of profiles/r06_mcep_big_twin.txt were taken with the run-time switch)."""
 import os, sys, torch

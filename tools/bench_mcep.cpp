@@ -2,7 +2,8 @@
 // step of its first tile (every other wave of the chip is in its steady state by then).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -mcode-object-version=5 -Wno-unused-value -ffp-contract=on -DDSA_MCEP_TIMING \
 //         -Iinclude tools/bench_mcep.cpp -o build/bench_mcep [-DDSA_MCEP_SOLVE_VALU ...] && build/bench_mcep
-#include "../diffsptk_amd/csrc/mcep_mfma.hip"
+#include "../diffsptk_amd/csrc/mcep_mfma.hip"       // the unit under measurement: the forward
+#include "../diffsptk_amd/csrc/mcep_mfma_bwd.hip"   // mcep_mfma_prepare writes the backward's images through this unit
 
 #include <cmath>
 #include <cstdio>

@@ -2,7 +2,8 @@
 // the reverse sweep over its first tile.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -mcode-object-version=5 -Wno-unused-value -ffp-contract=on -DDSA_MCEP_TIMING \
 //         -Iinclude tools/bench_mcep_bwd.cpp -o build/bench_mcep_bwd && build/bench_mcep_bwd
-#include "../diffsptk_amd/csrc/mcep_mfma.hip"
+#include "../diffsptk_amd/csrc/mcep_mfma_bwd.hip"   // the unit under measurement: the backward
+#include "../diffsptk_amd/csrc/mcep_mfma.hip"       // mcep_mfma_prepare and the forward that fills the history
 
 #include <cmath>
 #include <cstdio>

@@ -1,5 +1,5 @@
 """Cycle stamps of one Newton step (step 2 of workgroup 0's first tile) of the 48 kHz one-launch kernel, narrow and wide tile shapes
-(a library built with -DDSA_BIG_STAMPS: tools/build_variant.sh build/lib_bigstamps.so mcep_mfma.hip -DDSA_BIG_STAMPS)."""
+(a library built with -DDSA_BIG_STAMPS: tools/build_variant.sh build/lib_bigstamps.so mcep_big.hip -DDSA_BIG_STAMPS)."""
 import os, sys, torch
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
 import diffsptk_amd as dsp

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Library variants for the reduction of the stale-result effect: tools/hazard/build_variants.sh [name:flags ...]
-# Each variant recompiles csrc/mcep_mfma.hip with its -D flags and links it with the objects of the regular build
+# Each variant recompiles csrc/mcep_mfma.hip (the forward unit: the fused kernel's flags) with its -D flags and links it with the objects of the regular build
 # (diffsptk_amd/lib/obj) into build/hz/lib_<name>.so.  Without arguments: the matrix of round 5.
 cd "$(dirname "$0")/../.."
 mkdir -p build/hz

@@ -98,18 +98,20 @@ def crossed_packed_f32(kernels):
 # scalar integer ALU: address and loop set-up, which the compiler derives anew from the set of callers a translation unit holds
 SALU_INT = re.compile(r"s_(add|addc|sub|subb|mul|mul_hi|lshl|lshr|ashr|lshl[1-4]_add|and|or|xor|andn2|orn2|not|mov|movk|cmov|cmp|cmpk|cselect|"
                       r"bfe|bfm|min|max|sext|abs)_\w*[iub](16|32|64)$")
-TUNED = re.compile(r"stft512_|stft_big_|zerodf_\w*_rows")   # the kernels that must stay identical: classes (b) / (c)
+TUNED = re.compile(r"stft512_|stft_big_|zerodf_\w*_rows|mcep_|mgcep_|thsolve_quad")   # the kernels that must stay identical: classes (b) / (c)
 
 
 def _views(ins):
     """The three views of a kernel that diff_libs compares: as is; with the literal of pc-relative address formation (the s_add_u32 /
     s_addc_u32 pair behind s_getpc_b64) masked; and with, further, every scalar integer ALU instruction that touches neither exec nor
     vcc dropped and every SGPR operand replaced by a placeholder that keeps its width.  The s_nop run behind a final s_endpgm is
-    left out of all three: it is the padding of the code object's text section, which falls to whichever kernel is linked last."""
+    left out of all three: it is the padding of the code object's text section, which falls to whichever kernel is linked last.
+    (Likewise behind a final s_branch or s_setpc_b64 -- a kernel whose last block loops back, a noinline device function's
+    return: nothing falls through an unconditional transfer into the run.)"""
     end = len(ins)
     while end and ins[end - 1][1] == "s_nop":
         end -= 1
-    if end and ins[end - 1][1] == "s_endpgm":
+    if end and ins[end - 1][1] in ("s_endpgm", "s_branch", "s_setpc_b64"):
         ins = ins[:end]
     plain = [op + " " + txt for _, op, txt in ins]
     masked, since_getpc = [], 9
