@@ -17,7 +17,7 @@ _ROOT = os.path.dirname(_PKG)
 CSRC = os.path.join(_PKG, "csrc")
 LIB_DIR = os.path.join(_PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libdiffsptk_amd.so")
-SOURCES = ("core.hip", "stft.hip", "spec.hip", "griffin.hip", "mcep.hip", "mcep_mfma.hip", "mcep_mfma_bwd.hip", "mgcep_step.hip", "mcep_resid.hip", "mcep_big.hip", "lpc.hip", "fbank.hip", "fftcep.hip", "mgc.hip", "thsolve.hip",
+SOURCES = ("core.hip", "stft.hip", "spec.hip", "griffin.hip", "mcep.hip", "mcep_mfma.hip", "mcep_mfma_bwd.hip", "mgcep_step.hip", "mcep_resid.hip", "mcep_big.hip", "lpc.hip", "lpc24.hip", "lpc24_bwd.hip", "fbank.hip", "fftcep.hip", "mgc.hip", "thsolve.hip",
            "zerodf.hip", "rows_gemm.hip", "thsolve_quad.hip", "poledf.hip", "plp.hip", "pqmf.hip", "parcor.hip", "lsp.hip", "mlsacheck.hip", "excite.hip", "mdct.hip",
            "paramgen.hip")
 HIPCC_FLAGS = (

@@ -10,7 +10,7 @@
 // Both run in place on one array: level m touches entries 1 .. m-1 only, entry m is k_m before and after.
 //
 // Layout: one frame per lane, the recursion in float64 registers whatever the data's dtype, as the Levinson stage of
-// frame_window_lpc24_kernel (lpc.hip): no cross-lane traffic.  A workgroup is one wave = 64 frames; their rows are one contiguous
+// frame_window_lpc24_kernel (lpc24.hip): no cross-lane traffic.  A workgroup is one wave = 64 frames; their rows are one contiguous
 // stretch of memory that is copied to LDS (odd row stride) with coalesced loads, and each lane then reads its own row.  The loops
 // are unrolled to the order bucket NM (8, 16, 24, 32) and guarded by wave-uniform tests against M, so that every array index is a
 // constant and the arrays stay in registers.  Orders above DSA_PARCOR_MAX_ORDER take one wave per frame with the row in LDS.

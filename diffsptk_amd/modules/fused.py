@@ -126,7 +126,7 @@ class FusedSTFTMelCepstralAnalysis(nn.Module):
 
 class FusedFrameWindowLPC(nn.Module):
     """``lpc(window(frame(x)))`` -- the LPC branch of the reference's README (README.md:198-201; BASELINE configs[3]) -- as ONE
-    launch forward and ONE launch backward (dsa_frame_window_lpc_fwd / _bwd, csrc/lpc.hip): the framed and windowed (B N, L) tensors
+    launch forward and ONE launch backward (dsa_frame_window_lpc_fwd / _bwd, csrc/lpc24.hip / csrc/lpc24_bwd.hip): the framed and windowed (B N, L) tensors
     of the module chain (two of them forward, two more backward) never exist.  Same modules, same semantics; configurations the
     launches do not cover (float64, other orders, learnable windows, a gradient through non-constant padding, frame lengths
     above 512 ...) run the three modules unchanged.  ``exact_lag_sums``: float64 lag sums on the vector unit instead of binary16

@@ -1,4 +1,5 @@
-"""The LPC branch: autocorrelation, Levinson-Durbin, LPC, and frame + window + LPC in one launch (csrc/lpc.hip)."""
+"""The LPC branch: autocorrelation, Levinson-Durbin, LPC, and frame + window + LPC in one launch (csrc/lpc.hip; the kernels tuned for
+float32 and lpc_order 24: csrc/lpc24.hip, csrc/lpc24_bwd.hip)."""
 from __future__ import annotations
 
 import torch
@@ -116,7 +117,7 @@ def frame_window_lpc(x, window, L, P, M, eps, center=True, mode="constant", exac
 
 
 def frame_window_lpc_bwd_supported(x, L, P, M, center, mode) -> bool:
-    """dsa_frame_window_lpc_bwd takes this configuration (the conditions of its launcher, csrc/lpc.hip): float32, lpc_order 24,
+    """dsa_frame_window_lpc_bwd takes this configuration (the conditions of its launcher, csrc/lpc24_bwd.hip): float32, lpc_order 24,
     25 <= frame_length <= 512, constant padding, and a (frame_length, frame_period) pair whose overlap fits the wave's stretch."""
     if not (x.is_cuda and x.dtype == torch.float32 and M == 24 and 25 <= L <= 512 and mode == "constant" and P >= 1 and x.size(-1) >= 1):
         return False

@@ -17,7 +17,7 @@ ROWS = {
     "InverseShortTimeFourierTransform": ("dsa_istft_fwd", "dsa_stft_fwd"),
     "Unframe": ("dsa_window_fwd", "dsa_frame_bwd", "dsa_frame_fwd"),
     "GriffinLim": ("dsa_istft_fwd", "dsa_stft_fwd"),
-    # csrc/lpc.hip, parcor.hip, lsp.hip
+    # csrc/lpc.hip (tuned order 24: lpc24.hip, lpc24_bwd.hip), parcor.hip, lsp.hip
     "Autocorrelation": ("dsa_acorr_fwd", "dsa_acorr_bwd"),
     "LevinsonDurbin": ("dsa_levdur_fwd", "dsa_levdur_bwd"),
     "LinearPredictiveCodingAnalysis": ("dsa_lpc_fwd", "dsa_lpc_bwd"),

@@ -275,7 +275,7 @@ def test_fused_stft_fbank(P, T, k):
     assert torch.equal(grads[1], grads[0])
 
 
-# ---------------------------------------------------------------------------------------------------- LPC (csrc/lpc.hip)
+# ---------------------------------------------------------------------------------------------------- LPC (csrc/lpc.hip, lpc24.hip, lpc24_bwd.hip)
 def _lpc_fused(P, T):
     def make():
         x = randn(2, T, seed=P + T + 2).to(DEV)

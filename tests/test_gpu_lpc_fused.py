@@ -1,5 +1,5 @@
 """fuse(frame, window, lpc): the LPC branch of the reference's README (README.md:198-201; BASELINE configs[3]) through the
-reference's own modules, ONE launch forward and ONE launch backward (dsa_frame_window_lpc_fwd / _bwd, csrc/lpc.hip) -- against the
+reference's own modules, ONE launch forward and ONE launch backward (dsa_frame_window_lpc_fwd / _bwd, csrc/lpc24.hip / lpc24_bwd.hip) -- against the
 reference's exported outputs and gradients (tests/golden/randn.npz: lpc_f64, grad_lpc_wsum_f64), the module chain on the float64
 kernels, float64 gradcheck-grade finite differences of the chain, and the size-independent properties of the partition."""
 import numpy as np

@@ -98,7 +98,7 @@ def crossed_packed_f32(kernels):
 # scalar integer ALU: address and loop set-up, which the compiler derives anew from the set of callers a translation unit holds
 SALU_INT = re.compile(r"s_(add|addc|sub|subb|mul|mul_hi|lshl|lshr|ashr|lshl[1-4]_add|and|or|xor|andn2|orn2|not|mov|movk|cmov|cmp|cmpk|cselect|"
                       r"bfe|bfm|min|max|sext|abs)_\w*[iub](16|32|64)$")
-TUNED = re.compile(r"stft512_|stft_big_|zerodf_\w*_rows|mcep_|mgcep_|thsolve_quad")   # the kernels that must stay identical: classes (b) / (c)
+TUNED = re.compile(r"stft512_|stft_big_|zerodf_\w*_rows|mcep_|mgcep_|thsolve_quad|lpc24")   # the kernels that must stay identical: classes (b) / (c)
 
 
 def _views(ins):

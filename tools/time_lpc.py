@@ -19,4 +19,16 @@ with torch.no_grad():
         b.record()
         torch.cuda.synchronize()
         ts.append(a.elapsed_time(b) / 20)
-print(_lib.last_kernel(), "ms per launch:", " ".join(f"{t:.4f}" for t in ts))
+    k_default = _lib.last_kernel()
+    te = []   # the exact route: float64 lag sums on the vector unit
+    for _ in range(5):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(20):
+            y = ops.frame_window_lpc(x, w, 400, 80, 24, 1e-5, exact_lag_sums=True)
+        b.record()
+        torch.cuda.synchronize()
+        te.append(a.elapsed_time(b) / 20)
+    k_exact = _lib.last_kernel()
+print(k_exact, "(exact_lag_sums) ms per launch:", " ".join(f"{t:.4f}" for t in te))
+print(k_default, "ms per launch:", " ".join(f"{t:.4f}" for t in ts))
