@@ -192,6 +192,39 @@ __global__ void levdur_fwd_lds_kernel(const T* __restrict__ r, long F, int M, do
 // K = sqrt(p.a + r0).  With cotangents (Kbar, abar):
 //   sbar = Kbar / (2K); abar += sbar p; pbar = sbar a; r0bar = sbar;
 //   v = R^{-1} abar (R symmetric); pbar -= v; Rbar = -v a^T; rbar[m] += sum_{|i-j|=m} Rbar_ij.
+// The frame's operands into LDS: rr[0..M] = r, a[0..M-1] = a_1..a_M, ab = abar + sbar p; returns sbar.  Ends with a barrier.
+template <typename T>
+__device__ __forceinline__ double levdur_bwd_load(const T* __restrict__ gout, const T* __restrict__ r, const T* __restrict__ out,
+                                                  long f, int M, double* rr, double* a, double* ab)
+{
+    for (int j = threadIdx.x; j <= M; j += blockDim.x) rr[j] = (double)r[f * (M + 1) + j];
+    for (int j = threadIdx.x; j < M; j += blockDim.x) a[j] = (double)out[f * (M + 1) + 1 + j];
+    __syncthreads();
+    double K = (double)out[f * (M + 1)];
+    double sbar = (double)gout[f * (M + 1)] / (2.0 * K);
+    for (int j = threadIdx.x; j < M; j += blockDim.x) ab[j] = (double)gout[f * (M + 1) + 1 + j] + sbar * rr[j + 1];
+    __syncthreads();
+    return sbar;
+}
+
+// rbar from v = R^{-1} abar (in LDS, complete): the Toeplitz scatter of Rbar = -v a^T, pbar and the r0 inside the gain
+template <typename T>
+__device__ __forceinline__ void levdur_bwd_store(const double* v, const double* a, double sbar, long f, int M, T* __restrict__ gr)
+{
+    for (int m = threadIdx.x; m <= M; m += blockDim.x) {
+        double acc = 0;
+        if (m < M) {  // Toeplitz scatter of Rbar = -v a^T onto r[0..M-1]
+            for (int i = 0; i + m < M; ++i) {
+                acc -= v[i] * a[i + m];
+                if (m > 0) acc -= v[i + m] * a[i];
+            }
+        }
+        if (m >= 1) acc += sbar * a[m - 1] - v[m - 1];  // pbar
+        if (m == 0) acc += sbar;                        // r0 inside the gain
+        gr[f * (M + 1) + m] = (T)acc;
+    }
+}
+
 // One block (64 threads) per frame, dense Gauss-Jordan in LDS (float64).
 template <typename T>
 __global__ void levdur_bwd_kernel(const T* __restrict__ gout, const T* __restrict__ r,
@@ -206,13 +239,7 @@ __global__ void levdur_bwd_kernel(const T* __restrict__ gout, const T* __restric
     double* aug = fac + M;                             // M * (M+1)
     long f = blockIdx.x;
     const int W = M + 1;
-    for (int j = threadIdx.x; j <= M; j += blockDim.x) rr[j] = (double)r[f * (M + 1) + j];
-    for (int j = threadIdx.x; j < M; j += blockDim.x) a[j] = (double)out[f * (M + 1) + 1 + j];
-    __syncthreads();
-    double K = (double)out[f * (M + 1)];
-    double sbar = (double)gout[f * (M + 1)] / (2.0 * K);
-    for (int j = threadIdx.x; j < M; j += blockDim.x) ab[j] = (double)gout[f * (M + 1) + 1 + j] + sbar * rr[j + 1];
-    __syncthreads();
+    const double sbar = levdur_bwd_load(gout, r, out, f, M, rr, a, ab);
     for (int idx = threadIdx.x; idx < M * W; idx += blockDim.x) {
         int i = idx / W, j = idx - i * W;
         aug[idx] = j < M ? rr[i > j ? i - j : j - i] + (i == j ? eps : 0.0) : ab[i];
@@ -232,18 +259,65 @@ __global__ void levdur_bwd_kernel(const T* __restrict__ gout, const T* __restric
     __syncthreads();
     for (int i = threadIdx.x; i < M; i += blockDim.x) fac[i] = aug[i * W + M] / aug[i * W + i];  // v
     __syncthreads();
-    for (int m = threadIdx.x; m <= M; m += blockDim.x) {
+    levdur_bwd_store(fac, a, sbar, f, M, gr);
+}
+
+// The same backward for orders whose dense system does not fit LDS (M > 85).  R = toeplitz(r0 + eps, r1 .. r_{M-1}) is symmetric
+// Toeplitz, so its inverse has the Gohberg-Semencul form  R^{-1} = (L(c) L(c)^T - L(z) L(z)^T) / E  with c = (1, c_1 .. c_{M-1})
+// the predictor of order M - 1 of R's own generator, E its prediction error, z = (0, c_{M-1} .. c_1) and L(.) the lower-triangular
+// Toeplitz matrix of a first column: v = R^{-1} abar costs the Levinson recursion and four triangular products, in 7 M + 1 doubles.
+// One block (one wave) per frame, float64.
+template <typename T>
+__global__ void levdur_bwd_toeplitz_kernel(const T* __restrict__ gout, const T* __restrict__ r,
+                                           const T* __restrict__ out, long F, int M, double eps,
+                                           T* __restrict__ gr)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    double* rr = reinterpret_cast<double*>(smem_raw);  // M+1
+    double* a = rr + (M + 1);                          // M   (a[0..M-1] = a_1..a_M)
+    double* ab = a + M;                                // M
+    double* v = ab + M;                                // M
+    double* c = v + M;                                 // M   (c[0] = 1)
+    double* u = c + M;                                 // M   L(c)^T abar (and the recursion's scratch before that)
+    double* w = u + M;                                 // M   L(z)^T abar
+    const int lane = threadIdx.x;
+    long f = blockIdx.x;
+    const double sbar = levdur_bwd_load(gout, r, out, f, M, rr, a, ab);
+    for (int j = lane; j < M; j += 64) c[j] = j == 0 ? 1.0 : 0.0;
+    __syncthreads();
+    double E = rr[0] + eps;
+    for (int m = 1; m < M; ++m) {   // levdur_fwd_lds_kernel's recursion on (r0 + eps, r1 .. r_{M-1}), c[0] = 1 kept in the array
         double acc = 0;
-        if (m < M) {  // Toeplitz scatter of Rbar = -v a^T onto r[0..M-1]
-            for (int i = 0; i + m < M; ++i) {
-                acc -= fac[i] * a[i + m];
-                if (m > 0) acc -= fac[i + m] * a[i];
-            }
-        }
-        if (m >= 1) acc += sbar * a[m - 1] - fac[m - 1];  // pbar
-        if (m == 0) acc += sbar;                          // r0 inside the gain
-        gr[f * (M + 1) + m] = (T)acc;
+        for (int j = lane; j < m; j += 64) acc += c[j] * rr[m - j];
+        const double k = -wave_sum(acc) / E;
+        for (int j = 1 + lane; j < m; j += 64) u[j] = c[j] + k * c[m - j];
+        __syncthreads();
+        for (int j = 1 + lane; j < m; j += 64) c[j] = u[j];
+        if (lane == 0) c[m] = k;
+        __syncthreads();
+        E *= (1.0 - k * k);
     }
+    // z[0] = 0, z[d] = c[M - d]
+    for (int j = lane; j < M; j += 64) {
+        double su = 0, sw = 0;
+        for (int i = j; i < M; ++i) {
+            su += c[i - j] * ab[i];
+            if (i > j) sw += c[M - (i - j)] * ab[i];
+        }
+        u[j] = su;
+        w[j] = sw;
+    }
+    __syncthreads();
+    for (int i = lane; i < M; i += 64) {
+        double acc = 0;
+        for (int j = 0; j <= i; ++j) {
+            acc += c[i - j] * u[j];
+            if (j < i) acc -= c[M - (i - j)] * w[j];
+        }
+        v[i] = acc / E;
+    }
+    __syncthreads();
+    levdur_bwd_store(v, a, sbar, f, M, gr);
 }
 
 // Fused Frame -> Window -> autocorrelation -> Levinson (README.md:198-201 of the reference);
@@ -317,10 +391,18 @@ static int levdur_bwd_impl(const void* gout, const void* r, const void* out, int
                            void* gr, hipStream_t st)
 {
     size_t lds = sizeof(double) * ((size_t)(M + 1) + 3 * (size_t)M + (size_t)M * (M + 1));
-    if (lds > 60 * 1024) return fail(DSA_ERR_UNSUPPORTED, "levdur_bwd: order too large for LDS%s");
-    hipLaunchKernelGGL((levdur_bwd_kernel<T>), dim3((unsigned)F), dim3(64), lds, st, (const T*)gout,
+    // M <= 85: the dense system, an elimination on R itself; the Toeplitz form goes through the Levinson recursion, whose error grows
+    // with R's conditioning, and is kept for the orders the dense system has no room for
+    if (lds <= 60 * 1024) {
+        hipLaunchKernelGGL((levdur_bwd_kernel<T>), dim3((unsigned)F), dim3(64), lds, st, (const T*)gout,
+                           (const T*)r, (const T*)out, (long)F, M, eps, (T*)gr);
+        return check_launch("levdur_bwd");
+    }
+    lds = sizeof(double) * ((size_t)(M + 1) + 6 * (size_t)M);
+    if (lds > 60 * 1024) return fail(DSA_ERR_UNSUPPORTED, "levdur_bwd: order too large for LDS%s");   // M > 1097
+    hipLaunchKernelGGL((levdur_bwd_toeplitz_kernel<T>), dim3((unsigned)F), dim3(64), lds, st, (const T*)gout,
                        (const T*)r, (const T*)out, (long)F, M, eps, (T*)gr);
-    return check_launch("levdur_bwd");
+    return check_launch("levdur_bwd_toeplitz");
 }
 
 }  // namespace dsa

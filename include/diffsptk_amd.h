@@ -584,7 +584,8 @@ int dsa_acorr_bwd(const void* gr, const void* x, int64_t F, int32_t L, int32_t M
 /* ------------------------------------------------------------------ a12  Levinson-Durbin
  * LevinsonDurbin._forward, levdur.py:113-127: a = solve(toeplitz(r[:M]) + eps I, -r[1:]),
  * K = sqrt(sum r[1:] a + r[0]); out:(F,M+1) = [K, a].  Solved by the Levinson recursion on
- * (r0+eps, r1..rM) (the same system; float64 accumulation inside). */
+ * (r0+eps, r1..rM) (the same system; float64 accumulation inside).  Orders: forward M <= 2559, backward M <= 1097
+ * (dense solve to 85, the symmetric-Toeplitz inverse above); DSA_ERR_UNSUPPORTED beyond (INTEGRATION.md, the ceilings). */
 int dsa_levdur_fwd(const void* r, int64_t F, int32_t M, double eps, int32_t dtype, void* out,
                    void* stream);
 int dsa_levdur_bwd(const void* gout, const void* r, const void* out, int64_t F, int32_t M, double eps,
