@@ -346,6 +346,7 @@ __global__ __launch_bounds__(64) void mlsacheck_generic_kernel(const T* __restri
                     sincospi((double)(2 * m) * inv_n2, &wi, &wr);
                     double zr = 1.0, zi = 0.0, acc = 0.0;
                     for (int k = 0; k < K; ++k) {
+                        if ((k & 63) == 0 && k) sincospi((double)(2 * (((long)k * m) % N2)) * inv_n2, &zi, &zr);   // (anew every 64 bins: its rounding grows with the steps, 1e-13 at 9 000 bins)
                         acc = fma(Pr[k], zr, acc);
                         acc = fma(-Pi[k], zi, acc);
                         mc_rot(zr, zi, wr, wi);
@@ -413,6 +414,7 @@ __global__ __launch_bounds__(64) void mlsacheck_generic_kernel(const T* __restri
                         sincospi((double)(2 * m) / (double)n_fft, &wi, &wr);
                         double zr = 1.0, zi = 0.0, acc = 0.0;
                         for (int k = 0; k < K; ++k) {
+                            if ((k & 63) == 0 && k) sincospi((double)(2 * (((long)k * m) % n_fft)) / (double)n_fft, &zi, &zr);   // (as the forward)
                             acc = fma(Pr[k], zr, acc);
                             acc = fma(-Pi[k], zi, acc);
                             mc_rot(zr, zi, wr, wi);

@@ -8,7 +8,10 @@ exactly one of
   EXEMPT            route -> why no case can name it (at most 5)
 
 and FORWARDED lists the names that reach check_launch() through a variable, with the source line that spells them.
-tests/test_routes_cpu.py checks, without a GPU, that nothing is missing, stale or in two places.
+tests/test_routes_cpu.py checks, without a GPU, that nothing is missing, stale or in two places.  The same discipline holds the other
+end of every launcher: each DSA_ERR_UNSUPPORTED of the sources is claimed by exactly one of REFUSALS (the first refused shapes of
+csrc/lpc.hip), CEILINGS (every size condition that refuses or silently reshapes a launch: the last shape in by float64, the first
+shape out by message or by route) and NOT_A_CEILING (message -> why no size a caller can reach meets it).
 
 A case: the call (a key of CALLS in tests/test_gpu_routes.py and of INPUTS / REFS in tests/routes_ref.py), whether the name is read
 after the forward ("fwd") or on autograd's thread after the backward ("bwd", with the inputs `wrt` whose gradients are compared),
@@ -184,6 +187,320 @@ REFUSALS = [
     ("levdur", dict(M=1098, eps=1e-5, F=1), "f64", "bwd", "levdur_bwd: order too large for LDS"),
 ]
 
+# ---- the size ceilings.  One row per size condition of csrc/*.hip / *.h that refuses a launch (DSA_ERR_UNSUPPORTED) or silently
+# reshapes it (fewer waves per block, a table left in global memory, the direct sum instead of the FFT: the route name stays):
+#   where     "file:line" of the condition(s)
+#   says      the launcher's message, or "reshapes: ..." and what changes
+#   inside    (route, case) at the last accepted shape: every dtype, the forward, and the backward where there is one
+#   outside   the nearest shape past the condition: raises(message, shape) -- BackendError from the forward, RuntimeError from autograd
+#             for a backward whose forward ran -- or runs(route, case): that route runs instead and meets the same float64 comparison;
+#             IN_REFUSALS: the first refused shape is a row of REFUSALS
+#   shadowed  messages of the same condition in a backward launcher that the forward's refusal pre-empts (no call can show them)
+# The GPU run of both sides (tests/test_gpu_routes.py) proves that they are adjacent; no LDS formula is restated in Python -- the
+# arithmetic behind each shape is in the row's comment.  Batches are the smallest that use the launch's geometry.
+IN_REFUSALS = "REFUSALS"
+
+
+def shape(call, when, dtypes, wrt=(), **args):
+    """a call that is only expected to raise: nothing is compared"""
+    return case(call, when, dtypes, wrt=wrt, tol=(0.0, 0.0), tol_from="-", **args)
+
+
+def raises(message, c, text=None):
+    return {"expect": "raises", "message": message, "text": text or message, "case": c}
+
+
+def runs(route, c):
+    return {"expect": "route", "route": route, "case": c}
+
+
+def ceiling(where, says, inside, outside, shadowed=(), cited=None):
+    return {"where": (where,) if isinstance(where, str) else tuple(where), "says": says, "inside": inside, "outside": outside,
+            "shadowed": tuple(shadowed), "cited": cited}
+
+
+def per(pairs, make):
+    """[make(dtypes, size) ...] for ((F32, size32), (F64, size64)): the shapes of a ceiling counted in bytes differ by dtype"""
+    return [make(dt, n) for dt, n in pairs]
+
+
+GCF = dict(tol=(1e-9, 5e-5), tol_from="tests/test_gpu_synth.py::test_gc2gc_fused_kernel_equals_the_operator_chain")
+FBM = dict(tol=(None, 2e-5), tol_from="tests/test_gpu_parity.py::test_fbank_matrix_core_forward_matches_float64")
+MFCC = dict(tol=(1e-8, 2e-4), tol_from="tests/test_gpu_parity.py::test_fbank_mfcc_golden_forward_backward")   # (its relative part)
+ZDF_PIECES = "tests/test_gpu_mlsa_grad.py::test_a_filter_too_long_for_lds_is_the_sum_of_its_pieces"
+AC, LD = dict(M=2, fmt=0, F=1), dict(eps=1e-5, F=1)
+FW = dict(T=4000, P=2000, M=8, eps=1e-5, B=1)                    # 3 frames: one partial block of the fused kernel's 4
+FB = dict(C=80, use_power=False, gamma=0.0, F=13)                # 4 groups of 4 frames, the last partial: 4 waves
+FC0, FC2 = dict(M=5, accel=0.0, n_iter=0, F=2), dict(M=5, accel=0.5, n_iter=2, F=2)
+PL = dict(C=20, M=12, F=5)                                       # 5 frames: more than the 4 waves of a block
+SR = dict(lb=5, la=3, eps=1e-3, floor=None, fmt=3, F=2)
+GE = dict(g1=-0.5, g2=0.0, m1=8, m2=12, F=2)
+MG = dict(M=8, alpha=0.42, n_iter=2, F=2)
+ZF, ZB = dict(P=3, z0=0, ig=True, N=2, B=1), dict(z0=0, ig=False, N=1, B=1)
+E_ROW, E_ROWB = "row_dft: frame too long for LDS", "row_dft_bwd: frame too long for LDS"
+E_FB, E_MC = "fbank: spectrum too long for LDS", "%s: the row and the bins do not fit the LDS"
+E_PLP, E_PLPB = "plp: n_channel / n_fft too large for one wave's LDS", "plp_bwd: n_channel / n_fft too large for one wave's LDS"
+E_GC, E_GCB = "gc2gc: unsupported dtype or n_fft too long for LDS", "gc2gc_bwd: unsupported dtype or n_fft too long for LDS"
+
+
+def B32_64(n32, n64):
+    return ((F32, n32), (F64, n64))
+
+
+def mlsa_rows(mode, last_fwd, last_bwd, step, moves):
+    """dsa_mlsacheck / _vjp at 2 (forward) and 3 (backward) rows of M + 1 doubles plus 2 K doubles against 144 KB: one row of the table
+    per mode; `moves`: the argument that carries the size, its last forward and backward values, and its step.  Between the two
+    values there is a forward and no gradient."""
+    def a(v):
+        return dict(dict(M=24, mode=mode, n_fft=256, F=3), **{moves: v})
+
+    return ceiling("csrc/mlsacheck.hip:452", E_MC,
+                   inside=[("mlsacheck_generic_fwd", case("mlsacheck", "fwd", **a(last_fwd))),
+                           ("mlsacheck_generic_bwd", case("mlsacheck", "bwd", wrt=("mc",), **a(last_bwd)))],
+                   outside=[raises(E_MC, shape("mlsacheck", "fwd", BOTH, **a(last_fwd + step)), "mlsacheck_generic_fwd: the row and the bins"),
+                            raises(E_MC, shape("mlsacheck", "bwd", BOTH, wrt=("mc",), **a(last_bwd + step)), "mlsacheck_generic_bwd: the row and the bins")])
+
+
+def plp_waves(what, n32, n64):
+    """a block of plp_fwd / plp_bwd goes from 4 waves to 2 to 1 as a wave's slice (8 (C + 194) + sizeof(T) (128 + 2 J), J = n_fft / 2 + 1)
+    passes 16 KB and 32 KB: the last n_fft on one side, n_fft + 2 on the other, both under the same route name"""
+    return ceiling("csrc/plp.hip:288", "reshapes: " + what,
+                   inside=per(B32_64(n32, n64), lambda dt, n: ("plp_fwd", case("plp_tail", "fwd", dt, n_fft=n, **PL, **PLP_OUT)))
+                   + per(B32_64(n32, n64), lambda dt, n: ("plp_bwd", case("plp_tail", "bwd", dt, wrt=("y", "E"), n_fft=n, **PL))),
+                   outside=per(B32_64(n32 + 2, n64 + 2), lambda dt, n: runs("plp_fwd", case("plp_tail", "fwd", dt, n_fft=n, **PL, **PLP_OUT)))
+                   + per(B32_64(n32 + 2, n64 + 2), lambda dt, n: runs("plp_bwd", case("plp_tail", "bwd", dt, wrt=("y", "E"), n_fft=n, **PL))))
+
+
+CEILINGS = [
+    # ---- csrc/lpc.hip (60 KB of LDS each).  acorr_fwd keeps the frame: sizeof(T) L
+    ceiling("csrc/lpc.hip:357", "acorr: frame too long for LDS",
+            inside=per(B32_64(15360, 7680), lambda dt, L: ("acorr_fwd", case("acorr", "fwd", dt, L=L, **AC))), outside=IN_REFUSALS),
+    # acorr_bwd keeps the frame (rounded up to 8 bytes) and the M + 1 cotangents as doubles: with 3 lags the frame ends 6 (float32)
+    # and 3 (float64) samples sooner -- between the two ceilings Autocorrelation has a forward and no gradient
+    ceiling("csrc/lpc.hip:383", "acorr_bwd: frame too long for LDS",
+            inside=per(B32_64(15354, 7677), lambda dt, L: ("acorr_bwd", case("acorr", "bwd", dt, wrt=("x",), L=L, **AC))),
+            outside=per(B32_64(15355, 7678), lambda dt, L: raises("acorr_bwd: frame too long for LDS", shape("acorr", "bwd", dt, wrt=("x",), L=L, **AC)))),
+    # levdur_fwd_lds: 3 (M + 1) doubles.  The autocorrelation of white noise, frames four times the order, with the module's eps: the
+    # float32 restatement stays at 1e-6 of the largest entry at these orders (MEASURED), so no better-conditioned input is needed
+    ceiling("csrc/lpc.hip:372", "levdur: order too large for LDS",
+            inside=[("levdur_fwd_lds", case("levdur", "fwd", M=2559, **LD))], outside=IN_REFUSALS),
+    # levdur_bwd_toeplitz: 7 M + 1 doubles
+    ceiling("csrc/lpc.hip:402", "levdur_bwd: order too large for LDS",
+            inside=[("levdur_bwd_toeplitz", case("levdur", "bwd", wrt=("r",), M=1097, **LD))], outside=IN_REFUSALS),
+    # frame_window_lpc_kernel: 4 frames of sizeof(T) L per block.  Past it fuse(Frame, Window, LPC) runs the three modules
+    ceiling("csrc/lpc.hip:532", "frame_window_lpc: frame too long for LDS",
+            inside=per(B32_64(3840, 1920), lambda dt, L: ("frame_window_lpc_fwd", case("fwlpc", "fwd", dt, L=L, **FW))),
+            outside=per(B32_64(3841, 1921), lambda dt, L: raises("frame_window_lpc: frame too long for LDS", shape("fwlpc", "fwd", dt, L=L, **FW)))
+            + per(B32_64(3841, 1921), lambda dt, L: runs("levdur_fwd", case("fuse_fwlpc", "fwd", dt, L=L, **FW)))),
+    # ---- csrc/spec.hip.  The direct row DFT keeps the row: sizeof(T) L <= 60 KB (fft_length 30: not a power of two)
+    ceiling("csrc/spec.hip:658", E_ROW,
+            inside=per(B32_64(15360, 7680), lambda dt, L: ("row_dft_generic", case("fftr", "fwd", dt, len_in=L, nfft=30, fmt=0, F=1))),
+            outside=per(B32_64(15361, 7681), lambda dt, L: raises(E_ROW, shape("fftr", "fwd", dt, len_in=L, nfft=30, fmt=0, F=1)))),
+    # its backward keeps 3 (fft_length / 2 + 1) values more: 48 samples sooner at fft_length 30 (a forward and no gradient between)
+    ceiling("csrc/spec.hip:894", E_ROWB,
+            inside=per(B32_64(15312, 7632), lambda dt, L: ("row_dft_bwd_generic", case("fftr", "bwd", dt, wrt=("x",), len_in=L, nfft=30, fmt=0, F=1))),
+            outside=per(B32_64(15313, 7633), lambda dt, L: raises(E_ROWB, shape("fftr", "bwd", dt, wrt=("x",), len_in=L, nfft=30, fmt=0, F=1)))),
+    # the FFT in LDS: sizeof(T) (L + 2 fft_length) <= 150 KB, with the raised LDS attribute.  At fft_length 4096 the row past it is
+    # too long for the direct sum as well; float64 at 8192 (float32 at 16384) falls back to the direct sum 1 sample later, under the
+    # other route name; a float64 row of 8192 samples at fft_length 8192 fits neither
+    ceiling("csrc/spec.hip:648", "reshapes: the direct sum instead of the FFT in LDS, or " + E_ROW,
+            inside=per(B32_64(30208, 11008), lambda dt, L: ("row_fft_generic", case("fftr", "fwd", dt, len_in=L, nfft=4096, fmt=0, F=1)))
+            + [("row_fft_generic", case("fftr", "fwd", F64, len_in=2816, nfft=8192, fmt=0, F=1)),
+               ("row_fft_generic", case("fftr", "fwd", F32, len_in=5632, nfft=16384, fmt=0, F=1))],
+            outside=per(B32_64(30209, 11009), lambda dt, L: raises(E_ROW, shape("fftr", "fwd", dt, len_in=L, nfft=4096, fmt=0, F=1)))
+            + [runs("row_dft_generic", case("fftr", "fwd", F64, len_in=2817, nfft=8192, fmt=0, F=1)),
+               runs("row_dft_generic", case("fftr", "fwd", F32, len_in=5633, nfft=16384, fmt=0, F=1)),
+               raises(E_ROW, shape("fftr", "fwd", F64, len_in=8192, nfft=8192, fmt=0, F=1))]),
+    # its backward: sizeof(T) (L + 3 (fft_length / 2 + 1) + 2 fft_length) <= 150 KB, and the direct sum has no room either.  From
+    # fft_length 8192 (float64) and 16384 (float32) on no row has a gradient at all, where the forward runs
+    ceiling("csrc/spec.hip:884", "reshapes: the direct sum instead of the FFT in LDS, or " + E_ROWB,
+            inside=per(B32_64(24061, 4861), lambda dt, L: ("row_fft_bwd_generic", case("fftr", "bwd", dt, wrt=("x",), len_in=L, nfft=4096, fmt=0, F=1))),
+            outside=per(B32_64(24062, 4862), lambda dt, L: raises(E_ROWB, shape("fftr", "bwd", dt, wrt=("x",), len_in=L, nfft=4096, fmt=0, F=1)))
+            + per(B32_64(16384, 8192), lambda dt, n: raises(E_ROWB, shape("fftr", "bwd", dt, wrt=("x",), len_in=16, nfft=n, fmt=0, F=1)))),
+    # spec_ratio_bwd: sizeof(T) (lb + la + 5 (fft_length / 2 + 1)) <= 60 KB; the forward (two row transforms and spec_ratio) has the
+    # row transform's ceilings only
+    ceiling("csrc/spec.hip:981", "spec_bwd: rows too long for LDS",
+            inside=per(B32_64(6138, 3066), lambda dt, n: ("spec_ratio_bwd", case("spec", "bwd", dt, wrt=("b", "a"), nfft=n, **SR))),
+            outside=per(B32_64(6140, 3068), lambda dt, n: raises("spec_bwd: rows too long for LDS", shape("spec", "bwd", dt, wrt=("b", "a"), nfft=n, **SR)))),
+    # ---- csrc/fftcep.hip: more than 512 bins are refused in both dtypes and for every n_iter (float32 with n_iter = 0 has left the
+    # matrix-core kernel at 320 bins).  The backward shares the launcher: its forward refuses first
+    ceiling("csrc/fftcep.hip:344", "fftcep: fft_length above 1022 is not supported",
+            inside=[("fftcep_fwd", case("fftcep", "fwd", nfft=1022, **a, **FFTCEP)) for a in (FC0, FC2)]
+            + [("fftcep_bwd", case("fftcep", "bwd", wrt=("x",), nfft=1022, **a, **FFTCEP)) for a in (FC0, FC2)],
+            outside=[raises("fftcep: fft_length above 1022 is not supported", shape("fftcep", "fwd", BOTH, nfft=1024, **a)) for a in (FC0, FC2)]),
+    # ---- csrc/fbank.hip.  The generic kernels: 4 waves' tiles of 4 frames and the channel ranges in 150 KB --
+    # 16 sizeof(T) K + 8 C forward, (16 sizeof(T) + 8) (K + C) backward (a forward and no gradient between)
+    ceiling("csrc/fbank.hip:583", E_FB,
+            inside=per(B32_64(4778, 2388), lambda dt, n: ("fbank_fwd", case("fbank", "fwd", dt, nfft=n, **FB)))
+            + per(B32_64(4104, 2096), lambda dt, n: ("fbank_bwd", case("fbank", "bwd", dt, wrt=("x",), nfft=n, **FB))),
+            outside=per(B32_64(4780, 2390), lambda dt, n: raises(E_FB, shape("fbank", "fwd", dt, nfft=n, **FB)))
+            + per(B32_64(4106, 2098), lambda dt, n: raises(E_FB, shape("fbank", "bwd", dt, wrt=("x",), nfft=n, **FB)))),
+    # the filter matrix joins them in LDS while sizeof(T) K C more fits, else it stays in global memory (<T, false>: up to 16 waves
+    # of tiles, above 64 KB at the ordinary fft_length 1024 / 80 channels with 64 frames)
+    ceiling("csrc/fbank.hip:584", "reshapes: the filter matrix stays in global memory",
+            inside=per(B32_64(794, 396), lambda dt, n: ("fbank_fwd", case("fbank", "fwd", dt, nfft=n, **FB)))
+            + per(B32_64(752, 364), lambda dt, n: ("fbank_bwd", case("fbank", "bwd", dt, wrt=("x",), nfft=n, **FB))),
+            outside=per(B32_64(796, 398), lambda dt, n: runs("fbank_fwd", case("fbank", "fwd", dt, nfft=n, **FB)))
+            + per(B32_64(754, 366), lambda dt, n: runs("fbank_bwd", case("fbank", "bwd", dt, wrt=("x",), nfft=n, **FB)))
+            + [runs("fbank_fwd", case("fbank", "fwd", F32, nfft=1024, C=80, use_power=False, gamma=0.0, F=64)),
+               runs("fbank_bwd", case("fbank", "bwd", F32, wrt=("x",), nfft=1024, C=80, use_power=False, gamma=0.0, F=64))]),
+    # the matrix-core launcher takes float32 up to 320 bins and 48 channels (its LDS: 163 392 of 163 840 B at 320)
+    ceiling("csrc/fbank.hip:632", "reshapes: the generic kernel instead of the matrix-core kernel",
+            inside=[("fbank_mfma_fwd", case("fbank", "fwd", F32, nfft=638, C=12, use_power=False, gamma=0.0, F=5, **FBM))],
+            outside=[runs("fbank_fwd", case("fbank", "fwd", F32, nfft=640, C=12, use_power=False, gamma=0.0, F=5))]),
+    # MFCC: the second product costs the fused launch 3 KB more, so it ends at 309 bins; to 320 bins the two launches run
+    ceiling("csrc/fbank.hip:659", "reshapes: the filter bank and the DCT as two launches instead of one",
+            inside=[("fbank_dct_mfma_fwd", case("mfcc", "fwd", F32, nfft=616, C=40, M=12, F=7, **MFCC))],
+            outside=[runs("freqt_lds_fwd", case("mfcc", "fwd", F32, nfft=618, C=40, M=12, F=7, **MFCC))]),
+    # ---- csrc/plp.hip
+    plp_waves("2 waves per block instead of 4", 3538, 1704),
+    plp_waves("1 wave per block instead of 2", 7634, 3752),
+    # one wave's slice against 160 KB, with the raised attribute above 64 KB; the backward has the forward's geometry
+    ceiling(("csrc/plp.hip:301", "csrc/plp.hip:317"), E_PLP,
+            inside=per(B32_64(40402, 20136), lambda dt, n: ("plp_fwd", case("plp_tail", "fwd", dt, n_fft=n, **PL, **PLP_OUT)))
+            + per(B32_64(40402, 20136), lambda dt, n: ("plp_bwd", case("plp_tail", "bwd", dt, wrt=("y", "E"), n_fft=n, **PL))),
+            outside=per(B32_64(40404, 20138), lambda dt, n: raises(E_PLP, shape("plp_tail", "fwd", dt, n_fft=n, **PL))),
+            shadowed=(E_PLPB,)),
+    # ---- csrc/mlsacheck.hip (fast: one bin; scale and clip: fft_length / 2 + 1 bins at cep_order 24)
+    mlsa_rows("fast", 9214, 6142, 1, "M"),
+    mlsa_rows("scale", 18380, 18354, 2, "n_fft"),
+    mlsa_rows("clip", 18380, 18354, 2, "n_fft"),
+    # ---- csrc/zerodf.hip: what is still refused behind the tap pieces (ZDF_PIECES holds the accepted side of those): a filter too
+    # long for one launch with ignore_gain or a frame period that is no multiple of 4 -- 3 M + 2 + P values against 64 KB
+    ceiling("csrc/zerodf.hip:581", "zerodf: filter too long for LDS",
+            inside=per(B32_64(5459, 2729), lambda dt, M: ("zerodf_fwd", case("zerodf", "fwd", dt, M=M, **ZF, **ZDF_FWD))),
+            outside=per(B32_64(5460, 2730), lambda dt, M: raises("zerodf: filter too long for LDS", shape("zerodf", "fwd", dt, M=M, **ZF))),
+            cited=ZDF_PIECES),
+    # the tap gradient of the first kernels: 4 P + M + 256 values against 64 KB, which binds before the forward only at frame periods
+    # from 1421 (float64) and 2911 (float32) on
+    ceiling("csrc/zerodf.hip:836", "zerodf_bwd: filter too long for LDS",
+            inside=[("zerodf_bwd", case("zerodf", "bwd", F32, wrt=("x", "b"), M=4484, P=2911, **ZB, **ZDF_BWD)),
+                    ("zerodf_bwd", case("zerodf", "bwd", F64, wrt=("x", "b"), M=2252, P=1421, **ZB, **ZDF_BWD))],
+            outside=[raises("zerodf_bwd: filter too long for LDS", shape("zerodf", "bwd", F32, wrt=("x", "b"), M=4485, P=2911, **ZB)),
+                     raises("zerodf_bwd: filter too long for LDS", shape("zerodf", "bwd", F64, wrt=("x", "b"), M=2253, P=1421, **ZB))],
+            cited=ZDF_PIECES),
+    # ---- csrc/mgc.hip, at the entries themselves (ops.gc2gc_fused / gc2gc_fn test the same sizes first and hand longer transforms to
+    # the operator chain).  Forward: 2 sizeof(T) n_fft <= 150 KB; backward: 5 sizeof(T) n_fft / 2 + 64 -- one power of two sooner
+    ceiling(("csrc/mgc.hip:782", "csrc/mgc.hip:783"), E_GC,
+            inside=per(B32_64(16384, 8192), lambda dt, n: ("gc2gc_fused", case("gc2gc_entry", "fwd", dt, n_fft=n, **GE, **GCF))),
+            outside=per(B32_64(32768, 16384), lambda dt, n: raises(E_GC, shape("gc2gc_entry", "fwd", dt, n_fft=n, **GE)))),
+    ceiling(("csrc/mgc.hip:796", "csrc/mgc.hip:805"), E_GCB,
+            inside=per(B32_64(8192, 4096), lambda dt, n: ("gc2gc_fused_bwd", case("gc2gc_entry", "bwd", dt, wrt=("c",), n_fft=n, **GE, **GC))),
+            outside=per(B32_64(16384, 8192), lambda dt, n: raises(E_GCB, shape("gc2gc_entry", "bwd", dt, wrt=("c",), n_fft=n, **GE)))),
+    # (more than 2^31 - 1 rows share the message)
+    ceiling("csrc/mgc.hip:779", "gc2gc: out_order + 1 must not exceed n_fft",
+            inside=[("gc2gc_fused", case("gc2gc_entry", "fwd", g1=-0.5, g2=0.0, n_fft=4, m1=2, m2=3, F=2, **GCF))],
+            outside=[raises("gc2gc: out_order + 1 must not exceed n_fft", shape("gc2gc_entry", "fwd", BOTH, g1=-0.5, g2=0.0, n_fft=4, m1=2, m2=4, F=2))]),
+    ceiling("csrc/mgc.hip:764", "mgcep_spectra: cep_order above 64",
+            inside=[("mgcep_spectra", case("mgcep_spectra", "fwd", nfft=256, M=64, gamma=-0.5, F=3))],
+            outside=[raises("mgcep_spectra: cep_order above 64", shape("mgcep_spectra", "fwd", BOTH, nfft=256, M=65, gamma=-0.5, F=3))]),
+    # ---- csrc/mcep.hip, the generic pair (asked for by name: float32 geometries of this size go to the whole-batch composition):
+    # sizeof(T) (3 K + M1^2 + 7 M1 - 1) <= 160 KB, the attribute set on every launch.  The backward has the forward's size
+    ceiling(("csrc/mcep.hip:313", "csrc/mcep.hip:329"), "mcep: configuration exceeds LDS",
+            inside=per(B32_64(27208, 13556), lambda dt, n: ("mcep_generic_fwd", case("mcep_generic", "fwd", dt, nfft=n, **MG)))
+            + per(B32_64(27208, 13556), lambda dt, n: ("mcep_generic_bwd", case("mcep_generic", "bwd", dt, wrt=("X",), nfft=n, **MG))),
+            outside=per(B32_64(27210, 13558), lambda dt, n: raises("mcep: configuration exceeds LDS", shape("mcep_generic", "fwd", dt, nfft=n, **MG)))),
+    # ---- csrc/mdct.hip: the fast kernels end at frame length 4096 (48 KB of LDS in the synthesis: no attribute needed)
+    ceiling("csrc/mdct.hip:315", "reshapes: the generic kernels instead of the fast ones",
+            inside=[("mdct_analysis_fast", case("mdct", "fwd", F32, L=4096, T=5000, B=1)), ("mdct_synthesis_fast", case("imdct", "fwd", F32, L=4096, N=3, B=1))],
+            outside=[runs("mdct_analysis_generic", case("mdct", "fwd", F32, L=8192, T=9000, B=1)),
+                     runs("mdct_synthesis_generic", case("imdct", "fwd", F32, L=8192, N=3, B=1))]),
+]
+
+# launches above 48 KB of dynamic LDS whose size does not depend on the call, so every test of the route runs the largest shape
+LDS_FIXED = {
+    "poledf_ring_fwd": "tests/test_gpu_poledf.py::test_ring_kernels_are_the_ones_that_run",
+    "poledf_ring_bwd": "tests/test_gpu_poledf.py::test_ring_kernels_are_the_ones_that_run",
+    "lsp_lpc2lsp_fwd": "tests/test_gpu_lsp.py::test_tile_and_dispatch_edges",
+    "th_solve_quadn_fwd": "tests/test_gpu_synth.py::test_thsolve_kernel_vs_numpy_and_gradcheck",   # (41 984 B at most: below the attribute)
+}
+
+# ---- every other DSA_ERR_UNSUPPORTED of csrc/: message (as the source spells it, without the trailing %s) -> why no size a caller
+# can reach meets it.  tests/test_routes_cpu.py holds the three tables against the sources.
+DTYPE = "ops._core._dtype_code raises TypeError for anything but float32 / float64 before the entry is called"
+NOT_A_CEILING = {
+    **{f"{n}: unsupported dtype": DTYPE for n in (
+        "fbank", "fbank_bwd", "fftcep", "fftcep_bwd", "irfft_scale", "div_rows", "griffin_update", "acorr", "acorr_bwd", "levdur", "levdur_bwd",
+        "lpc", "lpc_bwd", "frame_window_lpc", "freqt", "freqt_bwd", "mcep", "mcep_bwd", "gnorm", "mgcep_gain", "mgcep_spectra", "plp", "plp_bwd",
+        "poledf", "poledf_bwd", "pqmf", "pqmf_bwd", "ipqmf", "ipqmf_bwd", "interpolate", "interpolate_bwd", "frame", "frame_bwd", "window",
+        "window_bwd", "fftr", "fftr_bwd", "spec", "spec_bwd", "stft", "stft_bwd", "thsolve", "thsolve_bwd", "zerodf", "zerodf_taylor", "zerodf_bwd",
+        "zerodf_taylor_bwd", "%s")},   # ("%s": the shared launchers of csrc/lsp.hip and csrc/parcor.hip)
+    "fbank_bins_bwd: float32 only (the fused forward it differentiates is)": "ops.StftFbankFn is the only caller and FusedSTFTFilterBank._fusable "
+        "admits float32 only",
+    "mcep_newton_update: float32 only": "ops.mcep._mcep_composed_applies admits float32 only",
+    "mcep_newton_update_bwd: float32 only": "the backward of ops.McepNewtonUpdateFn, whose forward is float32 (_mcep_composed_applies)",
+    "rows_gemm: float32 only": "ops.rows callers come from _mcep_composed_applies: float32 only",
+    "rows_ew: float32 only": "ops.rows.RowsLogFn / RowsExpSubFn are used by the float32 composition only (_mcep_composed_applies)",
+    "mcep_newton_steps: float32 only": "ops.mcep.mcep_newton_steps is reached from the float32 composition only",
+    "mcep_newton_resid_h_bwd: float32 only": "as mcep_newton_steps: the float32 composition only",
+    "mcep_newton_glogx_h: float32 only": "as mcep_newton_steps: the float32 composition only",
+    # the tuned entries: the caller tests the geometry before it calls
+    "stft: tuned kernel needs float32, fft_length 512, frame_length <= 512": "only with DSA_ALGO_TUNED asked for by name; ops.StftFn passes "
+        "ALGO_AUTO, which falls back to the generic route",
+    "stft_bwd: tuned kernel needs float32, fft_length 512, constant padding, no floor, fixed window": "as the forward: DSA_ALGO_TUNED by name only",
+    "stft_fbank: the fused kernel needs float32, fft_length 512, frame_length 400, an even frame period and at most 126 channels "
+    "(use dsa_stft_fwd + dsa_fbank_fwd)": "modules.fused.FusedSTFTFilterBank._fusable tests the same geometry first and runs the two modules otherwise",
+    "mcep: tuned kernel needs float32, fft_length 512, cep_order 24": "DSA_ALGO_TUNED by name only; the module passes ALGO_AUTO or ALGO_GENERIC",
+    "mcep_bwd: tuned kernel needs float32, fft_length 512, cep_order 24": "as the forward: DSA_ALGO_TUNED by name only",
+    "stft_mcep: the fused launch covers float32, frame_length 400, fft_length 512, cep_order 24": "modules.fused.FusedSTFTMelCepstralAnalysis "
+        "tests ops.stft_mcep_fusable first and runs the two stages otherwise",
+    "mgcep_step: needs float32, fft_length 512, cep_order <= 24": "modules.mgcep builds the step images only for that geometry and calls "
+        "ops.mgcep_step only with them",
+    "mgcep_step_bwd: needs float32, fft_length 512, cep_order <= 24": "the backward of ops.MgcepStepFn: same geometry as its forward",
+    "mgcep_step_bwd_h: needs float32, fft_length 512, cep_order 24": "ops.mgc._step_bwd_entry picks it from the binary16 images, which "
+        "modules.mgcep builds at cep_order 24 only",
+    "mgcep_step_solve: needs float32, fft_length 512, cep_order 24": "modules.mgcep calls it with the order-24 images only",
+    "thsolve_update: order 24 in float32 only (dsa_thsolve_fwd + an addition otherwise)": "ops.mgc.thsolve_update returns None for any "
+        "other order or dtype and the caller adds the solution itself",
+    "frame_window_lpc_bwd: the one-launch backward covers float32, lpc_order 24, 25 <= frame_length <= 512, constant padding":
+        "ops.frame_window_lpc_bwd_supported restates the launcher's conditions; FusedFrameWindowLPC asks it first",
+    "frame_window_lpc_bwd: frame_length + frame_period above 1024": "ops.frame_window_lpc_bwd_supported (L + P <= 1024)",
+    "frame_window_lpc_bwd: this frame_length / frame_period pair does not fit the one-launch backward": "ops.frame_window_lpc_bwd_supported (the halo test)",
+    "%s: the fast kernels take float32 and a power-of-two frame length in their range": "DSA_ALGO_TUNED by name only; ops.mdct passes "
+        "ALGO_AUTO, which takes the generic kernels (the CEILINGS row of csrc/mdct.hip:315 holds that edge)",
+    "fbank: spectrum too long for the matrix-core kernel's LDS": "every caller of fbank_mfma_launch_ex tests K <= 320 first (dsa_fbank_fwd, "
+        "dsa_freqt_fwd, dsa_fftcep_fwd: 163 392 B at 320), and dsa_fbank_dct_fwd tests fbank_mfma_lds_bytes(K, true) itself",
+    # orders and plans: dispatch inside the library, or properties of a matrix rather than a size
+    "thsolve_quad: order below 2": "dsa_thsolve_fwd and dsa_mcep_newton_update send order 1 to the one-wave kernel",
+    "thsolve_quad: order above 55": "dsa_thsolve_fwd sends orders above 55 to the one-wave kernel; the composition ends at order 54 + 1",
+    "mcep_resid: order above 55": "ops.mcep._mcep_composed_fwd uses two dsa_rows_gemm launches above order 54",
+    "mcep_newton_resid: float32, orders up to 54": "as mcep_resid: the caller's own order test",
+    "mcep_resid_prepare: float32, orders up to 54": "ops.mcep.mcep_resid_images returns None above order 54",
+    "mcep_newton_resid_h: float32, orders up to 54": "called with the images of mcep_resid_images only",
+    "mcep_newton_steps: no one-launch kernel for this order (32 .. 54)": "ops.mcep.mcep_newton_steps_applies tests the order; ERR_UNSUPPORTED "
+        "makes the caller alternate the two launches",
+    "mcep_resid_bwd_prepare: float32, orders 32 .. 54": "ops.mcep.mcep_resid_bwd_images asks dsa_mcep_resid_bwd_images_bytes first (0: composed gradient)",
+    "mcep_newton_resid_h_bwd: orders 32 .. 54": "called with the images of mcep_resid_bwd_images only",
+    "rows_gemm: unsupported combination of flags": "ops.rows passes the three combinations the switch has",
+    "rows_ew: unknown operation": "ops.rows passes operation 0 or 1",
+    "zerodf: the scaled / accumulating form needs P % 4 == 0 and M >= 16": "ops.filters.zerodf_taylor is used only where "
+        "ops.filters.zerodf_taylor_shapes_ok (the same test) holds",
+    "zerodf_bwd: the scaled / accumulating form needs P % 4 == 0 and M >= 16": "as its forward",
+    "fbank_bins_plan: non-finite matrix": "a property of the matrix, not a size: ops.fbank_bins_table keeps the dense backward then",
+    "fbank_bins_plan: a bin feeds more than two adjacent channels": "a property of the matrix: ops.fbank_bins_table keeps the dense backward",
+    "fbank_scan_plan: needs 257 bins and at most 126 channels": "ops.fbank_scan_plan tests both before it calls",
+    "fbank_scan_plan: non-finite weight": "a property of the matrix: ops.fbank_scan_plan returns None and the two modules run",
+    "fbank_scan_plan: channels are not ordered along the bins": "a property of the matrix: the two modules run",
+    "fbank_scan_plan: a bin feeds more than two adjacent channels": "a property of the matrix: the two modules run",
+    # more than 2^31 rows
+    "frame_bwd: batch too large for one launch": "more than 2^31 - 1 blocks of 256 threads: beyond any tensor the tests or a device can hold",
+    # without a message: the caller keeps the composed path
+    "return DSA_ERR_UNSUPPORTED @ mcep_big.hip x2": "dsa_mcep_newton_steps turns it into its own message (above); orders outside 32 .. 54",
+    "return DSA_ERR_UNSUPPORTED @ mcep_resid.hip x3": "dsa_mcep_newton_resid_h_bwd / _glogx_h: orders outside 32 .. 54 or more steps than one "
+        "workgroup's LDS holds; ops.mcep keeps the composed gradient",
+}
+
+
+def all_cases():
+    """(route, case) of everything that is compared: ROUTES, and both sides of CEILINGS"""
+    out = [(route, c) for route, cases in ROUTES.items() for c in cases]
+    for row in CEILINGS:
+        out += list(row["inside"])
+        if row["outside"] != IN_REFUSALS:
+            out += [(o["route"], o["case"]) for o in row["outside"] if o["expect"] == "route"]
+    return out
+
+
 PINNED_ELSEWHERE = {
     "delta_fwd": "tests/test_gpu_paramgen.py::test_delta_against_the_goldens",
     "div_rows": "tests/test_gpu_istft.py::test_unframe_matches_oracle_and_autograd",
@@ -259,8 +576,8 @@ FORWARDED = {
     "parcor_lane_par2lpc_bwd": "csrc/parcor.hip:30", "parcor_lane_lpccheck_fwd": "csrc/parcor.hip:30", "parcor_lane_lpccheck_bwd": "csrc/parcor.hip:30",
     "parcor_row_lpc2par_fwd": "csrc/parcor.hip:31", "parcor_row_lpc2par_bwd": "csrc/parcor.hip:31", "parcor_row_par2lpc_fwd": "csrc/parcor.hip:31",
     "parcor_row_par2lpc_bwd": "csrc/parcor.hip:32", "parcor_row_lpccheck_fwd": "csrc/parcor.hip:32", "parcor_row_lpccheck_bwd": "csrc/parcor.hip:32",
-    "mlsacheck_generic_fwd": "csrc/mlsacheck.hip:447", "mlsacheck_generic_bwd": "csrc/mlsacheck.hip:447",
-    "fbank_mfma_fwd": "csrc/fbank.hip:570", "fbank_dct_mfma_fwd": "csrc/fbank.hip:661", "freqt_mfma_fwd": "csrc/mcep.hip:358",
+    "mlsacheck_generic_fwd": "csrc/mlsacheck.hip:449", "mlsacheck_generic_bwd": "csrc/mlsacheck.hip:449",
+    "fbank_mfma_fwd": "csrc/fbank.hip:570", "fbank_dct_mfma_fwd": "csrc/fbank.hip:661", "freqt_mfma_fwd": "csrc/mcep.hip:359",
     "fftcep_mfma_fwd": "csrc/fftcep.hip:388",
     "frame_window_lpc24_mfma_fwd": "csrc/lpc24.hip:375", "frame_window_lpc24_bwd_mfma": "csrc/lpc24_bwd.hip:685",
 }
@@ -518,4 +835,69 @@ MEASURED = {
     "mdct_synthesis_fast-imdct-fwd-L16-N7-onlyf32": (0.00e+00, 1.11e-07),
     "mdct_synthesis_generic-imdct-fwd-L16-N7-onlyf64": (2.26e-16, 0.00e+00),
     "mdct_synthesis_generic-imdct-fwd-L12-N7": (1.69e-16, 6.78e-08),
+    # ---- CEILINGS, both sides
+    "acorr_fwd-acorr-fwd-L15360-M2-fmt0-F1-onlyf32": (0.00e+00, 1.63e-08),
+    "acorr_fwd-acorr-fwd-L7680-M2-fmt0-F1-onlyf64": (1.83e-18, 0.00e+00),
+    "acorr_bwd-acorr-bwd-L15354-M2-fmt0-F1-onlyf32": (0.00e+00, 8.42e-08),
+    "acorr_bwd-acorr-bwd-L7677-M2-fmt0-F1-onlyf64": (1.25e-16, 0.00e+00),
+    "levdur_fwd_lds-levdur-fwd-M2559-eps1e-05-F1": (2.66e-19, 9.21e-09),
+    "levdur_bwd_toeplitz-levdur-bwd-M1097-eps1e-05-F1": (2.77e-15, 9.24e-07),
+    "frame_window_lpc_fwd-fwlpc-fwd-L3840-T4000-P2000-M8-eps1e-05-B1-onlyf32": (0.00e+00, 7.51e-08),
+    "frame_window_lpc_fwd-fwlpc-fwd-L1920-T4000-P2000-M8-eps1e-05-B1-onlyf64": (1.38e-17, 0.00e+00),
+    "levdur_fwd-fuse_fwlpc-fwd-L3841-T4000-P2000-M8-eps1e-05-B1-onlyf32": (0.00e+00, 1.56e-08),
+    "levdur_fwd-fuse_fwlpc-fwd-L1921-T4000-P2000-M8-eps1e-05-B1-onlyf64": (4.15e-17, 0.00e+00),
+    "row_dft_generic-fftr-fwd-len_in15360-nfft30-fmt0-F1-onlyf32": (0.00e+00, 8.22e-08),
+    "row_dft_generic-fftr-fwd-len_in7680-nfft30-fmt0-F1-onlyf64": (3.35e-16, 0.00e+00),
+    "row_dft_bwd_generic-fftr-bwd-len_in15312-nfft30-fmt0-F1-onlyf32": (0.00e+00, 9.04e-08),
+    "row_dft_bwd_generic-fftr-bwd-len_in7632-nfft30-fmt0-F1-onlyf64": (0.00e+00, 0.00e+00),
+    "row_fft_generic-fftr-fwd-len_in30208-nfft4096-fmt0-F1-onlyf32": (0.00e+00, 3.32e-07),
+    "row_fft_generic-fftr-fwd-len_in11008-nfft4096-fmt0-F1-onlyf64": (1.19e-15, 0.00e+00),
+    "row_fft_generic-fftr-fwd-len_in2816-nfft8192-fmt0-F1-onlyf64": (1.08e-15, 0.00e+00),
+    "row_fft_generic-fftr-fwd-len_in5632-nfft16384-fmt0-F1-onlyf32": (0.00e+00, 4.64e-07),
+    "row_dft_generic-fftr-fwd-len_in2817-nfft8192-fmt0-F1-onlyf64": (1.11e-15, 0.00e+00),
+    "row_dft_generic-fftr-fwd-len_in5633-nfft16384-fmt0-F1-onlyf32": (0.00e+00, 4.44e-07),
+    "row_fft_bwd_generic-fftr-bwd-len_in24061-nfft4096-fmt0-F1-onlyf32": (0.00e+00, 1.55e-07),
+    "row_fft_bwd_generic-fftr-bwd-len_in4861-nfft4096-fmt0-F1-onlyf64": (3.57e-16, 0.00e+00),
+    "spec_ratio_bwd-spec-bwd-nfft6138-lb5-la3-eps0.001-floorNone-fmt3-F2-onlyf32": (0.00e+00, 2.36e-07),
+    "spec_ratio_bwd-spec-bwd-nfft3066-lb5-la3-eps0.001-floorNone-fmt3-F2-onlyf64": (8.15e-16, 0.00e+00),
+    "fbank_fwd-fbank-fwd-nfft4778-C80-use_powerFalse-gamma0.0-F13-onlyf32": (0.00e+00, 2.40e-07),
+    "fbank_fwd-fbank-fwd-nfft2388-C80-use_powerFalse-gamma0.0-F13-onlyf64": (4.13e-16, 0.00e+00),
+    "fbank_bwd-fbank-bwd-nfft4104-C80-use_powerFalse-gamma0.0-F13-onlyf32": (0.00e+00, 1.73e-07),
+    "fbank_bwd-fbank-bwd-nfft2096-C80-use_powerFalse-gamma0.0-F13-onlyf64": (2.76e-16, 0.00e+00),
+    "fbank_fwd-fbank-fwd-nfft794-C80-use_powerFalse-gamma0.0-F13-onlyf32": (0.00e+00, 1.99e-07),
+    "fbank_fwd-fbank-fwd-nfft396-C80-use_powerFalse-gamma0.0-F13-onlyf64": (3.71e-16, 0.00e+00),
+    "fbank_bwd-fbank-bwd-nfft752-C80-use_powerFalse-gamma0.0-F13-onlyf32": (0.00e+00, 1.18e-07),
+    "fbank_bwd-fbank-bwd-nfft364-C80-use_powerFalse-gamma0.0-F13-onlyf64": (1.71e-16, 0.00e+00),
+    "fbank_fwd-fbank-fwd-nfft796-C80-use_powerFalse-gamma0.0-F13-onlyf32": (0.00e+00, 2.64e-07),
+    "fbank_fwd-fbank-fwd-nfft398-C80-use_powerFalse-gamma0.0-F13-onlyf64": (8.00e-16, 0.00e+00),
+    "fbank_bwd-fbank-bwd-nfft754-C80-use_powerFalse-gamma0.0-F13-onlyf32": (0.00e+00, 1.39e-07),
+    "fbank_bwd-fbank-bwd-nfft366-C80-use_powerFalse-gamma0.0-F13-onlyf64": (1.67e-16, 0.00e+00),
+    "fbank_fwd-fbank-fwd-nfft1024-C80-use_powerFalse-gamma0.0-F64-onlyf32": (0.00e+00, 3.15e-07),
+    "fbank_bwd-fbank-bwd-nfft1024-C80-use_powerFalse-gamma0.0-F64-onlyf32": (0.00e+00, 1.37e-07),
+    "fbank_fwd-fbank-fwd-nfft640-C12-use_powerFalse-gamma0.0-F5-onlyf32": (0.00e+00, 2.91e-07),
+    "plp_bwd-plp_tail-bwd-n_fft3538-C20-M12-F5-onlyf32": (0.00e+00, 2.56e-07),
+    "plp_bwd-plp_tail-bwd-n_fft1704-C20-M12-F5-onlyf64": (1.38e-15, 0.00e+00),
+    "plp_bwd-plp_tail-bwd-n_fft3540-C20-M12-F5-onlyf32": (0.00e+00, 2.55e-07),
+    "plp_bwd-plp_tail-bwd-n_fft1706-C20-M12-F5-onlyf64": (1.96e-15, 0.00e+00),
+    "plp_bwd-plp_tail-bwd-n_fft7634-C20-M12-F5-onlyf32": (0.00e+00, 3.27e-07),
+    "plp_bwd-plp_tail-bwd-n_fft3752-C20-M12-F5-onlyf64": (1.38e-15, 0.00e+00),
+    "plp_bwd-plp_tail-bwd-n_fft7636-C20-M12-F5-onlyf32": (0.00e+00, 2.55e-07),
+    "plp_bwd-plp_tail-bwd-n_fft3754-C20-M12-F5-onlyf64": (6.92e-16, 0.00e+00),
+    "plp_bwd-plp_tail-bwd-n_fft40402-C20-M12-F5-onlyf32": (0.00e+00, 3.99e-07),
+    "plp_bwd-plp_tail-bwd-n_fft20136-C20-M12-F5-onlyf64": (1.56e-15, 0.00e+00),
+    "mlsacheck_generic_fwd-mlsacheck-fwd-M9214-modefast-n_fft256-F3": (1.28e-16, 2.13e-07),
+    "mlsacheck_generic_bwd-mlsacheck-bwd-M6142-modefast-n_fft256-F3": (0.00e+00, 9.07e-08),
+    "mgcep_spectra-mgcep_spectra-fwd-nfft256-M64-gamma-0.5-F3": (4.23e-16, 1.06e-07),
+    "mcep_generic_fwd-mcep_generic-fwd-nfft27208-M8-alpha0.42-n_iter2-F2-onlyf32": (0.00e+00, 1.74e-06),
+    "mcep_generic_fwd-mcep_generic-fwd-nfft13556-M8-alpha0.42-n_iter2-F2-onlyf64": (5.12e-15, 0.00e+00),
+    "mcep_generic_bwd-mcep_generic-bwd-nfft27208-M8-alpha0.42-n_iter2-F2-onlyf32": (0.00e+00, 5.85e-07),
+    "mcep_generic_bwd-mcep_generic-bwd-nfft13556-M8-alpha0.42-n_iter2-F2-onlyf64": (1.70e-15, 0.00e+00),
+    "mdct_analysis_fast-mdct-fwd-L4096-T5000-B1-onlyf32": (0.00e+00, 3.34e-07),
+    "mdct_synthesis_fast-imdct-fwd-L4096-N3-B1-onlyf32": (0.00e+00, 2.74e-07),
+    "mdct_analysis_generic-mdct-fwd-L8192-T9000-B1-onlyf32": (0.00e+00, 3.99e-07),
+    "mdct_synthesis_generic-imdct-fwd-L8192-N3-B1-onlyf32": (0.00e+00, 3.02e-07),
+    "mlsacheck_generic_fwd-mlsacheck-fwd-M24-modescale-n_fft18380-F3": (2.48e-16, 7.89e-08),
+    "mlsacheck_generic_bwd-mlsacheck-bwd-M24-modescale-n_fft18354-F3": (4.79e-16, 2.33e-07),
+    "mlsacheck_generic_fwd-mlsacheck-fwd-M24-modeclip-n_fft18380-F3": (3.33e-16, 7.81e-08),
+    "mlsacheck_generic_bwd-mlsacheck-bwd-M24-modeclip-n_fft18354-F3": (4.79e-16, 2.33e-07),
 }

@@ -128,6 +128,9 @@ def fwlpc_inputs(T, L, P, M, eps, center=True, B=2, exact=False):
     return {"x": gauss(L + P + M, B, T), "w": torch.from_numpy(tables.window_table(L))}
 
 
+fuse_fwlpc, fuse_fwlpc_inputs = fwlpc, fwlpc_inputs   # fuse(Frame, Window, LPC): the same definition, through the three modules where the one launch refuses
+
+
 # ----------------------------------------------------------------------------------------------- csrc/zerodf.hip
 def zerodf(inp, M, P, z0, ig, N, B=2):
     """zerodf.py:184-243: y[t] = sum_k h_t[k] x[t - k + z0], h_t the taps of frames n and n + 1 interpolated over P samples, divided by
@@ -158,8 +161,13 @@ def zerodf_inputs(M, P, z0, ig, N, B=2):
 def half_dft(x, nfft):
     """(re, im) of rfft(x, n = nfft): the first nfft samples, zero-padded, against the cosine and sine matrices"""
     L = min(x.size(-1), nfft)
-    ang = 2 * math.pi * ((torch.arange(L, dtype=torch.float64)[:, None] * torch.arange(nfft // 2 + 1, dtype=torch.float64)[None, :]) % nfft) / nfft
-    return rmm(x[..., :L], torch.cos(ang).to(x.dtype)), -rmm(x[..., :L], torch.sin(ang).to(x.dtype))
+    re, im = [], []
+    for k0 in range(0, nfft // 2 + 1, 1024):   # (1024 bins at a time: the rows at the LDS ceilings would need a gigabyte of angles otherwise)
+        k = torch.arange(k0, min(k0 + 1024, nfft // 2 + 1), dtype=torch.float64)
+        ang = 2 * math.pi * ((torch.arange(L, dtype=torch.float64)[:, None] * k[None, :]) % nfft) / nfft
+        re.append(rmm(x[..., :L], torch.cos(ang).to(x.dtype)))
+        im.append(-rmm(x[..., :L], torch.sin(ang).to(x.dtype)))
+    return torch.cat(re, -1), torch.cat(im, -1)
 
 
 def fftr(inp, len_in, nfft, fmt, F=5):
@@ -301,6 +309,17 @@ def fbank(inp, nfft, C, use_power, gamma, floor=1e-5, F=7):
 
 def fbank_inputs(nfft, C, use_power, gamma, floor=1e-5, F=7):
     return {"x": torch.rand(F, nfft // 2 + 1, generator=torch.Generator().manual_seed(nfft + C), dtype=torch.float64) + 0.1}
+
+
+def mfcc(inp, nfft, C, M, lifter=22, floor=1e-5, F=7):
+    """mfcc.py:244-256 as the entry returns it: (the amplitude-domain log filter bank times DCT-II x truncation x lifter, E)"""
+    x = inp["x"]
+    y, E = fbank(inp, nfft, C, False, 0.0, floor)
+    return rmm(y, const(tables.dct_matrix(C, 2)[:, :M + 1] * tables.mfcc_lifter(M, lifter)[None, :], x)), E
+
+
+def mfcc_inputs(nfft, C, M, lifter=22, floor=1e-5, F=7):
+    return fbank_inputs(nfft, C, False, 0.0, floor, F)
 
 
 def stft_fbank(inp, T, C, B=2):
@@ -462,6 +481,28 @@ def mcep_inputs(nfft, M, alpha, n_iter, F=70):
     return {"X": gauss(nfft + M, F, nfft // 2 + 1).square() + 0.05}
 
 
+def mcep_generic(inp, nfft, M, alpha, n_iter, F=70):
+    """mcep.py:189-224 as oracle/torch_port.py::mcep states it, for the generic kernel pair asked for by name (DSA_ALGO_GENERIC) at
+    its longest spectra: the warping products and the solve through rmm / rsolve, so that the second float64 evaluation reorders the
+    sums over the bins"""
+    X = inp["X"]
+    tab, H = TP.McepTables(nfft, M, alpha, X.dtype), nfft // 2
+    log_x = torch.log(X)
+    scale = torch.ones(nfft, dtype=X.dtype)
+    scale[0] = scale[H] = 0.5
+    mc = rmm((torch.fft.irfft(log_x) * scale)[..., :H + 1], tab.A_f)
+    for _ in range(n_iter):
+        d = torch.fft.rfft(rmm(mc, tab.A_i), n=nfft).real
+        rt = rmm(torch.fft.irfft(torch.exp(log_x - d - d))[..., :H + 1], tab.A_r)
+        r = rt[..., :M + 1]
+        i = torch.arange(M + 1)
+        mc = mc + rsolve(r[..., (i[:, None] - i[None, :]).abs()] + rt[..., i[:, None] + i[None, :]], r - tab.av)
+    return mc
+
+
+mcep_generic_inputs = mcep_inputs
+
+
 def newton_update(inp, n, F=65):
     """mcep.py:216-222: mc + solve(T(rt[:n]) + H(rt), rt[:n] - alpha_vector) (tests/test_gpu_configs.py::test_newton_update_with_a_gradient...)"""
     rt, av = inp["rt"], inp["av"]
@@ -514,6 +555,9 @@ def gc2gc(inp, g1, g2, n_fft, m1, m2, F=37):
 
 def gc2gc_inputs(g1, g2, n_fft, m1, m2, F=37):
     return {"c": 0.3 * gauss(n_fft + m1, F, m1 + 1)}
+
+
+gc2gc_entry, gc2gc_entry_inputs = gc2gc, gc2gc_inputs   # dsa_gc2gc_fwd / _bwd themselves, without the Python layer's own size test
 
 
 def _mgcep_spectra(x, b1, M, alpha, gamma):
@@ -577,6 +621,54 @@ def mcep_tuned_inputs(n_iter, keep_rt=True):
     return {"X": TP.stft_power(gauss(33, 2, 4800), 400, 80, 512).reshape(-1, 257)}
 
 
+# ----------------------------------------------------------------------------------------------- csrc/mlsacheck.hip
+def _mlsa_parts(mc, alpha, mode, n_fft):
+    """(gain, gain-free cepstrum, amplitudes (the plain sum as one column in fast mode), Cr, Ci) -- tests/test_gpu_mlsacheck.py::re_amplitudes"""
+    M = mc.size(-1) - 1
+    gain = rsum(mc * const((-float(alpha)) ** np.arange(M + 1), mc)).unsqueeze(-1)
+    c = torch.cat((mc[..., :1] - gain, mc[..., 1:]), -1)
+    if mode == "fast":
+        return gain, c, rsum(c).unsqueeze(-1), None, None
+    K = n_fft // 2 + 1
+    ang = 2 * math.pi * ((torch.arange(K)[:, None] * torch.arange(M + 1)[None]) % n_fft).double() / n_fft
+    Cr, Ci = rmm(c, torch.cos(ang).T.to(c.dtype)), -rmm(c, torch.sin(ang).T.to(c.dtype))
+    A2 = Cr * Cr + Ci * Ci
+    A = torch.where(A2 > 0, torch.sqrt(torch.where(A2 > 0, A2, torch.ones_like(A2))), torch.zeros_like(A2))
+    return gain, c, A, Cr, Ci
+
+
+def mlsacheck(inp, M, mode, n_fft, F=3, alpha=0.42, thr=4.5):
+    """mlsacheck.py of the reference (tests/test_gpu_mlsacheck.py::re_mlsacheck): the gain-free cepstrum scaled ("fast", "scale") or
+    its spectrum clipped bin by bin ("clip") down to the threshold, then the gain put back"""
+    mc = inp["mc"]
+    gain, c, A, Cr, Ci = _mlsa_parts(mc, alpha, mode, n_fft)
+    a = A.amax(-1, keepdim=True).clamp(min=1e-16)
+    if mode == "fast":
+        out = (thr / a).clamp(max=1) * c
+    else:
+        K = n_fft // 2 + 1
+        N2 = 2 * (K - 1)
+        s = (thr / a).clamp(max=1) if mode == "scale" else torch.where(A > 0, thr / torch.where(A > 0, A, torch.ones_like(A)), torch.ones_like(A)).clamp(max=1)
+        w = torch.full((K,), 2.0, dtype=mc.dtype)
+        w[0] = w[K - 1] = 1.0
+        ang = 2 * math.pi * ((torch.arange(K)[:, None] * torch.arange(M + 1)[None]) % N2).double() / N2
+        Ci = torch.cat((torch.zeros_like(Ci[..., :1]), Ci[..., 1:K - 1], torch.zeros_like(Ci[..., :1])), -1)   # ignored by the inverse
+        # (the sums over the bins through rsum, not rmm: up to 9 000 terms, and what a float32 matrix product loses on them depends on the
+        # host's blocking, eightfold between two machines -- a sum's own cascade does not)
+        out = rsum((w * s * Cr).unsqueeze(-2) * torch.cos(ang).T.to(mc.dtype) - (w * s * Ci).unsqueeze(-2) * torch.sin(ang).T.to(mc.dtype)) / N2
+    return torch.cat((out[..., :1] + gain, out[..., 1:]), -1)
+
+
+def mlsacheck_inputs(M, mode, n_fft, F=3, alpha=0.42, thr=4.5):
+    """rows of tests/test_gpu_mlsacheck.py::rough_mc, exact in float32: the first row's amplitude is twice the threshold (the check
+    moves it), the others' half of it (they pass through)"""
+    x = 0.5 * gauss(M + n_fft, F, M + 1) * torch.linspace(1, 0.05, M + 1, dtype=torch.float64)
+    A = _mlsa_parts(x, alpha, mode, n_fft)[2]
+    a = A[:, 0] if mode == "fast" else A.amax(-1)
+    want = torch.where(torch.arange(F) == 0, 2.0, 0.5).double() * thr
+    return {"mc": (x * (want / a)[:, None]).float().double()}
+
+
 # ----------------------------------------------------------------------------------------------- csrc/mdct.hip
 def mdct(inp, L, T, B=2):
     """mdct.py of the reference with the sine window (tests/mdct_ref.py::analysis): y[n, k] = sum_j w[j] x[(n - 1) P + j] C[j, k]"""
@@ -614,7 +706,8 @@ def imdct_inputs(L, N, B=2):
 
 NAMES = ("acorr", "levdur", "lpc", "fwlpc", "zerodf", "fftr", "spec", "stft", "irfft_scale", "thsolve", "freqt", "rows_log", "rows_expsub",
          "fftcep", "fbank", "stft_fbank", "pqmf", "ipqmf", "interpolate", "delta", "mlpg", "plp_tail", "poledf", "mcep", "newton_update",
-         "glogx", "gc2gc", "mgcep_spectra", "mgcep_step", "mgcep_gain", "mdct", "imdct", "fbank_bins", "mcep_tuned")
+         "glogx", "gc2gc", "mgcep_spectra", "mgcep_step", "mgcep_gain", "mdct", "imdct", "fbank_bins", "mcep_tuned", "fuse_fwlpc", "mfcc",
+         "mcep_generic", "gc2gc_entry", "mlsacheck")
 REFS = {name: globals()[name] for name in NAMES}
 INPUTS = {name: globals()[name + "_inputs"] for name in NAMES}
 
@@ -674,8 +767,7 @@ if __name__ == "__main__":
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     import kernel_routes as KR
 
-    for route, cases in KR.ROUTES.items():
-        for c in cases:
-            if c["tol_from"] == KR.MEAS:
-                b64, b32 = bases(c)
-                print(f'    "{KR.case_id(route, c)}": ({b64:.2e}, {b32:.2e}),')
+    for route, c in KR.all_cases():   # (ROUTES, then both sides of CEILINGS; with any argument: only the cases MEASURED does not have yet)
+        if c["tol_from"] == KR.MEAS and (len(sys.argv) < 2 or KR.case_id(route, c) not in KR.MEASURED):
+            b64, b32 = bases(c)
+            print(f'    "{KR.case_id(route, c)}": ({b64:.2e}, {b32:.2e}),', flush=True)

@@ -3,12 +3,18 @@ recorded (`_lib.last_kernel()` right after the forward; for a backward route on 
 in a hook on the first input, which runs right after the backward entry returned), and the outputs or the input gradients against
 the float64 restatement of tests/routes_ref.py evaluated on the same (rounded) inputs, the gradients with a stored Gaussian
 cotangent.  The neighbouring shape on the other side of a launcher's condition is a case of the neighbouring route: an edited
-condition fails here on the name.  Then the four refusals of csrc/lpc.hip.  Each case prints its figures before it asserts."""
+condition fails here on the name.  Then the four refusals of csrc/lpc.hip, and both sides of every size ceiling of
+tests/kernel_routes.py::CEILINGS: the last accepted shape like any route, the nearest shape past it by its message (or by the route
+that runs instead), and after every refusal a synchronisation and a valid call on the same stream.  Each case prints its figures
+before it asserts."""
+import re
+
 import numpy as np
 import pytest
 import torch
 
 import diffsptk_amd as dsp
+import diffsptk_amd.functional as DF
 from diffsptk_amd import _lib, ops
 from diffsptk_amd.modules.spec import device_twiddle
 from diffsptk_amd.utils import tables
@@ -111,7 +117,62 @@ def call_mgcep_step(t, nfft, M, gamma, alpha=0.42, F=9):
     return ops.MgcepStepFn.apply(t["x"], t["b1"], images, on_device(tables.mgcep_step_bwd_images(nfft, M, alpha), t["x"]), gamma)
 
 
+def call_fuse_fwlpc(t, T, L, P, M, eps, center=True, B=2, exact=False):
+    """fuse(Frame, Window, LPC) without a gradient: the one launch where it takes the geometry, the three modules where it refuses"""
+    dt = t["x"].dtype
+    fused = dsp.fuse(dsp.Frame(L, P, center=center), dsp.Window(L, device=DEV, dtype=dt), dsp.LPC(L, M, eps=eps, device=DEV, dtype=dt))
+    with torch.no_grad():
+        y = fused(t["x"])
+    assert fused.last_path == "three-stage", fused.last_path
+    return y
+
+
+def call_mfcc(t, nfft, C, M, lifter=22, floor=1e-5, F=7):
+    W = tables.dct_matrix(C, 2)[:, :M + 1] * tables.mfcc_lifter(M, lifter)[None, :]
+    return ops.MfccFn.apply(t["x"], on_device(tables.fbank_matrix(nfft, C, 16000), t["x"]), on_device(W, t["x"]), floor, 0.0, False)
+
+
+def call_mcep_generic(t, nfft, M, alpha, n_iter, F=70):
+    """the generic kernel pair asked for by name, as MelCepstralAnalysis does it for |alpha| > 0.95"""
+    m = dsp.MelCepstralAnalysis(fft_length=nfft, cep_order=M, alpha=alpha, n_iter=n_iter, device=DEV, dtype=t["X"].dtype)
+    return ops.McepFn.apply(t["X"], m.G, m.D, m.E, m.alpha_vector, nfft, M, n_iter, _lib.ALGO_GENERIC)
+
+
+class Gc2gcEntry(torch.autograd.Function):
+    """dsa_gc2gc_fwd / dsa_gc2gc_bwd themselves: ops.gc2gc_fused and ops.gc2gc_fn test the transform's size first and hand what the
+    entries would refuse to the operator chain, so the entries' own ceilings show only here"""
+
+    @staticmethod
+    def forward(ctx, c, m2, g1, g2, n_fft, tw):
+        cc = c.contiguous()
+        out = torch.empty(*cc.shape[:-1], m2 + 1, device=c.device, dtype=c.dtype)
+        ops._call("dsa_gc2gc_fwd", ops._p(cc), cc.numel() // cc.size(-1), cc.size(-1), m2, float(g1), float(g2), n_fft, ops._p(tw), 0,
+                  ops._dtype_code(cc), ops._p(out), ops._stream())
+        ctx.save_for_backward(cc, tw)
+        ctx.cfg = (m2, float(g1), float(g2), n_fft)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        cc, tw = ctx.saved_tensors
+        m2, g1, g2, n_fft = ctx.cfg
+        gc, gin = g.contiguous(), torch.empty_like(cc)
+        ops._call("dsa_gc2gc_bwd", ops._p(cc), ops._p(gc), cc.numel() // cc.size(-1), cc.size(-1), m2, g1, g2, n_fft, ops._p(tw),
+                  ops._dtype_code(cc), ops._p(gin), ops._stream())
+        return gin, None, None, None, None, None
+
+
+def call_mlsacheck(t, M, mode, n_fft, F=3, alpha=0.42, thr=4.5):
+    kw = {"fast": True} if mode == "fast" else {"fast": False, "mod_type": mode}
+    return DF.mlsacheck(t["mc"], alpha=alpha, threshold=thr, n_fft=n_fft, warn_type="ignore", **kw)
+
+
 CALLS = {
+    "fuse_fwlpc": call_fuse_fwlpc,
+    "mfcc": call_mfcc,
+    "mcep_generic": call_mcep_generic,
+    "gc2gc_entry": lambda t, g1, g2, n_fft, m1, m2, F=37: Gc2gcEntry.apply(t["c"], m2, g1, g2, n_fft, device_twiddle(n_fft, t["c"].device, t["c"].dtype)),
+    "mlsacheck": call_mlsacheck,
     "acorr": lambda t, L, M, fmt, F=3: dsp.Autocorrelation(L, M, fmt)(t["x"]),
     "levdur": lambda t, M, eps, F=5: dsp.LevinsonDurbin(M, eps)(t["r"]),
     "lpc": lambda t, L, M, eps, F=3: dsp.LPC(L, M, eps)(t["x"]),
@@ -167,10 +228,21 @@ def run(c, dt):
 CASES = [pytest.param(route, c, dt, id=KR.case_id(route, c) + "-" + dt) for route, cases in KR.ROUTES.items() for c in cases for dt in c["dtypes"]]
 
 
-@pytest.mark.parametrize("route,c,dt", CASES)
-def test_route_runs_and_matches_float64(route, c, dt):
+_REFS = {}
+
+
+def reference(route, c, dt, given):
+    """the float64 restatement of a case on its rounded inputs: computed once, shared by the tests that need it, never modified"""
+    key = KR.case_id(route, c) + "-" + dt
+    if key not in _REFS:
+        _REFS[key] = R.evaluate(c, {k: v.double() for k, v in given.items()})
+    return _REFS[key]
+
+
+def check_route(route, c, dt):
+    """name, shape, finiteness, bound"""
     name, given, got = run(c, dt)
-    ref = R.evaluate(c, {k: v.double() for k, v in given.items()})
+    ref = reference(route, c, dt, given)
     tol = KR.tolerance(route, c, dt)
     errs = [R.error(g, r, c["metric"]) for g, r in zip(got, ref)]
     print(f"{KR.case_id(route, c)} {dt}: kernel {name}, errors {['%.2e' % e for e in errs]}, bound {tol:.2e} ({c['tol_from']})")
@@ -180,26 +252,61 @@ def test_route_runs_and_matches_float64(route, c, dt):
     assert max(errs) <= tol, (errs, tol)
 
 
+@pytest.mark.parametrize("route,c,dt", CASES)
+def test_route_runs_and_matches_float64(route, c, dt):
+    check_route(route, c, dt)
+
+
 # ------------------------------------------------------------------ the refusals of csrc/lpc.hip
-VALID = KR.case("levdur", "bwd", wrt=("r",), M=24, eps=1e-5)   # (a case of ROUTES["levdur_bwd"]: its bound is the table's)
+VALID = ("levdur_bwd", KR.case("levdur", "bwd", wrt=("r",), M=24, eps=1e-5))   # (a case of ROUTES["levdur_bwd"]: its bound is the table's)
+
+
+def check_refusal(c, dt, text, then):
+    """A geometry past a launcher's ceiling raises the library's error with the launcher's message -- nothing about the output or the
+    gradient buffer is required --, the device is still in order (synchronize() succeeds), and the valid call `then` = (route, case)
+    that follows on the same stream runs its route and meets its bound."""
+    given = R.inputs_of(c, DT[dt])
+    t = {k: v.to(DEV).requires_grad_(k in c["wrt"]) for k, v in given.items()}
+    if c["when"] == "fwd":
+        with pytest.raises(_lib.BackendError, match=re.escape(text)):
+            CALLS[c["call"]](t, **c["args"])
+    else:
+        out = CALLS[c["call"]](t, **c["args"])          # (the forward of this shape is supported: that is the point)
+        outs = list(out) if isinstance(out, (tuple, list)) else [out]
+        assert all(bool(torch.isfinite(o).all()) for o in outs)
+        with pytest.raises(RuntimeError, match=re.escape(text)):
+            sum(o.sum() for o in outs).backward()
+    torch.cuda.synchronize()
+    check_route(then[0], then[1], dt if dt in then[1]["dtypes"] else then[1]["dtypes"][0])
 
 
 @pytest.mark.parametrize("call,args,dt,when,message", KR.REFUSALS, ids=[f"{r[0]}-{r[3]}-{r[2]}" for r in KR.REFUSALS])
 def test_refusal_raises_and_the_next_call_is_right(call, args, dt, when, message):
-    """A geometry past a launcher's ceiling raises the library's error with the launcher's message -- nothing about the output or the
-    gradient buffer is required -- and a valid call that follows on the same stream gives the reference's result."""
-    c = KR.case(call, when, dtypes=(dt,), wrt=("r",) if when == "bwd" else (), tol=(0, 0), tol_from="-", **args)
-    given = R.inputs_of(c, DT[dt])
-    t = {k: v.to(DEV).requires_grad_(k in c["wrt"]) for k, v in given.items()}
-    if when == "fwd":
-        with pytest.raises(_lib.BackendError, match=message):
-            CALLS[call](t, **args)
-    else:
-        out = CALLS[call](t, **args)          # (the forward of this order is supported)
-        assert bool(torch.isfinite(out).all())
-        with pytest.raises(RuntimeError, match=message):
-            out.sum().backward()
-    torch.cuda.synchronize()
-    name, given, got = run(VALID, "f64")
-    ref = R.evaluate(VALID, given)
-    assert name == "levdur_bwd" and R.error(got[0], ref[0], "max") <= KR.tolerance("levdur_bwd", VALID, "f64")
+    check_refusal(KR.shape(call, when, (dt,), wrt=("r",) if when == "bwd" else (), **args), dt, message, VALID)
+
+
+# ------------------------------------------------------------------ the size ceilings: the last shape in, the first shape out
+def _then(row):
+    """the valid call that follows a row's refusals: the row's smallest accepted case (its first), else the one of the lpc refusals"""
+    return row["inside"][0] if row["inside"] else VALID
+
+
+INSIDE = [pytest.param(route, c, dt, id=KR.case_id(route, c) + "-" + dt) for row in KR.CEILINGS for route, c in row["inside"] for dt in c["dtypes"]]
+OUTSIDE = [(row, o, dt) for row in KR.CEILINGS if row["outside"] != KR.IN_REFUSALS for o in row["outside"] for dt in o["case"]["dtypes"]]
+RESHAPED = [pytest.param(o["route"], o["case"], dt, id=KR.case_id(o["route"], o["case"]) + "-" + dt) for row, o, dt in OUTSIDE if o["expect"] == "route"]
+REFUSED = [pytest.param(o["case"], dt, o["text"], _then(row), id=KR.case_id("refused", o["case"]) + "-" + dt) for row, o, dt in OUTSIDE if o["expect"] == "raises"]
+
+
+@pytest.mark.parametrize("route,c,dt", INSIDE)
+def test_last_accepted_shape_runs_and_matches_float64(route, c, dt):
+    check_route(route, c, dt)
+
+
+@pytest.mark.parametrize("route,c,dt", RESHAPED)
+def test_first_reshaped_launch_runs_its_route_and_matches_float64(route, c, dt):
+    check_route(route, c, dt)
+
+
+@pytest.mark.parametrize("c,dt,text,then", REFUSED)
+def test_first_refused_shape_raises_and_the_next_call_is_right(c, dt, text, then):
+    check_refusal(c, dt, text, then)
