@@ -22,6 +22,8 @@ from .modules import __all__ as _module_names
 # exported from here and not from diffsptk_amd.modules: every name of modules.__all__ needs a row in the alignment sweep's table
 # (tests/alignment_rows.py); the change that adds that row moves the name into modules.__all__
 from .modules.delta import Delta
+from .modules.dtw import DynamicTimeWarping
+from .modules.dtw import DynamicTimeWarping as DTW
 from .modules.excite import ExcitationGeneration
 from .modules.imdct import InverseModifiedDiscreteCosineTransform, InverseModifiedDiscreteSineTransform, InverseModifiedDiscreteTransform
 from .modules.imdct import InverseModifiedDiscreteCosineTransform as IMDCT
@@ -40,4 +42,4 @@ __version__ = "0.1.0"
 __all__ = [*_module_names, "functional", "get_alpha", "read", "write", "Graphed", "MLSADigitalFilterStabilityCheck",
            "ExcitationGeneration", "mseq", "mseq_like", "nrand", "MDCT", "IMDCT", "MDST", "IMDST", "ModifiedDiscreteCosineTransform",
            "InverseModifiedDiscreteCosineTransform", "ModifiedDiscreteSineTransform", "InverseModifiedDiscreteSineTransform", "Delta", "MLPG",
-           "MaximumLikelihoodParameterGeneration", "MelCepstrumPostfiltering"]
+           "MaximumLikelihoodParameterGeneration", "MelCepstrumPostfiltering", "DynamicTimeWarping", "DTW"]

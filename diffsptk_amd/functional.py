@@ -12,6 +12,7 @@ from .modules.mlsacheck import MLSADigitalFilterStabilityCheck   # (not a name o
 from .modules.imdct import InverseModifiedDiscreteCosineTransform, InverseModifiedDiscreteSineTransform   # (the same)
 from .modules.mdct import ModifiedDiscreteCosineTransform, ModifiedDiscreteSineTransform
 from .modules.delta import Delta
+from .modules.dtw import DynamicTimeWarping
 from .modules.mcpf import MelCepstrumPostfiltering
 from .modules.mlpg import MaximumLikelihoodParameterGeneration
 
@@ -320,3 +321,14 @@ def mlpg(u: Tensor, seed=[[-0.5, 0, 0.5], [1, -2, 1]]) -> Tensor:
 def mcpf(mc: Tensor, alpha: float = 0, beta: float = 0, onset: int = 2, ir_length: int = 128) -> Tensor:
     """Mel-cepstrum postfiltering mc:(..., M+1) -> (..., M+1) (functional.py: mcpf)."""
     return MelCepstrumPostfiltering._func(mc, alpha=alpha, beta=beta, onset=onset, ir_length=ir_length)
+
+
+def dtw(x: Tensor, y: Tensor, lengths: Tensor | None = None, return_indices: bool = False, metric: str | int = "euclidean", p: int = 4,
+        softness: float = 1e-3) -> Tensor | tuple[Tensor, list[Tensor]]:
+    """Dynamic time warping distance of x:(B, T1, D) and y:(B, T2, D) -> (B,), and the Viterbi paths on request (functional.py: dtw)."""
+    return DynamicTimeWarping._func(x, y, lengths=lengths, return_indices=return_indices, metric=metric, p=p, softness=softness)
+
+
+def dtw_merge(x: Tensor, y: Tensor, indices: Tensor) -> Tensor:
+    """The frames of x:(T1, D) and y:(T2, D) along a Viterbi path indices:(T, 2) -> (T, 2D) (functional.py: dtw_merge)."""
+    return DynamicTimeWarping.merge(x=x, y=y, indices=indices)

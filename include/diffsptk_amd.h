@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define DSA_VERSION 139 /* 0.3.3: + DSA_ALGO_FIXED_STEPS (the tuned mel-cepstral forward stops a frame's Newton iteration once its update is rounding noise; the flag runs every step); 0.3.2: + dsa_delta / dsa_delta_vjp, dsa_mlpg, dsa_mcpf / dsa_mcpf_vjp (parameter generation: delta features, maximum likelihood parameter generation by a banded Cholesky solve, mel-cepstrum postfiltering in closed form); 0.3.1: + dsa_mdct_analysis / dsa_mdct_synthesis (MDCT / MDST and their inverses: window, fold, DCT-IV through a quarter-length complex FFT and overlap-add in one launch each way; each is the other's adjoint); 0.3.0: + dsa_excite (pitch to excitation: the voiced shapes of ExcitationGeneration on a segmented float64 phase sum, one launch); 0.2.9: + dsa_mlsacheck / dsa_mlsacheck_vjp (the stability check of the MLSA filter: the mel-cepstrum scaled or clipped where the amplitude of its gain-free part passes the threshold of the Pade approximation, forward and adjoint); 0.2.8: + dsa_lpc2lsp_fwd / _bwd, dsa_lsp2lpc_fwd / _bwd, dsa_lspcheck_fwd / _bwd (line spectral pairs by a Chebyshev-series root search, back by a product of real sections, and their stability check, forward and adjoint); 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
+#define DSA_VERSION 140 /* 0.3.4: + dsa_dtw / dsa_dtw_vjp / dsa_dtw_path (dynamic time warping with a soft minimum: the aligned distance of two vector sequences by an anti-diagonal wavefront, its gradient by the reverse sweep, the Viterbi path from the saved tables); 0.3.3: + DSA_ALGO_FIXED_STEPS (the tuned mel-cepstral forward stops a frame's Newton iteration once its update is rounding noise; the flag runs every step); 0.3.2: + dsa_delta / dsa_delta_vjp, dsa_mlpg, dsa_mcpf / dsa_mcpf_vjp (parameter generation: delta features, maximum likelihood parameter generation by a banded Cholesky solve, mel-cepstrum postfiltering in closed form); 0.3.1: + dsa_mdct_analysis / dsa_mdct_synthesis (MDCT / MDST and their inverses: window, fold, DCT-IV through a quarter-length complex FFT and overlap-add in one launch each way; each is the other's adjoint); 0.3.0: + dsa_excite (pitch to excitation: the voiced shapes of ExcitationGeneration on a segmented float64 phase sum, one launch); 0.2.9: + dsa_mlsacheck / dsa_mlsacheck_vjp (the stability check of the MLSA filter: the mel-cepstrum scaled or clipped where the amplitude of its gain-free part passes the threshold of the Pade approximation, forward and adjoint); 0.2.8: + dsa_lpc2lsp_fwd / _bwd, dsa_lsp2lpc_fwd / _bwd, dsa_lspcheck_fwd / _bwd (line spectral pairs by a Chebyshev-series root search, back by a product of real sections, and their stability check, forward and adjoint); 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
 
 typedef enum {
     DSA_OK = 0,
@@ -846,6 +846,42 @@ int dsa_mcpf(const void* mc, int64_t F, int32_t M1, const void* table_t, int32_t
                  void* stream);
 int dsa_mcpf_vjp(const void* mc, const void* g, int64_t F, int32_t M1, const void* table, const void* table_t, int32_t bins, double scale,
                  int32_t onset, int32_t dtype, void* gmc, void* stream);
+
+/* ------------------------------------------------------------------ a20  dynamic time warping with a soft minimum: dtw (0.3.4)
+ * DynamicTimeWarping._forward, dtw.py:301-338, with the core of dtw.py:26-125: the reference's T1 T2 Python iterations as one launch.
+ * x:(B,T1,D), y:(B,T2,D) of the dtype; lengths:(B,2) int64 on the device, or NULL for (T1, T2) everywhere.  float32 and float64, int64
+ * indexing, no allocation, no atomics, no host synchronisation.  A pair's bits depend on (T1, T2, D, options) and its own values, not on
+ * B or its place in the batch.  B = 0 is a no-op before any pointer is looked at.
+ *   d(i,j)    DSA_DTW_MANHATTAN sum |x - y|; _EUCLIDEAN sqrt(sum (x - y)^2); _SQUARED_EUCLIDEAN that root squared (as the reference);
+ *             _SYMMETRIC_KL sum x log(max(x / y, 1e-10)) + sum y log(max(y / x, 1e-10)): formed in the kernel, never stored
+ *   steps     of the local path constraint p = 0 .. 6, in the order of dtw.py:255-284; p = 4 and 6 keep a second table R_
+ *   R[i,j]    -softness logsumexp(-c_k / softness) over c_k = (a + b) d(i,j) + S[i - a, j - b] of the steps (a, b) whose source is inside
+ *             and not +inf; S = R_ for an axis step (a = 0 or b = 0) of p = 4, 6, else R; R_[i,j] the same over the other steps;
+ *             R[0,0] = d(0,0), R_[0,0] = +inf
+ *   dsa_dtw       distance[b] = R[len1 - 1, len2 - 1] / (len1 + len2), +inf when the end is unreachable; NaN for lengths outside
+ *                 1 .. T1, 1 .. T2.  R, R2: the tables, T1 T2 values of the dtype per pair each (R2 only for p = 4, 6; else NULL), laid
+ *                 out by anti-diagonal; cells outside the pair's lengths are not written.  R = NULL: nothing but the distance is stored.
+ *   dsa_dtw_vjp   dtw.py's autograd in closed form: gx:(B,T1,D), gy:(B,T2,D), every element written, for the cotangent gdistance:(B) and
+ *                 the tables of dsa_dtw.  Zero for a pair with an unreachable end or invalid lengths.  d/dx of |.| is sign with
+ *                 sign(0) = 0, of the Euclidean distance 0 where d = 0; a clipped quotient passes no derivative.
+ *   dsa_dtw_path  indices:(B, T1 + T2 - 1, 2) int64 and count:(B) int32: the pair's Viterbi path (dtw.py:106-123; the hard argmin of each
+ *                 visited cell recomputed from the tables, ties to the first step) is rows [T1 + T2 - 1 - count, T1 + T2 - 1) in forward
+ *                 order, the rows before them are not written; count = 1 for an unreachable end, 0 for invalid lengths.
+ * Workspace: the caller's R (and R2), T1 T2 elements per pair each, between dsa_dtw and the other two; the library owns no device memory.
+ * One workgroup per pair, x_b in LDS: T1 <= 64 runs in one wave, rows over the lanes, neighbours by lane exchange, no barrier; longer x
+ * runs rows strided over up to 1024 threads with the last three diagonals in LDS and one barrier per diagonal.  dsa_last_kernel():
+ * "dtw_wave_f32", "dtw_block_f32", "dtw_vjp_wave_f32", "dtw_vjp_block_f32", "dtw_path_f32" and the same with f64.
+ * DSA_ERR_INVALID_ARGUMENT with a message that names "dtw": a negative size, T1 or T2 = 0, sizes beyond int64, a metric / p / dtype
+ * that is none of the above, softness <= 0, a missing pointer, and T1 (D + 12) sizeof(dtype) > DSA_DTW_MAX_LDS_BYTES: one pair's x and
+ * the resident diagonals have to fit one compute unit's LDS (float32 at D = 25: T1 <= 1107). */
+enum { DSA_DTW_MANHATTAN = 0, DSA_DTW_EUCLIDEAN = 1, DSA_DTW_SQUARED_EUCLIDEAN = 2, DSA_DTW_SYMMETRIC_KL = 3 };
+#define DSA_DTW_MAX_LDS_BYTES 163840
+int dsa_dtw(const void* x, const void* y, const void* lengths, int64_t B, int64_t T1, int64_t T2, int64_t D, int32_t metric, int32_t p,
+            double softness, int32_t dtype, void* R, void* R2, void* distance, void* stream);
+int dsa_dtw_vjp(const void* x, const void* y, const void* lengths, const void* R, const void* R2, const void* gdistance, int64_t B, int64_t T1,
+                int64_t T2, int64_t D, int32_t metric, int32_t p, double softness, int32_t dtype, void* gx, void* gy, void* stream);
+int dsa_dtw_path(const void* x, const void* y, const void* lengths, const void* R, const void* R2, int64_t B, int64_t T1, int64_t T2, int64_t D,
+                 int32_t metric, int32_t p, int32_t dtype, void* indices, void* count, void* stream);
 
 #ifdef __cplusplus
 }
