@@ -108,6 +108,22 @@ SIGNATURES, CONSTANTS = parse_header(open(HEADER).read())   # name -> (restype, 
 globals().update({name[len("DSA_"):]: value for name, value in CONSTANTS.items()})
 
 
+def env_text(name: str) -> str:
+    """The value of a DSA_* switch, "" when it is unset (csrc/env.h has the same pair; the table of record: INTEGRATION.md,
+    "Environment switches").  Read at every call, never cached."""
+    return os.environ.get(name, "")
+
+
+def env_int(name: str, default: int) -> int:
+    """An optional '-' and 1 to 9 decimal digits, nothing else; any other value (unset, empty, spaces, trailing text) gives
+    `default`.  An on/off switch is env_int(name, d) != 0; a three-state one has default -1, 0 never, 1 always."""
+    v = os.environ.get(name)
+    if v is None:   # (the usual case costs what the bare read cost: these sit in front of launches of a few microseconds)
+        return default
+    digits = v[1:] if v[:1] == "-" else v
+    return int(v) if 1 <= len(digits) <= 9 and digits.isascii() and digits.isdigit() else default
+
+
 def algo_reserve_cus(n: int) -> int:
     """DSA_ALGO_RESERVE_CUS(n)"""
     return (int(n) & 63) << 16

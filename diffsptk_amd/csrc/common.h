@@ -20,7 +20,8 @@
 #include <atomic>
 
 #include "../../include/diffsptk_amd.h"
-#include "mcep_units.h"   // internal declarations of the mel-cepstral families, for the units that define and the units that call them
+#include "env.h"          // env_int / env_text: every DSA_* route switch is read through them, at every call
+#include "mcep_units.h"  // internal declarations of the mel-cepstral families, for the units that define and the units that call them
 
 #define DSA_EXPORT extern "C" __attribute__((visibility("default")))
 

@@ -19,13 +19,6 @@
 
 namespace dsa {
 
-static bool env_flag(const char* name)
-{
-    const char* v = std::getenv(name);
-    return v && v[0] && v[0] != '0';
-}
-
-
 constexpr int kFbFrames = 4;   // frames per wave and pass
 constexpr int kFbMaxWaves = 16;  // waves per workgroup (as many as the LDS tiles next to the H copy allow)
 
@@ -629,7 +622,7 @@ DSA_EXPORT int dsa_fbank_fwd(const void* x, int64_t F, int32_t K, const void* H,
     DSA_REQUIRE(F >= 0 && K >= 2 && C >= 1, "fbank: sizes must be positive");
     DSA_REQUIRE(floor > 0 && gamma >= -1 && gamma <= 1, "fbank: floor must be positive and gamma in [-1, 1]");
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == DSA_F32 && C <= 48 && K <= 16 * kFmPre && K > C && F > 0 && !env_flag("DSA_FBANK_GENERIC"))
+    if (dtype == DSA_F32 && C <= 48 && K <= 16 * kFmPre && K > C && F > 0 && env_int("DSA_FBANK_GENERIC", 0) == 0)
         return fbank_mfma_launch(x, F, K, H, C, floor, gamma, use_power, y, E, st);
     if (dtype == DSA_F32) return fbank_launch<float>(false, nullptr, nullptr, x, F, K, H, C, floor, gamma, use_power, y, E, nullptr, st);
     if (dtype == DSA_F64) return fbank_launch<double>(false, nullptr, nullptr, x, F, K, H, C, floor, gamma, use_power, y, E, nullptr, st);
@@ -657,7 +650,7 @@ DSA_EXPORT int dsa_fbank_dct_fwd(const void* x, int64_t F, int32_t K, const void
     if (F == 0) return DSA_OK;
     hipStream_t st = (hipStream_t)stream;
     if (dtype == DSA_F32 && C <= 48 && Mo <= 16 && K <= 16 * kFmPre && K > C && fbank_mfma_lds_bytes(K, true) <= 160 * 1024 &&
-        !env_flag("DSA_FBANK_GENERIC"))
+        env_int("DSA_FBANK_GENERIC", 0) == 0)
         return fbank_mfma_launch_ex(x, F, K, H, C, C, floor, gamma, use_power ? 1 : 0, 0, 1.0, nullptr, E, st, "fbank_dct_mfma_fwd",
                                     W, Mo, z);
     const size_t esz = dtype == DSA_F64 ? 8 : 4;

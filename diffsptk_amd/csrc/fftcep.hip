@@ -343,10 +343,7 @@ static int fftcep_launch(bool bwd, const void* gout, const void* x, int64_t F, i
     const size_t lds = sizeof(T) * (2 * (size_t)H + N);
     if (H > 512 || lds > 60 * 1024) return fail(DSA_ERR_UNSUPPORTED, "fftcep: fft_length above 1022 is not supported%s");
     const int L = 2 * (H - 1);
-    static const bool direct_only = [] {
-        const char* e = getenv("DSA_FFTCEP_DIRECT");
-        return e && atoi(e) != 0;
-    }();
+    const bool direct_only = env_int("DSA_FFTCEP_DIRECT", 0) != 0;
     if (n_iter > 0 && L >= 32 && (L & (L - 1)) == 0 && !direct_only) {   // full H x H products: FFT in LDS
         const size_t lds_fft = lds + sizeof(T) * (2 * (size_t)L + H);   // transform halves, real results, twiddles
         // one wave per frame: the barriers between the butterfly passes become single-wave barriers and a compute unit holds
@@ -382,11 +379,8 @@ DSA_EXPORT int dsa_fftcep_fwd(const void* x, int64_t F, int32_t fft_length, int3
     const int H = fft_length / 2 + 1, N = cep_order + 1;
     hipStream_t st = (hipStream_t)stream;
     // n_iter = 0: out = log(x) A[:, :N] / L with the first coefficient halved -- the matrix-core front-end kernel
-    if (dtype == DSA_F32 && n_iter == 0 && N <= 48 && N < H && H <= 320 && F > 0) {
-        const char* g = getenv("DSA_FFTCEP_GENERIC");
-        if (!(g && g[0] && g[0] != '0'))
-            return fbank_mfma_launch_ex(x, F, H, A, N, H, 1.0, 0.0, 2, 1, 1.0 / fft_length, out, nullptr, st, "fftcep_mfma_fwd");
-    }
+    if (dtype == DSA_F32 && n_iter == 0 && N <= 48 && N < H && H <= 320 && F > 0 && env_int("DSA_FFTCEP_GENERIC", 0) == 0)
+        return fbank_mfma_launch_ex(x, F, H, A, N, H, 1.0, 0.0, 2, 1, 1.0 / fft_length, out, nullptr, st, "fftcep_mfma_fwd");
     if (dtype == DSA_F32) return fftcep_launch<float>(false, nullptr, x, F, H, N, A, accel, n_iter, out, masks, nullptr, st);
     if (dtype == DSA_F64) return fftcep_launch<double>(false, nullptr, x, F, H, N, A, accel, n_iter, out, masks, nullptr, st);
     return fail(DSA_ERR_UNSUPPORTED, "fftcep: unsupported dtype%s");

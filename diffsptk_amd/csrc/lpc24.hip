@@ -348,8 +348,7 @@ int lpc24_fwd(const void* x, int64_t B, int64_t T, int64_t N, int L, int P, int 
     long total_sc = (long)B * sc_per_utt;
     if (grid > total_sc) grid = total_sc;
     // lag sums: float32 matrix instruction (default) or the float64 vector unit (DSA_LPC_LAGSUMS=f64: exact sums)
-    static const bool exact_env = [] { const char* e = getenv("DSA_LPC_LAGSUMS"); return e && e[0] == 'f' && e[1] == '6'; }();
-    const bool exact = exact_env || exact_flag;
+    const bool exact = exact_flag || strcmp(env_text("DSA_LPC_LAGSUMS"), "f64") == 0;
     // ticket counter (the float64 kernel; the default kernel deals its items out statically and needs none): the first word of
     // the caller's scratch, zeroed in stream order before the launch unless the caller says it is
     unsigned* queue = (unsigned*)scratch;

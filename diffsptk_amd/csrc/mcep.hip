@@ -347,10 +347,7 @@ DSA_EXPORT int dsa_freqt_fwd(const void* c, int64_t F, int32_t L1, const void* A
     hipStream_t st = (hipStream_t)stream;
     // long float32 rows (the 257-bin spectra of mgcep.py:199-209 against 25 .. 49-column matrices): the float32 matrix-core
     // row product of fbank.hip, 48 output columns per launch (exact float32 products, float32 accumulation, as here)
-    static const bool no_mfma = [] {
-        const char* e = getenv("DSA_FREQT_GENERIC");
-        return e && atoi(e) != 0;
-    }();
+    const bool no_mfma = env_int("DSA_FREQT_GENERIC", 0) != 0;
     // (chosen from the geometry alone: a row's result must not depend on how many rows share the call)
     if (dtype == DSA_F32 && L1 > 48 && L1 <= 320 && L2 <= 192 && !no_mfma) {
         for (int c0 = 0; c0 < L2; c0 += 48) {

@@ -1,8 +1,6 @@
 // All Newton steps of the mel-cepstral analysis at the 48 kHz set-ups in one persistent launch: the kernels (mcep_big_f16.h: eight
 // waves per workgroup, narrow and wide tiles; mcep_big4_f16.h: twin four-wave workgroups) and the plan that picks among them.  The
 // kernels read the operand images of mcep_resid.hip and run the solver templates of thsolve_tq.h.  (Caller: rows_gemm.hip.)
-#include <stdlib.h>
-
 #include "mcep_big4_f16.h"
 #include "mcep_big_f16.h"
 
@@ -17,8 +15,7 @@ int mcep_big_newton(const void* logx, int64_t F, int K, const void* mc_in, int M
     const int ks1 = (M1 + 31) / 32, nt = (2 * M1 - 1 + 15) / 16;
     // the orders of the octet-layout solver, 35 .. 54, and -- quad layout -- 32 .. 34 (the 48 kHz set-up fft_length 1024 / order 34)
     if (!(ks1 == 2 && M1 >= 33 && M1 <= 55 && K >= 4)) return DSA_ERR_UNSUPPORTED;
-    static const bool off = [] { const char* e = getenv("DSA_MCEP_BIG"); return e && e[0] == '0'; }();   // A/B: the two-launch step
-    if (off) return DSA_ERR_UNSUPPORTED;
+    if (env_int("DSA_MCEP_BIG", 1) == 0) return DSA_ERR_UNSUPPORTED;   // A/B: the two-launch step
     // The kernel's INSTANTIATION is chosen by the order alone; its tile shape by the batch.  A persistent launch is rounds of 256 tiles
     // (one eight-wave workgroup per CU) and a round takes a tile's time however few tiles it has.  Narrow tiles (64 frames, two
     // waves per 16-frame group: the shortest step) for up to one round; beyond it a PLAN: W rounds of wide tiles (128 frames, a wave per
@@ -29,15 +26,13 @@ int mcep_big_newton(const void* logx, int64_t F, int K, const void* mc_in, int M
     // Measured, us per analysis, fft_length 2048 / order 49, 10 steps (profiles/r06_mcep_big_newton.txt, two launches per step ->
     // narrow): 200 frames 696 -> 593, 3 200 724 -> 630, 12 800 920 -> 672, 20 000 1 250 -> 1 300, 40 000 2 027 -> 2 008, 102 400
     // 4 813 -> 4 720; with the plan: profiles/r06_mcep_big_wide.txt.
-    const char* wide_e = getenv("DSA_MCEP_BIG_WIDE");   // A/B and tests: 0 never, 1 always (read per call: the tests switch it in-process)
-    const int wide_env = wide_e ? atoi(wide_e) : -1;
+    const int wide_env = env_int("DSA_MCEP_BIG_WIDE", -1);   // A/B and tests: 0 never, 1 always
     const bool quad = M1 <= 35;
     // Quad-layout orders: the rounds of 32 768 frames run as TWIN workgroups (mcep_big4_f16.h: two four-wave workgroups per CU, the
     // second half a step late: 1024 / 34 at 122 880 frames 2.15 -> 1.99 ms, profiles/r06_mcep_big_twin.txt) instead of eight-wave wide
     // tiles (DSA_MCEP_BIG_TWIN=0, A/B); the same bits either way.  At the octet-layout orders the twin shape measured no faster than
     // the plan (each workgroup streams the images itself: twice the bytes from L2 per frame) and is not instantiated.
-    const char* twin_e = getenv("DSA_MCEP_BIG_TWIN");
-    const bool twin = quad && !(twin_e && twin_e[0] == '0');
+    const bool twin = quad && env_int("DSA_MCEP_BIG_TWIN", 1) != 0;
     const long FN = 256L * 64, FW = 256L * 128;          // frames a full round of narrow / wide (or twin) tiles takes
     long wide_rounds = 0;
     if (wide_env > 0 || (wide_env < 0 && twin && F > FN)) {
@@ -58,8 +53,7 @@ int mcep_big_newton(const void* logx, int64_t F, int K, const void* mc_in, int M
         }
     }
     const long F_wide = wide_rounds * FW < F ? wide_rounds * FW : (wide_rounds > 0 ? (long)F : 0);
-    const char* stag_e = getenv("DSA_MCEP_BIG_STAGGER");
-    const int stagger = stag_e ? atoi(stag_e) : 5;                // x ~8 k cycles (measured 4 .. 6 best: profiles/r06_mcep_big_twin.txt)
+    const int stagger = env_int("DSA_MCEP_BIG_STAGGER", 5);   // x ~8 k cycles (measured 4 .. 6 best: profiles/r06_mcep_big_twin.txt)
 #define DSA_BIG_NEWTON_1(NTV, NGV, NMINV, QUADV, WIDEV, F0, FC)                                                                         \
     do {                                                                                                                                \
         constexpr int lds_b = mbg::lds_floats<2, NTV, NGV, QUADV, WIDEV>() * 4;                                                         \

@@ -640,10 +640,7 @@ static int launch_row_dft(const void* x, int64_t B, int64_t Tlen, int64_t N, int
     size_t lds = sizeof(T) * (size_t)L;
     int threads = nfft / 2 + 1 >= 192 ? 256 : (nfft / 2 + 1 >= 96 ? 128 : 64);
     // power-of-two lengths: radix-2 FFT in LDS (DSA_ROWDFT_DIRECT=1 keeps the direct sum, for A/B runs and tests)
-    static const bool direct_only = [] {
-        const char* e = getenv("DSA_ROWDFT_DIRECT");
-        return e && atoi(e) != 0;
-    }();
+    const bool direct_only = env_int("DSA_ROWDFT_DIRECT", 0) != 0;
     const size_t lds_fft = lds + sizeof(T) * 2 * (size_t)nfft;
     if (!direct_only && nfft >= 32 && (nfft & (nfft - 1)) == 0 && lds_fft <= 150 * 1024) {
         static std::atomic<uint64_t> lds_set{0};
@@ -876,10 +873,7 @@ static int launch_row_dft_bwd(const void* x, int64_t B, int64_t Tlen, int64_t N,
     T floor_lin = use_floor ? (T)pow(10.0, floor_db / 10.0) : T(0);
     const int K = nfft / 2 + 1;
     size_t lds = sizeof(T) * ((size_t)L + 3 * (size_t)K);
-    static const bool direct_only = [] {
-        const char* e = getenv("DSA_ROWDFT_DIRECT");
-        return e && atoi(e) != 0;
-    }();
+    const bool direct_only = env_int("DSA_ROWDFT_DIRECT", 0) != 0;
     const size_t lds_fft = lds + sizeof(T) * 2 * (size_t)nfft;
     if (!direct_only && nfft >= 32 && (nfft & (nfft - 1)) == 0 && lds_fft <= 150 * 1024) {
         static std::atomic<uint64_t> lds_set{0};

@@ -775,7 +775,7 @@ DSA_EXPORT int dsa_stft_fwd(const void* x, int64_t B, int64_t T, int32_t L, int3
     }
     // fft_length 1024 / 2048 (the 44.1 / 48 kHz set-ups of utils/public.py:61-104), power format, constant padding, no zmean, no
     // relative floor: the packed kernel of stft_pk_big.h (round 6; DSA_STFT_BIG=0: the generic kernel, for A/B runs)
-    static const bool big_on = [] { const char* e = getenv("DSA_STFT_BIG"); return !(e && e[0] == '0'); }();
+    const bool big_on = env_int("DSA_STFT_BIG", 1) != 0;
     if (big_on && dtype == DSA_F32 && algo != DSA_ALGO_GENERIC && (nfft == 1024 || nfft == 2048) && !zmean && !use_floor &&
         out_format == DSA_SPEC_POWER && pad_mode == DSA_PAD_CONSTANT && L <= nfft && (L & 1) == 0 && (P & 1) == 0 && (left & 1) == 0 &&
         (T & 1) == 0 && (((size_t)x) & 7) == 0 && B * N < (int64_t(1) << 31)) {
@@ -854,8 +854,7 @@ static int stft_bwd_impl(const void* gy, const void* x, int64_t B, int64_t T, in
     {
         // fft_length 1024 / 2048 (the 44.1 / 48 kHz set-ups), power format, constant padding, no zmean, no relative floor, fixed window:
         // the packed kernel of stft_bwd_pk_big.h (round 6; DSA_STFT_BIG_BWD=0: the generic backward, for A/B runs)
-        const char* bigb_e = getenv("DSA_STFT_BIG_BWD");   // (read per call: the tests switch it in-process)
-        const bool bigb_on = !(bigb_e && bigb_e[0] == '0');
+        const bool bigb_on = env_int("DSA_STFT_BIG_BWD", 1) != 0;
         const int64_t Nb = dsa_num_frames(T, P);
         const int leftb = center ? L / 2 : 0;
         if (bigb_on && dtype == DSA_F32 && algo != DSA_ALGO_GENERIC && (nfft == 1024 || nfft == 2048) && !zmean && !use_floor && !gw && !div &&

@@ -214,10 +214,7 @@ DSA_EXPORT int dsa_thsolve_fwd(const void* p, const void* q, const void* r, int6
     DSA_REQUIRE(n >= 1 && n <= kThMax && F >= 0, "thsolve: order must be in [1, 64]");
     if (F == 0) return DSA_OK;
     // cepstral order 24, float32: the unpivoted quad-layout solve of the mel-cepstral kernels (DSA_THSOLVE_QUAD=0: A/B)
-    static const bool quad = [] {
-        const char* e = getenv("DSA_THSOLVE_QUAD");
-        return !e || atoi(e) != 0;
-    }();
+    const bool quad = env_int("DSA_THSOLVE_QUAD", 1) != 0;
     if (dtype == DSA_F32 && n == 24 && quad && F > 0) return thsolve_quad24_fwd(p, q, r, F, g, (hipStream_t)stream);
     // other orders up to 55, float32: the same scheme as a template over the size -- chosen from (n, dtype) ALONE, like
     // dsa_mcep_newton_update: a frame's rounding must not depend on how many frames travel with it (round 6: the F >= 64 test is gone)
@@ -361,10 +358,7 @@ DSA_EXPORT int dsa_thsolve_bwd(const void* gg, const void* p, const void* q, con
     if (F == 0) return DSA_OK;
     // order 24, float32: u = A^{-1} gbar on the quad-layout solve (A is symmetric; marked systems re-solved with pivoting as in
     // the forward), then the diagonal sums (DSA_THSOLVE_QUAD=0: the one-wave-per-system kernel, A/B)
-    static const bool quad = [] {
-        const char* e = getenv("DSA_THSOLVE_QUAD");
-        return !e || atoi(e) != 0;
-    }();
+    const bool quad = env_int("DSA_THSOLVE_QUAD", 1) != 0;
     if (dtype == DSA_F32 && n == 24 && quad && gp && gq && gr) {
         if (int rc = thsolve_quad24_fwd(p, q, gg, F, gr, (hipStream_t)stream)) return rc;
         hipLaunchKernelGGL(th_bwd_sums_kernel, dim3((unsigned)((F + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const float*)gr,

@@ -8,11 +8,12 @@ has no distributed code at all.
 """
 from __future__ import annotations
 
-import os
 from typing import Callable
 
 import torch
 import torch.distributed as dist
+
+from . import _lib
 
 
 def reserved_cus() -> int:
@@ -26,10 +27,7 @@ def reserved_cus() -> int:
       * completed TWO steps later (GATHER_DEPTH = 2, what bench.py does):  0.627 ms with none reserved, **0.618 with 8** (0.65 / 0.66 for
         32 / 64 workgroups: any channel count fits); three steps: the same.
     Hence 8 (the launcher rounds up to 9 where that costs no round of tiles: +1.2 % on the launch alone)."""
-    try:
-        return max(0, min(63, int(os.environ.get("DSA_RESERVE_CUS", "8"))))
-    except ValueError:
-        return 8
+    return max(0, min(63, _lib.env_int("DSA_RESERVE_CUS", 8)))
 
 
 #: how many batches later a streaming caller should complete a deferred gather (PendingGather.wait()): see reserved_cus()

@@ -8,13 +8,11 @@ Toeplitz-plus-Hankel solve kernel (csrc/thsolve.hip).  Gradients: the kernels' o
 """
 from __future__ import annotations
 
-import os
-
 import numpy as np
 import torch
 from torch import nn
 
-from .. import ops
+from .. import _lib, ops
 from ..utils import tables
 from ..utils.private import check_size, to
 from .gnorm import GeneralizedCepstrumGainNormalization as _Gnorm
@@ -78,8 +76,9 @@ class MelGeneralizedCepstralAnalysis(nn.Module):
         if self.step_images is not None and cep_order == 24 and -1 < gamma < 0:
             self.register_buffer("step_images_h", torch.from_numpy(tables.mgcep_step_h_buffer(fft_length, cep_order, float(alpha))).to(device),
                                  persistent=False)
-            # ... and the step's adjoint on the binary16 matrix pipe too (DSA_MGCEP_STEP_BWD_H=0: the float32 kernel, for A/B runs)
-            if os.environ.get("DSA_MGCEP_STEP_BWD_H") != "0":
+            # ... and the step's adjoint on the binary16 matrix pipe too (DSA_MGCEP_STEP_BWD_H=0, read HERE, at construction: the
+            # float32 kernel, for A/B runs)
+            if _lib.env_int("DSA_MGCEP_STEP_BWD_H", 1) != 0:
                 # (stored as int16 bit patterns like step_images_h's bytes: nn.Module.float() / .to(dtype) cast every FLOATING buffer, and
                 #  a binary16 image silently cast to float32 would be read by the float32 kernel in the wrong layout)
                 self.register_buffer("step_images_bwd", torch.from_numpy(tables.mgcep_step_bwd_h_images(fft_length, cep_order, float(alpha))
@@ -106,7 +105,7 @@ class MelGeneralizedCepstralAnalysis(nn.Module):
         def newton(gamma, b1, need_gain=True):   # need_gain: b0 = sqrt(eps) is only read after the LAST step of a run
             b1_old = b1
             if gamma != -1 and self.step_images_h is not None and x.dtype == torch.float32 and self.step_images_h.device == x.device \
-                    and os.environ.get("DSA_MGCEP_STEP_SOLVE") != "0":
+                    and _lib.env_int("DSA_MGCEP_STEP_SOLVE", 1) != 0:
                 # mgcep.py:199-230 in ONE launch; with a graph wanted the same launch keeps (pt, qt) and the backward is the adjoint
                 # solve + the step's adjoint (ops.MgcepStepSolveFn)
                 if torch.is_grad_enabled() and (x.requires_grad or b1.requires_grad):
@@ -192,8 +191,8 @@ class MelGeneralizedCepstralAnalysis(nn.Module):
             b1 = b[..., 1:]            # mgcep.py:244: only b1 of b2b's output is kept
             b = None
             one_launch = self.n_iter >= 1 and self.step_images_h is not None and x.dtype == torch.float32 and self.step_images_h.device == x.device \
-                and not (torch.is_grad_enabled() and (x.requires_grad or b1.requires_grad)) and os.environ.get("DSA_MGCEP_STEP_SOLVE") != "0" \
-                and os.environ.get("DSA_MGCEP_ALL_STEPS") != "0"
+                and not (torch.is_grad_enabled() and (x.requires_grad or b1.requires_grad)) and _lib.env_int("DSA_MGCEP_STEP_SOLVE", 1) != 0 \
+                and _lib.env_int("DSA_MGCEP_ALL_STEPS", 1) != 0
             if one_launch:
                 # no graph wanted: ALL n_iter Newton steps in one launch (a frame's iteration depends on the frame alone), then the gain
                 b1, r, b1_prev = ops.mgcep_step_solve(x, b1, self.step_images_h, self.gamma, n_steps=self.n_iter, want_prev=True)

@@ -1,7 +1,6 @@
 """Mel-cepstral analysis: the tuned kernels (csrc/mcep.hip, mcep_mfma.hip, mcep_mfma_bwd.hip), the composed Newton paths (rows_gemm.hip, thsolve.hip)."""
 from __future__ import annotations
 
-import os
 import weakref
 
 import torch
@@ -52,7 +51,7 @@ def _mcep_composed_applies(Xc, M) -> bool:
     and the dtype only -- never of the number of frames: a frame's mel-cepstrum does not depend on how many frames share its
     batch.  Short spectra (fft_length < 256: the reference's own test grids) keep the generic kernel pair."""
     return (Xc.dtype == torch.float32 and M + 1 <= 64 and M >= 1 and Xc.size(-1) >= 129
-            and os.environ.get("DSA_MCEP_COMPOSED", "1") != "0")   # float64 keeps the generic kernel pair
+            and _lib.env_int("DSA_MCEP_COMPOSED", 1) != 0)   # float64 keeps the generic kernel pair
 
 
 def mcep_composed(X, G, D, E, av, fft_length, M, n_iter, algo):
@@ -182,9 +181,6 @@ def mcep_resid_bwd_images(D, E):
     return images
 
 
-MCEP_GLOGX_ONE_PASS = True   # McepNewtonStepsHFn.backward: glogx in one pass after the sweep (dsa_mcep_newton_glogx_h)
-
-
 MCEP_GLOGX_MIN_FRAMES = 20480   # (tools/sweep_glogx_threshold.py: 16 384 frames 2.55 against 2.53 ms accumulating, 24 576: 3.40 against 3.73)
 
 
@@ -231,8 +227,8 @@ class McepNewtonStepsHFn(torch.autograd.Function):
         # as the in-place accumulation (DSA_MCEP_GLOGX_PASS=0, and n_iter beyond what the pass holds on chip).
         # (from MCEP_GLOGX_MIN_FRAMES frames on: below, the pass's one-tile workgroups leave CUs idle -- 12 800 frames at 2048 / 49: 2.42 ms
         #  accumulating, 2.48 with the pass; DSA_MCEP_GLOGX_PASS=1 forces it, =0 forbids it.  The bits do not depend on the choice.)
-        env = os.environ.get("DSA_MCEP_GLOGX_PASS", "")
-        one_pass = (MCEP_GLOGX_ONE_PASS and env != "0" and (F >= MCEP_GLOGX_MIN_FRAMES or env == "1")
+        env = _lib.env_int("DSA_MCEP_GLOGX_PASS", -1)
+        one_pass = (env != 0 and (F >= MCEP_GLOGX_MIN_FRAMES or env == 1)
                     and n_iter * ((4 + 2 * ((2 * n - 1 + 31) // 32)) * 1024 + 128) <= 156 * 1024)
         with torch.cuda.device(g.device):
             if one_pass:
@@ -266,7 +262,7 @@ class McepNewtonStepsHFn(torch.autograd.Function):
 def mcep_newton_steps_grad_applies(M1, D, E, av):
     """McepNewtonStepsHFn takes the analysis: orders 32 .. 54, float32 tables without a gradient of their own
     (DSA_MCEP_GRAD_H=0: the composed path, for A/B runs)."""
-    return (33 <= M1 <= 55 and os.environ.get("DSA_MCEP_GRAD_H", "1") != "0" and D.dtype == torch.float32 and E.dtype == torch.float32
+    return (33 <= M1 <= 55 and _lib.env_int("DSA_MCEP_GRAD_H", 1) != 0 and D.dtype == torch.float32 and E.dtype == torch.float32
             and av.dtype == torch.float32 and not (D.requires_grad or E.requires_grad or av.requires_grad)
             and D.device.type == "cuda" and _lib.load().dsa_mcep_resid_bwd_images_bytes(D.size(1), D.size(0)) > 0
             and _lib.load().dsa_mcep_resid_images_bytes(D.size(1), D.size(0)) > 0)
@@ -284,14 +280,14 @@ def mcep_newton_resid_h(logx, mc, images):
 
 def mcep_newton_steps_applies(M1: int) -> bool:
     """dsa_mcep_newton_steps has an instantiation for this order (32 .. 54, among them the 48 kHz set-ups fft_length 2048 / order 49
-    and 1024 / order 34; DSA_MCEP_BIG=0: the two-launch step, for A/B runs)."""
-    return 33 <= M1 <= 55 and os.environ.get("DSA_MCEP_BIG", "1") != "0"
+    and 1024 / order 34).  DSA_MCEP_BIG=0 (the two-launch step, for A/B runs) is the library's to read: the entry then refuses."""
+    return 33 <= M1 <= 55
 
 
 def mcep_newton_steps(logx, mc0, images, av, n_iter):
     """ALL n_iter Newton steps of mcep.py:208-222 in ONE persistent launch (dsa_mcep_newton_steps, csrc/mcep_big_f16.h): per step the
     products of mcep_newton_resid_h and the solve-and-update of mcep_newton_update, rt and mc staying on chip; forward only.
-    None: the library has no instantiation for this order after all (the caller runs the two launches per step)."""
+    None: the library has no instantiation for this order after all, or DSA_MCEP_BIG=0 (the caller runs the two launches per step)."""
     n, K = mc0.size(-1), logx.size(-1)
     mcc = mc0.contiguous()
     out = torch.empty_like(mcc)
@@ -323,10 +319,10 @@ def _mcep_composed_fwd(Xc, G, D, E, av, M, n_iter):
     else:
         logx = RowsLogFn.apply(X2)                                        # kept: every step's epilogue reads it
         mc = rows_gemm(logx, G)
-    one_launch_resid = os.environ.get("DSA_MCEP_RESID", "1") != "0" and Xc.size(-1) >= 4
+    one_launch_resid = _lib.env_int("DSA_MCEP_RESID", 1) != 0 and Xc.size(-1) >= 4
     # round 5: the step's two products as binary16 splits (DSA_MCEP_RESID_H=0: the float32 matrix instructions of round 4, for A/B runs)
     images_h = None
-    if not want_grad and 3 <= M1 <= 55 and one_launch_resid and os.environ.get("DSA_MCEP_RESID_H", "1") != "0" \
+    if not want_grad and 3 <= M1 <= 55 and one_launch_resid and _lib.env_int("DSA_MCEP_RESID_H", 1) != 0 \
             and D.dtype == torch.float32 and E.dtype == torch.float32:
         images_h = mcep_resid_images(D, E)
     if images_h is not None and n_iter >= 1 and mcep_newton_steps_applies(M1) and av.dtype == torch.float32:
@@ -367,9 +363,7 @@ MCEP_HIST_RT_MAX_BYTES = 4 << 30
 
 
 def _keep_rt_rows(n_iter, F, M, like):
-    if os.environ.get("DSA_MCEP_HIST_RT", "1") == "0":
-        return False
-    return n_iter * F * (2 * M + 1) * like.element_size() <= MCEP_HIST_RT_MAX_BYTES
+    return _lib.env_int("DSA_MCEP_HIST_RT", 1) != 0 and n_iter * F * (2 * M + 1) * like.element_size() <= MCEP_HIST_RT_MAX_BYTES
 
 
 def _mcep_history(n_iter, F, M, like, with_rt):

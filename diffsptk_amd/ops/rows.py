@@ -1,8 +1,6 @@
 """Row products and the element-wise ends of the untuned mel-cepstral step: csrc/rows_gemm.hip, dsa_freqt_* of csrc/mcep.hip."""
 from __future__ import annotations
 
-import os
-
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -32,10 +30,8 @@ def _row_product_is_long(Lin, Lout, elt) -> bool:
     range -- the 1025-bin products of the 48 kHz set-ups.  Those run on the general matrix-core row product (rows_gemm).  The
     choice is a function of the GEOMETRY only (never of the number of rows): a frame's result does not depend on how many frames
     share its batch (tests/test_gpu_parity.py::test_row_products_are_batch_invariant)."""
-    if os.environ.get("DSA_FREQT_GEMM", "1") == "0":
-        return False
     lds_fits = elt * (Lin * Lout + 64 * (Lin + 1)) <= 48 * 1024
-    return not lds_fits and max(Lin, Lout) >= 512
+    return _lib.env_int("DSA_FREQT_GEMM", 1) != 0 and not lds_fits and max(Lin, Lout) >= 512
 
 
 class MatmulRowsFn(torch.autograd.Function):

@@ -293,17 +293,17 @@ CEILINGS = [
             outside=per(B32_64(3841, 1921), lambda dt, L: raises("frame_window_lpc: frame too long for LDS", shape("fwlpc", "fwd", dt, L=L, **FW)))
             + per(B32_64(3841, 1921), lambda dt, L: runs("levdur_fwd", case("fuse_fwlpc", "fwd", dt, L=L, **FW)))),
     # ---- csrc/spec.hip.  The direct row DFT keeps the row: sizeof(T) L <= 60 KB (fft_length 30: not a power of two)
-    ceiling("csrc/spec.hip:658", E_ROW,
+    ceiling("csrc/spec.hip:655", E_ROW,
             inside=per(B32_64(15360, 7680), lambda dt, L: ("row_dft_generic", case("fftr", "fwd", dt, len_in=L, nfft=30, fmt=0, F=1))),
             outside=per(B32_64(15361, 7681), lambda dt, L: raises(E_ROW, shape("fftr", "fwd", dt, len_in=L, nfft=30, fmt=0, F=1)))),
     # its backward keeps 3 (fft_length / 2 + 1) values more: 48 samples sooner at fft_length 30 (a forward and no gradient between)
-    ceiling("csrc/spec.hip:894", E_ROWB,
+    ceiling("csrc/spec.hip:888", E_ROWB,
             inside=per(B32_64(15312, 7632), lambda dt, L: ("row_dft_bwd_generic", case("fftr", "bwd", dt, wrt=("x",), len_in=L, nfft=30, fmt=0, F=1))),
             outside=per(B32_64(15313, 7633), lambda dt, L: raises(E_ROWB, shape("fftr", "bwd", dt, wrt=("x",), len_in=L, nfft=30, fmt=0, F=1)))),
     # the FFT in LDS: sizeof(T) (L + 2 fft_length) <= 150 KB, with the raised LDS attribute.  At fft_length 4096 the row past it is
     # too long for the direct sum as well; float64 at 8192 (float32 at 16384) falls back to the direct sum 1 sample later, under the
     # other route name; a float64 row of 8192 samples at fft_length 8192 fits neither
-    ceiling("csrc/spec.hip:648", "reshapes: the direct sum instead of the FFT in LDS, or " + E_ROW,
+    ceiling("csrc/spec.hip:645", "reshapes: the direct sum instead of the FFT in LDS, or " + E_ROW,
             inside=per(B32_64(30208, 11008), lambda dt, L: ("row_fft_generic", case("fftr", "fwd", dt, len_in=L, nfft=4096, fmt=0, F=1)))
             + [("row_fft_generic", case("fftr", "fwd", F64, len_in=2816, nfft=8192, fmt=0, F=1)),
                ("row_fft_generic", case("fftr", "fwd", F32, len_in=5632, nfft=16384, fmt=0, F=1))],
@@ -313,13 +313,13 @@ CEILINGS = [
                raises(E_ROW, shape("fftr", "fwd", F64, len_in=8192, nfft=8192, fmt=0, F=1))]),
     # its backward: sizeof(T) (L + 3 (fft_length / 2 + 1) + 2 fft_length) <= 150 KB, and the direct sum has no room either.  From
     # fft_length 8192 (float64) and 16384 (float32) on no row has a gradient at all, where the forward runs
-    ceiling("csrc/spec.hip:884", "reshapes: the direct sum instead of the FFT in LDS, or " + E_ROWB,
+    ceiling("csrc/spec.hip:878", "reshapes: the direct sum instead of the FFT in LDS, or " + E_ROWB,
             inside=per(B32_64(24061, 4861), lambda dt, L: ("row_fft_bwd_generic", case("fftr", "bwd", dt, wrt=("x",), len_in=L, nfft=4096, fmt=0, F=1))),
             outside=per(B32_64(24062, 4862), lambda dt, L: raises(E_ROWB, shape("fftr", "bwd", dt, wrt=("x",), len_in=L, nfft=4096, fmt=0, F=1)))
             + per(B32_64(16384, 8192), lambda dt, n: raises(E_ROWB, shape("fftr", "bwd", dt, wrt=("x",), len_in=16, nfft=n, fmt=0, F=1)))),
     # spec_ratio_bwd: sizeof(T) (lb + la + 5 (fft_length / 2 + 1)) <= 60 KB; the forward (two row transforms and spec_ratio) has the
     # row transform's ceilings only
-    ceiling("csrc/spec.hip:981", "spec_bwd: rows too long for LDS",
+    ceiling("csrc/spec.hip:975", "spec_bwd: rows too long for LDS",
             inside=per(B32_64(6138, 3066), lambda dt, n: ("spec_ratio_bwd", case("spec", "bwd", dt, wrt=("b", "a"), nfft=n, **SR))),
             outside=per(B32_64(6140, 3068), lambda dt, n: raises("spec_bwd: rows too long for LDS", shape("spec", "bwd", dt, wrt=("b", "a"), nfft=n, **SR)))),
     # ---- csrc/fftcep.hip: more than 512 bins are refused in both dtypes and for every n_iter (float32 with n_iter = 0 has left the
@@ -330,14 +330,14 @@ CEILINGS = [
             outside=[raises("fftcep: fft_length above 1022 is not supported", shape("fftcep", "fwd", BOTH, nfft=1024, **a)) for a in (FC0, FC2)]),
     # ---- csrc/fbank.hip.  The generic kernels: 4 waves' tiles of 4 frames and the channel ranges in 150 KB --
     # 16 sizeof(T) K + 8 C forward, (16 sizeof(T) + 8) (K + C) backward (a forward and no gradient between)
-    ceiling("csrc/fbank.hip:583", E_FB,
+    ceiling("csrc/fbank.hip:576", E_FB,
             inside=per(B32_64(4778, 2388), lambda dt, n: ("fbank_fwd", case("fbank", "fwd", dt, nfft=n, **FB)))
             + per(B32_64(4104, 2096), lambda dt, n: ("fbank_bwd", case("fbank", "bwd", dt, wrt=("x",), nfft=n, **FB))),
             outside=per(B32_64(4780, 2390), lambda dt, n: raises(E_FB, shape("fbank", "fwd", dt, nfft=n, **FB)))
             + per(B32_64(4106, 2098), lambda dt, n: raises(E_FB, shape("fbank", "bwd", dt, wrt=("x",), nfft=n, **FB)))),
     # the filter matrix joins them in LDS while sizeof(T) K C more fits, else it stays in global memory (<T, false>: up to 16 waves
     # of tiles, above 64 KB at the ordinary fft_length 1024 / 80 channels with 64 frames)
-    ceiling("csrc/fbank.hip:584", "reshapes: the filter matrix stays in global memory",
+    ceiling("csrc/fbank.hip:577", "reshapes: the filter matrix stays in global memory",
             inside=per(B32_64(794, 396), lambda dt, n: ("fbank_fwd", case("fbank", "fwd", dt, nfft=n, **FB)))
             + per(B32_64(752, 364), lambda dt, n: ("fbank_bwd", case("fbank", "bwd", dt, wrt=("x",), nfft=n, **FB))),
             outside=per(B32_64(796, 398), lambda dt, n: runs("fbank_fwd", case("fbank", "fwd", dt, nfft=n, **FB)))
@@ -345,11 +345,11 @@ CEILINGS = [
             + [runs("fbank_fwd", case("fbank", "fwd", F32, nfft=1024, C=80, use_power=False, gamma=0.0, F=64)),
                runs("fbank_bwd", case("fbank", "bwd", F32, wrt=("x",), nfft=1024, C=80, use_power=False, gamma=0.0, F=64))]),
     # the matrix-core launcher takes float32 up to 320 bins and 48 channels (its LDS: 163 392 of 163 840 B at 320)
-    ceiling("csrc/fbank.hip:632", "reshapes: the generic kernel instead of the matrix-core kernel",
+    ceiling("csrc/fbank.hip:625", "reshapes: the generic kernel instead of the matrix-core kernel",
             inside=[("fbank_mfma_fwd", case("fbank", "fwd", F32, nfft=638, C=12, use_power=False, gamma=0.0, F=5, **FBM))],
             outside=[runs("fbank_fwd", case("fbank", "fwd", F32, nfft=640, C=12, use_power=False, gamma=0.0, F=5))]),
     # MFCC: the second product costs the fused launch 3 KB more, so it ends at 309 bins; to 320 bins the two launches run
-    ceiling("csrc/fbank.hip:659", "reshapes: the filter bank and the DCT as two launches instead of one",
+    ceiling("csrc/fbank.hip:652", "reshapes: the filter bank and the DCT as two launches instead of one",
             inside=[("fbank_dct_mfma_fwd", case("mfcc", "fwd", F32, nfft=616, C=40, M=12, F=7, **MFCC))],
             outside=[runs("freqt_lds_fwd", case("mfcc", "fwd", F32, nfft=618, C=40, M=12, F=7, **MFCC))]),
     # ---- csrc/plp.hip
@@ -577,9 +577,9 @@ FORWARDED = {
     "parcor_row_lpc2par_fwd": "csrc/parcor.hip:31", "parcor_row_lpc2par_bwd": "csrc/parcor.hip:31", "parcor_row_par2lpc_fwd": "csrc/parcor.hip:31",
     "parcor_row_par2lpc_bwd": "csrc/parcor.hip:32", "parcor_row_lpccheck_fwd": "csrc/parcor.hip:32", "parcor_row_lpccheck_bwd": "csrc/parcor.hip:32",
     "mlsacheck_generic_fwd": "csrc/mlsacheck.hip:449", "mlsacheck_generic_bwd": "csrc/mlsacheck.hip:449",
-    "fbank_mfma_fwd": "csrc/fbank.hip:570", "fbank_dct_mfma_fwd": "csrc/fbank.hip:661", "freqt_mfma_fwd": "csrc/mcep.hip:359",
-    "fftcep_mfma_fwd": "csrc/fftcep.hip:388",
-    "frame_window_lpc24_mfma_fwd": "csrc/lpc24.hip:375", "frame_window_lpc24_bwd_mfma": "csrc/lpc24_bwd.hip:685",
+    "fbank_mfma_fwd": "csrc/fbank.hip:563", "fbank_dct_mfma_fwd": "csrc/fbank.hip:654", "freqt_mfma_fwd": "csrc/mcep.hip:356",
+    "fftcep_mfma_fwd": "csrc/fftcep.hip:383",
+    "frame_window_lpc24_mfma_fwd": "csrc/lpc24.hip:374", "frame_window_lpc24_bwd_mfma": "csrc/lpc24_bwd.hip:685",
 }
 
 EXEMPT = {
