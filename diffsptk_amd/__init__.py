@@ -25,6 +25,8 @@ from .modules.delta import Delta
 from .modules.dtw import DynamicTimeWarping
 from .modules.dtw import DynamicTimeWarping as DTW
 from .modules.excite import ExcitationGeneration
+from .modules.gmm import GaussianMixtureModeling
+from .modules.gmm import GaussianMixtureModeling as GMM
 from .modules.imdct import InverseModifiedDiscreteCosineTransform, InverseModifiedDiscreteSineTransform, InverseModifiedDiscreteTransform
 from .modules.imdct import InverseModifiedDiscreteCosineTransform as IMDCT
 from .modules.imdct import InverseModifiedDiscreteSineTransform as IMDST
@@ -42,4 +44,4 @@ __version__ = "0.1.0"
 __all__ = [*_module_names, "functional", "get_alpha", "read", "write", "Graphed", "MLSADigitalFilterStabilityCheck",
            "ExcitationGeneration", "mseq", "mseq_like", "nrand", "MDCT", "IMDCT", "MDST", "IMDST", "ModifiedDiscreteCosineTransform",
            "InverseModifiedDiscreteCosineTransform", "ModifiedDiscreteSineTransform", "InverseModifiedDiscreteSineTransform", "Delta", "MLPG",
-           "MaximumLikelihoodParameterGeneration", "MelCepstrumPostfiltering", "DynamicTimeWarping", "DTW"]
+           "MaximumLikelihoodParameterGeneration", "MelCepstrumPostfiltering", "DynamicTimeWarping", "DTW", "GaussianMixtureModeling", "GMM"]

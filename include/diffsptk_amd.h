@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define DSA_VERSION 140 /* 0.3.4: + dsa_dtw / dsa_dtw_vjp / dsa_dtw_path (dynamic time warping with a soft minimum: the aligned distance of two vector sequences by an anti-diagonal wavefront, its gradient by the reverse sweep, the Viterbi path from the saved tables); 0.3.3: + DSA_ALGO_FIXED_STEPS (the tuned mel-cepstral forward stops a frame's Newton iteration once its update is rounding noise; the flag runs every step); 0.3.2: + dsa_delta / dsa_delta_vjp, dsa_mlpg, dsa_mcpf / dsa_mcpf_vjp (parameter generation: delta features, maximum likelihood parameter generation by a banded Cholesky solve, mel-cepstrum postfiltering in closed form); 0.3.1: + dsa_mdct_analysis / dsa_mdct_synthesis (MDCT / MDST and their inverses: window, fold, DCT-IV through a quarter-length complex FFT and overlap-add in one launch each way; each is the other's adjoint); 0.3.0: + dsa_excite (pitch to excitation: the voiced shapes of ExcitationGeneration on a segmented float64 phase sum, one launch); 0.2.9: + dsa_mlsacheck / dsa_mlsacheck_vjp (the stability check of the MLSA filter: the mel-cepstrum scaled or clipped where the amplitude of its gain-free part passes the threshold of the Pade approximation, forward and adjoint); 0.2.8: + dsa_lpc2lsp_fwd / _bwd, dsa_lsp2lpc_fwd / _bwd, dsa_lspcheck_fwd / _bwd (line spectral pairs by a Chebyshev-series root search, back by a product of real sections, and their stability check, forward and adjoint); 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
+#define DSA_VERSION 141 /* 0.3.5: + dsa_gmm_prepare / dsa_gmm_estep / dsa_gmm_accum / dsa_gmm_update / dsa_gmm_regress / dsa_gmm_transform (Gaussian mixture models: one EM iteration as factorisation, E-step, weighted moment sums and M-step on the device, and the conversion of a joint-density model); 0.3.4: + dsa_dtw / dsa_dtw_vjp / dsa_dtw_path (dynamic time warping with a soft minimum: the aligned distance of two vector sequences by an anti-diagonal wavefront, its gradient by the reverse sweep, the Viterbi path from the saved tables); 0.3.3: + DSA_ALGO_FIXED_STEPS (the tuned mel-cepstral forward stops a frame's Newton iteration once its update is rounding noise; the flag runs every step); 0.3.2: + dsa_delta / dsa_delta_vjp, dsa_mlpg, dsa_mcpf / dsa_mcpf_vjp (parameter generation: delta features, maximum likelihood parameter generation by a banded Cholesky solve, mel-cepstrum postfiltering in closed form); 0.3.1: + dsa_mdct_analysis / dsa_mdct_synthesis (MDCT / MDST and their inverses: window, fold, DCT-IV through a quarter-length complex FFT and overlap-add in one launch each way; each is the other's adjoint); 0.3.0: + dsa_excite (pitch to excitation: the voiced shapes of ExcitationGeneration on a segmented float64 phase sum, one launch); 0.2.9: + dsa_mlsacheck / dsa_mlsacheck_vjp (the stability check of the MLSA filter: the mel-cepstrum scaled or clipped where the amplitude of its gain-free part passes the threshold of the Pade approximation, forward and adjoint); 0.2.8: + dsa_lpc2lsp_fwd / _bwd, dsa_lsp2lpc_fwd / _bwd, dsa_lspcheck_fwd / _bwd (line spectral pairs by a Chebyshev-series root search, back by a product of real sections, and their stability check, forward and adjoint); 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
 
 typedef enum {
     DSA_OK = 0,
@@ -882,6 +882,54 @@ int dsa_dtw_vjp(const void* x, const void* y, const void* lengths, const void* R
                 int64_t T2, int64_t D, int32_t metric, int32_t p, double softness, int32_t dtype, void* gx, void* gy, void* stream);
 int dsa_dtw_path(const void* x, const void* y, const void* lengths, const void* R, const void* R2, int64_t B, int64_t T1, int64_t T2, int64_t D,
                  int32_t metric, int32_t p, int32_t dtype, void* indices, void* count, void* stream);
+
+/* ------------------------------------------------------------------ a21  Gaussian mixture models: gmm (0.3.5)
+ * GaussianMixtureModeling.forward / _e_step / transform, gmm.py:241-486.  K components of dimension L; w:(K), mu:(K,L), sigma:(K,L,L),
+ * x:(T,L') of the dtype, L' <= L the leading block an entry works on (L' = L while training; L' = N + 1 in transform: the pointers stay,
+ * the leading dimension L tells the rows apart, nothing is copied).  diag != 0 is the route of var_type "diag" with one block: only the
+ * diagonal of sigma is read and written.  float32 and float64, int64 indexing, no floating-point atomics: every sum has one fixed
+ * order, two runs give the same bits.  The library owns no device memory; the caller passes every workspace.
+ *   dsa_gmm_prepare   prec:(K,L',L') the inverse W_k of the Cholesky factor of sigma_k's leading block (zero above the diagonal), or on the
+ *                     diagonal route prec:(K,L') the reciprocal variances; cst:(K) c_k = log w_k - (L' log 2 pi + log det) / 2; failed:(K)
+ *                     int32, 1 where a pivot was not positive (then W_k = 0 and c_k = -inf), else 0.  The diagonal route never fails: a
+ *                     variance that is not positive gives the reference's inf / NaN.
+ *   dsa_gmm_estep     posterior:(T,K) exp(numer - logsumexp_k numer), numer[t,k] = c_k - |W_k (x_t - mu_k)|^2 / 2 (diagonal route: the
+ *                     weighted squares); loglik:(T) the log-sum-exp, maximum first as torch.logsumexp; partial: ceil(T / rows) float64
+ *                     per-workgroup sums, rows = DSA_GMM_TILE_BYTES / sizeof(dtype) vectors per workgroup; total (1 of the dtype, or NULL)
+ *                     their sum; readback (2 float64, or NULL): the total and the first k + 1 with failed[k], 0 when none -- what the
+ *                     host reads once per iteration.  Both NULL: no second launch.
+ *   dsa_gmm_accum     the weighted moment sums into workspace (dsa_gmm_accum_workspace_bytes: S K (L + 1)^2 elements, on the diagonal
+ *                     route S K (2 L + 1); S <= 64 segments of T of at least 256 vectors, and S > 1 only while S times the waves of one
+ *                     segment stay below 8192: at most 8192 32 x 32 tiles of the dtype, 64 MiB; 15 MiB at K = 64, L = 50, float32).  Segment s, component k: the lower triangle, by 32 x 32
+ *                     tiles, of sum_t p[t,k] a a^T, a = [x_t, 1] -- row L is px, the corner z; diagonal route: px (L), z, pxx (L).
+ *   dsa_gmm_update    gmm.py:303-378 from the partial sums, added in segment order: w (z / T or (z + alpha ubm_w) / (T + alpha), floored,
+ *                     renormalised a w + b), mu, sigma (MAP when alpha != 0, with nan_to_num on the data term; times mask:(L,L); the
+ *                     diagonal floored at var_floor), written in place.  readback != NULL and readback[1] != 0: nothing is written.
+ *   dsa_gmm_regress   M:(K, L - Lx, Lx) = sigma[:, Lx:, :Lx] inverse(sigma[:, :Lx, :Lx]) by Gauss-Jordan elimination with partial
+ *                     pivoting; a singular block gives inf / NaN, not an error.
+ *   dsa_gmm_transform indices:(T) int64 the first largest posterior; y:(T, L - Lx) = mu[k, Lx:] + M_k (x_t - mu[k, :Lx]), or y = NULL.
+ * dsa_last_kernel(): "gmm_prepare_full_f32", "gmm_prepare_diag_f32", "gmm_estep_*", "gmm_accum_*", "gmm_update_*" likewise,
+ * "gmm_regress_f32", "gmm_transform_f32", and the same with f64.
+ * DSA_ERR_INVALID_ARGUMENT with a message that names "gmm": a size below 1, L' > L, sizes beyond int64, an unknown dtype, a missing
+ * pointer, options outside their ranges, and 2 DSA_GMM_TILE_BYTES (L + 1) + L (L + 1) sizeof(dtype) + 64 > DSA_GMM_MAX_LDS_BYTES: the
+ * E-step's workgroup holds its vectors, their differences, one component's matrix and mean and its reduction scratch in LDS
+ * (float32: L <= 69, float64: L <= 63; L is L' for prepare, estep, regress and transform). */
+#define DSA_GMM_MAX_LDS_BYTES 163840
+#define DSA_GMM_TILE_BYTES 1024
+int dsa_gmm_prepare(const void* w, const void* sigma, int64_t K, int64_t L, int64_t Lp, int32_t diag, int32_t dtype, void* prec, void* cst,
+                    void* failed, void* stream);
+int dsa_gmm_estep(const void* x, const void* mu, const void* prec, const void* cst, const void* failed, int64_t T, int64_t K, int64_t L,
+                  int64_t Lp, int32_t diag, int32_t dtype, void* posterior, void* loglik, void* partial, void* total, void* readback,
+                  void* stream);
+int64_t dsa_gmm_accum_workspace_bytes(int64_t T, int64_t K, int64_t L, int32_t diag, int32_t dtype);
+int dsa_gmm_accum(const void* x, const void* posterior, int64_t T, int64_t K, int64_t L, int32_t diag, int32_t dtype, void* workspace,
+                  void* stream);
+int dsa_gmm_update(const void* workspace, const void* readback, const void* ubm_w, const void* ubm_mu, const void* ubm_sigma, const void* mask,
+                   int64_t T, int64_t K, int64_t L, int32_t diag, double alpha, double weight_floor, double var_floor, int32_t dtype, void* w,
+                   void* mu, void* sigma, void* stream);
+int dsa_gmm_regress(const void* sigma, int64_t K, int64_t L, int64_t Lx, int32_t dtype, void* M, void* stream);
+int dsa_gmm_transform(const void* x, const void* posterior, const void* mu, const void* M, int64_t T, int64_t K, int64_t L, int64_t Lx,
+                      int32_t dtype, void* indices, void* y, void* stream);
 
 #ifdef __cplusplus
 }
