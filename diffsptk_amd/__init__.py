@@ -37,6 +37,7 @@ from .modules.mcpf import MelCepstrumPostfiltering
 from .modules.mlpg import MaximumLikelihoodParameterGeneration
 from .modules.mlpg import MaximumLikelihoodParameterGeneration as MLPG
 from .modules.mlsacheck import MLSADigitalFilterStabilityCheck
+from .modules.yingram import Yingram
 from .signals import mseq, mseq_like, nrand
 from .utils.public import get_alpha, read, write
 
@@ -44,4 +45,4 @@ __version__ = "0.1.0"
 __all__ = [*_module_names, "functional", "get_alpha", "read", "write", "Graphed", "MLSADigitalFilterStabilityCheck",
            "ExcitationGeneration", "mseq", "mseq_like", "nrand", "MDCT", "IMDCT", "MDST", "IMDST", "ModifiedDiscreteCosineTransform",
            "InverseModifiedDiscreteCosineTransform", "ModifiedDiscreteSineTransform", "InverseModifiedDiscreteSineTransform", "Delta", "MLPG",
-           "MaximumLikelihoodParameterGeneration", "MelCepstrumPostfiltering", "DynamicTimeWarping", "DTW", "GaussianMixtureModeling", "GMM"]
+           "MaximumLikelihoodParameterGeneration", "MelCepstrumPostfiltering", "DynamicTimeWarping", "DTW", "GaussianMixtureModeling", "GMM", "Yingram"]

@@ -15,6 +15,7 @@ from .modules.delta import Delta
 from .modules.dtw import DynamicTimeWarping
 from .modules.mcpf import MelCepstrumPostfiltering
 from .modules.mlpg import MaximumLikelihoodParameterGeneration
+from .modules.yingram import Yingram
 
 
 def acorr(x: Tensor, acr_order: int, out_format: str | int = "naive") -> Tensor:
@@ -332,3 +333,8 @@ def dtw(x: Tensor, y: Tensor, lengths: Tensor | None = None, return_indices: boo
 def dtw_merge(x: Tensor, y: Tensor, indices: Tensor) -> Tensor:
     """The frames of x:(T1, D) and y:(T2, D) along a Viterbi path indices:(T, 2) -> (T, 2D) (functional.py: dtw_merge)."""
     return DynamicTimeWarping.merge(x=x, y=y, indices=indices)
+
+
+def yingram(x: Tensor, sample_rate: int = 22050, lag_min: int = 22, lag_max: int | None = None, n_bin: int = 20) -> Tensor:
+    """The Yingram of framed waveforms x:(..., L) -> (..., M) (functional.py: yingram)."""
+    return Yingram._func(x, sample_rate=sample_rate, lag_min=lag_min, lag_max=lag_max, n_bin=n_bin)

@@ -21,8 +21,10 @@ from .mcep import MelCepstralAnalysis
 from .mfcc import MelFrequencyCepstralCoefficientsAnalysis
 from .plp import PerceptualLinearPredictiveCoefficientsAnalysis
 from .pqmf import PseudoQuadratureMirrorFilterBankAnalysis, PseudoQuadratureMirrorFilterBankSynthesis
+from .spec import device_twiddle
 from .stft import ShortTimeFourierTransform
 from .window import Window
+from .yingram import Yingram
 
 _SPEC_POWER, _FFT, _FRAME = 3, 512, 400
 
@@ -216,6 +218,31 @@ class FusedInterpolationIPQMF(nn.Module):
         return q(i(y), keepdim=keepdim)
 
 
+class FusedFrameYingram(nn.Module):
+    """``yingram(frame(x))`` as ONE launch (dsa_frame_yingram, csrc/yingram.hip): the forward kernel of Yingram with a loader that
+    frames the waveform on the fly, so the (B N, L) frames -- L / P times the waveform -- never exist; the values are the module
+    chain's, bit for bit.  The backward frames x again and runs the two modules' own (dsa_yingram_vjp, dsa_frame_bwd).  A Frame with
+    zmean or a padding mode other than "constant" runs the two modules unchanged.  ``last_path``: "fused" / "two-stage"."""
+
+    def __init__(self, frame: Frame, yingram: Yingram) -> None:
+        super().__init__()
+        if frame.frame_length != yingram.in_dim:
+            raise ValueError("frame and yingram disagree on frame_length.")
+        self.frame, self.yingram = frame, yingram
+        self.last_path = None
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        f, yg = self.frame, self.yingram
+        if x.is_cuda and x.dim() >= 1 and x.size(-1) >= 1 and not f.zmean and f.mode == "constant":
+            self.last_path = "fused"
+            lag_max = len(yg.ramp) + 1
+            twiddle = device_twiddle(ops.yingram_fft_length(f.frame_length, lag_max), x.device, x.dtype)
+            return ops.FrameYingramFn.apply(x, yg.lags, yg.lags_floor, yg.lags_ceil, twiddle, f.frame_length, f.frame_period, f.center,
+                                            lag_max, yg.algo)
+        self.last_path = "two-stage"
+        return yg(f(x))
+
+
 def fuse(first: nn.Module, *rest: nn.Module, **options) -> nn.Module:
     """One launch where a fused kernel applies, the modules themselves elsewhere:
 
@@ -223,7 +250,12 @@ def fuse(first: nn.Module, *rest: nn.Module, **options) -> nn.Module:
       MelFilterBankAnalysis, a MelFrequencyCepstralCoefficientsAnalysis or a PerceptualLinearPredictiveCoefficientsAnalysis;
     * ``fuse(frame, window, lpc)(x) == lpc(window(frame(x)))`` -- the LPC branch, forward and backward;
     * ``fuse(pqmf, decimate)(x) == decimate(pqmf(x))`` and ``fuse(interpolate, ipqmf)(y) == ipqmf(interpolate(y))`` -- the
-      subband analysis and synthesis, forward and backward."""
+      subband analysis and synthesis, forward and backward;
+    * ``fuse(frame, yingram)(x) == yingram(frame(x))`` -- the pitch feature from the waveform, the frames never in memory."""
+    if isinstance(first, Frame) and len(rest) == 1 and isinstance(rest[0], Yingram):
+        if options:
+            raise ValueError("fuse(frame, yingram) takes a Frame and a Yingram, and no options.")
+        return FusedFrameYingram(first, rest[0])
     if isinstance(first, PseudoQuadratureMirrorFilterBankAnalysis):
         if len(rest) != 1 or options:
             raise ValueError("fuse(pqmf, decimate) takes a PseudoQuadratureMirrorFilterBankAnalysis and a Decimation.")

@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define DSA_VERSION 141 /* 0.3.5: + dsa_gmm_prepare / dsa_gmm_estep / dsa_gmm_accum / dsa_gmm_update / dsa_gmm_regress / dsa_gmm_transform (Gaussian mixture models: one EM iteration as factorisation, E-step, weighted moment sums and M-step on the device, and the conversion of a joint-density model); 0.3.4: + dsa_dtw / dsa_dtw_vjp / dsa_dtw_path (dynamic time warping with a soft minimum: the aligned distance of two vector sequences by an anti-diagonal wavefront, its gradient by the reverse sweep, the Viterbi path from the saved tables); 0.3.3: + DSA_ALGO_FIXED_STEPS (the tuned mel-cepstral forward stops a frame's Newton iteration once its update is rounding noise; the flag runs every step); 0.3.2: + dsa_delta / dsa_delta_vjp, dsa_mlpg, dsa_mcpf / dsa_mcpf_vjp (parameter generation: delta features, maximum likelihood parameter generation by a banded Cholesky solve, mel-cepstrum postfiltering in closed form); 0.3.1: + dsa_mdct_analysis / dsa_mdct_synthesis (MDCT / MDST and their inverses: window, fold, DCT-IV through a quarter-length complex FFT and overlap-add in one launch each way; each is the other's adjoint); 0.3.0: + dsa_excite (pitch to excitation: the voiced shapes of ExcitationGeneration on a segmented float64 phase sum, one launch); 0.2.9: + dsa_mlsacheck / dsa_mlsacheck_vjp (the stability check of the MLSA filter: the mel-cepstrum scaled or clipped where the amplitude of its gain-free part passes the threshold of the Pade approximation, forward and adjoint); 0.2.8: + dsa_lpc2lsp_fwd / _bwd, dsa_lsp2lpc_fwd / _bwd, dsa_lspcheck_fwd / _bwd (line spectral pairs by a Chebyshev-series root search, back by a product of real sections, and their stability check, forward and adjoint); 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
+#define DSA_VERSION 142 /* 0.3.6: + dsa_yingram / dsa_yingram_vjp / dsa_frame_yingram (Yingram: YIN's cumulative-mean-normalised difference function on a semitone grid, from frames or from the waveform in one launch, and its adjoint; lag sums directly or through the LDS transform); 0.3.5: + dsa_gmm_prepare / dsa_gmm_estep / dsa_gmm_accum / dsa_gmm_update / dsa_gmm_regress / dsa_gmm_transform (Gaussian mixture models: one EM iteration as factorisation, E-step, weighted moment sums and M-step on the device, and the conversion of a joint-density model); 0.3.4: + dsa_dtw / dsa_dtw_vjp / dsa_dtw_path (dynamic time warping with a soft minimum: the aligned distance of two vector sequences by an anti-diagonal wavefront, its gradient by the reverse sweep, the Viterbi path from the saved tables); 0.3.3: + DSA_ALGO_FIXED_STEPS (the tuned mel-cepstral forward stops a frame's Newton iteration once its update is rounding noise; the flag runs every step); 0.3.2: + dsa_delta / dsa_delta_vjp, dsa_mlpg, dsa_mcpf / dsa_mcpf_vjp (parameter generation: delta features, maximum likelihood parameter generation by a banded Cholesky solve, mel-cepstrum postfiltering in closed form); 0.3.1: + dsa_mdct_analysis / dsa_mdct_synthesis (MDCT / MDST and their inverses: window, fold, DCT-IV through a quarter-length complex FFT and overlap-add in one launch each way; each is the other's adjoint); 0.3.0: + dsa_excite (pitch to excitation: the voiced shapes of ExcitationGeneration on a segmented float64 phase sum, one launch); 0.2.9: + dsa_mlsacheck / dsa_mlsacheck_vjp (the stability check of the MLSA filter: the mel-cepstrum scaled or clipped where the amplitude of its gain-free part passes the threshold of the Pade approximation, forward and adjoint); 0.2.8: + dsa_lpc2lsp_fwd / _bwd, dsa_lsp2lpc_fwd / _bwd, dsa_lspcheck_fwd / _bwd (line spectral pairs by a Chebyshev-series root search, back by a product of real sections, and their stability check, forward and adjoint); 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
 
 typedef enum {
     DSA_OK = 0,
@@ -930,6 +930,40 @@ int dsa_gmm_update(const void* workspace, const void* readback, const void* ubm_
 int dsa_gmm_regress(const void* sigma, int64_t K, int64_t L, int64_t Lx, int32_t dtype, void* M, void* stream);
 int dsa_gmm_transform(const void* x, const void* posterior, const void* mu, const void* M, int64_t T, int64_t K, int64_t L, int64_t Lx,
                       int32_t dtype, void* indices, void* y, void* stream);
+
+/* ------------------------------------------------------------------ a22  Yingram, the pitch feature of YIN on a semitone grid (0.3.6)
+ * Yingram._forward, yingram.py:167-194.  x:(F,L) frames of the dtype, lag_max = K with 1 <= K < L; the tables of Yingram._precompute,
+ * yingram.py:127-164, as the module holds them: lags:(M) of the dtype, non-increasing, lags_floor, lags_ceil:(M) int64 with
+ * 0 <= floor <= ceil <= K - 1 (the kernels clamp what they index with).  Per frame
+ *   d[tau]  = sum_{j < L - tau} (x[j] - x[j + tau])^2, tau = 1 .. K - 1;   d'[tau] = tau d[tau] / (sum_{k <= tau} d[k] + 1e-7), d'[0] = 1;
+ *   y[m]    = d'[floor_m] + (lags_m - floor_m) (d'[ceil_m] - d'[floor_m]):  where ceil_m = floor_m (an integral lag) y[m] = d'[floor_m].
+ * float32 and float64, int64 indexing, no allocation, no atomics, no host synchronisation; the scans run in float64.  A frame's bits
+ * depend on (L, K, the tables, the route) and its own values, not on F or its place in the batch.  F = 0 or M = 0 is a no-op before any
+ * pointer is looked at.
+ *   dsa_yingram        y:(F,M).  One launch; no (F, K) intermediate in memory.
+ *   dsa_yingram_vjp        gx:(F,L), every element written, for the cotangent gy:(F,M): the adjoint of the three steps, d recomputed.
+ *   dsa_frame_yingram  y:(B,N,M) from the waveform x:(B,T): Frame(L, P, center) with constant padding and zmean = False
+ *                          (frame.py:120-141) read on the fly, then the same arithmetic as dsa_yingram, bit for bit.
+ * algo: DSA_ALGO_GENERIC the direct route (the lag sums as written, each square added in float64; up to four short frames per
+ * workgroup), DSA_ALGO_TUNED the fft route (d from float64 prefix sums of x^2 and the autocorrelation through the LDS transform of
+ * 2 H >= L + K points, H a power of two, real input packed as H complex points; needs twiddle: (cos, -sin)(2 pi m / 2H), m < H, of the
+ * dtype, else NULL), DSA_ALGO_AUTO the fft route from L = DSA_YINGRAM_FFT_MIN_FRAME_LENGTH on.  dsa_last_kernel():
+ * "yingram_direct_f32", "yingram_fft_f32", "yingram_vjp_direct_f32", "yingram_vjp_fft_f32", "frame_yingram_direct_f32",
+ * "frame_yingram_fft_f32" and the same with f64.
+ * DSA_ERR_INVALID_ARGUMENT with a message that names "yingram": a negative size, L < 2, K outside 1 .. L - 1, F beyond int32, an unknown
+ * dtype or algo, a missing pointer, and DSA_YINGRAM_LDS_BYTES(H, L, sizeof(dtype)) > DSA_YINGRAM_MAX_LDS_BYTES at the H of the longest
+ * lag range, 2 H the power of two from 2 L - 1 on: the fft route holds the transform's two arrays, one more of H + 1 values, L + 1
+ * float64 prefix sums and its scan's exchange in LDS (float32: L <= 8174, float64: L <= 4096; the same ceiling on both routes). */
+#define DSA_YINGRAM_MAX_LDS_BYTES 163840
+#define DSA_YINGRAM_LDS_BYTES(H, L, size) ((3 * (H) + 1) * (size) + 8 * ((L) + 1) + 128)
+#define DSA_YINGRAM_FFT_MIN_FRAME_LENGTH 76
+int dsa_yingram(const void* x, int64_t F, int32_t L, int32_t lag_max, const void* lags, const void* lags_floor, const void* lags_ceil,
+                    int32_t M, const void* twiddle, int32_t algo, int32_t dtype, void* y, void* stream);
+int dsa_yingram_vjp(const void* gy, const void* x, int64_t F, int32_t L, int32_t lag_max, const void* lags, const void* lags_floor,
+                    const void* lags_ceil, int32_t M, const void* twiddle, int32_t algo, int32_t dtype, void* gx, void* stream);
+int dsa_frame_yingram(const void* x, int64_t B, int64_t T, int32_t L, int32_t P, int32_t center, int32_t lag_max, const void* lags,
+                          const void* lags_floor, const void* lags_ceil, int32_t M, const void* twiddle, int32_t algo, int32_t dtype, void* y,
+                          void* stream);
 
 #ifdef __cplusplus
 }
