@@ -246,7 +246,7 @@ __global__ __launch_bounds__(kFmWaves * 64) void fbank_mfma_fwd_kernel(const flo
     float* tile = tiles + (size_t)wave * tile_floats;
     const float* arow = tile + i * K;
     const float* arow_kq = arow + (kq << 4);
-    const int klim = K - (kq << 4);   // k-slot kq of an entry is inside the row iff off < klim
+    const int klim = K > (kq << 4) ? K - (kq << 4) : 0;   // k-slot kq is inside the row iff off < klim (unsigned test: never below 0, or a slot past a short row passes)
     const long ntiles = (F + kFmRows - 1) / kFmRows;
     const long stride = (long)gridDim.x * kFmWaves;
     const int n4 = (kFmRows * K) >> 2;  // 16 K floats = 4 K float4
