@@ -27,6 +27,10 @@ from .modules.dtw import DynamicTimeWarping as DTW
 from .modules.excite import ExcitationGeneration
 from .modules.gmm import GaussianMixtureModeling
 from .modules.gmm import GaussianMixtureModeling as GMM
+from .modules.ivq import InverseVectorQuantization
+from .modules.lbg import LindeBuzoGrayAlgorithm
+from .modules.lbg import LindeBuzoGrayAlgorithm as LBG
+from .modules.vq import VectorQuantization
 from .modules.imdct import InverseModifiedDiscreteCosineTransform, InverseModifiedDiscreteSineTransform, InverseModifiedDiscreteTransform
 from .modules.imdct import InverseModifiedDiscreteCosineTransform as IMDCT
 from .modules.imdct import InverseModifiedDiscreteSineTransform as IMDST
@@ -45,4 +49,5 @@ __version__ = "0.1.0"
 __all__ = [*_module_names, "functional", "get_alpha", "read", "write", "Graphed", "MLSADigitalFilterStabilityCheck",
            "ExcitationGeneration", "mseq", "mseq_like", "nrand", "MDCT", "IMDCT", "MDST", "IMDST", "ModifiedDiscreteCosineTransform",
            "InverseModifiedDiscreteCosineTransform", "ModifiedDiscreteSineTransform", "InverseModifiedDiscreteSineTransform", "Delta", "MLPG",
-           "MaximumLikelihoodParameterGeneration", "MelCepstrumPostfiltering", "DynamicTimeWarping", "DTW", "GaussianMixtureModeling", "GMM", "Yingram"]
+           "MaximumLikelihoodParameterGeneration", "MelCepstrumPostfiltering", "DynamicTimeWarping", "DTW", "GaussianMixtureModeling", "GMM", "Yingram",
+           "VectorQuantization", "InverseVectorQuantization", "LindeBuzoGrayAlgorithm", "LBG"]

@@ -15,7 +15,8 @@ What differs from the reference (include/diffsptk_amd.h, section a21; DESIGN.md 
     `_e_step` do not read the status: there such a component has posterior 0 and, if every component fails, the result is NaN;
   * `transform` forms sigma_yx sigma_xx^-1 in a kernel of its own (Gauss-Jordan with partial pivoting on the block as it is), not with
     torch.inverse; a singular block gives inf / NaN instead of an error;
-  * `warmup` raises NotImplementedError: it needs LindeBuzoGrayAlgorithm, which this backend does not have.  Initialise with `set_params`;
+  * `warmup` still raises NotImplementedError; what it computes in the reference -- K-means clustering by LindeBuzoGrayAlgorithm, then
+    weights, means and covariances of the clusters -- is `init_by_lbg(x, **lbg_params)` here, on the device (modules/lbg.py);
   * L is bounded by the E-step's LDS: 2048 (L + 1) + L (L + 1) sizeof(dtype) + 64 <= DSA_GMM_MAX_LDS_BYTES (float32: L <= 69,
     float64: L <= 63).
 
@@ -123,9 +124,25 @@ class GaussianMixtureModeling(nn.Module):
             self.sigma[:] = sigma
 
     def warmup(self, x: torch.Tensor | DataLoader, **lbg_params) -> None:
-        """The reference initialises the model by K-means clustering here (gmm.py:199-239)."""
-        raise NotImplementedError("GaussianMixtureModeling.warmup needs LindeBuzoGrayAlgorithm, which diffsptk_amd does not have: "
-                                  "initialise the model with set_params")
+        """The reference initialises the model by K-means clustering here (gmm.py:199-239); this backend does that in `init_by_lbg`."""
+        raise NotImplementedError("GaussianMixtureModeling.warmup is not implemented: call init_by_lbg(x, **lbg_params), which initialises "
+                                  "the model with LindeBuzoGrayAlgorithm on the device, or set_params")
+
+    @torch.no_grad()
+    def init_by_lbg(self, x: torch.Tensor | DataLoader, **lbg_params) -> None:
+        """x:(T, M+1) of the module's dtype, or a DataLoader: the parameters from K-means clustering, as gmm.py:199-239 computes them --
+        w = count / T, mu = the codebook of LindeBuzoGrayAlgorithm(order, n_mixture, **lbg_params), sigma = (sum of x x^T of the cluster /
+        count - mu mu^T) * mask -- and `set_params`.  A cluster without data gives the reference's 0 / 0."""
+        from .lbg import LindeBuzoGrayAlgorithm
+
+        x = self._gather(x)
+        lbg = LindeBuzoGrayAlgorithm(self.order, self.n_mixture, device=self.w.device, **lbg_params)
+        codebook, indices, _ = lbg(x, return_indices=True)
+        count, kxx = ops.gmm_cluster_moments(x.to(self.w.dtype), indices, self.n_mixture)
+        mm = codebook.unsqueeze(-1) * codebook.unsqueeze(-2)   # (K, L, L), in the codebook's float32 as the reference forms it
+        sigma = (kxx / count.view(-1, 1, 1) - mm) * self.mask
+        w = count / torch.full_like(count, len(indices))   # a true division (by a Python number torch multiplies by the reciprocal)
+        self.set_params((w, codebook, sigma))
 
     def _gather(self, x: torch.Tensor | DataLoader) -> torch.Tensor:
         if isinstance(x, DataLoader):   # the batches on the device, once

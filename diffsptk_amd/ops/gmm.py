@@ -75,6 +75,29 @@ def gmm_em_step(x, w, mu, sigma, mask, ubm, diag, alpha, weight_floor, var_floor
     return total
 
 
+def gmm_cluster_moments(x, indices, K):
+    """(count:(K), kxx:(K, L, L)) of a hard assignment indices:(T) in 0 .. K - 1: the number of vectors of every cluster and the sum of
+    their x x^T (gmm.py:222-233), by dsa_gmm_accum on the one-hot posterior -- K times the work of a direct sum, for a one-off
+    initialisation.  No host read."""
+    if x.dim() != 2 or x.size(0) < 1 or tuple(indices.shape) != (x.size(0),):
+        raise ValueError(f"gmm: x must be (T, L) and indices (T,), got {tuple(x.shape)} and {tuple(indices.shape)}")
+    code = _dtype_code(x)
+    _require_device(x, indices)
+    xc = x.contiguous()
+    T, L = xc.shape
+    post = torch.zeros(T, K, device=xc.device, dtype=xc.dtype).scatter_(1, indices.view(-1, 1), 1)
+    with torch.cuda.device(xc.device):
+        size = _lib.load().dsa_gmm_accum_workspace_bytes(T, K, L, 0, code)
+        if size < 0:
+            _lib.check(_lib.ERR_INVALID_ARGUMENT, "dsa_gmm_accum_workspace_bytes")
+        ws = torch.zeros(size // xc.element_size(), device=xc.device, dtype=xc.dtype)   # (the tiles above the diagonal stay unwritten)
+        _call("dsa_gmm_accum", _p(xc), _p(post), T, K, L, 0, code, _p(ws), _stream())
+    low = torch.tril(ws.view(-1, K, L + 1, L + 1).sum(0))   # the lower triangle of sum [x, 1] [x, 1]^T per cluster
+    full = low + torch.tril(low, -1).transpose(-1, -2)
+    count = torch.bincount(indices, minlength=K).to(xc.dtype)
+    return count, full[:, :L, :L]
+
+
 def gmm_transform(x, post, mu, sigma, Lx):
     """(y:(T, L - Lx) or None, indices:(T) int64): gmm.py:418-432 from the posterior of the leading block.  No host read."""
     xc, pc, mc, sc = x.contiguous(), post.contiguous(), mu.contiguous(), sigma.contiguous()

@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define DSA_VERSION 142 /* 0.3.6: + dsa_yingram / dsa_yingram_vjp / dsa_frame_yingram (Yingram: YIN's cumulative-mean-normalised difference function on a semitone grid, from frames or from the waveform in one launch, and its adjoint; lag sums directly or through the LDS transform); 0.3.5: + dsa_gmm_prepare / dsa_gmm_estep / dsa_gmm_accum / dsa_gmm_update / dsa_gmm_regress / dsa_gmm_transform (Gaussian mixture models: one EM iteration as factorisation, E-step, weighted moment sums and M-step on the device, and the conversion of a joint-density model); 0.3.4: + dsa_dtw / dsa_dtw_vjp / dsa_dtw_path (dynamic time warping with a soft minimum: the aligned distance of two vector sequences by an anti-diagonal wavefront, its gradient by the reverse sweep, the Viterbi path from the saved tables); 0.3.3: + DSA_ALGO_FIXED_STEPS (the tuned mel-cepstral forward stops a frame's Newton iteration once its update is rounding noise; the flag runs every step); 0.3.2: + dsa_delta / dsa_delta_vjp, dsa_mlpg, dsa_mcpf / dsa_mcpf_vjp (parameter generation: delta features, maximum likelihood parameter generation by a banded Cholesky solve, mel-cepstrum postfiltering in closed form); 0.3.1: + dsa_mdct_analysis / dsa_mdct_synthesis (MDCT / MDST and their inverses: window, fold, DCT-IV through a quarter-length complex FFT and overlap-add in one launch each way; each is the other's adjoint); 0.3.0: + dsa_excite (pitch to excitation: the voiced shapes of ExcitationGeneration on a segmented float64 phase sum, one launch); 0.2.9: + dsa_mlsacheck / dsa_mlsacheck_vjp (the stability check of the MLSA filter: the mel-cepstrum scaled or clipped where the amplitude of its gain-free part passes the threshold of the Pade approximation, forward and adjoint); 0.2.8: + dsa_lpc2lsp_fwd / _bwd, dsa_lsp2lpc_fwd / _bwd, dsa_lspcheck_fwd / _bwd (line spectral pairs by a Chebyshev-series root search, back by a product of real sections, and their stability check, forward and adjoint); 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
+#define DSA_VERSION 143 /* 0.3.7: + dsa_vq_search / dsa_vq_accum / dsa_vq_update / dsa_vq_lookup / dsa_vq_vjp (vector quantisation and the Linde-Buzo-Gray codebook design: nearest-codeword search on float64 sums, per-codeword counts and float64 sums in fixed-order segments without atomics, centroids with the iteration's three scalars, the lookup and the quantiser's adjoint); 0.3.6: + dsa_yingram / dsa_yingram_vjp / dsa_frame_yingram (Yingram: YIN's cumulative-mean-normalised difference function on a semitone grid, from frames or from the waveform in one launch, and its adjoint; lag sums directly or through the LDS transform); 0.3.5: + dsa_gmm_prepare / dsa_gmm_estep / dsa_gmm_accum / dsa_gmm_update / dsa_gmm_regress / dsa_gmm_transform (Gaussian mixture models: one EM iteration as factorisation, E-step, weighted moment sums and M-step on the device, and the conversion of a joint-density model); 0.3.4: + dsa_dtw / dsa_dtw_vjp / dsa_dtw_path (dynamic time warping with a soft minimum: the aligned distance of two vector sequences by an anti-diagonal wavefront, its gradient by the reverse sweep, the Viterbi path from the saved tables); 0.3.3: + DSA_ALGO_FIXED_STEPS (the tuned mel-cepstral forward stops a frame's Newton iteration once its update is rounding noise; the flag runs every step); 0.3.2: + dsa_delta / dsa_delta_vjp, dsa_mlpg, dsa_mcpf / dsa_mcpf_vjp (parameter generation: delta features, maximum likelihood parameter generation by a banded Cholesky solve, mel-cepstrum postfiltering in closed form); 0.3.1: + dsa_mdct_analysis / dsa_mdct_synthesis (MDCT / MDST and their inverses: window, fold, DCT-IV through a quarter-length complex FFT and overlap-add in one launch each way; each is the other's adjoint); 0.3.0: + dsa_excite (pitch to excitation: the voiced shapes of ExcitationGeneration on a segmented float64 phase sum, one launch); 0.2.9: + dsa_mlsacheck / dsa_mlsacheck_vjp (the stability check of the MLSA filter: the mel-cepstrum scaled or clipped where the amplitude of its gain-free part passes the threshold of the Pade approximation, forward and adjoint); 0.2.8: + dsa_lpc2lsp_fwd / _bwd, dsa_lsp2lpc_fwd / _bwd, dsa_lspcheck_fwd / _bwd (line spectral pairs by a Chebyshev-series root search, back by a product of real sections, and their stability check, forward and adjoint); 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
 
 typedef enum {
     DSA_OK = 0,
@@ -964,6 +964,49 @@ int dsa_yingram_vjp(const void* gy, const void* x, int64_t F, int32_t L, int32_t
 int dsa_frame_yingram(const void* x, int64_t B, int64_t T, int32_t L, int32_t P, int32_t center, int32_t lag_max, const void* lags,
                           const void* lags_floor, const void* lags_ceil, int32_t M, const void* twiddle, int32_t algo, int32_t dtype, void* y,
                           void* stream);
+
+/* ------------------------------------------------------------------ a23  Vector quantisation and codebook design: vq (0.3.7)
+ * VectorQuantization.forward, vq.py:110-125 (nearest codeword, there inside the package vector_quantize_pytorch); InverseVectorQuantization
+ * .forward, ivq.py:63-67; one iteration of LindeBuzoGrayAlgorithm.forward, lbg.py:214-224 (E-step) and lbg.py:264-285 (counts and
+ * centroids; there a (B, K) distance matrix, histc and scatter_add_ per DataLoader batch).  x:(T,L) of the dtype (float32 or float64),
+ * codebook:(K,L) float32 whatever the dtype, indices:(T) int64.  int64 indexing, no allocation, no host synchronisation, no
+ * floating-point atomics: every sum has one fixed order, two runs give the same bits.  The library owns no device memory.  T = 0 (and
+ * n = 0 of dsa_vq_vjp) is a no-op before any pointer is looked at.
+ *   dsa_vq_search   indices[t] = the first k that minimises sum_j (x[t,j] - codebook[k,j])^2, the differences and the sums formed in
+ *                   float64 from the values as stored, j ascending: the assignment of exact arithmetic apart from ties closer than
+ *                   float64 rounding.  xq:(T,L) of the dtype = codebook[indices], or NULL.  partial: ceil(T / rows) float64, the
+ *                   per-workgroup sums of the minimal distances, rows = DSA_VQ_TILE_BYTES / sizeof(dtype) vectors per workgroup (one
+ *                   thread per vector, the tile in LDS, the codebook staged through LDS DSA_VQ_CHUNK codewords at a time: K has no
+ *                   ceiling).  total (1 of the dtype, or NULL): scale times the sum of the partials, by a second launch of one workgroup.
+ *   dsa_vq_accum    per codeword the number and the float64 sum of the vectors assigned to it, into workspace
+ *                   (dsa_vq_accum_workspace_bytes: S K L float64 sums, then S K int64 counts; S <= DSA_VQ_MAX_SEGMENTS segments of T of
+ *                   at least 256 vectors, as many as fill the chip).  A workgroup takes one segment and as many codewords as fit 64 KiB
+ *                   of LDS (16384 / (8 L + 4)); its four waves take every fourth run of 64 vectors each, a lane one column, so every LDS cell
+ *                   belongs to one thread.  An index outside 0 .. K - 1 is counted nowhere.
+ *   dsa_vq_update   from the workspace (per column the segments s = g, g + 4, ... added in order for g = 0 .. 3, the four runs then in the
+ *                   order of g: one fixed order), two launches: n_data:(K) int64; pending:(K,L) float32 = (float)(sum / count) where
+ *                   count >= min_data, else 0 (lbg.py:265-285) -- a buffer of the caller's, not the codebook the search read; readback
+ *                   (3 float64): the sum of `partial` (n_partial values, may be 0) / T, the number of codewords with count < min_data,
+ *                   the first k with the largest count -- what the host reads once per iteration.
+ *   dsa_vq_lookup   xq:(T,L) of the dtype = codebook[indices] (ivq.py:65); an index outside 0 .. K - 1 gives a row of NaN.
+ *   dsa_vq_vjp      gx[i] = g_xq[i] + g_loss[0] 2 (x[i] - xq[i]) / n, i < n = T L: the straight-through estimator plus the gradient of
+ *                   loss = mean((x - xq)^2); g_xq (n of the dtype) or g_loss (1 of the dtype) may be NULL: zero.  One launch.
+ * dsa_last_kernel(): "vq_search_f32", "vq_accum_f32", "vq_lookup_f32", "vq_vjp_f32" and the same with f64; "vq_update".
+ * DSA_ERR_INVALID_ARGUMENT with a message that names "vq": a negative T, K < 1, L < 1, sizes beyond int64 / int32 launch dimensions,
+ * min_data < 1, an unknown dtype, a missing pointer, and L > DSA_VQ_MAX_LENGTH: the accumulation gives a lane of its wave to each
+ * column, and the search's tile of vectors (DSA_VQ_TILE_BYTES (L | 1) bytes) shares LDS with the staged codewords. */
+#define DSA_VQ_MAX_LENGTH 64
+#define DSA_VQ_TILE_BYTES 1024
+#define DSA_VQ_CHUNK 64
+#define DSA_VQ_MAX_SEGMENTS 256
+int dsa_vq_search(const void* x, const void* codebook, int64_t T, int64_t K, int64_t L, int32_t dtype, void* indices, void* xq, void* partial,
+                  void* total, double scale, void* stream);
+int64_t dsa_vq_accum_workspace_bytes(int64_t T, int64_t K, int64_t L);
+int dsa_vq_accum(const void* x, const void* indices, int64_t T, int64_t K, int64_t L, int32_t dtype, void* workspace, void* stream);
+int dsa_vq_update(const void* workspace, const void* partial, int64_t n_partial, int64_t T, int64_t K, int64_t L, int64_t min_data,
+                  void* n_data, void* pending, void* readback, void* stream);
+int dsa_vq_lookup(const void* indices, const void* codebook, int64_t T, int64_t K, int64_t L, int32_t dtype, void* xq, void* stream);
+int dsa_vq_vjp(const void* g_xq, const void* g_loss, const void* x, const void* xq, int64_t n, int32_t dtype, void* gx, void* stream);
 
 #ifdef __cplusplus
 }
