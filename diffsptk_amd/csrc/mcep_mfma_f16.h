@@ -19,6 +19,8 @@
 // elimination) is the code of mcep_mfma_fwd_kernel_v2.
 #pragma once
 
+#include <type_traits>
+
 #include "common.h"
 #include "f16_split.h"
 #include "mcep_solve.h"
@@ -96,7 +98,7 @@ constexpr int h_lds_floats_fused(int waves) { return h_lds_floats(waves) + FU_FL
 #endif
 template <bool PK> __device__ __forceinline__ v2f fu_mul(v2f a, v2f b) { if constexpr (PK) return pk_mul(a, b); else return sc_mul(a, b); }
 template <bool PK> __device__ __forceinline__ v2f fu_cmul(v2f a, v2f t) { if constexpr (PK) return pk_cmul(a, t); else return sc_cmul(a, t); }
-template <bool PK, bool ZT> __device__ __forceinline__ void fu_fft16(v2f (&v)[16]) { if constexpr (PK) pk_fft16<ZT>(v); else sc_fft16<ZT>(v); }
+template <bool PK, bool ZT> __device__ __forceinline__ void fu_fft16(v2f (&v)[16]) { if constexpr (PK) pk_fft16_il<ZT>(v); else sc_fft16<ZT>(v); }
 
 // Operand images of the three constant matrices, split into binary16 hi / lo, in the exact
 // per-lane order the MFMAs consume them (one 16-byte element per lane and k-step).  One tiny launch
@@ -282,18 +284,42 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) DSA_PK_TARGET void mcep_mfma
             v2f* zf = zbuf + fl * 272;
             const float* fu = lds + h_lds_floats(WAVES);
             v2f raw[FU_NR];
-            auto fetch = [&](int p) __attribute__((always_inline)) {
+            // Round 10: a lane's frame is addressed ONCE per tile.  Pass 0 derives (utterance, sample offset of the frame in it) with
+            // the division; the lane's frame of the next pass is four frames on, so passes 1 - 3 step the pair: the offset by 4 P,
+            // and where that leaves the utterance (frame-in-utterance >= N) back by N P with the utterance index up by one.  One
+            // wrap per step needs N >= 4, and the tile must not be clamped against F (only the launch's last tile can be): where
+            // either fails the tile derives each pass as before (wave-uniform choice, a scalar branch).  The two values are 32-bit, formed at
+            // the head of the tile and dead behind the last fetch: nothing of them is live across the Newton loop.
+            const int tile16 = __builtin_amdgcn_readfirstlane((int)(tile * 16));
+            // (opaque per tile, and per pass below: as loop invariants these scalars would be kept -- spilled -- across the Newton loop)
+            int fr_ns = (int)sti.N, fr_ts = (int)sti.Tlen;
+            asm volatile("" : "+s"(fr_ns), "+s"(fr_ts));
+            const bool fr_step = tile16 + 16 <= (int)F && fr_ns >= 4 && fr_ts < (1 << 29);   // (the last: N P + 4 P below 2^31)
+            unsigned fr_sl = 0u, fr_ub = 0u;   // frame-in-utterance x P (the start before the left padding comes off), utterance
+            auto fetch = [&](int p, auto first) __attribute__((always_inline)) {
                 // 32-bit arithmetic from an opaque copy of the lane's frame slot, formed here (F, Tlen < 2^31, host-checked): as 64-bit
                 // values derived from `fl` these were hoisted out of the pass loop, spilled across the Newton iteration, and each
                 // reload was a `s_waitcnt vmcnt(0)` in front of the fetch it feeds
-                int flo = fl;
-                asm volatile("" : "+v"(flo));
-                int fr = (int)(tile * 16) + 4 * p + flo;
-                fr = fr < (int)F ? fr : (int)F - 1;
-                const unsigned ub = (unsigned)fr / (unsigned)sti.N;
-                const int nf = fr - (int)(ub * (unsigned)sti.N);
-                const int start = nf * sti.P - sti.left;
-                const float* xb = sti.x + (long)ub * sti.Tlen;
+                if (first() || !fr_step) {
+                    int flo = fl;
+                    asm volatile("" : "+v"(flo));
+                    int fr = tile16 + 4 * p + flo;
+                    fr = fr < (int)F ? fr : (int)F - 1;
+                    fr_ub = (unsigned)fr / (unsigned)sti.N;
+                    fr_sl = ((unsigned)fr - fr_ub * (unsigned)sti.N) * (unsigned)sti.P;
+                } else {
+                    // (unsigned: N P <= Tlen - 1 + P may pass 2^31; the difference is exact modulo 2^32)
+                    unsigned n_s = (unsigned)sti.N, p_s = (unsigned)sti.P;
+                    asm volatile("" : "+s"(n_s), "+s"(p_s));
+                    const unsigned np = n_s * p_s;
+                    const unsigned s = fr_sl + 4u * p_s;
+                    const bool wrap = s >= np;
+                    fr_sl = wrap ? s - np : s;
+                    fr_ub = wrap ? fr_ub + 1u : fr_ub;
+                }
+                const unsigned ub = fr_ub;
+                const int start = (int)fr_sl - sti.left;
+                const float* xb = sti.x + (unsigned long)ub * (unsigned)sti.Tlen;
                 const bool interior = start >= 0 && start + 32 * FU_NR <= (int)sti.Tlen;
                 if (__builtin_amdgcn_ballot_w64(!interior) == 0) {
                     const v2f_u4* src = reinterpret_cast<const v2f_u4*>(xb + start + 2 * j);
@@ -334,7 +360,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) DSA_PK_TARGET void mcep_mfma
                     }
                 }
             };
-            fetch(0);
+            fetch(0, std::true_type{});
 #pragma unroll 1
             for (int p = 0; p < 4; ++p) {
                 // (opaque per pass: the table reads below are loop invariant, and hoisted out of the pass / tile loops their 62
@@ -364,7 +390,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) DSA_PK_TARGET void mcep_mfma
                 }
 #pragma unroll
                 for (int m1 = FU_NR; m1 < 16; ++m1) v[m1] = v2f{0.f, 0.f};
-                if (p < 3) fetch(p + 1);
+                if (p < 3) fetch(p + 1, std::false_type{});
 #if DSA_FUSED_DBG & 8
                 {   // reduction build: the packed transform against its scalar twin on the same inputs; mismatches logged with a re-run
                     v2f vin[16], vs[16];
@@ -409,9 +435,19 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) DSA_PK_TARGET void mcep_mfma
 #else
                 fu_fft16<(PKM & 2) != 0, true>(v);
 #endif
+                if constexpr ((PKM & 4) != 0) {   // two products side by side: no multiply-add right behind its own multiply (pk_math.h)
 #pragma unroll
-                for (int k1 = 0; k1 < 16; ++k1) {
-                    zf[k1 * 17 + j] = fu_cmul<(PKM & 4) != 0>(v[FFT16_OUT(k1)], t256[k1 * 16]);
+                    for (int k1 = 0; k1 < 16; k1 += 2) {
+                        const v2f ta = t256[k1 * 16], tb = t256[(k1 + 1) * 16];
+                        const v2f ma = pk_cmul_m(v[FFT16_OUT(k1)], ta), mb = pk_cmul_m(v[FFT16_OUT(k1 + 1)], tb);
+                        zf[k1 * 17 + j] = pk_cmul_f(v[FFT16_OUT(k1)], ta, ma);
+                        zf[(k1 + 1) * 17 + j] = pk_cmul_f(v[FFT16_OUT(k1 + 1)], tb, mb);
+                    }
+                } else {
+#pragma unroll
+                    for (int k1 = 0; k1 < 16; ++k1) {
+                        zf[k1 * 17 + j] = fu_cmul<(PKM & 4) != 0>(v[FFT16_OUT(k1)], t256[k1 * 16]);
+                    }
                 }
                 __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -446,20 +482,24 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) DSA_PK_TARGET void mcep_mfma
                     v2f se, sp[2];
                     if constexpr ((PKM & 16) != 0) {   // the packed form of csrc/stft_pk.h, instruction for instruction
                         const v2f eps2 = v2f{sti.eps, sti.eps};
+                        // (round 10: the two bin pairs and the bins 0 / 256 run side by side, so that no instruction reads the result
+                        //  of the one before it -- see pk_fft16_il; instruction for instruction the chains of csrc/stft_pk.h)
                         v2f Ee;
                         Ee = pk_lo_pm_hi(z0[q], z0[q]);
+                        const v2f S0 = pk_add_conj(pa[q][0], pb[q][0]), S1 = pk_add_conj(pa[q][1], pb[q][1]);
+                        const v2f Dd0 = pk_sub_conj(pa[q][0], pb[q][0]), Dd1 = pk_sub_conj(pa[q][1], pb[q][1]);
                         const v2f E4 = pk_mul_s(Ee, v2f{4.f, 4.f});
+                        const v2f M0 = pk_cmul_m(Dd0, twA), M1 = pk_cmul_m(Dd1, twB);
                         se = pk_fma_sc(E4, Ee, eps2);
-#pragma unroll
-                        for (int part = 0; part < 2; ++part) {
-                            const v2f S = pk_add_conj(pa[q][part], pb[q][part]);
-                            const v2f Dd = pk_sub_conj(pa[q][part], pb[q][part]);
-                            const v2f Pp = pk_cmul(Dd, part == 0 ? twA : twB);
-                            v2f R, I;
-                            R = pk_lo_pm_hi(S, Pp);
-                            I = pk_hi_mp_lo(S, Pp);
-                            sp[part] = pk_fma(I, I, pk_fma_sc(R, R, eps2));
-                        }
+                        const v2f Pp0 = pk_cmul_f(Dd0, twA, M0), Pp1 = pk_cmul_f(Dd1, twB, M1);
+                        v2f R0, I0, R1, I1;
+                        R0 = pk_lo_pm_hi(S0, Pp0);
+                        I0 = pk_hi_mp_lo(S0, Pp0);
+                        R1 = pk_lo_pm_hi(S1, Pp1);
+                        I1 = pk_hi_mp_lo(S1, Pp1);
+                        const v2f f0 = pk_fma_sc(R0, R0, eps2), f1 = pk_fma_sc(R1, R1, eps2);
+                        sp[0] = pk_fma(I0, I0, f0);
+                        sp[1] = pk_fma(I1, I1, f1);
                     } else {
                     const v2f Ee = v2f{sc_add1(z0[q].x, z0[q].y), sc_sub1(z0[q].x, z0[q].y)};
                     const v2f E4 = v2f{sc_mul1s(Ee.x, 4.f), sc_mul1s(Ee.y, 4.f)};
@@ -526,8 +566,34 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) DSA_PK_TARGET void mcep_mfma
             // (opaque per tile: hoisted out of the tile loop the 32 operand loads would live in scratch)
             const _Float16* imgt = img;
             asm volatile("" : "+s"(imgt));
-            const gf16x8_ptr GH = (gf16x8_ptr)(imgt + IMG_GH) + lane;
-            const gf16x8_ptr GL = (gf16x8_ptr)(imgt + IMG_GL) + lane;
+            // a uniform base and an unsigned 32-bit lane offset, written so that the loads could take the scalar-base form; the
+            // compiler still forms 64-bit per-lane addresses (eight 4 KB windows: eight carry-chained vector adds, as before)
+            typedef const __attribute__((address_space(1))) char* gbyte_ptr;
+            const gbyte_ptr gimg = (gbyte_ptr)imgt;
+            int lane_o = lane;   // (opaque per tile as well: the offsets are loop invariants)
+            asm volatile("" : "+v"(lane_o));
+            const unsigned lane16 = 16u * (unsigned)lane_o, n4 = 4u * ((unsigned)lane_o & 15u);
+            // Round 10: the image's 32 operand loads (16 bytes per lane each) are issued G_AHEAD k-steps ahead of the products that
+            // consume them, in program order pinned by scheduling barriers: 16 loads in flight (64 registers; the Newton loop's block
+            // registers and tt[16] are dead here), counted down by exact vmcnt waits.  Left to the scheduler the loads came out four
+            // to six at a time, each batch waited for in full in front of its products: eight L2 round trips per tile in a row
+            // (profiles/r06_mcep_phase_stamps.txt: 4.9 - 6.9 k cycles for 0.8 k cycles of matrix time), now one.  The Nyquist row's
+            // two values travel with the first batch (its 32 floats are zero past coefficient 24: no select, no branch).
+            constexpr int G_AHEAD = 4;
+            f16x8 gh[G_AHEAD][2], gl[G_AHEAD][2];
+            auto gload = [&](int j) __attribute__((always_inline)) {
+#pragma unroll
+                for (int it = 0; it < 2; ++it) {
+                    gh[j % G_AHEAD][it] = *(gf16x8_ptr)(gimg + (2 * IMG_GH + 1024 * (it * 8 + j)) + lane16);
+                    gl[j % G_AHEAD][it] = *(gf16x8_ptr)(gimg + (2 * IMG_GL + 1024 * (it * 8 + j)) + lane16);
+                }
+            };
+#pragma unroll
+            for (int j = 0; j < G_AHEAD; ++j) gload(j);
+            float gnyq[2];
+#pragma unroll
+            for (int it = 0; it < 2; ++it) gnyq[it] = *(gf32_ptr)(gimg + (2 * IMG_HALVES + 64 * it) + n4);
+            __builtin_amdgcn_sched_barrier(0);
             f32x4 accG[2] = {f32x4{0, 0, 0, 0}, f32x4{0, 0, 0, 0}};
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -543,16 +609,20 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) DSA_PK_TARGET void mcep_mfma
                     }
 #pragma unroll
                 for (int it = 0; it < 2; ++it) {
-                    const f16x8 ah = GH[(it * 8 + j) * 64], al = GL[(it * 8 + j) * 64];
+                    const f16x8 ah = gh[j % G_AHEAD][it], al = gl[j % G_AHEAD][it];
                     accG[it] = mfma_h(al, lh, accG[it]);
                     accG[it] = mfma_h(ah, ll, accG[it]);
                     accG[it] = mfma_h(ah, lh, accG[it]);
                 }
+                if (j + G_AHEAD < 8) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    gload(j + G_AHEAD);
+                }
+                __builtin_amdgcn_sched_barrier(0);
             }
 #pragma unroll
             for (int it = 0; it < 2; ++it) {  // Nyquist bin: one float32 k-step on k-slot 0
-                const int out = it * 16 + n;
-                const float gv = out < M1 ? (kLn2 * SG * SL) * ((gf32_ptr)(imgt + IMG_HALVES))[out] : 0.f;
+                const float gv = (kLn2 * SG * SL) * gnyq[it];
                 accG[it] = mfma4(keep_if(g_eq0, gv), keep_if(g_eq0, logx256), accG[it]);
                 accG[it] *= 1.f / (SG * SL);
             }

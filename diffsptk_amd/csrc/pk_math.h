@@ -300,6 +300,97 @@ __device__ __forceinline__ void pk_fft16(v2f (&v)[16])
     pk_dft4(v[12], v[13], v[14], v[15]);
 }
 
+// ---- the same transform in an order without back-to-back dependences (round 10; the fused STFT -> mel-cepstrum prologue) ----
+// The result of a one-instruction `asm` statement read by the very next instruction costs a wait state: the compiler cannot see
+// what the statement's last instruction is and puts `s_nop 0` behind it (for a packed producer it does so for its own code too).
+// pk_fft16 runs one butterfly after the other, so each of its dependent pairs ends up adjacent: ~94 wait states per pass of the
+// prologue, an issue slot each.  Here every butterfly is cut in two halves -- `_p1`: the four independent sums / differences,
+// `_p2`: the four outputs -- and the halves of TWO butterflies alternate; a complex product is cut into its multiply (`_m`) and its
+// two multiply-adds (`_f`) likewise.  The same instructions on the same operands: bit-identical to pk_fft16.
+struct PkDft4Mid { v2f s02, d02, s13, d13; };
+__device__ __forceinline__ PkDft4Mid pk_dft4_p1(v2f a0, v2f a1, v2f a2, v2f a3)
+{
+    return PkDft4Mid{pk_add(a0, a2), pk_sub(a0, a2), pk_add(a1, a3), pk_sub(a1, a3)};
+}
+__device__ __forceinline__ PkDft4Mid pk_dft4_z3_p1(v2f a0, v2f a1, v2f a2)   // a3 == 0
+{
+    return PkDft4Mid{pk_add(a0, a2), pk_sub(a0, a2), a1, a1};
+}
+__device__ __forceinline__ PkDft4Mid pk_dft4_negi2_p1(v2f a0, v2f a1, v2f a2, v2f a3)   // a2 stands for -i a2
+{
+    return PkDft4Mid{pk_add_negi(a0, a2), pk_add_posi(a0, a2), pk_add(a1, a3), pk_sub(a1, a3)};
+}
+__device__ __forceinline__ void pk_dft4_p2(const PkDft4Mid& m, v2f& a0, v2f& a1, v2f& a2, v2f& a3)
+{
+    a0 = pk_add(m.s02, m.s13);
+    a2 = pk_sub(m.s02, m.s13);
+    a1 = pk_add_negi(m.d02, m.d13);
+    a3 = pk_add_posi(m.d02, m.d13);
+}
+__device__ __forceinline__ v2f pk_cmul_m(v2f a, v2f t)     // first instruction of pk_cmul
+{
+    v2f t1;
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(t1) : "v"(a), "v"(t));
+    return t1;
+}
+__device__ __forceinline__ v2f pk_cmul_f(v2f a, v2f t, v2f t1)   // its two multiply-adds
+{
+    v2f r;
+    asm("v_fma_f32 %0, -%1, %2, %3" : "=v"(r.x) : "v"(a.y), "v"(t.y), "v"(t1.x));
+    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r.y) : "v"(a.x), "v"(t.y), "v"(t1.y));
+    return r;
+}
+__device__ __forceinline__ v2f pk_cmul_s_m(v2f a, v2f t)   // the same with t in a scalar register pair (pk_cmul_s)
+{
+    v2f t1;
+    asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(t1) : "v"(a), "s"(t));
+    return t1;
+}
+__device__ __forceinline__ v2f pk_cmul_s_f(v2f a, v2f t, v2f t1)
+{
+    v2f r;
+    asm("v_fma_f32 %0, -%1, %2, %3" : "=v"(r.x) : "v"(a.y), "s"(t.y), "v"(t1.x));
+    asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r.y) : "v"(a.x), "s"(t.y), "v"(t1.y));
+    return r;
+}
+// two twiddle products side by side: multiply, multiply, then the multiply-adds
+__device__ __forceinline__ void pk_cmul_s_x2(v2f& a, v2f ta, v2f& b, v2f tb)
+{
+    const v2f ma = pk_cmul_s_m(a, ta), mb = pk_cmul_s_m(b, tb);
+    a = pk_cmul_s_f(a, ta, ma);
+    b = pk_cmul_s_f(b, tb, mb);
+}
+template <bool ZTAIL>
+__device__ __forceinline__ void pk_fft16_il(v2f (&v)[16])
+{
+    constexpr float C1 = 0.92387953251128674f, S1 = 0.38268343236508977f, R2 = 0.70710678118654752f;
+    {
+        const PkDft4Mid m0 = pk_dft4_p1(v[0], v[4], v[8], v[12]);
+        const PkDft4Mid m1 = ZTAIL ? pk_dft4_z3_p1(v[1], v[5], v[9]) : pk_dft4_p1(v[1], v[5], v[9], v[13]);
+        pk_dft4_p2(m0, v[0], v[4], v[8], v[12]);
+        pk_dft4_p2(m1, v[1], v[5], v[9], v[13]);
+        const PkDft4Mid m2 = ZTAIL ? pk_dft4_z3_p1(v[2], v[6], v[10]) : pk_dft4_p1(v[2], v[6], v[10], v[14]);
+        const PkDft4Mid m3 = ZTAIL ? pk_dft4_z3_p1(v[3], v[7], v[11]) : pk_dft4_p1(v[3], v[7], v[11], v[15]);
+        pk_dft4_p2(m2, v[2], v[6], v[10], v[14]);
+        pk_dft4_p2(m3, v[3], v[7], v[11], v[15]);
+    }
+    // twiddles W16^(n0 q) as in pk_fft16 (v[10]: the factor -i, folded into its butterfly below)
+    pk_cmul_s_x2(v[5], v2f{C1, -S1}, v[9], v2f{R2, -R2});
+    pk_cmul_s_x2(v[13], v2f{S1, -C1}, v[6], v2f{R2, -R2});
+    pk_cmul_s_x2(v[14], v2f{-R2, -R2}, v[7], v2f{S1, -C1});
+    pk_cmul_s_x2(v[11], v2f{-R2, -R2}, v[15], v2f{-C1, S1});
+    {
+        const PkDft4Mid m0 = pk_dft4_p1(v[0], v[1], v[2], v[3]);
+        const PkDft4Mid m1 = pk_dft4_p1(v[4], v[5], v[6], v[7]);
+        pk_dft4_p2(m0, v[0], v[1], v[2], v[3]);
+        pk_dft4_p2(m1, v[4], v[5], v[6], v[7]);
+        const PkDft4Mid m2 = pk_dft4_negi2_p1(v[8], v[9], v[10], v[11]);
+        const PkDft4Mid m3 = pk_dft4_p1(v[12], v[13], v[14], v[15]);
+        pk_dft4_p2(m2, v[8], v[9], v[10], v[11]);
+        pk_dft4_p2(m3, v[12], v[13], v[14], v[15]);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Scalar twins (one v_add / v_mul / v_fma per component, hand-placed like the packed forms so that the compiler's packed-float32
 // selection cannot re-pair them), same roundings as the packed helpers -- the results are bit-identical.
