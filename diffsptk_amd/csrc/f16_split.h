@@ -100,6 +100,11 @@ __device__ __forceinline__ void split2(float x0, float x1, f16x2& hi, f16x2& lo)
         : "=&v"(lb) : "v"(hb), "v"(x0), "v"(x1));
     lo = __builtin_bit_cast(f16x2, lb);
 }
+// the hi piece alone (the one-term products of a coarse Newton step): the packed conversion of split2, no lo piece
+__device__ __forceinline__ f16x2 split2_hi(float x0, float x1)
+{
+    return __builtin_convertvector(f32x2v{x0, x1}, f16x2);
+}
 // four values at a time: the two pairs' half-register writes interleaved, so that the wait state between the low-half write and
 // the high half's read-modify-write of one destination is the other pair's instruction (3 of 4 s_nop fewer per four values)
 __device__ __forceinline__ void split4(float x0, float x1, float x2, float x3, f16x2& hiA, f16x2& hiB, f16x2& loA, f16x2& loB)

@@ -421,7 +421,9 @@ DSA_EXPORT int dsa_mcep_fwd(const void* X, int64_t F, int32_t nfft, int32_t M, i
     const bool overlapped = (algo & DSA_ALGO_OVERLAPPED_LAUNCHES) != 0;
     const int reserve_cus = DSA_ALGO_RESERVED_CUS(algo);
     const bool fixed_steps = (algo & DSA_ALGO_FIXED_STEPS) != 0;
-    algo &= ~(DSA_ALGO_SCRATCH_IS_CLEAN | DSA_ALGO_HIST_HAS_RT | DSA_ALGO_OVERLAPPED_LAUNCHES | DSA_ALGO_RESERVE_CUS(63) | DSA_ALGO_FIXED_STEPS);
+    const bool full_chains = (algo & DSA_ALGO_FULL_CHAINS) != 0;
+    algo &= ~(DSA_ALGO_SCRATCH_IS_CLEAN | DSA_ALGO_HIST_HAS_RT | DSA_ALGO_OVERLAPPED_LAUNCHES | DSA_ALGO_RESERVE_CUS(63) | DSA_ALGO_FIXED_STEPS |
+              DSA_ALGO_FULL_CHAINS);
     bool tuned_ok = mcep_mfma_supported(nfft, M, dtype) != 0;
     if (algo == DSA_ALGO_TUNED && !tuned_ok)
         return fail(DSA_ERR_UNSUPPORTED, "mcep: tuned kernel needs float32, fft_length 512, cep_order 24%s");
@@ -429,7 +431,7 @@ DSA_EXPORT int dsa_mcep_fwd(const void* X, int64_t F, int32_t nfft, int32_t M, i
         return fail(DSA_ERR_INVALID_ARGUMENT, "mcep: the tuned kernel needs the prepared images (dsa_mcep_prepare) and a scratch buffer%s");
     if (tuned_ok && algo != DSA_ALGO_GENERIC && images && scratch)
         return mcep_mfma_fwd(X, F, n_iter, G, D, E, alpha_vec, images, scratch, mc, mc_hist, st, scratch_clean, nullptr, hist_has_rt, overlapped,
-                             reserve_cus, fixed_steps);
+                             reserve_cus, fixed_steps, full_chains);
     if (dtype == DSA_F32) return mcep_generic_fwd<float>(X, F, nfft, M, n_iter, G, D, E, alpha_vec, mc, mc_hist, st);
     if (dtype == DSA_F64) return mcep_generic_fwd<double>(X, F, nfft, M, n_iter, G, D, E, alpha_vec, mc, mc_hist, st);
     return fail(DSA_ERR_UNSUPPORTED, "mcep: unsupported dtype%s");
@@ -458,7 +460,7 @@ DSA_EXPORT int dsa_stft_mcep_opts_fwd(const void* x, int64_t B, int64_t T, int32
     const float floor_lin = use_floor ? (float)pow(10.0, relative_floor_db / 10.0) : -1.f;
     return stft_mcep_fused_fwd(x, B, T, P, center, window, twiddle, eps, n_iter, G, D, E, alpha_vec, images, scratch, mc, mc_hist,
                                X_out, (hipStream_t)stream, scratch_clean, hist_has_rt, overlapped, pad_mode, zmean != 0, floor_lin,
-                               DSA_ALGO_RESERVED_CUS(algo), (algo & DSA_ALGO_FIXED_STEPS) != 0);
+                               DSA_ALGO_RESERVED_CUS(algo), (algo & DSA_ALGO_FIXED_STEPS) != 0, (algo & DSA_ALGO_FULL_CHAINS) != 0);
 }
 
 DSA_EXPORT int dsa_stft_mcep_fwd(const void* x, int64_t B, int64_t T, int32_t L, int32_t P, int32_t nfft, const void* window,

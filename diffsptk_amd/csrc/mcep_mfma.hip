@@ -56,7 +56,7 @@ static int mcep_mfma_fwd_launch(long grid, int lds_bytes, hipStream_t st, Args..
 // `sti`: NULL (spectra in X) or the waveform side of the fused STFT -> mel-cepstrum launch (X is then unused)
 int mcep_mfma_fwd(const void* X, int64_t F, int n_iter, const void* G, const void* D, const void* E, const void* av,
                   const void* images, void* scratch, void* mc, void* hist, hipStream_t st, bool scratch_clean, const StftIn* sti,
-                  bool hist_has_rt, bool overlapped, int reserve_cus, bool fixed_steps)
+                  bool hist_has_rt, bool overlapped, int reserve_cus, bool fixed_steps, bool full_chains)
 {
     // DSA_ALGO_HIST_HAS_RT: the caller's history buffer continues behind the (n_iter + 1, F, 25) iterates with (n_iter, F, 49) rows of rt
     float* hist_rt = (hist && hist_has_rt) ? (float*)hist + (size_t)(n_iter + 1) * (size_t)F * mm::M1 : nullptr;
@@ -102,11 +102,16 @@ int mcep_mfma_fwd(const void* X, int64_t F, int n_iter, const void* G, const voi
     }
     // DSA_ALGO_FIXED_STEPS: a threshold no update compares below -- every step runs and every update is applied
     const float tau = fixed_steps ? -1.f : mh::STOP_TAU;
+    // Round 11: the first n_coarse steps run their chains on the hi pieces alone (one product for three), each with at least six full
+    // steps behind it.  A static schedule of (step, n_iter), whatever the stopping rule does.  DSA_ALGO_FULL_CHAINS, or
+    // DSA_MCEP_FULL_CHAINS=1 in the environment: none -- every step on three-term chains, the arithmetic of versions before 0.3.8.
+    const bool three_terms = full_chains || env_int("DSA_MCEP_FULL_CHAINS", 0) != 0;
+    const int n_coarse = three_terms ? 0 : (n_iter - 6 < 0 ? 0 : n_iter - 6 > 2 ? 2 : n_iter - 6);
     auto launch = [&](auto fused, auto with_rt, auto options) {
         return mcep_mfma_fwd_launch<WAVES, fused(), with_rt(), options()>(
             grid, lds_bytes, st, sti ? nullptr : (const float*)X, (long)F, n_iter, (const float*)G, (const float*)D, (const float*)E,
             (const float*)av, (float*)mc, (float*)hist, ntiles16, tiles_shared, queue, (const _Float16*)images, sti ? *sti : StftIn{},
-            hist_rt, tail_wgs, tau);
+            hist_rt, tail_wgs, tau, n_coarse);
     };
     constexpr std::true_type yes{};
     constexpr std::false_type no{};
@@ -119,7 +124,7 @@ int mcep_mfma_fwd(const void* X, int64_t F, int n_iter, const void* G, const voi
 int stft_mcep_fused_fwd(const void* x, int64_t B, int64_t T, int P, int center, const void* window, const void* twiddle, double eps,
                         int n_iter, const void* G, const void* D, const void* E, const void* av, const void* images, void* scratch,
                         void* mc, void* hist, void* X_out, hipStream_t st, bool scratch_clean, bool hist_has_rt, bool overlapped, int pad_mode,
-                        int zmean, float floor_lin, int reserve_cus, bool fixed_steps)
+                        int zmean, float floor_lin, int reserve_cus, bool fixed_steps, bool full_chains)
 {
     const int64_t N = T <= 0 ? 0 : (T - 1) / P + 1;
     StftIn sti;
@@ -135,7 +140,7 @@ int stft_mcep_fused_fwd(const void* x, int64_t B, int64_t T, int P, int center, 
     sti.pad_mode = pad_mode;
     sti.zmean = zmean;
     sti.floor_lin = floor_lin;
-    return mcep_mfma_fwd(nullptr, B * N, n_iter, G, D, E, av, images, scratch, mc, hist, st, scratch_clean, &sti, hist_has_rt, overlapped, reserve_cus, fixed_steps);
+    return mcep_mfma_fwd(nullptr, B * N, n_iter, G, D, E, av, images, scratch, mc, hist, st, scratch_clean, &sti, hist_has_rt, overlapped, reserve_cus, fixed_steps, full_chains);
 }
 
 }  // namespace dsa

@@ -61,7 +61,7 @@ constexpr int H_UPREV = 56;   // slot of u_(k-1) in a frame's rt window (the ste
 static_assert(H_UPREV > 48 && H_UPREV < RS, "u_prev sits in the unused tail of the frame's rt window");
 // LDS carve-up behind the images (float units)
 constexpr int H_E48 = EL_OFF + 24 * 64 * 4;  // [16 mt][4 g][4 r] float
-constexpr int H_E256 = H_E48 + 256;      // [48] scaled by SE, [48] = unscaled E[256][48], [50] = the stopping rule's tau
+constexpr int H_E256 = H_E48 + 256;      // [48] scaled by SE, [48] = unscaled E[256][48], [49] = -2 log2(e) D[0][0], [50] = the stopping rule's tau, [51] = n_coarse (int)
 constexpr int H_D256 = H_E256 + 52;      // [32]
 constexpr int H_AV = H_D256 + 32;        // [28]
 constexpr int H_NAV = H_AV + 28;         // [28] -alpha_vec, zero-padded
@@ -147,6 +147,141 @@ __device__ __forceinline__ void store_mc_row(float* row, int g, const float (&mc
     }
 }
 
+// The chain phase of a COARSE Newton step (round 11): both chains on the hi pieces alone,
+//     t = log2 X + (DH^T mch^T) / (SD SM),   rt^T = EH^T eh^T,
+// one binary16 product where the full step runs three: 40 products instead of 120, no lo splits, no DL / EL reads.  The operands
+// are good to 2^-11, which is enough for a step whose update is 5e-2 .. 2e-1 of the iterate: Newton corrects itself, and the launcher
+// puts at least six full steps behind every coarse one.  Everything but the dropped terms is the full step's, instruction for
+// instruction on float32: the Nyquist bin, the running maximum and the exponent shift, exp2, the rt[48] column on the vector unit,
+// the Nyquist preload of the second chain.  Slotting: pass A one product per slot around the previous group's vector work, as in the
+// full step; pass B has three products per body (48 matrix-pipe cycles) around eight exp2 and the packed adds, multiply-adds and
+// conversions of its 32 bins -- a third of the body's vector work behind each product, no empty product slots.
+// One rounding error is NOT left to the later steps: that of the gain coefficient.  Row 0 of D is constant over the bins (c[0] of
+// the inverse warp is mc[0] alone and reaches every bin through cos 0), so what mc[0] and that row lose in binary16 is ONE number per
+// frame added to every t -- a factor on every e, up to 1.5 % on quiet input (|mc[0]| ~ 14), which measured as 3.5 % of such frames
+// stopping a step later.  It is formed in float32 (mc[0] c0 - hi(mc[0]) hi(c0), c0 = -2 log2(e) D[0][.] from LDS) and travels with
+// the exponent shift that every t receives anyway: a handful of instructions per step, none per bin.
+__device__ __forceinline__ void chains_hi_only(const float (&mcv)[8], const f32x4 (&logx)[16], float logx256, const f16x8* DH,
+                                               const f16x8* EH, const f32x4* E484, const float* lds, int g, f32x4 (&accB)[3],
+                                               float& rt48, int& back)
+{
+    using namespace mh;
+    constexpr float kInvSDM = 1.f / (SD * SM);
+#define DSA_SB() __builtin_amdgcn_sched_barrier(0x0004)
+    f16x8 bh;
+#pragma unroll
+    for (int i = 0; i < 8; i += 2) {
+        const f16x2 h = split2_hi(mcv[i] * SM, mcv[i + 1] * SM);
+        bh[i] = h[0]; bh[i + 1] = h[1];
+    }
+    float d256 = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) d256 = __builtin_fmaf(mcv[i], lds[H_D256 + 8 * g + i], d256);
+    d256 = rows_sum4(d256);
+    const float t256 = logx256 + d256;
+    // the gain residual (see above), the same value on the four lanes of a frame: mc[0] sits in lane group 0
+    const float c0 = lds[H_E256 + 49];
+    const float c0h = (float)(_Float16)(c0 * SD) * (1.f / SD), m0h = (float)bh[0] * (1.f / SM);
+    const float gres = rows_sum4(g == 0 ? __builtin_fmaf(mcv[0], c0, -(m0h * c0h)) : 0.f);
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    f32x4 tt[16];
+    float tmax = -__builtin_inff();   // of the 256 bins of the chain; the Nyquist bin joins behind the residual
+    {
+        // pass A: products of group q, vector work of group q - 1
+        f16x8 ah[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ah[i] = DH[i * 64];
+        f32x4 c[4] = {zero4, zero4, zero4, zero4}, pc[4] = {zero4, zero4, zero4, zero4};
+#pragma unroll
+        for (int q = 0; q < 5; ++q) {
+            const bool pm = q < 4, vw = q > 0;
+            f16x8 ah_n[4] = {ah[0], ah[1], ah[2], ah[3]};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (q < 3) ah_n[i] = DH[(4 * q + 4 + i) * 64];
+                if (pm) c[i] = mfma_h(ah[i], bh, zero4);
+                DSA_SB();
+                if (vw) {
+                    const f32x2v ta = fma2(lo2(pc[i]), kInvSDM, lo2(logx[4 * q - 4 + i]));
+                    const f32x2v tb = fma2(hi2(pc[i]), kInvSDM, hi2(logx[4 * q - 4 + i]));
+                    tt[4 * q - 4 + i] = f32x4{ta[0], ta[1], tb[0], tb[1]};
+                    tmax = __builtin_fmaxf(__builtin_fmaxf(tmax, ta[0]), ta[1]);
+                    tmax = __builtin_fmaxf(__builtin_fmaxf(tmax, tb[0]), tb[1]);
+                }
+                DSA_SB();
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { pc[i] = c[i]; ah[i] = ah_n[i]; }
+        }
+    }
+    f16x8 eah[3];
+#pragma unroll
+    for (int it = 0; it < 3; ++it) eah[it] = EH[(it * 8) * 64];
+    tmax = __builtin_fmaxf(rows_max4(tmax) + gres, t256);
+    const float mi = __builtin_ceilf(tmax);
+    const float sh = (float)EMAX_LOG2 - mi;
+    const float shg = sh + gres;   // what the chain's bins are shifted by
+    back = (int)mi - EMAX_LOG2;
+    // pass B: body j runs the three products of bins 32 (j - 1) .. around the vector work of bins 32 j ..
+    const float e256 = __builtin_amdgcn_exp2f(t256 + sh);
+#pragma unroll
+    for (int it = 0; it < 3; ++it) accB[it] = *reinterpret_cast<const f32x4*>(lds + H_E256 + it * 16 + 4 * g) * e256;
+    const float rt48n = e256 * lds[H_E256 + 48];
+    f32x2v rt48v = {0.f, 0.f};
+    f16x8 eh_p = {};
+    DSA_SB();
+#pragma unroll
+    for (int j = 0; j < 9; ++j) {
+        f16x8 eh = eh_p;
+        f16x8 eah_n[3] = {eah[0], eah[1], eah[2]};
+        f32x4 c48[2] = {zero4, zero4};
+        if (j < 8) {
+            c48[0] = E484[(2 * j) * 4 + g];
+            c48[1] = E484[(2 * j + 1) * 4 + g];
+        }
+        if (j > 0 && j < 8) {
+#pragma unroll
+            for (int it = 0; it < 3; ++it) eah_n[it] = EH[(it * 8 + j) * 64];
+        }
+        auto prodE = [&](int it) __attribute__((always_inline)) {
+            if (j > 0) accB[it] = mfma_h(eah[it], eh_p, accB[it]);
+        };
+        f32x2v ta[2], tb[2];
+        float e[2][4];
+        auto vecA = [&](int t_) __attribute__((always_inline)) {
+            const f32x4 v = tt[(2 * j + t_) & 15];
+            ta[t_] = lo2(v) + f32x2v{shg, shg};
+            tb[t_] = hi2(v) + f32x2v{shg, shg};
+        };
+        auto vecB = [&](int t_) __attribute__((always_inline)) {
+            e[t_][0] = __builtin_amdgcn_exp2f(ta[t_][0]);  // mcep.py:212
+            e[t_][1] = __builtin_amdgcn_exp2f(ta[t_][1]);
+            e[t_][2] = __builtin_amdgcn_exp2f(tb[t_][0]);
+            e[t_][3] = __builtin_amdgcn_exp2f(tb[t_][1]);
+        };
+        auto vecD = [&](int t_) __attribute__((always_inline)) {
+            rt48v = f32x2v{e[t_][0], e[t_][1]} * lo2(c48[t_]) + rt48v;
+            rt48v = f32x2v{e[t_][2], e[t_][3]} * hi2(c48[t_]) + rt48v;
+        };
+        auto vecH = [&](int t_) __attribute__((always_inline)) {
+            const f16x2 h0 = split2_hi(e[t_][0], e[t_][1]), h1 = split2_hi(e[t_][2], e[t_][3]);
+            eh[4 * t_] = h0[0]; eh[4 * t_ + 1] = h0[1]; eh[4 * t_ + 2] = h1[0]; eh[4 * t_ + 3] = h1[1];
+        };
+        const bool vw = j < 8;   // body 8 only drains the second chain
+        prodE(0); DSA_SB(); if (vw) { vecA(0); vecB(0); vecA(1); } DSA_SB();
+        prodE(1); DSA_SB(); if (vw) { vecD(0); vecB(1); vecH(0); } DSA_SB();
+        // (a one-component add: left to the compiler the two halves' sum came out as a packed add with a set op_sel bit, the
+        //  instruction class no kernel here may execute -- pk_math.h)
+        if (j == 8) rt48 = rows_sum4(sc_add1(rt48v[0], rt48v[1])) + rt48n;
+        prodE(2); DSA_SB(); if (vw) { vecD(1); vecH(1); } DSA_SB();
+        eh_p = eh;
+#pragma unroll
+        for (int it = 0; it < 3; ++it) eah[it] = eah_n[it];
+    }
+#undef DSA_SB
+    rt48 = __builtin_ldexpf(rt48, back);
+}
+
 template <int WAVES, bool FUSED = false, bool HIST_RT = false, bool PADM = false>   // HIST_RT: also keep every step's rt row (its own
                                                                  // instantiation: the plain kernels' code and register allocation are
                                                                  // untouched); PADM: the options instantiation -- reflect / replicate /
@@ -155,7 +290,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) DSA_PK_TARGET void mcep_mfma
     const float* __restrict__ X, long F, int n_iter, const float* __restrict__ G,
     const float* __restrict__ D, const float* __restrict__ E, const float* __restrict__ av,
     float* __restrict__ mc_out, float* __restrict__ hist, long ntiles16, long tiles_shared,
-    unsigned int* __restrict__ queue, const _Float16* __restrict__ img, StftIn sti, float* __restrict__ hist_rt, int tail_wgs, float tau)
+    unsigned int* __restrict__ queue, const _Float16* __restrict__ img, StftIn sti, float* __restrict__ hist_rt, int tail_wgs, float tau, int n_coarse)
 {
     // hist_rt (round 5; NULL or (n_iter, F, 49)): every step's rt = e E row, kept for the backward, which then skips its own second
     // forward chain (DSA_ALGO_HIST_HAS_RT; 196 more bytes per frame and step)
@@ -181,6 +316,8 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) DSA_PK_TARGET void mcep_mfma
     if (tid < 48) lds[H_E256 + tid] = SE * E[H * M2 + tid];
     if (tid == 48) lds[H_E256 + 48] = E[H * M2 + 48];
     if (tid == 50) lds[H_E256 + 50] = tau;   // (a free slot of the region) the stopping rule's threshold, read where it is used
+    if (tid == 49) lds[H_E256 + 49] = kNeg2Log2e * D[0];   // row 0 of D is constant over the bins: the gain residual of a coarse step
+    if (tid == 51) lds[H_E256 + 51] = __int_as_float(n_coarse);   // (likewise) the number of coarse steps, read once per step
     if (tid < 32) lds[H_D256 + tid] = tid < M1 ? kNeg2Log2e * D[tid * K + H] : 0.f;
     if (tid < 28) {
         const float a_ = tid < M1 ? av[tid] : 0.f;
@@ -256,7 +393,8 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) DSA_PK_TARGET void mcep_mfma
 #endif
         const long f_raw = tile * 16 + n;
         const bool f_ok = f_raw < F;
-        const long f = f_ok ? f_raw : F - 1;
+        // (the fused launches have F < 2^31, host-checked: the frame index is ONE register across the Newton loop)
+        const std::conditional_t<FUSED, int, long> f = f_ok ? f_raw : F - 1;
 
         f32x4 logx[16];
         float logx256;
@@ -635,7 +773,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) DSA_PK_TARGET void mcep_mfma
             for (int i = 0; i < 8; ++i) mcv[i] = rt_lds[8 * g + i];  // coefficients >= 25 come out 0
             __builtin_amdgcn_wave_barrier();
         }
-        if (!(DSA_FUSED_DBG & 8) && hist && f_ok) store_mc_row(hist + f * M1, g, mcv);
+        if (!(DSA_FUSED_DBG & 8) && hist && f_ok) store_mc_row(hist + (long)f * M1, g, mcv);
 
         DSA_STAMP_T(18);
         // Ticket for this wave's next tile, drawn now: the atomic's round trip hides behind the iterations.
@@ -664,6 +802,10 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) DSA_PK_TARGET void mcep_mfma
         }
         unsigned frozen = 0u;   // frames whose iteration has stopped, frame n at bits n and n + 16 (see the end of the step)
         rt_lds[H_UPREV] = 0.f;  // no update before the first step (the fused prologue's tile in this region has been consumed)
+        // Round 11: is the NEXT step coarse?  Read from LDS one step ahead -- here for step 1, with the stopping rule's reads for the
+        // steps after it -- so that the branch at the head of a step does not wait for an LDS round trip: the flag lives in one scalar
+        // register from the end of a step to the head of the next, and nothing of it across the chains or the solve.
+        bool coarse_next = 0 < __builtin_amdgcn_readfirstlane(__float_as_int(lds[H_E256 + 51]));
         for (int iter = 0; iter < n_iter; ++iter) {
             DSA_STAMPS_DECL;
             DSA_STAMP(0);
@@ -673,190 +815,198 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) DSA_PK_TARGET void mcep_mfma
             float rt48 = logx256;
             const int back = 0;
 #else
-            // ------------- first chain: t = log2 X - 2 log2(e) d,  d^T = D^T mc^T  (mcep.py:210-212) -----
-            f16x8 bh, bl;
-#pragma unroll
-            for (int i = 0; i < 8; i += 2) {
-                f16x2 h, l;
-                split2(mcv[i] * SM, mcv[i + 1] * SM, h, l);
-                bh[i] = h[0]; bh[i + 1] = h[1];
-                bl[i] = l[0]; bl[i + 1] = l[1];
-            }
-            float d256 = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) d256 = __builtin_fmaf(mcv[i], lds[H_D256 + 8 * g + i], d256);
-            d256 = rows_sum4(d256);
-            const float t256 = logx256 + d256;
-            DSA_STAMP(6);
-            // Round 3: the two chains as an explicit software pipeline, the first chain run ONCE.
-            // A wave issues in order, at most one instruction per ~4.3 cycles whatever its kind (tools/bench_issue.cpp), and a
-            // binary16 product occupies the matrix pipe for 16 cycles; a product that accumulates into the result of the
-            // previous one waits out its full latency (27 cycles per product measured for two interleaved chains).  Left to the
-            // compiler, the products came out in clusters with the wave's own vector work waiting behind them (one wave alone
-            // spent 6.8 k cycles in this phase against 2.7 k of matrix time and ~2 k of vector time).  Here every product is
-            // followed by a few vector instructions of the PREVIOUS group of tiles (sched_barrier pins the order between the slots,
-            // LDS reads included: the operand images are read one body ahead of their products), and products into one
-            // accumulator are at least four slots apart.
-            // With the elimination in register quadruples that are dead during this phase there is room to KEEP t (64
-            // registers): the first chain no longer runs a second time for the shifted exponent (48 products, 16 LDS reads and
-            // their issue slots per step); the shift is one packed add per value pair.
-#define DSA_SB() __builtin_amdgcn_sched_barrier(0x0004)
-            const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-            f32x4 tt[16];
-            float tmax = t256;
-            {
-                // pass A: t = log2 X + (D^T mc^T) / (SD SM) in groups of four tiles, running maximum
-                f16x8 al[4], ah[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { al[i] = DL[i * 64]; ah[i] = DH[i * 64]; }
-                f32x4 c[4] = {zero4, zero4, zero4, zero4}, pc[4] = {zero4, zero4, zero4, zero4};
-#pragma unroll
-                for (int q = 0; q < 5; ++q) {
-                    const bool pm = q < 4, vw = q > 0;   // products of group q, vector work of group q - 1
-                    f16x8 ah_n[4] = {ah[0], ah[1], ah[2], ah[3]};
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        if (q < 3) ah_n[i] = DH[(4 * q + 4 + i) * 64];
-                        if (pm) c[i] = mfma_h(al[i], bh, zero4);
-                        DSA_SB();
-                        if (vw) tt[4 * q - 4 + i] = f32x4{0.f, 0.f, 0.f, 0.f};
-                        if (vw) {
-                            const f32x2v ta = fma2(lo2(pc[i]), kInvSDM, lo2(logx[4 * q - 4 + i]));
-                            const f32x2v tb = fma2(hi2(pc[i]), kInvSDM, hi2(logx[4 * q - 4 + i]));
-                            tt[4 * q - 4 + i] = f32x4{ta[0], ta[1], tb[0], tb[1]};
-                        }
-                        DSA_SB();
-                    }
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        if (pm) c[i] = mfma_h(ah[i], bl, c[i]);
-                        if (q < 3) al[i] = DL[(4 * q + 4 + i) * 64];
-                        DSA_SB();
-                        if (vw) {
-                            const f32x4 v = tt[4 * q - 4 + i];
-                            tmax = __builtin_fmaxf(__builtin_fmaxf(tmax, v[0]), v[1]);
-                            tmax = __builtin_fmaxf(__builtin_fmaxf(tmax, v[2]), v[3]);
-                        }
-                        DSA_SB();
-                    }
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        if (pm) c[i] = mfma_h(ah[i], bh, c[i]);
-                        DSA_SB();
-                    }
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) { pc[i] = c[i]; ah[i] = ah_n[i]; }
-                }
-            }
-            DSA_STAMP(7);
-            // operands of the first body of pass B, read behind the reduction of the maximum
-            f16x8 eah[3], eal[3];
-#pragma unroll
-            for (int it = 0; it < 3; ++it) { eah[it] = EH[(it * 8) * 64]; eal[it] = EL[(it * 8) * 64]; }
-            tmax = rows_max4(tmax);
-            const float mi = __builtin_ceilf(tmax);
-            const float sh = (float)EMAX_LOG2 - mi;
-            const int back = (int)mi - EMAX_LOG2;  // rt = 2^back (scaled sums)
-            DSA_STAMP(8);
-
-            // ------------- pass B: e = exp2(t + sh), second chain rt^T += E^T e^T  (mcep.py:212-215).  Body j: the nine products
-            // for bins 32 (j - 1) .. (three terms x three output tiles), one per slot, around the vector work of bins 32 j ..
-            // (shift, exp2, the rt[48] column, the binary16 split) -------------
-            // the Nyquist bin first: rt[16 it + 4 g + r] = E[256][.] e[256] preloads the accumulators of the second chain (body 0 has
-            // no products to wait for), its share of rt[48] is added with the reduction at the end
-            const float e256 = __builtin_amdgcn_exp2f(t256 + sh);
             f32x4 accB[3];
-#pragma unroll
-            for (int it = 0; it < 3; ++it) accB[it] = *reinterpret_cast<const f32x4*>(lds + H_E256 + it * 16 + 4 * g) * e256;
-            const float rt48n = e256 * lds[H_E256 + 48];
-            f32x2v rt48v = {0.f, 0.f};
             float rt48 = 0.f;
-            f16x8 eh_p = {}, el_p = {};
-            DSA_SB();
+            int back = 0;
+            // Round 11: step k (1-based) is coarse when k <= n_coarse = clamp(n_iter - 6, 0, 2) (the launcher's; 0 with
+            // DSA_ALGO_FULL_CHAINS) -- a static schedule: a frame's bits still depend on nothing but its own values.  The count comes from
+            // LDS like tau (a live kernel argument costs the fused instantiations scratch); the branch is wave-uniform.
+            if (coarse_next) {
+                chains_hi_only(mcv, logx, logx256, DH, EH, E484, lds, g, accB, rt48, back);
+            } else {
+                // ------------- first chain: t = log2 X - 2 log2(e) d,  d^T = D^T mc^T  (mcep.py:210-212) -----
+                f16x8 bh, bl;
 #pragma unroll
-            for (int j = 0; j < 9; ++j) {
-                f16x8 eh = eh_p, el = el_p;
-                f16x8 eah_n[3] = {eah[0], eah[1], eah[2]};
-                f32x4 c48[2] = {zero4, zero4};
-                if (j < 8) {
-                    c48[0] = E484[(2 * j) * 4 + g];
-                    c48[1] = E484[(2 * j + 1) * 4 + g];
-                }
-                if (j > 0 && j < 8) {
-#pragma unroll
-                    for (int it = 0; it < 3; ++it) eah_n[it] = EH[(it * 8 + j) * 64];
-                }
-                auto prodE = [&](int i) __attribute__((always_inline)) {   // i = 3 term + it
-                    if (j > 0) {
-                        const int it = i % 3, term = i / 3;
-                        accB[it] = mfma_h(term == 0 ? eal[it] : eah[it], term == 1 ? el_p : eh_p, accB[it]);
-                    }
-                };
-                f32x2v ta[2], tb[2];
-                float e[2][4];
-                auto vecA = [&](int t_) __attribute__((always_inline)) {
-                    const f32x4 v = tt[(2 * j + t_) & 15];
-                    ta[t_] = lo2(v) + f32x2v{sh, sh};
-                    tb[t_] = hi2(v) + f32x2v{sh, sh};
-                };
-                auto vecB = [&](int t_) __attribute__((always_inline)) {
-                    e[t_][0] = __builtin_amdgcn_exp2f(ta[t_][0]);  // mcep.py:212
-                    e[t_][1] = __builtin_amdgcn_exp2f(ta[t_][1]);
-                };
-                auto vecC = [&](int t_) __attribute__((always_inline)) {
-                    e[t_][2] = __builtin_amdgcn_exp2f(tb[t_][0]);
-                    e[t_][3] = __builtin_amdgcn_exp2f(tb[t_][1]);
-                };
-                auto vecD = [&](int t_) __attribute__((always_inline)) {
-                    rt48v = f32x2v{e[t_][0], e[t_][1]} * lo2(c48[t_]) + rt48v;
-                    rt48v = f32x2v{e[t_][2], e[t_][3]} * hi2(c48[t_]) + rt48v;
-                };
-                auto vecE = [&](int t_, int r) __attribute__((always_inline)) {
+                for (int i = 0; i < 8; i += 2) {
                     f16x2 h, l;
-                    split2(e[t_][r], e[t_][r + 1], h, l);
-                    eh[4 * t_ + r] = h[0]; eh[4 * t_ + r + 1] = h[1];
-                    el[4 * t_ + r] = l[0]; el[4 * t_ + r + 1] = l[1];
-                };
-                const bool vw = j < 8;   // body 8 only drains the second chain
-                prodE(0); DSA_SB(); if (vw) { vecA(0); vecB(0); } DSA_SB();
-                prodE(1); DSA_SB(); if (vw) { vecC(0); vecA(1); } DSA_SB();
-                if (j == 8) rt48 = rows_sum4(rt48v[0] + rt48v[1]) + rt48n;   // the drain body has room for the rt[48] reduction
-                prodE(2);
-                if (j > 0 && j < 8) {
-#pragma unroll
-                    for (int it = 0; it < 3; ++it) eal[it] = EL[(it * 8 + j) * 64];
+                    split2(mcv[i] * SM, mcv[i + 1] * SM, h, l);
+                    bh[i] = h[0]; bh[i + 1] = h[1];
+                    bl[i] = l[0]; bl[i + 1] = l[1];
                 }
-                DSA_SB(); if (vw) { vecD(0); vecB(1); } DSA_SB();
-                // the binary16 split of e: in the one-launch kernel a tile's four values go in ONE slot with the half-register writes of
-                // the two pairs interleaved (split4: 3 of 4 wait states gone; fused step 0.5927 -> 0.5882 ms); in the spectrogram-in
-                // kernel the four separate slots measure faster (0.5223 against 0.5280 ms), so each keeps its own schedule
-                auto vecE4 = [&](int t_) __attribute__((always_inline)) {
-                    f16x2 h0, h1, l0, l1;
-                    split4(e[t_][0], e[t_][1], e[t_][2], e[t_][3], h0, h1, l0, l1);
-                    eh[4 * t_] = h0[0]; eh[4 * t_ + 1] = h0[1]; eh[4 * t_ + 2] = h1[0]; eh[4 * t_ + 3] = h1[1];
-                    el[4 * t_] = l0[0]; el[4 * t_ + 1] = l0[1]; el[4 * t_ + 2] = l1[0]; el[4 * t_ + 3] = l1[1];
-                };
-                if constexpr (FUSED) {
-                    prodE(3); DSA_SB(); if (vw) vecE4(0); DSA_SB();
-                    prodE(4); DSA_SB(); if (vw) { vecC(1); vecD(1); } DSA_SB();
-                    prodE(5); DSA_SB();
-                    prodE(6); DSA_SB(); if (vw) vecE4(1); DSA_SB();
-                    prodE(7); DSA_SB();
-                } else {
-                    prodE(3); DSA_SB(); if (vw) vecE(0, 0); DSA_SB();
-                    prodE(4); DSA_SB(); if (vw) { vecC(1); vecD(1); } DSA_SB();
-                    prodE(5); DSA_SB(); if (vw) vecE(0, 2); DSA_SB();
-                    prodE(6); DSA_SB(); if (vw) vecE(1, 0); DSA_SB();
-                    prodE(7); DSA_SB(); if (vw) vecE(1, 2); DSA_SB();
-                }
-                prodE(8); DSA_SB();
-                eh_p = eh; el_p = el;
+                float d256 = 0.f;
 #pragma unroll
-                for (int it = 0; it < 3; ++it) eah[it] = eah_n[it];
-            }
+                for (int i = 0; i < 8; ++i) d256 = __builtin_fmaf(mcv[i], lds[H_D256 + 8 * g + i], d256);
+                d256 = rows_sum4(d256);
+                const float t256 = logx256 + d256;
+                DSA_STAMP(6);
+                // Round 3: the two chains as an explicit software pipeline, the first chain run ONCE.
+                // A wave issues in order, at most one instruction per ~4.3 cycles whatever its kind (tools/bench_issue.cpp), and a
+                // binary16 product occupies the matrix pipe for 16 cycles; a product that accumulates into the result of the
+                // previous one waits out its full latency (27 cycles per product measured for two interleaved chains).  Left to the
+                // compiler, the products came out in clusters with the wave's own vector work waiting behind them (one wave alone
+                // spent 6.8 k cycles in this phase against 2.7 k of matrix time and ~2 k of vector time).  Here every product is
+                // followed by a few vector instructions of the PREVIOUS group of tiles (sched_barrier pins the order between the slots,
+                // LDS reads included: the operand images are read one body ahead of their products), and products into one
+                // accumulator are at least four slots apart.
+                // With the elimination in register quadruples that are dead during this phase there is room to KEEP t (64
+                // registers): the first chain no longer runs a second time for the shifted exponent (48 products, 16 LDS reads and
+                // their issue slots per step); the shift is one packed add per value pair.
+#define DSA_SB() __builtin_amdgcn_sched_barrier(0x0004)
+                const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+                f32x4 tt[16];
+                float tmax = t256;
+                {
+                    // pass A: t = log2 X + (D^T mc^T) / (SD SM) in groups of four tiles, running maximum
+                    f16x8 al[4], ah[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) { al[i] = DL[i * 64]; ah[i] = DH[i * 64]; }
+                    f32x4 c[4] = {zero4, zero4, zero4, zero4}, pc[4] = {zero4, zero4, zero4, zero4};
+#pragma unroll
+                    for (int q = 0; q < 5; ++q) {
+                        const bool pm = q < 4, vw = q > 0;   // products of group q, vector work of group q - 1
+                        f16x8 ah_n[4] = {ah[0], ah[1], ah[2], ah[3]};
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            if (q < 3) ah_n[i] = DH[(4 * q + 4 + i) * 64];
+                            if (pm) c[i] = mfma_h(al[i], bh, zero4);
+                            DSA_SB();
+                            if (vw) tt[4 * q - 4 + i] = f32x4{0.f, 0.f, 0.f, 0.f};
+                            if (vw) {
+                                const f32x2v ta = fma2(lo2(pc[i]), kInvSDM, lo2(logx[4 * q - 4 + i]));
+                                const f32x2v tb = fma2(hi2(pc[i]), kInvSDM, hi2(logx[4 * q - 4 + i]));
+                                tt[4 * q - 4 + i] = f32x4{ta[0], ta[1], tb[0], tb[1]};
+                            }
+                            DSA_SB();
+                        }
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            if (pm) c[i] = mfma_h(ah[i], bl, c[i]);
+                            if (q < 3) al[i] = DL[(4 * q + 4 + i) * 64];
+                            DSA_SB();
+                            if (vw) {
+                                const f32x4 v = tt[4 * q - 4 + i];
+                                tmax = __builtin_fmaxf(__builtin_fmaxf(tmax, v[0]), v[1]);
+                                tmax = __builtin_fmaxf(__builtin_fmaxf(tmax, v[2]), v[3]);
+                            }
+                            DSA_SB();
+                        }
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            if (pm) c[i] = mfma_h(ah[i], bh, c[i]);
+                            DSA_SB();
+                        }
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) { pc[i] = c[i]; ah[i] = ah_n[i]; }
+                    }
+                }
+                DSA_STAMP(7);
+                // operands of the first body of pass B, read behind the reduction of the maximum
+                f16x8 eah[3], eal[3];
+#pragma unroll
+                for (int it = 0; it < 3; ++it) { eah[it] = EH[(it * 8) * 64]; eal[it] = EL[(it * 8) * 64]; }
+                tmax = rows_max4(tmax);
+                const float mi = __builtin_ceilf(tmax);
+                const float sh = (float)EMAX_LOG2 - mi;
+                back = (int)mi - EMAX_LOG2;  // rt = 2^back (scaled sums)
+                DSA_STAMP(8);
+
+                // ------------- pass B: e = exp2(t + sh), second chain rt^T += E^T e^T  (mcep.py:212-215).  Body j: the nine products
+                // for bins 32 (j - 1) .. (three terms x three output tiles), one per slot, around the vector work of bins 32 j ..
+                // (shift, exp2, the rt[48] column, the binary16 split) -------------
+                // the Nyquist bin first: rt[16 it + 4 g + r] = E[256][.] e[256] preloads the accumulators of the second chain (body 0 has
+                // no products to wait for), its share of rt[48] is added with the reduction at the end
+                const float e256 = __builtin_amdgcn_exp2f(t256 + sh);
+#pragma unroll
+                for (int it = 0; it < 3; ++it) accB[it] = *reinterpret_cast<const f32x4*>(lds + H_E256 + it * 16 + 4 * g) * e256;
+                const float rt48n = e256 * lds[H_E256 + 48];
+                f32x2v rt48v = {0.f, 0.f};
+                f16x8 eh_p = {}, el_p = {};
+                DSA_SB();
+#pragma unroll
+                for (int j = 0; j < 9; ++j) {
+                    f16x8 eh = eh_p, el = el_p;
+                    f16x8 eah_n[3] = {eah[0], eah[1], eah[2]};
+                    f32x4 c48[2] = {zero4, zero4};
+                    if (j < 8) {
+                        c48[0] = E484[(2 * j) * 4 + g];
+                        c48[1] = E484[(2 * j + 1) * 4 + g];
+                    }
+                    if (j > 0 && j < 8) {
+#pragma unroll
+                        for (int it = 0; it < 3; ++it) eah_n[it] = EH[(it * 8 + j) * 64];
+                    }
+                    auto prodE = [&](int i) __attribute__((always_inline)) {   // i = 3 term + it
+                        if (j > 0) {
+                            const int it = i % 3, term = i / 3;
+                            accB[it] = mfma_h(term == 0 ? eal[it] : eah[it], term == 1 ? el_p : eh_p, accB[it]);
+                        }
+                    };
+                    f32x2v ta[2], tb[2];
+                    float e[2][4];
+                    auto vecA = [&](int t_) __attribute__((always_inline)) {
+                        const f32x4 v = tt[(2 * j + t_) & 15];
+                        ta[t_] = lo2(v) + f32x2v{sh, sh};
+                        tb[t_] = hi2(v) + f32x2v{sh, sh};
+                    };
+                    auto vecB = [&](int t_) __attribute__((always_inline)) {
+                        e[t_][0] = __builtin_amdgcn_exp2f(ta[t_][0]);  // mcep.py:212
+                        e[t_][1] = __builtin_amdgcn_exp2f(ta[t_][1]);
+                    };
+                    auto vecC = [&](int t_) __attribute__((always_inline)) {
+                        e[t_][2] = __builtin_amdgcn_exp2f(tb[t_][0]);
+                        e[t_][3] = __builtin_amdgcn_exp2f(tb[t_][1]);
+                    };
+                    auto vecD = [&](int t_) __attribute__((always_inline)) {
+                        rt48v = f32x2v{e[t_][0], e[t_][1]} * lo2(c48[t_]) + rt48v;
+                        rt48v = f32x2v{e[t_][2], e[t_][3]} * hi2(c48[t_]) + rt48v;
+                    };
+                    auto vecE = [&](int t_, int r) __attribute__((always_inline)) {
+                        f16x2 h, l;
+                        split2(e[t_][r], e[t_][r + 1], h, l);
+                        eh[4 * t_ + r] = h[0]; eh[4 * t_ + r + 1] = h[1];
+                        el[4 * t_ + r] = l[0]; el[4 * t_ + r + 1] = l[1];
+                    };
+                    const bool vw = j < 8;   // body 8 only drains the second chain
+                    prodE(0); DSA_SB(); if (vw) { vecA(0); vecB(0); } DSA_SB();
+                    prodE(1); DSA_SB(); if (vw) { vecC(0); vecA(1); } DSA_SB();
+                    if (j == 8) rt48 = rows_sum4(rt48v[0] + rt48v[1]) + rt48n;   // the drain body has room for the rt[48] reduction
+                    prodE(2);
+                    if (j > 0 && j < 8) {
+#pragma unroll
+                        for (int it = 0; it < 3; ++it) eal[it] = EL[(it * 8 + j) * 64];
+                    }
+                    DSA_SB(); if (vw) { vecD(0); vecB(1); } DSA_SB();
+                    // the binary16 split of e: in the one-launch kernel a tile's four values go in ONE slot with the half-register writes of
+                    // the two pairs interleaved (split4: 3 of 4 wait states gone; fused step 0.5927 -> 0.5882 ms); in the spectrogram-in
+                    // kernel the four separate slots measure faster (0.5223 against 0.5280 ms), so each keeps its own schedule
+                    auto vecE4 = [&](int t_) __attribute__((always_inline)) {
+                        f16x2 h0, h1, l0, l1;
+                        split4(e[t_][0], e[t_][1], e[t_][2], e[t_][3], h0, h1, l0, l1);
+                        eh[4 * t_] = h0[0]; eh[4 * t_ + 1] = h0[1]; eh[4 * t_ + 2] = h1[0]; eh[4 * t_ + 3] = h1[1];
+                        el[4 * t_] = l0[0]; el[4 * t_ + 1] = l0[1]; el[4 * t_ + 2] = l1[0]; el[4 * t_ + 3] = l1[1];
+                    };
+                    if constexpr (FUSED) {
+                        prodE(3); DSA_SB(); if (vw) vecE4(0); DSA_SB();
+                        prodE(4); DSA_SB(); if (vw) { vecC(1); vecD(1); } DSA_SB();
+                        prodE(5); DSA_SB();
+                        prodE(6); DSA_SB(); if (vw) vecE4(1); DSA_SB();
+                        prodE(7); DSA_SB();
+                    } else {
+                        prodE(3); DSA_SB(); if (vw) vecE(0, 0); DSA_SB();
+                        prodE(4); DSA_SB(); if (vw) { vecC(1); vecD(1); } DSA_SB();
+                        prodE(5); DSA_SB(); if (vw) vecE(0, 2); DSA_SB();
+                        prodE(6); DSA_SB(); if (vw) vecE(1, 0); DSA_SB();
+                        prodE(7); DSA_SB(); if (vw) vecE(1, 2); DSA_SB();
+                    }
+                    prodE(8); DSA_SB();
+                    eh_p = eh; el_p = el;
+#pragma unroll
+                    for (int it = 0; it < 3; ++it) eah[it] = eah_n[it];
+                }
 #undef DSA_SB
-            DSA_STAMP(9);
-            rt48 = __builtin_ldexpf(rt48, back);
+                DSA_STAMP(9);
+                rt48 = __builtin_ldexpf(rt48, back);
+            }
 #endif
 
             // ------------- rt and its reflection into this frame's LDS windows -------------
@@ -993,8 +1143,15 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) DSA_PK_TARGET void mcep_mfma
             // |x|_inf is formed on the bit patterns (unsigned maximum of |x|): a NaN is larger than every number there, stays a NaN as a
             // float and compares false in both clauses, where a float maximum would drop it.  It is reduced over the frame's four
             // lane groups, so the four lanes decide alike and the ballot needs no combining.
+            // Round 11: no frame stops on a COARSE step -- a small update there is no evidence of a small error.  The step takes a negative
+            // threshold (both clauses false, as with DSA_ALGO_FIXED_STEPS) and leaves u_prev = 0 behind, so the second clause is false on
+            // the first full step as it is at step 1.  (The count is read again here: nothing of it lives across the solve.  The same read
+            // tells the next step's head which chain phase to run.)
             {
-                const float tau = lds[H_E256 + 50];
+                const int n_coarse_now = __builtin_amdgcn_readfirstlane(__float_as_int(lds[H_E256 + 51]));
+                const bool coarse = iter < n_coarse_now;
+                coarse_next = iter + 1 < n_coarse_now;
+                const float tau = coarse ? -1.f : lds[H_E256 + 50];
                 float mabs = __builtin_fmaxf(__builtin_fabsf(mcv[0]), __builtin_fabsf(mcv[1]));
 #pragma unroll
                 for (int i = 2; i < 8; ++i) mabs = __builtin_fmaxf(mabs, __builtin_fabsf(mcv[i]));
@@ -1009,7 +1166,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) DSA_PK_TARGET void mcep_mfma
                 const float xinf = __uint_as_float(rows_maxu4(xb));
                 const float u = xinf * __builtin_amdgcn_rcpf(mnorm);
                 const float u_prev = rt_lds[H_UPREV];
-                rt_lds[H_UPREV] = u;
+                rt_lds[H_UPREV] = coarse ? 0.f : u;
                 // (bitwise on purpose: && / || on lane-dependent conditions become exec-mask branches)
                 const bool small = (xinf <= thr) | ((xinf <= STOP_FACTOR * thr) & (STOP_FACTOR * u <= u_prev));
                 const unsigned conv = (unsigned)__builtin_amdgcn_ballot_w64(small);   // frame n at bits n and n + 16 (and n + 32, n + 48)
@@ -1032,7 +1189,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES / 4) DSA_PK_TARGET void mcep_mfma
             if (!hist && frozen == 0xffffffffu) break;
         }
         DSA_STAMP_T(19);
-        if (f_ok) store_mc_row(mc_out + f * M1, g, mcv);
+        if (f_ok) store_mc_row(mc_out + (long)f * M1, g, mcv);
         DSA_STAMP_T(20);
         tile = tile_next;
         DSA_STAMP_T(21);

@@ -16,11 +16,11 @@ int mcep_mfma_prepare(const void* G, const void* D, const void* E, void* images,
 int mcep_mfma_fwd(const void* X, int64_t F, int n_iter, const void* G, const void* D, const void* E, const void* av,
                   const void* images, void* scratch, void* mc, void* hist, hipStream_t st, bool scratch_clean = false,
                   const StftIn* sti = nullptr, bool hist_has_rt = false, bool overlapped = false, int reserve_cus = 0,
-                  bool fixed_steps = false);
+                  bool fixed_steps = false, bool full_chains = false);
 int stft_mcep_fused_fwd(const void* x, int64_t B, int64_t T, int P, int center, const void* window, const void* twiddle, double eps,
                         int n_iter, const void* G, const void* D, const void* E, const void* av, const void* images, void* scratch,
                         void* mc, void* hist, void* X_out, hipStream_t st, bool scratch_clean, bool hist_has_rt, bool overlapped, int pad_mode,
-                        int zmean, float floor_lin, int reserve_cus, bool fixed_steps);
+                        int zmean, float floor_lin, int reserve_cus, bool fixed_steps, bool full_chains);
 
 // ---- csrc/mcep_mfma_bwd.hip: its backward (mcep_mfma_bwd_f16.h, mcep_mfma_bwd2_f16.h)
 int mcep_mfma_bwd(const void* gmc, const void* X, const void* hist, int64_t F, int n_iter, const void* av,

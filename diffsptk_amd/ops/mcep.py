@@ -421,6 +421,29 @@ class fixed_newton_steps:
         return False
 
 
+_full_chains = [False]
+
+
+class full_precision_chains:
+    """``with ops.full_precision_chains():`` -- the tuned mel-cepstral forward launches run every Newton step on three-term binary16
+    chains (DSA_ALGO_FULL_CHAINS, include/diffsptk_amd.h; the environment form is DSA_MCEP_FULL_CHAINS=1).  By default step k is coarse
+    when k <= clamp(n_iter - 6, 0, 2): one product per chain instead of three, operands good to 2^-11, with at least six full steps
+    behind it -- Newton's method removes an early step's rounding error.  Inside the context the results are those of the kernels
+    before the coarse steps bit for bit; together with fixed_newton_steps(), those of the fixed-step kernels."""
+
+    def __init__(self, on: bool = True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.prev = _full_chains[0]
+        _full_chains[0] = self.on
+        return self
+
+    def __exit__(self, *exc):
+        _full_chains[0] = self.prev
+        return False
+
+
 _reserved_cus = [0]
 
 
@@ -446,9 +469,9 @@ class reserve_cus:
 
 def _mcep_algo(clean: bool) -> int:
     """The algo bits of a tuned mel-cepstral forward launch: DSA_ALGO_SCRATCH_IS_CLEAN with DSA_ALGO_OVERLAPPED_LAUNCHES
-    (overlapped_launches()) on the kept-zero scratch, DSA_ALGO_RESERVE_CUS (reserve_cus()) and DSA_ALGO_FIXED_STEPS
-    (fixed_newton_steps())."""
-    flag = _lib.algo_reserve_cus(_reserved_cus[0]) | (_lib.ALGO_FIXED_STEPS if _fixed_steps[0] else 0)
+    (overlapped_launches()) on the kept-zero scratch, DSA_ALGO_RESERVE_CUS (reserve_cus()), DSA_ALGO_FIXED_STEPS
+    (fixed_newton_steps()) and DSA_ALGO_FULL_CHAINS (full_precision_chains())."""
+    flag = _lib.algo_reserve_cus(_reserved_cus[0]) | (_lib.ALGO_FIXED_STEPS if _fixed_steps[0] else 0) | (_lib.ALGO_FULL_CHAINS if _full_chains[0] else 0)
     if clean:
         flag |= _lib.ALGO_SCRATCH_IS_CLEAN | (_lib.ALGO_OVERLAPPED_LAUNCHES if _overlapped[0] else 0)
     return flag

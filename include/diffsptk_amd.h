@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define DSA_VERSION 143 /* 0.3.7: + dsa_vq_search / dsa_vq_accum / dsa_vq_update / dsa_vq_lookup / dsa_vq_vjp (vector quantisation and the Linde-Buzo-Gray codebook design: nearest-codeword search on float64 sums, per-codeword counts and float64 sums in fixed-order segments without atomics, centroids with the iteration's three scalars, the lookup and the quantiser's adjoint); 0.3.6: + dsa_yingram / dsa_yingram_vjp / dsa_frame_yingram (Yingram: YIN's cumulative-mean-normalised difference function on a semitone grid, from frames or from the waveform in one launch, and its adjoint; lag sums directly or through the LDS transform); 0.3.5: + dsa_gmm_prepare / dsa_gmm_estep / dsa_gmm_accum / dsa_gmm_update / dsa_gmm_regress / dsa_gmm_transform (Gaussian mixture models: one EM iteration as factorisation, E-step, weighted moment sums and M-step on the device, and the conversion of a joint-density model); 0.3.4: + dsa_dtw / dsa_dtw_vjp / dsa_dtw_path (dynamic time warping with a soft minimum: the aligned distance of two vector sequences by an anti-diagonal wavefront, its gradient by the reverse sweep, the Viterbi path from the saved tables); 0.3.3: + DSA_ALGO_FIXED_STEPS (the tuned mel-cepstral forward stops a frame's Newton iteration once its update is rounding noise; the flag runs every step); 0.3.2: + dsa_delta / dsa_delta_vjp, dsa_mlpg, dsa_mcpf / dsa_mcpf_vjp (parameter generation: delta features, maximum likelihood parameter generation by a banded Cholesky solve, mel-cepstrum postfiltering in closed form); 0.3.1: + dsa_mdct_analysis / dsa_mdct_synthesis (MDCT / MDST and their inverses: window, fold, DCT-IV through a quarter-length complex FFT and overlap-add in one launch each way; each is the other's adjoint); 0.3.0: + dsa_excite (pitch to excitation: the voiced shapes of ExcitationGeneration on a segmented float64 phase sum, one launch); 0.2.9: + dsa_mlsacheck / dsa_mlsacheck_vjp (the stability check of the MLSA filter: the mel-cepstrum scaled or clipped where the amplitude of its gain-free part passes the threshold of the Pade approximation, forward and adjoint); 0.2.8: + dsa_lpc2lsp_fwd / _bwd, dsa_lsp2lpc_fwd / _bwd, dsa_lspcheck_fwd / _bwd (line spectral pairs by a Chebyshev-series root search, back by a product of real sections, and their stability check, forward and adjoint); 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
+#define DSA_VERSION 144 /* 0.3.8: + DSA_ALGO_FULL_CHAINS (the tuned mel-cepstral forward runs the first clamp(n_iter - 6, 0, 2) Newton steps on one-term binary16 chains; the flag keeps every step on three terms); 0.3.7: + dsa_vq_search / dsa_vq_accum / dsa_vq_update / dsa_vq_lookup / dsa_vq_vjp (vector quantisation and the Linde-Buzo-Gray codebook design: nearest-codeword search on float64 sums, per-codeword counts and float64 sums in fixed-order segments without atomics, centroids with the iteration's three scalars, the lookup and the quantiser's adjoint); 0.3.6: + dsa_yingram / dsa_yingram_vjp / dsa_frame_yingram (Yingram: YIN's cumulative-mean-normalised difference function on a semitone grid, from frames or from the waveform in one launch, and its adjoint; lag sums directly or through the LDS transform); 0.3.5: + dsa_gmm_prepare / dsa_gmm_estep / dsa_gmm_accum / dsa_gmm_update / dsa_gmm_regress / dsa_gmm_transform (Gaussian mixture models: one EM iteration as factorisation, E-step, weighted moment sums and M-step on the device, and the conversion of a joint-density model); 0.3.4: + dsa_dtw / dsa_dtw_vjp / dsa_dtw_path (dynamic time warping with a soft minimum: the aligned distance of two vector sequences by an anti-diagonal wavefront, its gradient by the reverse sweep, the Viterbi path from the saved tables); 0.3.3: + DSA_ALGO_FIXED_STEPS (the tuned mel-cepstral forward stops a frame's Newton iteration once its update is rounding noise; the flag runs every step); 0.3.2: + dsa_delta / dsa_delta_vjp, dsa_mlpg, dsa_mcpf / dsa_mcpf_vjp (parameter generation: delta features, maximum likelihood parameter generation by a banded Cholesky solve, mel-cepstrum postfiltering in closed form); 0.3.1: + dsa_mdct_analysis / dsa_mdct_synthesis (MDCT / MDST and their inverses: window, fold, DCT-IV through a quarter-length complex FFT and overlap-add in one launch each way; each is the other's adjoint); 0.3.0: + dsa_excite (pitch to excitation: the voiced shapes of ExcitationGeneration on a segmented float64 phase sum, one launch); 0.2.9: + dsa_mlsacheck / dsa_mlsacheck_vjp (the stability check of the MLSA filter: the mel-cepstrum scaled or clipped where the amplitude of its gain-free part passes the threshold of the Pade approximation, forward and adjoint); 0.2.8: + dsa_lpc2lsp_fwd / _bwd, dsa_lsp2lpc_fwd / _bwd, dsa_lspcheck_fwd / _bwd (line spectral pairs by a Chebyshev-series root search, back by a product of real sections, and their stability check, forward and adjoint); 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
 
 typedef enum {
     DSA_OK = 0,
@@ -120,9 +120,18 @@ enum { DSA_ALGO_AUTO = 0, DSA_ALGO_GENERIC = 1, DSA_ALGO_TUNED = 2 };
  * Newton steps only add the solve's rounding error to a finished answer (DESIGN.md 3.1).  The rule reads the frame's own values only, so a frame's result does
  * not depend on its batch, its neighbours or the kernel path; a frame with a NaN never stops early.  Without a history (mc_hist = NULL)
  * a 16-frame tile leaves the step loop once all its frames have stopped; with one, all n_iter steps run with the stopped frames'
- * updates masked, so the iterates repeat from the stopping step on and the rt rows are complete.  With the flag the results are those
- * of 0.3.2 bit for bit.  The generic kernels, dsa_mgcep_* and the 48 kHz family always run exactly n_iter steps. */
+ * updates masked, so the iterates repeat from the stopping step on and the rt rows are complete.  With the flag and DSA_ALGO_FULL_CHAINS the results
+ * are those of 0.3.2 bit for bit.  The generic kernels, dsa_mgcep_* and the 48 kHz family always run exactly n_iter steps. */
 #define DSA_ALGO_FIXED_STEPS 0x4000
+/* OR-ed into `algo` of dsa_mcep_fwd / dsa_stft_mcep_fwd / dsa_stft_mcep_opts_fwd (0.3.8): every Newton step on three-term chains.
+ * Each matrix chain of a step of the tuned forward is three binary16 products, ah bh + ah bl + al bh, for float32-grade accuracy.
+ * Without the flag step k (1-based) is COARSE when k <= clamp(n_iter - 6, 0, 2): its two chains run the ah bh product alone (operands
+ * good to 2^-11).  Newton's method corrects itself: those steps move the iterate by 5e-2 .. 2e-1 of its size, and at least six full
+ * steps follow every coarse one (n_iter <= 6 has none).  The schedule depends on k and n_iter only, with or without
+ * DSA_ALGO_FIXED_STEPS, so a frame's result still depends on nothing but its own values.  No frame stops on a coarse step (all-zero and
+ * padding-like frames, which stopped after step 1 - 2, now run to about step 4 - 5).  With the flag, or DSA_MCEP_FULL_CHAINS=1 in the
+ * environment, the results are those of 0.3.7 bit for bit; with DSA_ALGO_FIXED_STEPS as well, those of 0.3.2. */
+#define DSA_ALGO_FULL_CHAINS 0x8000
 
 int dsa_version(void);
 const char* dsa_last_error(void);

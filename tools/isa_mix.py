@@ -7,7 +7,9 @@ binary16 matrix products run on the separate matrix pipe: 16 cycles each, listed
     python tools/isa_mix.py [diffsptk_amd/lib/libdiffsptk_amd.so] [kernel-name-substring ...]      -> JSON per kernel
     python tools/isa_mix.py --diff parent.so branch.so      -> per-kernel comparison of two builds (diff_libs), exit status 1 if it fails
 
-The loop taken is the LAST innermost loop of the kernel (for the mel-cepstral kernels: the Newton step; one pass = 16 frames)."""
+The loop taken is the LAST innermost loop of the kernel (for the mel-cepstral kernels: the Newton step; one pass = 16 frames).  Where
+that loop holds an if / else whose two arms both contain binary16 matrix products -- the coarse and the full chain phase of the
+tuned forward -- the arms and the rest of the step are listed separately: a pass runs one arm, not both."""
 import collections
 import json
 import os
@@ -182,6 +184,35 @@ def innermost_last_loop(ins):
     return max(inner, key=lambda l: l[1] - l[0]) if inner else None
 
 
+def _target(a, txt):
+    simm = int(txt.split()[0], 0)
+    return a + 4 + 4 * (simm - 0x10000 if simm >= 0x8000 else simm)
+
+
+def chain_arms(ins, lp):
+    """The two arms of the if / else inside the loop `lp` that both hold binary16 matrix products (round 11: the chain phase of a
+    coarse and of a full Newton step): ((start, end), (start, end)) index spans in layout order, or None.  An arm is the span a
+    forward conditional branch of the loop skips; taken are the spans with such products that contain no other such span, and
+    there must be exactly two (the compiler lays the else arm out behind a second test of the condition, not behind an s_branch)."""
+    addr = {a: i for i, (a, _, _) in enumerate(ins)}
+    spans = []
+    for h in range(lp[0], lp[1]):
+        a, op, txt = ins[h]
+        t = addr.get(_target(a, txt), -1) if op.startswith("s_cbranch") else -1
+        if h < t <= lp[1] + 1 and any(op_.startswith("v_mfma") and "f16" in op_ for _, op_, _ in ins[h + 1: t]):
+            spans.append((h + 1, t - 1))
+    inner = [s_ for s_ in spans if not any(o != s_ and s_[0] <= o[0] and o[1] <= s_[1] for o in spans)]
+    return tuple(sorted(inner)) if len(inner) == 2 else None
+
+
+def _summary(part):
+    c, cyc = mix(part)
+    vec = c["valu_multiply_add_class"] + c["valu_two_operand"] + c["valu_transcendental"]
+    return {"instructions": len(part), "counts": dict(c), "f32_datapath_cycles": sum(cyc.values()), "vector_instructions": vec,
+            "xdl_cycles": 16 * c["mfma_f16_xdl"], "v_fma_mix": sum(1 for _, op, _ in part if op.startswith("v_fma_mix")),
+            "lds_reads_16_bytes": sum(1 for _, op, _ in part if op == "ds_read_b128")}
+
+
 def mix(ins):
     c, cyc = collections.Counter(), collections.Counter()
     for _, op, txt in ins:
@@ -228,6 +259,11 @@ def main():
         res[sym] = {"loop_instructions": lp[1] - lp[0] + 1, "counts": dict(c), "f32_datapath_cycles_per_pass": sum(cyc.values()),
                     "vector_instructions_per_pass": vec, "matrix_f32_instructions_per_pass": c["mfma_f32_4x4x1"] + c["mfma_f32_16x16x4"],
                     "xdl_cycles_per_pass": 16 * c["mfma_f16_xdl"], "frames_per_pass": 16}
+        arms = chain_arms(ins, lp)
+        if arms:   # the loop holds BOTH variants of the chain phase; a pass runs one of them
+            parts = sorted((_summary(ins[s0: s1 + 1]) for s0, s1 in arms), key=lambda d: d["xdl_cycles"])
+            res[sym]["chain_phase_coarse"], res[sym]["chain_phase_full"] = parts
+            res[sym]["rest_of_the_step"] = _summary(ins[lp[0]: arms[0][0]] + ins[arms[1][1] + 1: lp[1] + 1])
     print(json.dumps(res, indent=1))
 
 
