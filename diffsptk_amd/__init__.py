@@ -41,6 +41,7 @@ from .modules.mcpf import MelCepstrumPostfiltering
 from .modules.mlpg import MaximumLikelihoodParameterGeneration
 from .modules.mlpg import MaximumLikelihoodParameterGeneration as MLPG
 from .modules.mlsacheck import MLSADigitalFilterStabilityCheck
+from .modules.world_synth import WorldSynthesis
 from .modules.yingram import Yingram
 from .signals import mseq, mseq_like, nrand
 from .utils.public import get_alpha, read, write
@@ -50,4 +51,4 @@ __all__ = [*_module_names, "functional", "get_alpha", "read", "write", "Graphed"
            "ExcitationGeneration", "mseq", "mseq_like", "nrand", "MDCT", "IMDCT", "MDST", "IMDST", "ModifiedDiscreteCosineTransform",
            "InverseModifiedDiscreteCosineTransform", "ModifiedDiscreteSineTransform", "InverseModifiedDiscreteSineTransform", "Delta", "MLPG",
            "MaximumLikelihoodParameterGeneration", "MelCepstrumPostfiltering", "DynamicTimeWarping", "DTW", "GaussianMixtureModeling", "GMM", "Yingram",
-           "VectorQuantization", "InverseVectorQuantization", "LindeBuzoGrayAlgorithm", "LBG"]
+           "VectorQuantization", "InverseVectorQuantization", "LindeBuzoGrayAlgorithm", "LBG", "WorldSynthesis"]

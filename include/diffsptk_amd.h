@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define DSA_VERSION 144 /* 0.3.8: + DSA_ALGO_FULL_CHAINS (the tuned mel-cepstral forward runs the first clamp(n_iter - 6, 0, 2) Newton steps on one-term binary16 chains; the flag keeps every step on three terms); 0.3.7: + dsa_vq_search / dsa_vq_accum / dsa_vq_update / dsa_vq_lookup / dsa_vq_vjp (vector quantisation and the Linde-Buzo-Gray codebook design: nearest-codeword search on float64 sums, per-codeword counts and float64 sums in fixed-order segments without atomics, centroids with the iteration's three scalars, the lookup and the quantiser's adjoint); 0.3.6: + dsa_yingram / dsa_yingram_vjp / dsa_frame_yingram (Yingram: YIN's cumulative-mean-normalised difference function on a semitone grid, from frames or from the waveform in one launch, and its adjoint; lag sums directly or through the LDS transform); 0.3.5: + dsa_gmm_prepare / dsa_gmm_estep / dsa_gmm_accum / dsa_gmm_update / dsa_gmm_regress / dsa_gmm_transform (Gaussian mixture models: one EM iteration as factorisation, E-step, weighted moment sums and M-step on the device, and the conversion of a joint-density model); 0.3.4: + dsa_dtw / dsa_dtw_vjp / dsa_dtw_path (dynamic time warping with a soft minimum: the aligned distance of two vector sequences by an anti-diagonal wavefront, its gradient by the reverse sweep, the Viterbi path from the saved tables); 0.3.3: + DSA_ALGO_FIXED_STEPS (the tuned mel-cepstral forward stops a frame's Newton iteration once its update is rounding noise; the flag runs every step); 0.3.2: + dsa_delta / dsa_delta_vjp, dsa_mlpg, dsa_mcpf / dsa_mcpf_vjp (parameter generation: delta features, maximum likelihood parameter generation by a banded Cholesky solve, mel-cepstrum postfiltering in closed form); 0.3.1: + dsa_mdct_analysis / dsa_mdct_synthesis (MDCT / MDST and their inverses: window, fold, DCT-IV through a quarter-length complex FFT and overlap-add in one launch each way; each is the other's adjoint); 0.3.0: + dsa_excite (pitch to excitation: the voiced shapes of ExcitationGeneration on a segmented float64 phase sum, one launch); 0.2.9: + dsa_mlsacheck / dsa_mlsacheck_vjp (the stability check of the MLSA filter: the mel-cepstrum scaled or clipped where the amplitude of its gain-free part passes the threshold of the Pade approximation, forward and adjoint); 0.2.8: + dsa_lpc2lsp_fwd / _bwd, dsa_lsp2lpc_fwd / _bwd, dsa_lspcheck_fwd / _bwd (line spectral pairs by a Chebyshev-series root search, back by a product of real sections, and their stability check, forward and adjoint); 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
+#define DSA_VERSION 145 /* 0.3.9: + dsa_world_synth_pulses / dsa_world_synth_responses / dsa_world_synth_overlap_add / dsa_world_synth_vjp_pulses / dsa_world_synth_vjp_frames (WORLD synthesis: the time base and pulse list of an utterance in one workgroup, a pulse's periodic and aperiodic response through four complex transforms in LDS, the overlap-add as a gather, and the adjoint down to sp and ap in two launches); 0.3.8: + DSA_ALGO_FULL_CHAINS (the tuned mel-cepstral forward runs the first clamp(n_iter - 6, 0, 2) Newton steps on one-term binary16 chains; the flag keeps every step on three terms); 0.3.7: + dsa_vq_search / dsa_vq_accum / dsa_vq_update / dsa_vq_lookup / dsa_vq_vjp (vector quantisation and the Linde-Buzo-Gray codebook design: nearest-codeword search on float64 sums, per-codeword counts and float64 sums in fixed-order segments without atomics, centroids with the iteration's three scalars, the lookup and the quantiser's adjoint); 0.3.6: + dsa_yingram / dsa_yingram_vjp / dsa_frame_yingram (Yingram: YIN's cumulative-mean-normalised difference function on a semitone grid, from frames or from the waveform in one launch, and its adjoint; lag sums directly or through the LDS transform); 0.3.5: + dsa_gmm_prepare / dsa_gmm_estep / dsa_gmm_accum / dsa_gmm_update / dsa_gmm_regress / dsa_gmm_transform (Gaussian mixture models: one EM iteration as factorisation, E-step, weighted moment sums and M-step on the device, and the conversion of a joint-density model); 0.3.4: + dsa_dtw / dsa_dtw_vjp / dsa_dtw_path (dynamic time warping with a soft minimum: the aligned distance of two vector sequences by an anti-diagonal wavefront, its gradient by the reverse sweep, the Viterbi path from the saved tables); 0.3.3: + DSA_ALGO_FIXED_STEPS (the tuned mel-cepstral forward stops a frame's Newton iteration once its update is rounding noise; the flag runs every step); 0.3.2: + dsa_delta / dsa_delta_vjp, dsa_mlpg, dsa_mcpf / dsa_mcpf_vjp (parameter generation: delta features, maximum likelihood parameter generation by a banded Cholesky solve, mel-cepstrum postfiltering in closed form); 0.3.1: + dsa_mdct_analysis / dsa_mdct_synthesis (MDCT / MDST and their inverses: window, fold, DCT-IV through a quarter-length complex FFT and overlap-add in one launch each way; each is the other's adjoint); 0.3.0: + dsa_excite (pitch to excitation: the voiced shapes of ExcitationGeneration on a segmented float64 phase sum, one launch); 0.2.9: + dsa_mlsacheck / dsa_mlsacheck_vjp (the stability check of the MLSA filter: the mel-cepstrum scaled or clipped where the amplitude of its gain-free part passes the threshold of the Pade approximation, forward and adjoint); 0.2.8: + dsa_lpc2lsp_fwd / _bwd, dsa_lsp2lpc_fwd / _bwd, dsa_lspcheck_fwd / _bwd (line spectral pairs by a Chebyshev-series root search, back by a product of real sections, and their stability check, forward and adjoint); 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
 
 typedef enum {
     DSA_OK = 0,
@@ -1016,6 +1016,63 @@ int dsa_vq_update(const void* workspace, const void* partial, int64_t n_partial,
                   void* n_data, void* pending, void* readback, void* stream);
 int dsa_vq_lookup(const void* indices, const void* codebook, int64_t T, int64_t K, int64_t L, int32_t dtype, void* xq, void* stream);
 int dsa_vq_vjp(const void* g_xq, const void* g_loss, const void* x, const void* xq, int64_t n, int32_t dtype, void* gx, void* stream);
+
+/* ------------------------------------------------------------------ a24  WORLD synthesis: world_synth (0.3.9)
+ * WorldSynthesis.forward, world_synth.py:166-321, with get_minimum_phase_spectrum and interp1 of third_party/world/common.py:73-84, 141-163.
+ * f0:(B,N) in Hz, ap, sp:(B,N,D) with D = L / 2 + 1, all of the dtype (float32 or float64); P = frame_period, L = fft_length; the waveform has
+ * N P samples per utterance.  int64 indexing, no atomics, no allocation: the same inputs give the same bits every run, and an utterance's
+ * bits are those of the utterance run alone.  B = 0, N = 0 or pulses = 0 is a no-op before any pointer is looked at.
+ *   dsa_world_synth_pulses       world_synth.py:193-237, one workgroup per utterance: F0 and the voicing flag interpolated to the samples
+ *                                (interp1 as it is written: arange(T) / sr, arange(N) (P / sr), diff(y) / diff(x), b = y - m x, m xq + b, the
+ *                                segment of searchsorted(right = False) with its padded ends), every product and sum rounded on its own
+ *                                in the dtype; the float64 sum of (tau / sr) f0, added in order by one lane (the bits of torch.cumsum:
+ *                                the fractional shifts follow the last place of the phase), cast to the dtype, fmod tau, a pulse
+ *                                where pi < |the difference of neighbours|.
+ *                                counts:(B) int64 is always written.  With irec = frec = NULL nothing else is; with offsets:(B + 1) int64
+ *                                (the exclusive prefix sums of counts, which the HOST forms: its one read) the pulses of utterance b go,
+ *                                in time order, to rows offsets[b] .. offsets[b + 1] - 1 of irec:(pulses,4) int64 = sample index,
+ *                                utterance, floor frame, ceil frame (both clipped to N - 1) and frec:(pulses,3) of the dtype = the
+ *                                fractional time shift in seconds, the upper weight frame - floor, the voiced flag (0 or 1).
+ *   dsa_world_synth_responses    world_synth.py:233-301, one workgroup per pulse: response:(pulses,L) from the two rows of sp and ap
+ *                                (interpolated, clipped at 1e-6 / 1 - 1e-6), noise:(pulses,L) standard normal numbers, dc_remover:(L) as the
+ *                                module holds it and twiddle:(L,2) = (cos, -sin)(2 pi m / L).  noise_size of a pulse is the distance to the
+ *                                next pulse OF ITS UTTERANCE, 0 for the last one (the reference takes diff over the flattened batch: the
+ *                                last pulse of an utterance that is not the last gets max(0, first index of the next - its own)).
+ *                                sqrt(noise_size) is rounded to float32 in both dtypes, as torch.sqrt of the reference's int64 tensor is.
+ *                                Nothing between the rows and the response leaves LDS.
+ *   dsa_world_synth_overlap_add  world_synth.py:302-315: y:(B,T), T <= N P the output length; y[b,j] = the responses of utterance b that
+ *                                cover sample j + L / 2 of the padded waveform, added in ascending pulse order (a bisection over the
+ *                                sorted indices, one thread per sample).
+ *   dsa_world_synth_vjp_pulses   one workgroup per pulse: the forward again, the response's cotangent read from gy:(B,T) (zero outside it),
+ *                                the adjoint down to grows:(pulses,2,D) = the cotangents of the interpolated sp row and of the
+ *                                interpolated ap row (before squaring).
+ *   dsa_world_synth_vjp_frames   one workgroup per frame: gsp, gap:(B,N,D), every element written: the pulses whose floor or ceil frame
+ *                                it is (one run, by bisection) added in pulse order with the lower / upper weights; exactly zero where
+ *                                sp < 1e-6 or ap outside [1e-6, 1 - 1e-6].  No gradient reaches f0 (the reference detaches it).
+ * The host layer draws the noise with the device's generator (for one seed other numbers than the reference's CPU generator).  A call in
+ * which no pulse falls anywhere returns zeros: pulses = 0 launches nothing per pulse and the overlap-add writes zeros (the reference
+ * fails there inside its FFT).
+ * dsa_last_kernel(): "world_synth_pulses_f32", "world_synth_responses_f32", "world_synth_overlap_add_f32", "world_synth_vjp_pulses_f32",
+ * "world_synth_vjp_frames_f32" and the same with f64.
+ * DSA_ERR_INVALID_ARGUMENT with a message that names "world_synth": a negative size, B beyond 65535, N P beyond 2^24 in float32 (the time axis
+ * is exact up to there) or beyond int32, an unknown dtype, a missing pointer, an L that is no power of two (the reference takes any
+ * L >= 1024; WORLD itself uses powers of two), and DSA_WORLD_LDS_BYTES(L, sizeof(dtype)) > DSA_WORLD_MAX_LDS_BYTES: the per-pulse
+ * workgroup holds one complex transform of L points, the two half spectra it carries (4 (L / 2 + 1) values) and its reductions'
+ * exchange in LDS (float32: L <= 8192, float64: L <= 4096). */
+#define DSA_WORLD_MAX_LDS_BYTES 163840
+#define DSA_WORLD_LDS_BYTES(L, size) ((4 * (L) + 4) * (size) + 256)
+int dsa_world_synth_pulses(const void* f0, int64_t B, int64_t N, int32_t P, int32_t sample_rate, int32_t L, double default_f0, const void* offsets,
+                           int32_t dtype, void* counts, void* irec, void* frec, void* stream);
+int dsa_world_synth_responses(const void* ap, const void* sp, const void* noise, const void* irec, const void* frec, const void* offsets,
+                              const void* dc_remover, const void* twiddle, int64_t B, int64_t N, int32_t sample_rate, int32_t L, int64_t pulses,
+                              int32_t dtype, void* response, void* stream);
+int dsa_world_synth_overlap_add(const void* response, const void* irec, const void* offsets, int64_t B, int64_t T, int32_t L, int64_t pulses,
+                                int32_t dtype, void* y, void* stream);
+int dsa_world_synth_vjp_pulses(const void* gy, const void* ap, const void* sp, const void* noise, const void* irec, const void* frec,
+                               const void* offsets, const void* dc_remover, const void* twiddle, int64_t B, int64_t N, int64_t T,
+                               int32_t sample_rate, int32_t L, int64_t pulses, int32_t dtype, void* grows, void* stream);
+int dsa_world_synth_vjp_frames(const void* grows, const void* ap, const void* sp, const void* irec, const void* frec, const void* offsets, int64_t B,
+                               int64_t N, int32_t L, int64_t pulses, int32_t dtype, void* gap, void* gsp, void* stream);
 
 #ifdef __cplusplus
 }
