@@ -6,7 +6,7 @@
 // phases use different units, and with all eight waves in the same phase one set of units idles: stamps of a wide step at 2048 / 49
 // say stage loop 122-139 k cycles against 35 k of matrix-pipe time and 47 k of LDS operand reads, solve 2 x 50 k against 58 k of
 // float32 datapath time (profiles/r06_mcep_big_wide.txt).
-// Here a workgroup is FOUR waves, each with its own 16 frames (the stage body of mcep_resid_h_kernel: one stage per barrier, images
+// Here a workgroup is FOUR waves, each with its own 16 frames (the stage arithmetic of mcep_stage48_f16.h: one stage per barrier, images
 // one stage ahead in registers, even / odd stages summed separately -- the same sums in the same order as every other path: the same
 // bits), and TWO workgroups share a CU (74-76 KB of LDS each, one wave of each per SIMD, 256 registers).  The second workgroup of a
 // CU starts half a step late (`stagger`: the workgroups of the second half of the grid sleep once, before their first step), so while
@@ -69,6 +69,7 @@ __global__ __launch_bounds__(256, 2) void mcep_big_newton4_kernel(const float* _
         const long tb = tile_ok ? t16 : 0;
         const int rows_here = (int)((F - tb < 16) ? F - tb : 16);
         // ---- the wave's 16 rows of mc into LDS (rows past the batch repeat the last one: finite, never stored) ----
+        // (the same loop in mcep_big_newton_kernel, must stay in step: as a shared function it flipped a branch of this kernel)
         for (int e = (threadIdx.x & 63); e < 16 * MS; e += 64) {
             const int row = e / MS, col = e % MS;
             const int rr = row < rows_here ? row : rows_here - 1;
@@ -90,9 +91,9 @@ __global__ __launch_bounds__(256, 2) void mcep_big_newton4_kernel(const float* _
             const int tid = tid_s, lane = tid_s & 63, n = lane & 15, g = lane >> 4;
             const int rn = n < rows_here ? n : rows_here - 1;
             const float* xt = logx + tb * (long)K + (long)rn * K;
-            // ================= rt = exp(logx - 2 mc D) E: the stage body of mcep_resid_h_kernel =================
+            // ================= rt = exp(logx - 2 mc D) E: chain1 / exp_split / chain2 (mcep_stage48_f16.h) =================
             // ONE register set: a stage's images are requested at the head of the stage before it.  (Measured, quad-layout orders: a
-            // second set requested two stages ahead -- the stage body of mcep_resid_h_kernel -- shortens the bare staging skeleton,
+            // second set requested two stages ahead -- the staging of mcep_resid_h_kernel -- shortens the bare staging skeleton,
             // 286 -> 260 us per 32 768 frames, and lengthens the whole kernel, 578 -> 604 us; at the octet-layout orders it spills.)
             f32x4 st0[PER];
             auto fetch = [&](int j, f32x4 (&sv)[PER]) __attribute__((always_inline)) {
@@ -125,23 +126,14 @@ __global__ __launch_bounds__(256, 2) void mcep_big_newton4_kernel(const float* _
                         bv[ks][i] = c < MS ? mcs[n * MS + (c < MS ? c : 0)] : 0.f;   // (columns M1 .. MS - 1 hold zeros)
                         bmax = __builtin_fmaxf(bmax, __builtin_fabsf(bv[ks][i]));
                     }
-                bmax = rows_max4(bmax);
-                const int s_b = 12 - __builtin_amdgcn_frexp_expf(bmax);
-#pragma unroll
-                for (int ks = 0; ks < KS1; ++ks) {
-                    float ms[8];
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) ms[i] = __builtin_ldexpf(bv[ks][i], s_b);
-                    split8(ms, bh[ks], bl[ks]);
-                }
-                k1 = -s_b - LOG2_SD;
+                k1 = -scale_split<KS1>(bv, bmax, MC_LOG2, bh, bl) - LOG2_SD;
             }
             f32x4 acc[2][NT];   // [0] the even stages' sums, [1] the odd stages'
 #pragma unroll
             for (int hs = 0; hs < 2; ++hs)
 #pragma unroll
                 for (int t = 0; t < NT; ++t) acc[hs][t] = zero4;
-            f32x4 x0[2], x1[2];
+            f32x4 x0[2], x1[2];   // (the clamped load: in step with the xfetch of mcep_resid_f16.h, which lists its siblings)
             auto xfetch = [&](int j, f32x4 (&xr)[2]) __attribute__((always_inline)) {
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
@@ -169,44 +161,10 @@ __global__ __launch_bounds__(256, 2) void mcep_big_newton4_kernel(const float* _
                     const f16x8* c1 = reinterpret_cast<const f16x8*>(sbuf0 + buf * SH) + lane;
                     const f16x8* w2 = c1 + (4 * KS1 * 512) / 8;
                     f32x4 s[2] = {zero4, zero4};
-#pragma unroll
-                    for (int ks = 0; ks < KS1; ++ks)
-#pragma unroll
-                        for (int t = 0; t < 2; ++t) {
-                            const f16x8 dh = c1[((t * KS1 + ks) * 2 + 0) * 64], dl = c1[((t * KS1 + ks) * 2 + 1) * 64];
-                            s[t] = mfma_h(dl, bh[ks], s[t]);
-                            s[t] = mfma_h(dh, bl[ks], s[t]);
-                            s[t] = mfma_h(dh, bh[ks], s[t]);
-                        }
-                    float tv[8];
-                    float tmax = -3.0e38f;
-#pragma unroll
-                    for (int t = 0; t < 2; ++t)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const bool live = 32 * j + 16 * t + 4 * g + r < K;
-                            const float v = __builtin_fmaf(xv[t][r], 1.4426950408889634f, __builtin_ldexpf(s[t][r], k1));
-                            tv[4 * t + r] = live ? v : -3.0e38f;
-                            tmax = __builtin_fmaxf(tmax, tv[4 * t + r]);
-                        }
-                    tmax = rows_max4(tmax);
-                    const float mi = __builtin_ceilf(tmax);
-                    const float shf = (float)EMAX_LOG2 - mi;
-                    float ev[8];
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) ev[i] = __builtin_amdgcn_exp2f(tv[i] + shf);   // (dead bins: exp2(-huge) = 0)
+                    chain1<KS1>(c1, bh, bl, s);
                     f16x8 eh, el;
-                    split8(ev, eh, el);
-                    const int k2 = (int)mi - EMAX_LOG2 - LOG2_SE;
-#pragma unroll
-                    for (int tc = 0; tc < NT; ++tc) {
-                        const f16x8 wh = w2[(tc * 2 + 0) * 64], wlo = w2[(tc * 2 + 1) * 64];
-                        f32x4 a_ = mfma_h(wlo, eh, zero4);
-                        a_ = mfma_h(wh, el, a_);
-                        a_ = mfma_h(wh, eh, a_);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) accj[tc][r] += __builtin_ldexpf(a_[r], k2);
-                    }
+                    const int k2 = exp_split(j, g, K, k1, xv, s, eh, el);
+                    chain2<NT>(w2, eh, el, k2, accj);
                 }
                 stage(buf ^ 1, st0);   // the other buffer: its readers finished before the barrier that ended stage j - 1 (after the last
                                        // stage: the clamped piece again, never read)
@@ -229,6 +187,8 @@ __global__ __launch_bounds__(256, 2) void mcep_big_newton4_kernel(const float* _
                     int ln = lane;
                     asm volatile("" : "+v"(ln));
                     const int row0 = QUAD ? 0 : 8 * rnd;
+                    // (the record build of mcep_big_newton_kernel: must stay in step with it -- as a shared function it flipped a branch
+                    //  of that kernel's wide octet-layout instantiations)
                     {
                         f32x4* z4 = reinterpret_cast<f32x4*>(wl);
                         for (int e = ln; e < SYS * REC / 4; e += 64) z4[e] = zero4;
@@ -259,12 +219,7 @@ __global__ __launch_bounds__(256, 2) void mcep_big_newton4_kernel(const float* _
         }
         // ---- the result: the wave's rows of mc (its own rows: no barrier; the next tile's first step starts with one) ----
         __builtin_amdgcn_wave_barrier();
-        if (tile_ok) {
-            for (int e = (threadIdx.x & 63); e < 16 * M1; e += 64) {
-                const int row = e / M1, col = e % M1;
-                if (row < rows_here) mc_out[(tb + row) * (long)M1 + col] = mcs[row * MS + col];
-            }
-        }
+        if (tile_ok) big_mc_rows_out<MS>(mc_out, mcs, tb, rows_here, M1, 0, 16, threadIdx.x & 63);
         __builtin_amdgcn_wave_barrier();
     }
 }

@@ -7,7 +7,8 @@
 // of a 92 us step, the rest is the boundary between two dependent launches, twenty times.  A frame's iteration depends on the
 // frame alone, so here a wave keeps its 16 frames for all steps:
 //   * the step's products exactly as mcep_resid_h_kernel computes them (same images, same stages of 32 bins staged through LDS for
-//     the workgroup's four waves, same splits and scales: rt is bit-identical);
+//     the workgroup's four waves, the stage arithmetic the same functions -- chain1, exp_split, chain2 of mcep_stage48_f16.h: rt
+//     is bit-identical);
 //   * EIGHT waves per workgroup, 64 frames: waves w and w + 4 share 16 frames.  In the products they take alternate stages (the
 //     double-buffered staging holds two consecutive stages anyway) -- a lone wave's stage is a chain of dependent matrix products and
 //     an exp, so two waves halve the phase; the two partial sums meet in LDS (even stages + odd stages: a fixed order, but not the
@@ -23,7 +24,8 @@
 #pragma once
 
 #include "common.h"
-#include "f16_split.h"   // the splits; namespace mrh: the stage geometry of mcep_resid_f16.h, whose images this kernel reads
+#include "f16_split.h"          // the splits; namespace mrh: the stage geometry of mcep_resid_f16.h, whose images this kernel reads
+#include "mcep_stage48_f16.h"   // the stage's arithmetic (chain1, exp_split, chain2), shared with mcep_resid_f16.h: the same bits
 #include "thsolve_tq.h"
 
 #ifndef DSA_BIG_ABL
@@ -194,6 +196,17 @@ __device__ __attribute__((noinline)) void big_solve16q(mbg::lds_f* wl, mbg::lds_
     }
 }
 
+// The result: a wave's share of its group's 16 rows of mc, rows row0 .. row0 + nrows - 1 of the tile at frame tb (rows_here of them inside
+// the batch), from the group's LDS copy `mcs` (row stride MS) to memory; `ln`: the lane.  Shared with mcep_big_newton4_kernel
+template <int MS>
+__device__ __forceinline__ void big_mc_rows_out(float* mc_out, const float* mcs, long tb, int rows_here, int M1, int row0, int nrows, int ln)
+{
+    for (int e = ln; e < nrows * M1; e += 64) {
+        const int row = row0 + e / M1, col = e % M1;
+        if (row < rows_here) mc_out[(tb + row) * (long)M1 + col] = mcs[row * MS + col];
+    }
+}
+
 // WIDE (second cut of the round): EIGHT 16-frame groups per workgroup -- every wave keeps its OWN 16 frames and runs BOTH stages of a
 // staged pair (two accumulator sets, even and odd stages, added at the end: the same sums in the same order as the two waves of a
 // narrow group, the same bits), then solves its 16 systems itself (octet layout: two rounds of 8).  The narrow kernel is a LATENCY
@@ -242,6 +255,7 @@ __global__ __launch_bounds__(512, 1) void mcep_big_newton_kernel(const float* __
         const int rows_here = (int)((F - tb < 16) ? F - tb : 16);
         __syncthreads();   // the previous tile's result rows have left the LDS copy of mc
         // ---- the group's 16 rows of mc into LDS, RPW per wave (rows past the batch repeat the last one: finite, never stored) ----
+        // (the same loop in mcep_big_newton4_kernel, must stay in step: as a shared function it flipped a branch of that kernel)
         for (int e = (tid & 63); e < RPW * MS; e += 64) {
             const int row = 8 * hsel + e / MS, col = e % MS;
             const int rr = row < rows_here ? row : rows_here - 1;
@@ -266,7 +280,7 @@ __global__ __launch_bounds__(512, 1) void mcep_big_newton_kernel(const float* __
             const int lane = lane_s, n = lane_s & 15, g = lane_s >> 4;
             const int rn = n < rows_here ? n : rows_here - 1;
             const float* xt = logx + tb * (long)K + (long)rn * K;
-            // ================= rt = exp(logx - 2 mc D) E: the stage body of mcep_resid_h_kernel, two stages per barrier =================
+            // ================= rt = exp(logx - 2 mc D) E: chain1 / exp_split / chain2 (mcep_stage48_f16.h), two stages per barrier =================
             // A stage PAIR (2 i, 2 i + 1) is staged together (four buffers: the pair in use, the pair being written); between two
             // barriers the group's first wave runs the even stage, its second wave the odd one -- concurrently (WIDE: the group's one
             // wave runs both).  (First 8-wave cut: one stage per barrier, the waves alternating -- a stage's arithmetic never
@@ -306,16 +320,7 @@ __global__ __launch_bounds__(512, 1) void mcep_big_newton_kernel(const float* __
                         bv[ks][i] = c < MS ? mcs[n * MS + (c < MS ? c : 0)] : 0.f;   // (columns M1 .. MS - 1 hold zeros)
                         bmax = __builtin_fmaxf(bmax, __builtin_fabsf(bv[ks][i]));
                     }
-                bmax = rows_max4(bmax);
-                const int s_b = 12 - __builtin_amdgcn_frexp_expf(bmax);
-#pragma unroll
-                for (int ks = 0; ks < KS1; ++ks) {
-                    float ms[8];
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) ms[i] = __builtin_ldexpf(bv[ks][i], s_b);
-                    split8(ms, bh[ks], bl[ks]);
-                }
-                k1 = -s_b - LOG2_SD;
+                k1 = -scale_split<KS1>(bv, bmax, MC_LOG2, bh, bl) - LOG2_SD;
             }
             f32x4 acc[NSTG][NT];   // (WIDE: [0] the even stages' sums, [1] the odd stages')
 #pragma unroll
@@ -323,6 +328,7 @@ __global__ __launch_bounds__(512, 1) void mcep_big_newton_kernel(const float* __
 #pragma unroll
                 for (int t = 0; t < NT; ++t) acc[hs][t] = zero4;
             // the lane's log-spectrum values of ITS stage(s) of a pair (narrow: 2 ip + hsel), requested two pairs ahead
+            // (the clamped load: in step with the xfetch of mcep_resid_f16.h, which lists its siblings)
             f32x4 x0[NSTG][2], x1[NSTG][2];
             auto xfetch = [&](int ip, f32x4 (&xr)[NSTG][2]) __attribute__((always_inline)) {
 #pragma unroll
@@ -370,63 +376,19 @@ __global__ __launch_bounds__(512, 1) void mcep_big_newton_kernel(const float* __
                         // pipes, and a stage alone uses them one after the other (stamps: first chain, t / max / exp / split, second chain
                         // ~0.45 / 0.6 / 0.7 k cycles, each at its own pipe's rate when both waves of a SIMD are in the same phase).  Here the
                         // second stage's first chain issues between the first stage's exponentials, the first stage's second chain between
-                        // the second stage's: [c1 a] [c1 b | exp a] [c2 a | exp b] [c2 b].  Same instructions, same operands, same order
-                        // of every sum: the same bits.
+                        // the second stage's: [c1 a] [c1 b | exp a] [c2 a | exp b] [c2 b].  The same three functions as the straight
+                        // path below on the same operands, the same order of every sum: the same bits.
                         done_ = true;
                         const f16x8* c1a = reinterpret_cast<const f16x8*>(sbuf0 + (set * 2 + 0) * SH) + lane;
                         const f16x8* c1b = c1a + SH / 8;
-                        auto chain1 = [&](const f16x8* c1, f32x4 (&s2)[2]) __attribute__((always_inline)) {
-#pragma unroll
-                            for (int ks = 0; ks < KS1; ++ks)
-#pragma unroll
-                                for (int t = 0; t < 2; ++t) {
-                                    const f16x8 dh = c1[((t * KS1 + ks) * 2 + 0) * 64], dl = c1[((t * KS1 + ks) * 2 + 1) * 64];
-                                    s2[t] = mfma_h(dl, bh[ks], s2[t]);
-                                    s2[t] = mfma_h(dh, bl[ks], s2[t]);
-                                    s2[t] = mfma_h(dh, bh[ks], s2[t]);
-                                }
-                        };
-                        auto expsplit = [&](int j, const f32x4 (&xq)[2], const f32x4 (&s2)[2], f16x8& eh, f16x8& el, int& k2) __attribute__((always_inline)) {
-                            float tv[8];
-                            float tmax = -3.0e38f;
-#pragma unroll
-                            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                                for (int r = 0; r < 4; ++r) {
-                                    const bool live = 32 * j + 16 * t + 4 * g + r < K;
-                                    const float v = __builtin_fmaf(xq[t][r], 1.4426950408889634f, __builtin_ldexpf(s2[t][r], k1));
-                                    tv[4 * t + r] = live ? v : -3.0e38f;
-                                    tmax = __builtin_fmaxf(tmax, tv[4 * t + r]);
-                                }
-                            tmax = rows_max4(tmax);
-                            const float mi = __builtin_ceilf(tmax);
-                            const float shf = (float)EMAX_LOG2 - mi;
-                            float ev[8];
-#pragma unroll
-                            for (int i = 0; i < 8; ++i) ev[i] = __builtin_amdgcn_exp2f(tv[i] + shf);
-                            split8(ev, eh, el);
-                            k2 = (int)mi - EMAX_LOG2 - LOG2_SE;
-                        };
-                        auto chain2 = [&](const f16x8* w2, const f16x8& eh, const f16x8& el, int k2, f32x4 (&ac)[NT]) __attribute__((always_inline)) {
-#pragma unroll
-                            for (int tc = 0; tc < NT; ++tc) {
-                                const f16x8 wh = w2[(tc * 2 + 0) * 64], wlo = w2[(tc * 2 + 1) * 64];
-                                f32x4 a_ = mfma_h(wlo, eh, zero4);
-                                a_ = mfma_h(wh, el, a_);
-                                a_ = mfma_h(wh, eh, a_);
-#pragma unroll
-                                for (int r = 0; r < 4; ++r) ac[tc][r] += __builtin_ldexpf(a_[r], k2);
-                            }
-                        };
                         f32x4 sa[2] = {zero4, zero4}, sb[2] = {zero4, zero4};
                         f16x8 eha, ela, ehb, elb;
-                        int k2a, k2b;
                         __builtin_amdgcn_sched_barrier(0);
-                        chain1(c1a, sa);
+                        chain1<KS1>(c1a, bh, bl, sa);
                         __builtin_amdgcn_sched_barrier(0);
                         BIG_STAMP_P(10);
-                        chain1(c1b, sb);
-                        expsplit(2 * ip, xv[0], sa, eha, ela, k2a);
+                        chain1<KS1>(c1b, bh, bl, sb);
+                        const int k2a = exp_split(2 * ip, g, K, k1, xv[0], sa, eha, ela);
 #pragma unroll
                         for (int i_ = 0; i_ < 6 * KS1; ++i_) {   // one product, then a handful of the exponentials' vector instructions
                             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -434,8 +396,8 @@ __global__ __launch_bounds__(512, 1) void mcep_big_newton_kernel(const float* __
                         }
                         __builtin_amdgcn_sched_barrier(0);
                         BIG_STAMP_P(11);
-                        chain2(c1a + (4 * KS1 * 512) / 8, eha, ela, k2a, acc[0]);
-                        expsplit(2 * ip + 1, xv[NSTG - 1], sb, ehb, elb, k2b);
+                        chain2<NT>(c1a + (4 * KS1 * 512) / 8, eha, ela, k2a, acc[0]);
+                        const int k2b = exp_split(2 * ip + 1, g, K, k1, xv[NSTG - 1], sb, ehb, elb);
 #pragma unroll
                         for (int i_ = 0; i_ < 3 * NT; ++i_) {
                             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -443,7 +405,7 @@ __global__ __launch_bounds__(512, 1) void mcep_big_newton_kernel(const float* __
                         }
                         __builtin_amdgcn_sched_barrier(0);
                         BIG_STAMP_P(12);
-                        chain2(c1b + (4 * KS1 * 512) / 8, ehb, elb, k2b, acc[NSTG - 1]);
+                        chain2<NT>(c1b + (4 * KS1 * 512) / 8, ehb, elb, k2b, acc[NSTG - 1]);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
@@ -456,46 +418,12 @@ __global__ __launch_bounds__(512, 1) void mcep_big_newton_kernel(const float* __
                         const f16x8* c1 = reinterpret_cast<const f16x8*>(sbuf0 + (set * 2 + hsx) * SH) + lane;
                         const f16x8* w2 = c1 + (4 * KS1 * 512) / 8;
                         f32x4 s[2] = {zero4, zero4};
-#pragma unroll
-                        for (int ks = 0; ks < KS1; ++ks)
-#pragma unroll
-                            for (int t = 0; t < 2; ++t) {
-                                const f16x8 dh = c1[((t * KS1 + ks) * 2 + 0) * 64], dl = c1[((t * KS1 + ks) * 2 + 1) * 64];
-                                s[t] = mfma_h(dl, bh[ks], s[t]);
-                                s[t] = mfma_h(dh, bl[ks], s[t]);
-                                s[t] = mfma_h(dh, bh[ks], s[t]);
-                            }
+                        chain1<KS1>(c1, bh, bl, s);
                         if (hs == 0) BIG_STAMP_P(10);
-                        float tv[8];
-                        float tmax = -3.0e38f;
-#pragma unroll
-                        for (int t = 0; t < 2; ++t)
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                const bool live = 32 * j + 16 * t + 4 * g + r < K;
-                                const float v = __builtin_fmaf(xv[hs][t][r], 1.4426950408889634f, __builtin_ldexpf(s[t][r], k1));
-                                tv[4 * t + r] = live ? v : -3.0e38f;
-                                tmax = __builtin_fmaxf(tmax, tv[4 * t + r]);
-                            }
-                        tmax = rows_max4(tmax);
-                        const float mi = __builtin_ceilf(tmax);
-                        const float shf = (float)EMAX_LOG2 - mi;
-                        float ev[8];
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) ev[i] = __builtin_amdgcn_exp2f(tv[i] + shf);
                         f16x8 eh, el;
-                        split8(ev, eh, el);
+                        const int k2 = exp_split(j, g, K, k1, xv[hs], s, eh, el);
                         if (hs == 0) BIG_STAMP_P(11);
-                        const int k2 = (int)mi - EMAX_LOG2 - LOG2_SE;
-#pragma unroll
-                        for (int tc = 0; tc < NT; ++tc) {
-                            const f16x8 wh = w2[(tc * 2 + 0) * 64], wlo = w2[(tc * 2 + 1) * 64];
-                            f32x4 a_ = mfma_h(wlo, eh, zero4);
-                            a_ = mfma_h(wh, el, a_);
-                            a_ = mfma_h(wh, eh, a_);
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) acc[hs][tc][r] += __builtin_ldexpf(a_[r], k2);
-                        }
+                        chain2<NT>(w2, eh, el, k2, acc[hs]);
                         if (hs == 0) BIG_STAMP_P(12);
                     }
                 }
@@ -543,6 +471,8 @@ __global__ __launch_bounds__(512, 1) void mcep_big_newton_kernel(const float* __
                     int ln = lane;
                     asm volatile("" : "+v"(ln));   // (lane-derived values re-derived here: see thsolve_octn_kernel)
                     const int row0 = WIDE ? 8 * rnd : (QUAD ? 0 : 8 * hsel);   // the group's rows this solve takes (QUAD: all 16)
+                    // (the record build: the same text in mcep_big_newton4_kernel, must stay in step -- as a shared function it flipped a
+                    //  branch of the wide octet-layout instantiations here)
                     {
                         f32x4* z4 = reinterpret_cast<f32x4*>(wl);
                         for (int e = ln; e < SYS * REC / 4; e += 64) z4[e] = zero4;
@@ -578,12 +508,7 @@ __global__ __launch_bounds__(512, 1) void mcep_big_newton_kernel(const float* __
         }
         // ---- the result: the group's rows of mc, RPW per wave ----
         __syncthreads();
-        if (tile_ok) {
-            for (int e = (tid & 63); e < RPW * M1; e += 64) {
-                const int row = 8 * hsel + e / M1, col = e % M1;
-                if (row < rows_here) mc_out[(tb + row) * (long)M1 + col] = mcs[row * MS + col];
-            }
-        }
+        if (tile_ok) big_mc_rows_out<MS>(mc_out, mcs, tb, rows_here, M1, 8 * hsel, RPW, tid & 63);
 #ifdef DSA_BIG_STAMPS
         if (blockIdx.x == 0 && pair == 0 && (tid & 63) == 0 && tile == 0)
             for (int i = 1; i < 16; ++i) mc_out[(8 * hsel) * (long)M1 + i] = (float)(tsv[i] - tsv[i - 1]);

@@ -14,7 +14,7 @@
 // the 16 frames, scaled per frame by a power of two and split into binary16 pieces exactly as mcep_resid_bwd_h_kernel does -- go to LDS
 // once (12 KB per step: the reason for one tile per workgroup and one workgroup per CU).  Then the 16-bin half stages (stage j, tile t)
 // are dealt round-robin to the waves: the unit's operand images straight from L2 into registers (this wave is their only reader on the
-// CU), and per step the two chains, the exponential and z_s -- the same instructions on the same values as the sweep's kernel --
+// CU), and per step the two chains, the exponential and z_s -- mfma_h3 and z_bin of mcep_stage48_f16.h on the same values as the sweep's kernel --
 // summed over the steps IN THE SWEEP'S ORDER (last step first), so the result equals the in-place accumulation bit for bit.
 // (First cut: four waves, a whole stage per wave -- one wave per SIMD with nothing to hide its dependent chains behind, and 33 stages
 // over 4 waves is 9 against 8.25: 1.45 ms per 102 400 frames at 1 025 bins; see profiles/r06_48khz_gradient_one_node.txt.)
@@ -69,8 +69,10 @@ __global__ __launch_bounds__(512, 1) DSA_PK_TARGET void mcep_glogx_h_kernel(cons
                 bv[ks][i] = c < M1 ? mc[(tb + rn) * (long)M1 + c] : 0.f;
                 bmax = __builtin_fmaxf(bmax, __builtin_fabsf(bv[ks][i]));
             }
+        // (this split and the cotangent's below are the text of mrh::scale_split, as the sweep's kernel has it: must stay in step with
+        //  both -- called here, it changed this kernel's instruction order)
         bmax = rows_max4(bmax);
-        const int s_b = 12 - __builtin_amdgcn_frexp_expf(bmax);
+        const int s_b = MC_LOG2 - __builtin_amdgcn_frexp_expf(bmax);
 #pragma unroll
         for (int ks = 0; ks < KS1; ++ks) {
             float ms[8];
@@ -124,7 +126,7 @@ __global__ __launch_bounds__(512, 1) DSA_PK_TARGET void mcep_glogx_h_kernel(cons
 #pragma unroll
         for (int q = 0; q < 2 * KSE; ++q) iv[2 * KS1 + q] = p[OFF2 + (t * KSE * 2 + q) * 64];
     };
-    f32x4 xa, xb;
+    f32x4 xa, xb;   // (the clamped load: in step with the xfetch of mcep_resid_f16.h, which lists its siblings)
     auto xfetch = [&](int u, f32x4& xr) __attribute__((always_inline)) {
         const int uu = u < nunit ? u : nunit - 1;
         const int b0 = 16 * uu + 4 * g;
@@ -151,24 +153,15 @@ __global__ __launch_bounds__(512, 1) DSA_PK_TARGET void mcep_glogx_h_kernel(cons
 #pragma unroll
             for (int ks = 0; ks < KS1; ++ks) {
                 const f16x8 dh = iv[ks * 2 + 0], dl = iv[ks * 2 + 1];
-                sc = mfma_h(dl, bh[ks], sc);
-                sc = mfma_h(dh, bl[ks], sc);
-                sc = mfma_h(dh, bh[ks], sc);
+                sc = mfma_h3(dh, dl, bh[ks], bl[ks], sc);
             }
 #pragma unroll
             for (int ks = 0; ks < KSE; ++ks) {
                 const f16x8 eh_ = iv[2 * KS1 + ks * 2 + 0], el_ = iv[2 * KS1 + ks * 2 + 1];
-                eb = mfma_h(el_, rh[ks], eb);
-                eb = mfma_h(eh_, rl[ks], eb);
-                eb = mfma_h(eh_, rh[ks], eb);
+                eb = mfma_h3(eh_, el_, rh[ks], rl[ks], eb);
             }
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const bool live = 16 * u + 4 * g + r < K;
-                const float tv = __builtin_fmaf(xv[r], 1.4426950408889634f, __builtin_ldexpf(sc[r], k1));
-                const float e_ = live ? __builtin_amdgcn_exp2f(tv) : 0.f;
-                zsum[r] += __builtin_ldexpf(eb[r] * e_, ke);
-            }
+            for (int r = 0; r < 4; ++r) zsum[r] += z_bin(16 * u + 4 * g + r < K, xv[r], sc[r], k1, eb[r], ke);
         }
         if (row_ok) {
             const int b0 = 16 * u + 4 * g;

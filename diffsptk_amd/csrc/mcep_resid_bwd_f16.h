@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "f16_split.h"
+#include "mcep_stage48_f16.h"   // mfma_h3, scale_split, z_bin: shared with the forward and with mcep_glogx_f16.h
 
 namespace dsa {
 
@@ -146,8 +147,10 @@ __global__ __launch_bounds__(256, 2) DSA_PK_TARGET void mcep_resid_bwd_h_kernel(
                 bv[ks][i] = c < M1 ? mc[(tb + rn) * (long)M1 + c] : 0.f;
                 bmax = __builtin_fmaxf(bmax, __builtin_fabsf(bv[ks][i]));
             }
+        // (the text of mrh::scale_split, which the cotangent below calls: must stay in step with it and with mcep_glogx_h_kernel's
+        //  prologue -- called here, it changed this kernel's instruction order)
         bmax = rows_max4(bmax);
-        const int s_b = 12 - __builtin_amdgcn_frexp_expf(bmax);
+        const int s_b = MC_LOG2 - __builtin_amdgcn_frexp_expf(bmax);
 #pragma unroll
         for (int ks = 0; ks < KS1; ++ks) {
             float ms[8];
@@ -166,22 +169,14 @@ __global__ __launch_bounds__(256, 2) DSA_PK_TARGET void mcep_resid_bwd_h_kernel(
                 rv[ks][i] = m < N ? grt[(tb + rn) * (long)N + m] : 0.f;
                 rmax = __builtin_fmaxf(rmax, __builtin_fabsf(rv[ks][i]));
             }
-        rmax = rows_max4(rmax);
-        const int s_g = VMAX_LOG2 - __builtin_amdgcn_frexp_expf(rmax);
-#pragma unroll
-        for (int ks = 0; ks < KSE; ++ks) {
-            float ms[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) ms[i] = __builtin_ldexpf(rv[ks][i], s_g);
-            split8(ms, rh[ks], rl[ks]);
-        }
-        ke = -s_g - LOG2_SE;     // the ebar chain's accumulators x 2^ke = E grt^T
+        ke = -scale_split<KSE>(rv, rmax, VMAX_LOG2, rh, rl) - LOG2_SE;     // the ebar chain's accumulators x 2^ke = E grt^T
     }
     f32x4 acc[NT3];
 #pragma unroll
     for (int t = 0; t < NT3; ++t) acc[t] = zero4;
     // the lane's log-spectrum values and gradient sums of a stage: bins 32 j + 16 t + 4 g + r; bins past the end read the row's last
-    // value, are masked to e = 0 below and never stored
+    // value, are masked to e = 0 below and never stored  (the clamped load: in step with the xfetch of mcep_resid_f16.h, which lists its
+    // siblings)
     f32x4 x0[2], x1[2], a0[2], a1[2];
     auto xfetch = [&](int j, f32x4 (&xr)[2], f32x4 (&ar)[2]) __attribute__((always_inline)) {
 #pragma unroll
@@ -226,19 +221,15 @@ __global__ __launch_bounds__(256, 2) DSA_PK_TARGET void mcep_resid_bwd_h_kernel(
 #pragma unroll
                 for (int ks = 0; ks < KS1; ++ks) {
                     const f16x8 dh = c1[((t * KS1 + ks) * 2 + 0) * 64], dl = c1[((t * KS1 + ks) * 2 + 1) * 64];
-                    s[t] = mfma_h(dl, bh[ks], s[t]);
-                    s[t] = mfma_h(dh, bl[ks], s[t]);
-                    s[t] = mfma_h(dh, bh[ks], s[t]);
+                    s[t] = mfma_h3(dh, dl, bh[ks], bl[ks], s[t]);
                 }
 #pragma unroll
                 for (int ks = 0; ks < KSE; ++ks) {
                     const f16x8 eh_ = c2[((t * KSE + ks) * 2 + 0) * 64], el_ = c2[((t * KSE + ks) * 2 + 1) * 64];
-                    eb[t] = mfma_h(el_, rh[ks], eb[t]);
-                    eb[t] = mfma_h(eh_, rl[ks], eb[t]);
-                    eb[t] = mfma_h(eh_, rh[ks], eb[t]);
+                    eb[t] = mfma_h3(eh_, el_, rh[ks], rl[ks], eb[t]);
                 }
             }
-            // e = exp(tau) (dead bins: 0), z = ebar e, glogx += z
+            // e = exp(tau) (dead bins: 0), z = ebar e (z_bin: the expression mcep_glogx_h_kernel sums), glogx += z
             float zv[8];
             float zm = 0.f;
 #pragma unroll
@@ -246,10 +237,7 @@ __global__ __launch_bounds__(256, 2) DSA_PK_TARGET void mcep_resid_bwd_h_kernel(
                 f32x4 o = av_[t];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const bool live = 32 * j + 16 * t + 4 * g + r < K;
-                    const float tv = __builtin_fmaf(xv[t][r], 1.4426950408889634f, __builtin_ldexpf(s[t][r], k1));
-                    const float e_ = live ? __builtin_amdgcn_exp2f(tv) : 0.f;
-                    const float z = __builtin_ldexpf(eb[t][r] * e_, ke);
+                    const float z = z_bin(32 * j + 16 * t + 4 * g + r < K, xv[t][r], s[t][r], k1, eb[t][r], ke);
                     zv[4 * t + r] = z;
                     zm = __builtin_fmaxf(zm, __builtin_fabsf(z));
                     o[r] += z;
@@ -265,7 +253,8 @@ __global__ __launch_bounds__(256, 2) DSA_PK_TARGET void mcep_resid_bwd_h_kernel(
                     }
                 }
             }
-            // third chain: gmc += (-2 D) z with the stage's own scale
+            // third chain: gmc += (-2 D) z with the stage's own scale (the loop below has the text of mrh::chain2 and stays written out:
+            // called as chain2<NT3>, the <2, 4, 4, false> instantiation got another register assignment, profiles/mcep48_share_isa.txt)
             zm = rows_max4(zm);
             const int s_z = VMAX_LOG2 - __builtin_amdgcn_frexp_expf(zm);
             float zs[8];
@@ -277,9 +266,7 @@ __global__ __launch_bounds__(256, 2) DSA_PK_TARGET void mcep_resid_bwd_h_kernel(
 #pragma unroll
             for (int tc = 0; tc < NT3; ++tc) {
                 const f16x8 wh = c3[(tc * 2 + 0) * 64], wlo = c3[(tc * 2 + 1) * 64];
-                f32x4 a_ = mfma_h(wlo, zh, zero4);
-                a_ = mfma_h(wh, zl, a_);
-                a_ = mfma_h(wh, zh, a_);
+                const f32x4 a_ = mfma_h3(wh, wlo, zh, zl, zero4);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) acc[tc][r] += __builtin_ldexpf(a_[r], k3);
             }

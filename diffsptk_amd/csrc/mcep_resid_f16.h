@@ -14,7 +14,8 @@
 #pragma once
 
 #include "common.h"
-#include "f16_split.h"   // the splits; namespace mrh: the stage geometry, shared with mcep_big_f16.h
+#include "f16_split.h"          // the splits; namespace mrh: the stage geometry, shared with mcep_big_f16.h
+#include "mcep_stage48_f16.h"   // the stage's arithmetic (chain1, exp_split, chain2), shared with mcep_big_f16.h / mcep_big4_f16.h
 
 namespace dsa {
 
@@ -110,16 +111,7 @@ __global__ __launch_bounds__(256, 2) DSA_PK_TARGET void mcep_resid_h_kernel(cons
                 bv[ks][i] = c < M1 ? mc[(tb + rn) * (long)M1 + c] : 0.f;
                 bmax = __builtin_fmaxf(bmax, __builtin_fabsf(bv[ks][i]));
             }
-        bmax = rows_max4(bmax);
-        const int s_b = 12 - __builtin_amdgcn_frexp_expf(bmax);
-#pragma unroll
-        for (int ks = 0; ks < KS1; ++ks) {
-            float ms[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) ms[i] = __builtin_ldexpf(bv[ks][i], s_b);
-            split8(ms, bh[ks], bl[ks]);
-        }
-        k1 = -s_b - LOG2_SD;     // the first chain's accumulators x 2^k1 = (-2 log2(e) D)^T mc
+        k1 = -scale_split<KS1>(bv, bmax, MC_LOG2, bh, bl) - LOG2_SD;     // the first chain's accumulators x 2^k1 = (-2 log2(e) D)^T mc
     }
     // TWO sets of sums, the even and the odd stages': added once at the end.  The one-launch kernel of round 6 (mcep_big_f16.h) gives
     // the stages of a tile to two waves alternately and adds their partial sums -- with the same order here, rt is bit-identical
@@ -133,7 +125,8 @@ __global__ __launch_bounds__(256, 2) DSA_PK_TARGET void mcep_resid_h_kernel(cons
 #pragma unroll
     for (int t = 0; t < (SPLIT ? NT : 1); ++t) acc_odd[t] = zero4;
     // the lane's log-spectrum values of a stage: bins 32 j + 16 t + 4 g + r; bins past the end read the row's last value and are
-    // masked below
+    // masked below  (the clamped load stays written out here and in its siblings, the xfetch of mcep_big_f16.h, mcep_big4_f16.h,
+    // mcep_resid_bwd_f16.h and mcep_glogx_f16.h -- as a shared function it changed the kernels' code: they must stay in step)
     f32x4 x0[2], x1[2];
     auto xfetch = [&](int j, f32x4 (&xr)[2]) __attribute__((always_inline)) {
 #pragma unroll
@@ -163,48 +156,12 @@ __global__ __launch_bounds__(256, 2) DSA_PK_TARGET void mcep_resid_h_kernel(cons
         if (tile_ok) {
             const f16x8* c1 = reinterpret_cast<const f16x8*>(sbuf[buf]) + lane;
             const f16x8* w2 = c1 + (4 * KS1 * 512) / 8;
-            // first chain
+            // first chain; t, the stage's shift, e; second chain (mcep_stage48_f16.h)
             f32x4 s[2] = {zero4, zero4};
-#pragma unroll
-            for (int ks = 0; ks < KS1; ++ks)
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    const f16x8 dh = c1[((t * KS1 + ks) * 2 + 0) * 64], dl = c1[((t * KS1 + ks) * 2 + 1) * 64];
-                    s[t] = mfma_h(dl, bh[ks], s[t]);
-                    s[t] = mfma_h(dh, bl[ks], s[t]);
-                    s[t] = mfma_h(dh, bh[ks], s[t]);
-                }
-            // t = log2(e) logx - 2 log2(e) (mc D); the stage's shift; e
-            float tv[8];
-            float tmax = -3.0e38f;
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const bool live = 32 * j + 16 * t + 4 * g + r < K;
-                    const float v = __builtin_fmaf(xv[t][r], 1.4426950408889634f, __builtin_ldexpf(s[t][r], k1));
-                    tv[4 * t + r] = live ? v : -3.0e38f;
-                    tmax = __builtin_fmaxf(tmax, tv[4 * t + r]);
-                }
-            tmax = rows_max4(tmax);
-            const float mi = __builtin_ceilf(tmax);
-            const float shf = (float)EMAX_LOG2 - mi;
-            float ev[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) ev[i] = __builtin_amdgcn_exp2f(tv[i] + shf);   // (dead bins: exp2(-huge) = 0)
+            chain1<KS1>(c1, bh, bl, s);
             f16x8 eh, el;
-            split8(ev, eh, el);
-            // second chain
-            const int k2 = (int)mi - EMAX_LOG2 - LOG2_SE;
-#pragma unroll
-            for (int tc = 0; tc < NT; ++tc) {
-                const f16x8 wh = w2[(tc * 2 + 0) * 64], wlo = w2[(tc * 2 + 1) * 64];
-                f32x4 a_ = mfma_h(wlo, eh, zero4);
-                a_ = mfma_h(wh, el, a_);
-                a_ = mfma_h(wh, eh, a_);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) accj[tc][r] += __builtin_ldexpf(a_[r], k2);
-            }
+            const int k2 = exp_split(j, g, K, k1, xv, s, eh, el);
+            chain2<NT>(w2, eh, el, k2, accj);
         }
         if (j + 1 < nstage) stage(buf ^ 1, sa);   // the other buffer: its readers finished before the barrier that ended stage j - 1
         __syncthreads();
