@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define DSA_VERSION 145 /* 0.3.9: + dsa_world_synth_pulses / dsa_world_synth_responses / dsa_world_synth_overlap_add / dsa_world_synth_vjp_pulses / dsa_world_synth_vjp_frames (WORLD synthesis: the time base and pulse list of an utterance in one workgroup, a pulse's periodic and aperiodic response through four complex transforms in LDS, the overlap-add as a gather, and the adjoint down to sp and ap in two launches); 0.3.8: + DSA_ALGO_FULL_CHAINS (the tuned mel-cepstral forward runs the first clamp(n_iter - 6, 0, 2) Newton steps on one-term binary16 chains; the flag keeps every step on three terms); 0.3.7: + dsa_vq_search / dsa_vq_accum / dsa_vq_update / dsa_vq_lookup / dsa_vq_vjp (vector quantisation and the Linde-Buzo-Gray codebook design: nearest-codeword search on float64 sums, per-codeword counts and float64 sums in fixed-order segments without atomics, centroids with the iteration's three scalars, the lookup and the quantiser's adjoint); 0.3.6: + dsa_yingram / dsa_yingram_vjp / dsa_frame_yingram (Yingram: YIN's cumulative-mean-normalised difference function on a semitone grid, from frames or from the waveform in one launch, and its adjoint; lag sums directly or through the LDS transform); 0.3.5: + dsa_gmm_prepare / dsa_gmm_estep / dsa_gmm_accum / dsa_gmm_update / dsa_gmm_regress / dsa_gmm_transform (Gaussian mixture models: one EM iteration as factorisation, E-step, weighted moment sums and M-step on the device, and the conversion of a joint-density model); 0.3.4: + dsa_dtw / dsa_dtw_vjp / dsa_dtw_path (dynamic time warping with a soft minimum: the aligned distance of two vector sequences by an anti-diagonal wavefront, its gradient by the reverse sweep, the Viterbi path from the saved tables); 0.3.3: + DSA_ALGO_FIXED_STEPS (the tuned mel-cepstral forward stops a frame's Newton iteration once its update is rounding noise; the flag runs every step); 0.3.2: + dsa_delta / dsa_delta_vjp, dsa_mlpg, dsa_mcpf / dsa_mcpf_vjp (parameter generation: delta features, maximum likelihood parameter generation by a banded Cholesky solve, mel-cepstrum postfiltering in closed form); 0.3.1: + dsa_mdct_analysis / dsa_mdct_synthesis (MDCT / MDST and their inverses: window, fold, DCT-IV through a quarter-length complex FFT and overlap-add in one launch each way; each is the other's adjoint); 0.3.0: + dsa_excite (pitch to excitation: the voiced shapes of ExcitationGeneration on a segmented float64 phase sum, one launch); 0.2.9: + dsa_mlsacheck / dsa_mlsacheck_vjp (the stability check of the MLSA filter: the mel-cepstrum scaled or clipped where the amplitude of its gain-free part passes the threshold of the Pade approximation, forward and adjoint); 0.2.8: + dsa_lpc2lsp_fwd / _bwd, dsa_lsp2lpc_fwd / _bwd, dsa_lspcheck_fwd / _bwd (line spectral pairs by a Chebyshev-series root search, back by a product of real sections, and their stability check, forward and adjoint); 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
+#define DSA_VERSION 146 /* 0.4.0: + dsa_ap_qmf / dsa_ap_qmf_vjp / dsa_ap_tandem / dsa_ap_tandem_vjp (band aperiodicity by TANDEM-STRAIGHT: a level of the QMF pyramid and its transpose, the per-band least-squares fits of a frame with their own regulariser escalation and the interpolated, clipped output in one launch, and the adjoint down to the band signals without atomics); 0.3.9: + dsa_world_synth_pulses / dsa_world_synth_responses / dsa_world_synth_overlap_add / dsa_world_synth_vjp_pulses / dsa_world_synth_vjp_frames (WORLD synthesis: the time base and pulse list of an utterance in one workgroup, a pulse's periodic and aperiodic response through four complex transforms in LDS, the overlap-add as a gather, and the adjoint down to sp and ap in two launches); 0.3.8: + DSA_ALGO_FULL_CHAINS (the tuned mel-cepstral forward runs the first clamp(n_iter - 6, 0, 2) Newton steps on one-term binary16 chains; the flag keeps every step on three terms); 0.3.7: + dsa_vq_search / dsa_vq_accum / dsa_vq_update / dsa_vq_lookup / dsa_vq_vjp (vector quantisation and the Linde-Buzo-Gray codebook design: nearest-codeword search on float64 sums, per-codeword counts and float64 sums in fixed-order segments without atomics, centroids with the iteration's three scalars, the lookup and the quantiser's adjoint); 0.3.6: + dsa_yingram / dsa_yingram_vjp / dsa_frame_yingram (Yingram: YIN's cumulative-mean-normalised difference function on a semitone grid, from frames or from the waveform in one launch, and its adjoint; lag sums directly or through the LDS transform); 0.3.5: + dsa_gmm_prepare / dsa_gmm_estep / dsa_gmm_accum / dsa_gmm_update / dsa_gmm_regress / dsa_gmm_transform (Gaussian mixture models: one EM iteration as factorisation, E-step, weighted moment sums and M-step on the device, and the conversion of a joint-density model); 0.3.4: + dsa_dtw / dsa_dtw_vjp / dsa_dtw_path (dynamic time warping with a soft minimum: the aligned distance of two vector sequences by an anti-diagonal wavefront, its gradient by the reverse sweep, the Viterbi path from the saved tables); 0.3.3: + DSA_ALGO_FIXED_STEPS (the tuned mel-cepstral forward stops a frame's Newton iteration once its update is rounding noise; the flag runs every step); 0.3.2: + dsa_delta / dsa_delta_vjp, dsa_mlpg, dsa_mcpf / dsa_mcpf_vjp (parameter generation: delta features, maximum likelihood parameter generation by a banded Cholesky solve, mel-cepstrum postfiltering in closed form); 0.3.1: + dsa_mdct_analysis / dsa_mdct_synthesis (MDCT / MDST and their inverses: window, fold, DCT-IV through a quarter-length complex FFT and overlap-add in one launch each way; each is the other's adjoint); 0.3.0: + dsa_excite (pitch to excitation: the voiced shapes of ExcitationGeneration on a segmented float64 phase sum, one launch); 0.2.9: + dsa_mlsacheck / dsa_mlsacheck_vjp (the stability check of the MLSA filter: the mel-cepstrum scaled or clipped where the amplitude of its gain-free part passes the threshold of the Pade approximation, forward and adjoint); 0.2.8: + dsa_lpc2lsp_fwd / _bwd, dsa_lsp2lpc_fwd / _bwd, dsa_lspcheck_fwd / _bwd (line spectral pairs by a Chebyshev-series root search, back by a product of real sections, and their stability check, forward and adjoint); 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
 
 typedef enum {
     DSA_OK = 0,
@@ -1073,6 +1073,67 @@ int dsa_world_synth_vjp_pulses(const void* gy, const void* ap, const void* sp, c
                                int32_t sample_rate, int32_t L, int64_t pulses, int32_t dtype, void* grows, void* stream);
 int dsa_world_synth_vjp_frames(const void* grows, const void* ap, const void* sp, const void* irec, const void* frec, const void* offsets, int64_t B,
                                int64_t N, int32_t L, int64_t pulses, int32_t dtype, void* gap, void* gsp, void* stream);
+
+/* ------------------------------------------------------------------ a25  Band aperiodicity by TANDEM-STRAIGHT: ap (0.4.0)
+ * AperiodicityExtractionByTANDEM.forward, ap.py:294-374, with the clip and the output format of Aperiodicity.forward, ap.py:166-167.
+ * x:(B,T) and f0:(B,N) in Hz, of the dtype (float32 or float64); N is f0's own, not tied to T / P.  n_band = int(log2(sample_rate / 600))
+ * <= DSA_AP_MAX_BANDS; band i has cutoff_i = sample_rate / 2^min(i + 2, n_band), tmp_fs_i = 2 cutoff_i, the segment
+ * J_i = int(cutoff_i window_length_ms / 500 + 1.5) and T_i samples, T_0 = ceil(T / 2), T_(i+1) = ceil(T_i / 2), the last band as long as
+ * the one before it.  `bands`:(B,ldb) holds them side by side in a row, band i from column sum_{k<i} T_k on, in FLOAT64 whatever the dtype,
+ * as are their cotangents gbands: on a clean periodic signal the aperiodicity is the rounding noise of the band signals (float32 bands, or
+ * the taps rounded to float32, each moved a float32 sinusoid's result by 1e-5; the float32 window: 3e-9).  int64 indexing, no
+ * allocation, no host synchronisation, no atomics: every sum has one fixed order, two runs give the same bits, and an utterance's bits
+ * are those of the utterance run alone.  B = 0 (and N = 0, T = 0 where nothing is to be written) is a no-op before any pointer is
+ * looked at.
+ *   dsa_ap_qmf         one level of the pyramid (ap.py:304-310): from x:(B,T) of the dtype with row stride ldx (the waveform; a deeper level
+ *                      is float64: dtype = DSA_F64), hp, lp:(B, ceil(T / 2)) float64 with their row strides: the 41-tap high-pass and the
+ *                      37-tap low-pass of ap.py:376-424 (float64 constants of the library; the module's hHP / hLP buffers hold the same
+ *                      values in its dtype) at stride 2 over the input reflected by 20 / 18 samples; T >= 21.  The taps are added in
+ *                      ascending order.
+ *   dsa_ap_qmf_vjp     its transpose: gx:(B,T) of the dtype, every element written, = the taps of ghp and glp:(B, ceil(T / 2)), float64,
+ *                      that read the sample, directly and through the two reflections, in that order.
+ *   dsa_ap_tandem      y:(B,N,K).  One workgroup per (utterance, frame), one wave per band.  Per band the decisions
+ *                      pitch = tmp_fs / f0 (f0 <= 32 reads as 150), t0 = int(pitch + 0.5), index_bias = int(pitch 0.5 + 0.5),
+ *                      curr_pos = int(fl(fl(n fl(P / sr)) tmp_fs) + 1.5), every operation rounded on its own in the dtype; three runs of
+ *                      J + 2 samples from curr_pos - index_bias - 1 -/+ t0 and from curr_pos - index_bias - 1, indices clamped to the band;
+ *                      R = H' W H, b = H' W X with the window:(n_band,ldw) rows of the module; a = (R + eps m I)^-1 b by Cholesky with
+ *                      m = 1, 10, ... 10^8, the first m at which every pivot is positive and finite -- PER FIT (the reference escalates
+ *                      the whole batch together, so there a frame depends on its neighbours); A = std(sqrt(w) (X - H a)) /
+ *                      (std(sqrt(w) X) + 1e-16), unbiased, sqrt(w) = window_sqrt; a fit that no m factors gives upper_bound (the reference
+ *                      raises).  The sums, the factorisation and the stds run in float64 for both dtypes, so a float32 fit escalates only
+ *                      where a float64 one does.  Then the lowest band doubled, the order reversed; with interp_indices:(K) int64 and
+ *                      interp_weights:(K) of the dtype, K = L / 2 + 1, exp(log A[i] + w (log A[i + 1] - log A[i])) -- 0 where one of the
+ *                      two is exactly 0 (the reference: NaN from log 0) --, with both NULL the K = n_band + 1 band values; clipped to
+ *                      [lower_bound, upper_bound]; out_format 0 a, 1 1 - a, 2 a / (1 - a), 3 (1 - a) / a.
+ *   dsa_ap_tandem_vjp  gbands:(B,ldg) float64, every band sample written, for the cotangent gy:(B,N,K): the fits again, the adjoint of the
+ *                      epilogue (nothing passes a clipped or silent bin), the stds (a zero-variance denominator: no gradient), the
+ *                      residual and the regularised solve (eps m I a constant) into gruns:(B,N,3 sum(J + 2)) of the dtype, the run starts
+ *                      curr_pos and the number of failed trials (m = 10^that; 9 = none factored) into
+ *                      starts:(B,N,n_band,DSA_AP_START_WORDS) int64 -- both scratch of the caller --, then a second launch: one thread per
+ *                      band sample adds the run elements that read it in ascending (frame, run) order -- curr_pos does not decrease with
+ *                      n, so the frames are one range, found by bisection --, and a workgroup each adds what the clamp piled onto samples
+ *                      0 and T_i - 1.  No gradient reaches f0 (the reference detaches it).
+ * dsa_last_kernel(): "ap_qmf_f32", "ap_qmf_vjp_f32", "ap_tandem_f32", "ap_tandem_vjp_f32" and the same with f64.
+ * DSA_ERR_INVALID_ARGUMENT with a message that names "ap": a negative size, B beyond 65535, N beyond 2^24 in float32 (the frame index is
+ * exact up to there) or beyond int32, a level shorter than 21 samples, rows too short for their bands, options outside their ranges, an
+ * unknown dtype, a missing pointer, n_band > DSA_AP_MAX_BANDS and DSA_AP_LDS_BYTES(sum(J), n_band) > DSA_AP_MAX_LDS_BYTES: the workgroup
+ * holds, in float64, the three runs of every band and two more arrays of J + 2 for the adjoint (the same ceiling forward and backward;
+ * with window_length_ms = 30 up to sample_rate = 135699; 96 kHz takes 116168 bytes). */
+#define DSA_AP_MAX_BANDS 8
+#define DSA_AP_START_WORDS 5
+#define DSA_AP_MAX_LDS_BYTES 163840
+#define DSA_AP_LDS_BYTES(S, n_band) (40 * ((S) + 2 * (n_band)) + 128)
+int dsa_ap_qmf(const void* x, int64_t B, int64_t T, int64_t ldx, int32_t dtype, void* hp, int64_t ldhp, void* lp, int64_t ldlp, void* stream);
+int dsa_ap_qmf_vjp(const void* ghp, int64_t ldghp, const void* glp, int64_t ldglp, int64_t B, int64_t T, int32_t dtype, void* gx, int64_t ldgx,
+                   void* stream);
+int dsa_ap_tandem(const void* bands, int64_t ldb, const void* f0, const void* window, const void* window_sqrt, int64_t ldw,
+                  const void* interp_indices, const void* interp_weights, int64_t B, int64_t N, int64_t T, int32_t P, int32_t sample_rate,
+                  double window_length_ms, int32_t K, double eps, double lower_bound, double upper_bound, int32_t out_format, int32_t dtype,
+                  void* y, void* stream);
+int dsa_ap_tandem_vjp(const void* gy, const void* bands, int64_t ldb, const void* f0, const void* window, const void* window_sqrt, int64_t ldw,
+                      const void* interp_indices, const void* interp_weights, int64_t B, int64_t N, int64_t T, int32_t P, int32_t sample_rate,
+                      double window_length_ms, int32_t K, double eps, double lower_bound, double upper_bound, int32_t out_format, int32_t dtype,
+                      void* gruns, void* starts, void* gbands, int64_t ldg, void* stream);
 
 #ifdef __cplusplus
 }
