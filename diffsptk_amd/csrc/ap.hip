@@ -70,13 +70,6 @@ struct ApGeom {
     long runs;                     // sum of J + 2
 };
 
-// roundings that the compiler may not contract with their neighbours
-__device__ __forceinline__ float ap_mul(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ double ap_mul(double a, double b) { return __dmul_rn(a, b); }
-__device__ __forceinline__ float ap_add(float a, float b) { return __fadd_rn(a, b); }
-__device__ __forceinline__ double ap_add(double a, double b) { return __dadd_rn(a, b); }
-__device__ __forceinline__ float ap_div(float a, float b) { return __fdiv_rn(a, b); }
-__device__ __forceinline__ double ap_div(double a, double b) { return __ddiv_rn(a, b); }
 template <typename T>
 __device__ __forceinline__ long ap_trunc(T v)   // Tensor.int(); what no int32 holds is pinned, a NaN is 0: the indices are clamped anyway
 {
@@ -225,10 +218,10 @@ __global__ __launch_bounds__(64 * DSA_AP_MAX_BANDS) void ap_tandem_kernel(
     T f = f0[b * N + n];
     if (f <= T(32)) f = T(150);
     const T fs = (T)g.fs[band];
-    const T pitch = ap_div(fs, f);
-    const long t0 = ap_trunc(ap_add(pitch, T(0.5)));
-    const long bias = ap_trunc(ap_add(ap_mul(pitch, T(0.5)), T(0.5)));
-    const long cpos = ap_trunc(ap_add(ap_mul(ap_mul((T)n, step), fs), T(1.5)));
+    const T pitch = rn_div(fs, f);
+    const long t0 = ap_trunc(rn_add(pitch, T(0.5)));
+    const long bias = ap_trunc(rn_add(rn_mul(pitch, T(0.5)), T(0.5)));
+    const long cpos = ap_trunc(rn_add(rn_mul(rn_mul((T)n, step), fs), T(1.5)));
     const long origin = cpos - bias;
     const long sa = origin - t0 - 1, sb = origin + t0 - 1, sg = origin - 1;
     const long last = g.len[band] - 1;
@@ -272,8 +265,8 @@ __global__ __launch_bounds__(64 * DSA_AP_MAX_BANDS) void ap_tandem_kernel(
     bool ok = false;
     T m = 1;
     int trials = 0;   // the failed ones: m = 10^trials is the factor's; AP_TRIALS when none factors
-    for (; trials < AP_TRIALS; ++trials, m = ap_mul(m, T(10))) {
-        ok = ap_cholesky(Rm, (double)ap_mul(eps, m), Lm);
+    for (; trials < AP_TRIALS; ++trials, m = rn_mul(m, T(10))) {
+        ok = ap_cholesky(Rm, (double)rn_mul(eps, m), Lm);
         if (ok) break;
     }
     if (VJP && lane == 0) starts[((b * N + n) * g.n_band + band) * DSA_AP_START_WORDS + 4] = trials;

@@ -18,6 +18,7 @@
 #include <string.h>
 
 #include <atomic>
+#include <limits>
 
 #include "../../include/diffsptk_amd.h"
 #include "env.h"          // env_int / env_text: every DSA_* route switch is read through them, at every call
@@ -164,6 +165,94 @@ __device__ __forceinline__ T block_max(T v, T* scratch)
     return s;
 }
 
+// inclusive prefix sum over the wave; `lane`: the caller's lane index, in the form the caller already holds it
+template <typename T>
+__device__ __forceinline__ T wave_scan_incl(T v, int lane)
+{
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T u = __shfl_up(v, o, 64);
+        if (lane >= o) v += u;
+    }
+    return v;
+}
+// The exclusive prefix of v over a team's threads (rank t of `team`, a multiple of 64; the team's waves are whole waves of the
+// workgroup) and the team's total; red: team / 64 slots of the team's own.  Every thread of the workgroup calls it (two barriers).
+template <typename V>
+__device__ __forceinline__ V team_scan_excl(V v, V* red, int t, int team, V& total)
+{
+    const int lane = t & 63, w = t >> 6, nw = team >> 6;
+    const V inc = wave_scan_incl(v, lane);
+    __syncthreads();   // an earlier call's slots may still be read
+    if (lane == 63) red[w] = inc;
+    __syncthreads();
+    V before = 0, all = 0;
+    for (int i = 0; i < nw; ++i) {
+        if (i < w) before += red[i];
+        all += red[i];
+    }
+    total = all;
+    return before + inc - v;
+}
+
+// one value of a wave-wide register, from the lane `src` (wave-uniform), as a scalar: v_readlane, no LDS crossbar round trip
+template <typename T>
+__device__ __forceinline__ T wave_readlane(T v, int src)
+{
+    if constexpr (sizeof(T) == 4) {
+        return __builtin_bit_cast(T, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), src));
+    } else {
+        const long long b = __builtin_bit_cast(long long, v);
+        const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(b & 0xffffffffll), src);
+        const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(b >> 32), src);
+        return __builtin_bit_cast(T, (long long)(((unsigned long long)hi << 32) | lo));
+    }
+}
+
+// a tile of `cnt` consecutive elements (rows of M1) between global memory and LDS rows of stride S, by one wave: coalesced on the
+// global side, and with an odd S free of bank conflicts for the lane-per-row access that follows
+template <typename T>
+__device__ __forceinline__ void wave_tile_in(T* lds, const T* __restrict__ g, long base, int cnt, int M1, int S)
+{
+    int r = threadIdx.x / M1, c = threadIdx.x - r * M1;
+    const int dq = 64 / M1, dr = 64 - dq * M1;
+    for (int i = threadIdx.x; i < cnt; i += 64) {
+        lds[r * S + c] = g[base + i];
+        r += dq;
+        c += dr;
+        if (c >= M1) { c -= M1; ++r; }
+    }
+}
+template <typename T>
+__device__ __forceinline__ void wave_tile_out(const T* lds, T* __restrict__ g, long base, int cnt, int M1, int S)
+{
+    int r = threadIdx.x / M1, c = threadIdx.x - r * M1;
+    const int dq = 64 / M1, dr = 64 - dq * M1;
+    for (int i = threadIdx.x; i < cnt; i += 64) {
+        g[base + i] = lds[r * S + c];
+        r += dq;
+        c += dr;
+        if (c >= M1) { c -= M1; ++r; }
+    }
+}
+
+// the lg low bits of k in reverse order, lg in 1 .. 32: where a radix-2 transform of 2^lg points that does not reorder leaves X[k]
+__device__ __forceinline__ int fft_brev(int k, int lg) { return (int)(__brev((unsigned)k) >> (32 - lg)); }
+
+constexpr double kPi = 3.14159265358979323846264338327950288;
+constexpr double kTau = 6.283185307179586476925286766559;   // math.tau (utils/private.py)
+
+// products, sums, differences and quotients that the compiler may not contract with their neighbours (the units are built with
+// -ffp-contract=on, which fuses within one expression only; these are expressions of their own)
+__device__ __forceinline__ float rn_mul(float a, float b) { return __fmul_rn(a, b); }
+__device__ __forceinline__ double rn_mul(double a, double b) { return __dmul_rn(a, b); }
+__device__ __forceinline__ float rn_add(float a, float b) { return __fadd_rn(a, b); }
+__device__ __forceinline__ double rn_add(double a, double b) { return __dadd_rn(a, b); }
+__device__ __forceinline__ float rn_sub(float a, float b) { return __fsub_rn(a, b); }
+__device__ __forceinline__ double rn_sub(double a, double b) { return __dsub_rn(a, b); }
+__device__ __forceinline__ float rn_div(float a, float b) { return __fdiv_rn(a, b); }
+__device__ __forceinline__ double rn_div(double a, double b) { return __ddiv_rn(a, b); }
+
 __device__ __forceinline__ float dsa_log(float v) { return logf(v); }
 __device__ __forceinline__ double dsa_log(double v) { return log(v); }
 __device__ __forceinline__ float dsa_exp(float v) { return expf(v); }
@@ -178,6 +267,19 @@ __device__ __forceinline__ float dsa_sin(float v) { return sinf(v); }
 __device__ __forceinline__ double dsa_sin(double v) { return sin(v); }
 __device__ __forceinline__ float dsa_log10(float v) { return log10f(v); }
 __device__ __forceinline__ double dsa_log10(double v) { return log10(v); }
+__device__ __forceinline__ float dsa_abs(float v) { return fabsf(v); }
+__device__ __forceinline__ double dsa_abs(double v) { return fabs(v); }
+__device__ __forceinline__ float dsa_floor(float v) { return floorf(v); }
+__device__ __forceinline__ double dsa_floor(double v) { return floor(v); }
+__device__ __forceinline__ float dsa_ceil(float v) { return ceilf(v); }
+__device__ __forceinline__ double dsa_ceil(double v) { return ceil(v); }
+__device__ __forceinline__ float dsa_trunc(float v) { return truncf(v); }
+__device__ __forceinline__ double dsa_trunc(double v) { return trunc(v); }
+__device__ __forceinline__ float dsa_fmod(float a, float b) { return fmodf(a, b); }
+__device__ __forceinline__ double dsa_fmod(double a, double b) { return fmod(a, b); }
+__device__ __forceinline__ bool dsa_isfinite(float v) { return isfinite(v); }
+__device__ __forceinline__ bool dsa_isfinite(double v) { return isfinite(v); }
+template <typename T> __device__ __forceinline__ T dsa_inf() { return std::numeric_limits<T>::infinity(); }
 
 // spectrum formatter of spec.py:123-132 applied to s = |X|^2 + eps (already floored)
 template <typename T>

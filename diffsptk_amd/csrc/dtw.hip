@@ -60,10 +60,6 @@ inline DtwSteps dtw_steps(int p)
     }
 }
 
-template <typename T> __device__ __forceinline__ T dtw_inf() { return std::numeric_limits<T>::infinity(); }
-__device__ __forceinline__ float dtw_abs(float v) { return fabsf(v); }
-__device__ __forceinline__ double dtw_abs(double v) { return fabs(v); }
-
 // the tables' layout: cell (i, j) of a T1 x T2 grid, diagonals s = i + j one after another, a diagonal's cells by ascending row
 __device__ __forceinline__ long dtw_cell(long i, long j, long T1, long T2)
 {
@@ -86,7 +82,7 @@ __device__ __forceinline__ T dtw_dist(const T* xi, const T* __restrict__ yj, int
     T s = (T)0;
     switch (metric) {
     case DSA_DTW_MANHATTAN:
-        for (int k = 0; k < D; ++k) s += dtw_abs(xi[k] - yj[k]);
+        for (int k = 0; k < D; ++k) s += dsa_abs(xi[k] - yj[k]);
         return s;
     case DSA_DTW_EUCLIDEAN:
     case DSA_DTW_SQUARED_EUCLIDEAN: {
@@ -147,13 +143,13 @@ __device__ __forceinline__ void dtw_dist_vjp(const T* xi, const T* __restrict__ 
 template <typename T>
 __device__ __forceinline__ T dtw_softmin(const T* c, const bool* use, int n, T gamma)
 {
-    T m = dtw_inf<T>();
+    T m = dsa_inf<T>();
     for (int k = 0; k < 3; ++k)
         if (k < n && use[k] && c[k] < m) m = c[k];
-    if (m == dtw_inf<T>()) return m;
+    if (m == dsa_inf<T>()) return m;
     T sum = (T)0;
     for (int k = 0; k < 3; ++k)
-        if (k < n && use[k] && c[k] != dtw_inf<T>()) sum += dsa_exp(-(c[k] - m) / gamma);
+        if (k < n && use[k] && c[k] != dsa_inf<T>()) sum += dsa_exp(-(c[k] - m) / gamma);
     return m - gamma * dsa_log(sum);
 }
 
@@ -176,7 +172,7 @@ __global__ __launch_bounds__(WAVE ? DTW_WAVE_ROWS : DTW_BLOCK_THREADS) void dtw_
     T* ring_r = xs + (size_t)T1 * D;                              // block route: (DTW_RING, T1) of R
     T* ring_q = ring_r + (size_t)DTW_RING * T1;                   //              (DTW_RING, T1) of R_
     const int t = threadIdx.x, NT = blockDim.x;
-    const T inf = dtw_inf<T>();
+    const T inf = dsa_inf<T>();
 
     for (long u = blockIdx.x; u < B; u += gridDim.x) {
         long len1, len2;
@@ -272,7 +268,7 @@ __global__ __launch_bounds__(WAVE ? DTW_WAVE_ROWS : DTW_BLOCK_THREADS) void dtw_
     T* xs = reinterpret_cast<T*>(dtw_lds);      // (T1, D)
     T* ring = xs + (size_t)T1 * D;              // block route: (DTW_RING, 3, T1) messages
     const int t = threadIdx.x, NT = blockDim.x;
-    const T inf = dtw_inf<T>();
+    const T inf = dsa_inf<T>();
 
     for (long u = blockIdx.x; u < B; u += gridDim.x) {
         long len1, len2;
@@ -396,7 +392,7 @@ __global__ __launch_bounds__(64) void dtw_path_kernel(const T* __restrict__ x, c
 {
     const long u = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (u >= B) return;
-    const T inf = dtw_inf<T>();
+    const T inf = dsa_inf<T>();
     long len1, len2;
     if (!dtw_lengths(lengths, u, T1, T2, len1, len2)) {
         count[u] = 0;

@@ -37,24 +37,9 @@ constexpr int EX_THREADS = 256;
 constexpr int EX_CHUNK = 256;        // frames per chunk: one per thread in phase A
 constexpr int EX_WTAB = 512;         // the weights j / P are tabulated up to this frame period
 constexpr int EX_MAX_PERIOD = 1 << 20;   // 256 frames of samples are indexed in 32 bits
-constexpr double kTau = 6.283185307179586476925286766559;   // math.tau (utils/private.py:32)
 
-template <typename T> __device__ __forceinline__ T ex_sin(T v);
-template <> __device__ __forceinline__ float ex_sin<float>(float v) { return sinf(v); }
-template <> __device__ __forceinline__ double ex_sin<double>(double v) { return sin(v); }
-template <typename T> __device__ __forceinline__ T ex_cos(T v);
-template <> __device__ __forceinline__ float ex_cos<float>(float v) { return cosf(v); }
-template <> __device__ __forceinline__ double ex_cos<double>(double v) { return cos(v); }
-__device__ __forceinline__ float ex_ceil(float v) { return ceilf(v); }
-__device__ __forceinline__ double ex_ceil(double v) { return ceil(v); }
-__device__ __forceinline__ float ex_floor(float v) { return floorf(v); }
-__device__ __forceinline__ double ex_floor(double v) { return floor(v); }
-__device__ __forceinline__ float ex_trunc(float v) { return truncf(v); }
-__device__ __forceinline__ double ex_trunc(double v) { return trunc(v); }
-__device__ __forceinline__ float ex_abs(float v) { return fabsf(v); }
-__device__ __forceinline__ double ex_abs(double v) { return fabs(v); }
 // torch.fmod(v, 1): exact, the sign of v
-template <typename T> __device__ __forceinline__ T ex_frac(T v) { return v - ex_trunc(v); }
+template <typename T> __device__ __forceinline__ T ex_frac(T v) { return v - dsa_trunc(v); }
 
 // inclusive segmented sum over the wave: an element with `head` starts a new segment with its own value.  On return `head` says
 // whether a segment starts at or before this lane.
@@ -89,20 +74,20 @@ __device__ __forceinline__ T ex_shape(int type, bool bipolar, T pitch, T cur, T 
     const T tau = (T)kTau;
     switch (type) {
     case DSA_EXCITE_PULSE: {
-        if (!(ex_ceil(cur) - ex_ceil(prev) >= (T)1)) return (T)0;
+        if (!(dsa_ceil(cur) - dsa_ceil(prev) >= (T)1)) return (T)0;
         const T e = dsa_sqrt(pitch);
-        const bool twice = ex_ceil((T)0.5 * cur) - ex_ceil((T)0.5 * prev) >= (T)1;
+        const bool twice = dsa_ceil((T)0.5 * cur) - dsa_ceil((T)0.5 * prev) >= (T)1;
         return bipolar && !twice ? -e : e;
     }
     case DSA_EXCITE_HARMONIC_PULSE: {
-        const T nh = ex_floor((T)0.5 * pitch);
+        const T nh = dsa_floor((T)0.5 * pitch);
         const T theta = tau * prev, half = (T)0.5 * theta, wide = (nh + (T)0.5) * theta;
-        const T numer = bipolar ? ex_cos(half) - ex_cos(wide) : -ex_sin(half) + ex_sin(wide);
-        const T denom = (T)2 * ex_sin(half);
-        const T e = ex_abs(denom) < (T)1e-6 ? (bipolar ? (T)0 : nh) : numer / denom;
+        const T numer = bipolar ? dsa_cos(half) - dsa_cos(wide) : -dsa_sin(half) + dsa_sin(wide);
+        const T denom = (T)2 * dsa_sin(half);
+        const T e = dsa_abs(denom) < (T)1e-6 ? (bipolar ? (T)0 : nh) : numer / denom;
         return dsa_sqrt((T)2 / (nh < (T)1 ? (T)1 : nh)) * e;
     }
-    case DSA_EXCITE_SINUSOIDAL: return bipolar ? ex_sin(tau * cur) : (T)0.5 * ((T)1 - ex_cos(tau * cur));
+    case DSA_EXCITE_SINUSOIDAL: return bipolar ? dsa_sin(tau * cur) : (T)0.5 * ((T)1 - dsa_cos(tau * cur));
     case DSA_EXCITE_SAWTOOTH: {
         const T e = ex_frac(cur);
         return bipolar ? (T)2 * e - (T)1 : e;
@@ -112,7 +97,7 @@ __device__ __forceinline__ T ex_shape(int type, bool bipolar, T pitch, T cur, T 
         return bipolar ? (T)2 * e - (T)1 : e;
     }
     case DSA_EXCITE_TRIANGLE:
-        return bipolar ? (T)2 * ex_abs((T)2 * ex_frac(cur + (T)0.75) - (T)1) - (T)1 : ex_abs((T)2 * ex_frac(cur + (T)0.5) - (T)1);
+        return bipolar ? (T)2 * dsa_abs((T)2 * ex_frac(cur + (T)0.75) - (T)1) - (T)1 : dsa_abs((T)2 * ex_frac(cur + (T)0.5) - (T)1);
     default: {   // DSA_EXCITE_SQUARE
         const T e = ex_frac(cur) <= (T)0.5 ? (T)1 : (T)0;
         return bipolar ? (T)2 * e - (T)1 : e;

@@ -53,7 +53,7 @@ __device__ __forceinline__ void fc_fft_twiddles(const T* __restrict__ A, int H, 
         tw[2 * m + 1] = T(-0.5) * A[H + (q < 0 ? -q : q)];     // -sin = -cos(2 pi (m - L/4) / L)
     }
 }
-__device__ __forceinline__ int fc_brev(int k, int lg) { return (int)(__brev((unsigned)k) >> (32 - lg)); }
+// (X[k] of the transform below sits at fft_brev(k, lg), common.h)
 // Round 3: the even extension of src is REAL, so the L-point transform runs as a complex transform of HALF the length on the
 // packed sequence z[n] = x[2n] + i x[2n+1], followed by the split's real part
 //   Re X[k] = (Zr[k] + Zr[L/2 - k]) / 2 + cos(2 pi k / L) (Zi[k] + Zi[L/2 - k]) / 2 - sin(2 pi k / L) (Zr[k] - Zr[L/2 - k]) / 2
@@ -120,7 +120,7 @@ __device__ __forceinline__ void fc_fft_product(const T* src, int klim, int H, T*
         } else if (k == n) {
             v = fre[0] - fim[0];
         } else {
-            const int pa = fc_brev(k, lg), pb = fc_brev(n - k, lg);
+            const int pa = fft_brev(k, lg), pb = fft_brev(n - k, lg);
             const T ar = fre[pa], ai = fim[pa], br = fre[pb], bi = -fim[pb];
             const T dr = T(0.5) * (ar - br), di = T(0.5) * (ai - bi);
             v = T(0.5) * (ar + br) + tw[2 * k] * di + tw[2 * k + 1] * dr;   // tw = (cos, -sin)(2 pi k / L)

@@ -20,8 +20,6 @@
 //   transform  the first largest posterior per vector and y_t = mu_y[k] + Myx_k (x_t - mu_x[k]).
 #include "common.h"
 
-#include <limits>
-
 namespace dsa {
 namespace {
 
@@ -43,12 +41,6 @@ constexpr int GMM_MAX_SEGMENTS = 64;
 constexpr int GMM_FILL_WAVES = 4096;   // waves below which T is split into segments: four per SIMD of 256 compute units
 constexpr int GMM_SEGMENT_MIN = 256;   // vectors per segment at least
 constexpr double GMM_LOG_2PI = 1.8378770664093453;
-
-template <typename T> __device__ __forceinline__ T gmm_inf() { return std::numeric_limits<T>::infinity(); }
-__device__ __forceinline__ bool gmm_finite(float v) { return isfinite(v); }
-__device__ __forceinline__ bool gmm_finite(double v) { return isfinite(v); }
-__device__ __forceinline__ float gmm_abs(float v) { return fabsf(v); }
-__device__ __forceinline__ double gmm_abs(double v) { return fabs(v); }
 
 inline int64_t gmm_lds_bytes(int64_t L, int64_t size) { return 2 * DSA_GMM_TILE_BYTES * (L + 1) + L * (L + 1) * size + 64; }
 
@@ -108,7 +100,7 @@ __global__ __launch_bounds__(64) void gmm_prepare_full_kernel(const T* __restric
     if (bad) {
         for (int e = lane; e < Lp * Lp; e += 64) P[e] = (T)0;
         if (lane == 0) {
-            cst[k] = -gmm_inf<T>();
+            cst[k] = -dsa_inf<T>();
             fail[k] = 1;
         }
         return;
@@ -169,7 +161,7 @@ __global__ __launch_bounds__(DSA_GMM_TILE_BYTES / sizeof(T)) void gmm_estep_kern
     const T* xt = xs + tid * S;
     T* dt = ds + tid * S;
     T* pt = post + t * K;
-    T top = -gmm_inf<T>();
+    T top = -dsa_inf<T>();
     for (int k = 0; k < K; ++k) {
         __syncthreads();   // the component before this one has been read out of LDS (and, at k = 0, the tile is in)
         const int nw = DIAG ? Lp : Lp * Lp;
@@ -212,7 +204,7 @@ __global__ __launch_bounds__(DSA_GMM_TILE_BYTES / sizeof(T)) void gmm_estep_kern
     }
     double mine = 0.0;
     if (live) {   // torch.logsumexp: the maximum first (0 in its place when it is not finite), then log sum exp(numer - maximum)
-        const T ref = gmm_finite(top) ? top : (T)0;
+        const T ref = dsa_isfinite(top) ? top : (T)0;
         T sum = (T)0;
         for (int k = 0; k < K; ++k) sum += dsa_exp(pt[k] - ref);
         const T denom = dsa_log(sum) + ref;
@@ -411,7 +403,7 @@ __global__ __launch_bounds__(256) void gmm_update_kernel(const T* __restrict__ w
                 v = pxx * zi - mm;
             } else {
                 T a = pxx - y * ((T)2 * (nus[j] * mus[j]) - mm);
-                a = gmm_finite(a) ? a : (T)0;
+                a = dsa_isfinite(a) ? a : (T)0;
                 const T um = ubm_mu[(long)k * L + j] - mus[j];
                 v = (a + xi * ubm_sigma[((long)k * L + j) * L + j] + xi * (um * um)) * zi;
             }
@@ -428,7 +420,7 @@ __global__ __launch_bounds__(256) void gmm_update_kernel(const T* __restrict__ w
                 v = pxx * zi - mm;
             } else {
                 T a = pxx - y * ((nus[i] * mus[j] + nus[j] * mus[i]) - mm);
-                a = gmm_finite(a) ? a : (T)0;
+                a = dsa_isfinite(a) ? a : (T)0;
                 const T ui = ubm_mu[(long)k * L + i] - mus[i], uj = ubm_mu[(long)k * L + j] - mus[j];
                 v = (a + xi * ubm_sigma[(long)k * L * L + e] + xi * (ui * uj)) * zi;
             }
@@ -458,10 +450,10 @@ __global__ __launch_bounds__(256) void gmm_regress_kernel(const T* __restrict__ 
     for (int c = 0; c < Lx; ++c) {
         if (tid == 0) {
             int p = c;
-            T best = gmm_abs(Am[c * Lx + c]);
+            T best = dsa_abs(Am[c * Lx + c]);
             for (int i = c + 1; i < Lx; ++i)
-                if (gmm_abs(Am[i * Lx + c]) > best) {
-                    best = gmm_abs(Am[i * Lx + c]);
+                if (dsa_abs(Am[i * Lx + c]) > best) {
+                    best = dsa_abs(Am[i * Lx + c]);
                     p = i;
                 }
             pivot = p;

@@ -5,7 +5,7 @@
 namespace dsa {
 
 // In-place radix-2 decimation-in-frequency FFT of n = 2^lg complex points held in LDS, run by the whole workgroup
-// (forward sign; tw = (cos, -sin)(2 pi m / n)).  Natural-order input, BIT-REVERSED output: X[k] sits at fft_brev(k, lg).
+// (forward sign; tw = (cos, -sin)(2 pi m / n)).  Natural-order input, BIT-REVERSED output: X[k] sits at fft_brev(k, lg) (common.h).
 // The generic row transforms use it whenever fft_length is a power of two (FFT = true): the direct sum they fall
 // back to costs n^2 / 2 multiply-adds per row -- 8.4 M at the 4096 points the MLSA filter's impulse responses use.
 template <typename T>
@@ -60,6 +60,5 @@ __device__ __forceinline__ void lds_fft_pow2(T* re, T* im, int n, int lg, const 
         __syncthreads();
     }
 }
-__device__ __forceinline__ int fft_brev(int k, int lg) { return (int)(__brev((unsigned)k) >> (32 - lg)); }
 
 }  // namespace dsa

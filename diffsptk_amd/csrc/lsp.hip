@@ -36,7 +36,7 @@
 namespace dsa {
 namespace {
 
-constexpr double kLsPi = 3.14159265358979323846;
+// (pi is kPi of common.h)
 constexpr int LS_LEVELS = 7;    // grid steps pi / 64 .. pi / 4096
 constexpr int LS_BISECT = 16;   // a level-0 bracket of 4.9e-2 rad shrinks to 7.5e-7 before the first Newton step
 constexpr int LS_NEWTON = 6;
@@ -103,16 +103,6 @@ __device__ __forceinline__ void ls_walk(const double* cq, const double* cp, int 
         sp = tp;
     }
 }
-__device__ __forceinline__ int ls_scan_excl(int n)
-{
-    int x = n;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o, 64);
-        if ((int)threadIdx.x >= o) x += y;
-    }
-    return x - n;
-}
 
 template <typename T>
 __global__ __launch_bounds__(64) void lsp_lpc2lsp_fwd_kernel(const T* __restrict__ a, long F, int M, int log_gain, double unit,
@@ -153,14 +143,14 @@ __global__ __launch_bounds__(64) void lsp_lpc2lsp_fwd_kernel(const T* __restrict
         bool found = M == 0;
         int nq = 0, np = 0, level = 0;
         for (int r = 0; !found && r < LS_LEVELS; ++r) {
-            ls_walk(cq, cp, Dq, 1 << r, kLsPi / (double)(64 << r), nq, np, false, lq, lp, 0, 0);
+            ls_walk(cq, cp, Dq, 1 << r, kPi / (double)(64 << r), nq, np, false, lq, lp, 0, 0);
             found = wave_sum(nq) == Dq && wave_sum(np) == Dp;
             level = r;
         }
         double x = __builtin_nan("");
         if (found && M > 0) {
-            const double h = kLsPi / (double)(64 << level);
-            ls_walk(cq, cp, Dq, 1 << level, h, nq, np, true, lq, lp, ls_scan_excl(nq), ls_scan_excl(np));
+            const double h = kPi / (double)(64 << level);
+            ls_walk(cq, cp, Dq, 1 << level, h, nq, np, true, lq, lp, wave_scan_incl(nq, lane) - nq, wave_scan_incl(np, lane) - np);
             __syncthreads();
             if (lane < M) {
                 const bool isq = !(lane & 1);
@@ -185,7 +175,7 @@ __global__ __launch_bounds__(64) void lsp_lpc2lsp_fwd_kernel(const T* __restrict
                 }
             }
             const double prev = __shfl_up(x, 1, 64);
-            const bool bad = lane < M && !(x > (lane ? prev : 0.0) && x < kLsPi);   // the roots of Q' and P' interlace, or A is not minimum phase
+            const bool bad = lane < M && !(x > (lane ? prev : 0.0) && x < kPi);   // the roots of Q' and P' interlace, or A is not minimum phase
             if (__ballot(bad)) found = false;
         }
         if (lane < M) out[base + 1 + lane] = found ? (T)(x / unit) : (T)__builtin_nan("");
@@ -239,32 +229,7 @@ __global__ __launch_bounds__(64) void lsp_lpc2lsp_bwd_kernel(const T* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------- one frame per lane
-// a tile of `cnt` consecutive elements (rows of M1) between global memory and LDS rows of stride S
-template <typename T>
-__device__ __forceinline__ void ls_tile_in(T* lds, const T* __restrict__ g, long base, int cnt, int M1, int S)
-{
-    int r = threadIdx.x / M1, c = threadIdx.x - r * M1;
-    const int dq = 64 / M1, dr = 64 - dq * M1;
-    for (int i = threadIdx.x; i < cnt; i += 64) {
-        lds[r * S + c] = g[base + i];
-        r += dq;
-        c += dr;
-        if (c >= M1) { c -= M1; ++r; }
-    }
-}
-template <typename T>
-__device__ __forceinline__ void ls_tile_out(const T* lds, T* __restrict__ g, long base, int cnt, int M1, int S)
-{
-    int r = threadIdx.x / M1, c = threadIdx.x - r * M1;
-    const int dq = 64 / M1, dr = 64 - dq * M1;
-    for (int i = threadIdx.x; i < cnt; i += 64) {
-        g[base + i] = lds[r * S + c];
-        r += dq;
-        c += dr;
-        if (c >= M1) { c -= M1; ++r; }
-    }
-}
-
+// (tiles of rows travel between global memory and LDS rows of stride S by wave_tile_in / wave_tile_out, common.h)
 // per-lane arrays in LDS: element k of the lane's array is v[64 k]
 #define LS_AT(v, k) (v)[(k) << 6]
 
@@ -283,7 +248,7 @@ __device__ __forceinline__ void ls_sections(double* c, const T* wrow, int first,
     while ((1 << bits) < D) ++bits;
     int d = 0;
     for (int t = 0; D > 0 && t < (1 << bits); ++t) {
-        const int j = bits ? (int)(__brev((unsigned)t) >> (32 - bits)) : 0;
+        const int j = bits ? fft_brev(t, bits) : 0;
         if (j >= D) continue;
         const int i = first + 2 * j;
         const double a = (double)wrow[i] * unit;
@@ -352,7 +317,7 @@ __global__ __launch_bounds__(64) void lsp_lane_kernel(const T* __restrict__ in0,
 
     if (OP == LS_LSP2LPC_FWD) {
         double *cq = work, *cp = work + 64 * HP;
-        ls_tile_in(rows, in0, base, cnt, M1, S);
+        wave_tile_in(rows, in0, base, cnt, M1, S);
         __syncthreads();
         if (live) {   // (a lane beyond the last row has no row in LDS)
             const T k0 = mine[0];
@@ -367,7 +332,7 @@ __global__ __launch_bounds__(64) void lsp_lane_kernel(const T* __restrict__ in0,
         }
     } else if (OP == LS_LSP2LPC_BWD) {
         double *cq = work, *cp = work + 64 * HP, *th = work + 128 * HP;
-        ls_tile_in(rows, in1, base, cnt, M1, S);
+        wave_tile_in(rows, in1, base, cnt, M1, S);
         __syncthreads();
         const T k0 = live ? mine[0] : T(0);
         if (live) {
@@ -375,7 +340,7 @@ __global__ __launch_bounds__(64) void lsp_lane_kernel(const T* __restrict__ in0,
             ls_sections(cp, mine, 2, M, p, th);
         }
         __syncthreads();
-        ls_tile_in(rows, in0, base, cnt, M1, S);
+        wave_tile_in(rows, in0, base, cnt, M1, S);
         __syncthreads();
         for (int i = 1; live && i <= M; ++i) {
             const bool isq = i & 1;
@@ -404,8 +369,8 @@ __global__ __launch_bounds__(64) void lsp_lane_kernel(const T* __restrict__ in0,
         for (int i = 1; live && i <= M; ++i) mine[i] = (T)LS_AT(th, i - 1);
     } else if (OP == LS_CHECK_FWD) {
         double* w = work;
-        const double d = (double)(T)p, lo = d, hi = (double)(T)(kLsPi - p), thr = (double)(T)(p - 1e-16), pi_t = (double)(T)kLsPi;
-        ls_tile_in(rows, in0, base, cnt, M1, S);
+        const double d = (double)(T)p, lo = d, hi = (double)(T)(kPi - p), thr = (double)(T)(p - 1e-16), pi_t = (double)(T)kPi;
+        wave_tile_in(rows, in0, base, cnt, M1, S);
         __syncthreads();
         bool bad = false;
         double prev = 0.0;
@@ -425,13 +390,13 @@ __global__ __launch_bounds__(64) void lsp_lane_kernel(const T* __restrict__ in0,
         for (int j = 1; live && j <= M; ++j) mine[j] = (T)LS_AT(w, j - 1);
     } else {
         double *w = work, *g = work + 64 * M;
-        const double d = (double)(T)p, lo = d, hi = (double)(T)(kLsPi - p), thr = (double)(T)(p - 1e-16);
-        ls_tile_in(rows, in0, base, cnt, M1, S);
+        const double d = (double)(T)p, lo = d, hi = (double)(T)(kPi - p), thr = (double)(T)(p - 1e-16);
+        wave_tile_in(rows, in0, base, cnt, M1, S);
         __syncthreads();
         const T gk = live ? mine[0] : T(0);
         for (int j = 1; live && j <= M; ++j) LS_AT(g, j - 1) = (double)mine[j];
         __syncthreads();
-        ls_tile_in(rows, in1, base, cnt, M1, S);
+        wave_tile_in(rows, in1, base, cnt, M1, S);
         __syncthreads();
         unsigned long long pm, cm;
         int ran = 0;   // the sweeps this row ran
@@ -461,7 +426,7 @@ __global__ __launch_bounds__(64) void lsp_lane_kernel(const T* __restrict__ in0,
         for (int j = 1; live && j <= M; ++j) mine[j] = (T)LS_AT(g, j - 1);
     }
     __syncthreads();
-    ls_tile_out(rows, out0, base, cnt, M1, S);
+    wave_tile_out(rows, out0, base, cnt, M1, S);
 }
 #undef LS_AT
 

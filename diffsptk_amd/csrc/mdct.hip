@@ -92,7 +92,7 @@ __device__ __forceinline__ void md_fft_batch(float* re, float* im, int nf, int l
         __syncthreads();
     }
 }
-__device__ __forceinline__ int md_brev(int k, int lg) { return (int)(__brev((unsigned)k) >> (32 - lg)); }
+// (X[k] of the transform above sits at fft_brev(k, lg), common.h)
 
 // the folded frame: v_m of the windowed 2P samples u (cosine: (-c_r - d, a - b_r) of the quarters a b c d; sine: (c_r - d, a + b_r)
 // with alternating sign)
@@ -123,7 +123,7 @@ __device__ __forceinline__ void md_post(const float* re, const float* im, int nf
     const int M = 1 << lgM;
     for (int g = threadIdx.x; g < (nf << lgM); g += MD_THREADS) {
         const int f = g >> lgM, k = g & (M - 1);
-        const int pos = (f << lgM) + md_brev(k, lgM);
+        const int pos = (f << lgM) + fft_brev(k, lgM);
         const float tr = re[pos], ti = im[pos], pr = tw[2 * k], pi = tw[2 * k + 1];
         const float cr = tr * pr - ti * pi, ci = tr * pi + ti * pr;
         const int i0 = 2 * k, i1 = P - 1 - 2 * k;

@@ -390,7 +390,7 @@ __global__ __launch_bounds__(256) void gc2gc_fused_kernel(const T* __restrict__ 
     }
     __syncthreads();
     lds_fft_pow2(re, im, H, lgh, tw, 2);   // Z[k] at position brev(k)
-    constexpr T kPi = T(3.14159265358979323846);
+    constexpr T pi = T(kPi);
     auto gmap = [&](T cr, T ci) -> T {
         T lmag, ang;   // log |s|, angle(s) (wrapped to (-pi, pi] as .angle() of the reference's polar(r, theta) is)
         if (g1 == T(0)) {
@@ -402,7 +402,7 @@ __global__ __launch_bounds__(256) void gc2gc_fused_kernel(const T* __restrict__ 
             ang = atan2(zi, zr) / g1;
         }
         if (g2 == T(0)) return lmag;
-        ang -= T(2) * kPi * rint(ang / (T(2) * kPi));
+        ang -= T(2) * pi * rint(ang / (T(2) * pi));
         return (dsa_exp(g2 * lmag) * cos(ang * g2) - T(1)) / g2;
     };
     // split into X[k], X[H - k] and map both (C2 is real and even: cb[k], k = 0 .. H, carries it all)
@@ -486,7 +486,7 @@ __global__ __launch_bounds__(256) void gc2gc_fused_bwd_kernel(const T* __restric
     const T* row = c1 + f * n_in;
     const T* grow = g2row + f * (long)(out_order + 1);
     const int lgh = 30 - __clz(nfft);
-    constexpr T kPi = T(3.14159265358979323846);
+    constexpr T pi = T(kPi);
     // half-length transform of a packed real sequence, then the split into the half spectrum (dr, di)[0 .. H]
     auto split_to = [&](T* dr, T* di) {
         for (int k = threadIdx.x; k <= (H >> 1); k += blockDim.x) {
@@ -551,7 +551,7 @@ __global__ __launch_bounds__(256) void gc2gc_fused_bwd_kernel(const T* __restric
         if (g2 == T(0)) {
             f_l = T(1); f_a = T(0);
         } else {
-            ang -= T(2) * kPi * rint(ang / (T(2) * kPi));
+            ang -= T(2) * pi * rint(ang / (T(2) * pi));
             const T e = dsa_exp(g2 * lmag);
             f_l = e * cos(ang * g2);
             f_a = -e * sin(ang * g2);
@@ -665,8 +665,8 @@ __global__ __launch_bounds__(256) void mgcep_gain_kernel(const T* __restrict__ r
         acc += r[f * (M + 1) + m + 1] * b_eps[f * M + m];
         b[f * (M + 1) + m + 1] = b_join[f * M + m];
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    // lane 0 has the row's whole sum
+    acc = wave_sum(acc);
     if (lane == 0) b[f * (M + 1)] = sqrt(r[f * (M + 1)] + gamma * acc);
 }
 }  // namespace dsa

@@ -147,8 +147,9 @@ template <int K> struct MlpgRing {
     }
 };
 
-// one value of a wave-wide register, from the lane `l` (a compile-time constant once the loops are unrolled), as a scalar
-__device__ __forceinline__ float pg_lane(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+// one value of a wave-wide register, from the lane `l` (a compile-time constant once the loops are unrolled), as a scalar.  The
+// double keeps this spelling of its own: with wave_readlane's the compiler schedules mlpg_sweep_kernel<double, 0> differently.
+__device__ __forceinline__ float pg_lane(float v, int l) { return wave_readlane(v, l); }
 __device__ __forceinline__ double pg_lane(double v, int l)
 {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));

@@ -35,31 +35,7 @@ __device__ __forceinline__ double pc_clip(double v, double b) { return v < -b ? 
 __device__ __forceinline__ bool pc_inside(double v, double b) { return v >= -b && v <= b; }              // torch.clip's gradient mask
 
 // ---------------------------------------------------------------------------------------------- one frame per lane
-// a tile of `cnt` consecutive elements (rows of M1) between global memory and LDS rows of stride S
-template <typename T>
-__device__ __forceinline__ void pc_tile_in(T* lds, const T* __restrict__ g, long base, int cnt, int M1, int S)
-{
-    int r = threadIdx.x / M1, c = threadIdx.x - r * M1;
-    const int dq = 64 / M1, dr = 64 - dq * M1;
-    for (int i = threadIdx.x; i < cnt; i += 64) {
-        lds[r * S + c] = g[base + i];
-        r += dq;
-        c += dr;
-        if (c >= M1) { c -= M1; ++r; }
-    }
-}
-template <typename T>
-__device__ __forceinline__ void pc_tile_out(const T* lds, T* __restrict__ g, long base, int cnt, int M1, int S)
-{
-    int r = threadIdx.x / M1, c = threadIdx.x - r * M1;
-    const int dq = 64 / M1, dr = 64 - dq * M1;
-    for (int i = threadIdx.x; i < cnt; i += 64) {
-        g[base + i] = lds[r * S + c];
-        r += dq;
-        c += dr;
-        if (c >= M1) { c -= M1; ++r; }
-    }
-}
+// (tiles of rows travel between global memory and LDS rows of stride S by wave_tile_in / wave_tile_out, common.h)
 template <typename T, int NM>
 __device__ __forceinline__ void pc_row_get(double (&v)[NM + 1], const T* lds, int S, int M, bool live)
 {
@@ -183,12 +159,12 @@ __global__ __launch_bounds__(64) void parcor_lane_kernel(const T* __restrict__ i
     const bool live = (int)threadIdx.x < n;
     double v[NM + 1], k[NM + 1];
 
-    pc_tile_in(lds, in0, base, cnt, M1, S);
+    wave_tile_in(lds, in0, base, cnt, M1, S);
     __syncthreads();
     pc_row_get<T, NM>(v, lds, S, M, live);
     if (OP == PC_LPC2PAR_BWD || OP == PC_PAR2LPC_BWD || OP == PC_CHECK_BWD) {
         __syncthreads();
-        pc_tile_in(lds, in1, base, cnt, M1, S);
+        wave_tile_in(lds, in1, base, cnt, M1, S);
         __syncthreads();
         pc_row_get<T, NM>(k, lds, S, M, live);
     }
@@ -226,7 +202,7 @@ __global__ __launch_bounds__(64) void parcor_lane_kernel(const T* __restrict__ i
             __syncthreads();
             pc_row_put<T, NM>(v, lds, S, M);
             __syncthreads();
-            pc_tile_out(lds, out1, base, cnt, M1, S);
+            wave_tile_out(lds, out1, base, cnt, M1, S);
         }
 #pragma unroll
         for (int j = 1; j <= NM; ++j) v[j] = pc_clip(v[j], p);
@@ -244,7 +220,7 @@ __global__ __launch_bounds__(64) void parcor_lane_kernel(const T* __restrict__ i
     __syncthreads();
     pc_row_put<T, NM>(v, lds, S, M);
     __syncthreads();
-    pc_tile_out(lds, out0, base, cnt, M1, S);
+    wave_tile_out(lds, out0, base, cnt, M1, S);
 }
 
 // ---------------------------------------------------------------------------------------------- one frame per wave, the row in LDS

@@ -32,15 +32,6 @@ constexpr int kPdR = 8;         // registers per lane of the row-window prefetch
 constexpr int kPdE = 64 * 64;   // one E table
 constexpr int kPdCh = 256;      // samples per LDS chunk of the ga kernel
 
-__device__ __forceinline__ float pd_readlane(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
-__device__ __forceinline__ double pd_readlane(double v, int l)
-{
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), l);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
 __device__ __forceinline__ long pd_clamp(long t, long Tlen) { return t < 0 ? 0 : (t >= Tlen ? Tlen - 1 : t); }
 
 __device__ __forceinline__ long pd_div(long t, int P, bool small) { return small ? (long)((unsigned)t / (unsigned)P) : t / P; }
@@ -116,7 +107,7 @@ __device__ __forceinline__ void pd_ring(T& acc, T& yv, T seed, const T* Eb, int 
             yv = m ? acc : yv;
             acc = m ? seed : acc;
         }
-        const T yj = pd_readlane(acc, j);
+        const T yj = wave_readlane(acc, j);
         acc = fma(-Eb[j * 64 + lane], yj, acc);
     }
     const bool m = lane >= 64 - Q;

@@ -13,18 +13,6 @@ namespace dsa {
 // larger systems: that one spends ~80 cycles per element on dependent LDS round trips (0.53 ms per 51 200 frames of 24 x 24,
 // 43 % of a mel-generalized analysis), this one ~6 k cycles per frame.
 // Returns in (col, sol): lane i < n was the pivot row of column `col`, and x[col] = sol.
-template <typename T>
-__device__ __forceinline__ T th_readlane(T v, int src)
-{
-    if constexpr (sizeof(T) == 4) {
-        return __builtin_bit_cast(T, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), src));
-    } else {
-        const long long b = __builtin_bit_cast(long long, v);
-        const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(b & 0xffffffffll), src);
-        const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(b >> 32), src);
-        return __builtin_bit_cast(T, (long long)(((unsigned long long)hi << 32) | lo));
-    }
-}
 template <typename T, int NMAX>
 __device__ __forceinline__ void th_solve_reg(const T* ps, const T* qs, T rhs, int n, int lane, int& col, T& sol)
 {
@@ -54,8 +42,9 @@ __device__ __forceinline__ void th_solve_reg(const T* ps, const T* qs, T rhs, in
             DSA_TH_MAX(0x111, 0xf) DSA_TH_MAX(0x112, 0xf) DSA_TH_MAX(0x114, 0xf) DSA_TH_MAX(0x118, 0xf)   // row_shr:1, 2, 4, 8
             DSA_TH_MAX(0x142, 0xa) DSA_TH_MAX(0x143, 0xc)                                                 // row_bcast:15, :31
 #undef DSA_TH_MAX
+            // (the builtin itself: through wave_readlane the compiler swaps operands of scalar ORs in 25 kernels that inline this)
             const int p = 63 - (int)(__builtin_amdgcn_readlane((int)key, 63) & 63);
-            const T pk = th_readlane(row[k], p);
+            const T pk = wave_readlane(row[k], p);
             const T fac = (lane != p) ? row[k] / pk : T(0);
             if (lane == p) {
                 used = true;
@@ -63,8 +52,8 @@ __device__ __forceinline__ void th_solve_reg(const T* ps, const T* qs, T rhs, in
                 piv = row[k];
             }
 #pragma unroll
-            for (int j = k + 1; j < NMAX; ++j) row[j] -= fac * th_readlane(row[j], p);
-            rhs -= fac * th_readlane(rhs, p);
+            for (int j = k + 1; j < NMAX; ++j) row[j] -= fac * wave_readlane(row[j], p);
+            rhs -= fac * wave_readlane(rhs, p);
         }
     }
     sol = rhs / piv;

@@ -70,7 +70,7 @@ __global__ __launch_bounds__(DSA_VQ_TILE_BYTES / sizeof(T)) void vq_search_kerne
     for (long e = tid; e < rows * L; e += TILE) xs[(e / L) * S + e % L] = x[t0 * L + e];
     const bool live = t < Tn;
     const T* xt = xs + tid * S;
-    double best = std::numeric_limits<double>::infinity();
+    double best = dsa_inf<double>();
     int arg = 0;
     for (int k0 = 0; k0 < K; k0 += DSA_VQ_CHUNK) {
         const int kn = K - k0 < DSA_VQ_CHUNK ? K - k0 : DSA_VQ_CHUNK, kn4 = (kn + 3) & ~3;

@@ -46,26 +46,7 @@ constexpr int WS_THREADS = 256;        // the time-base workgroup, and the overl
 constexpr int WS_CHUNK = 2048;         // samples of the time base in LDS at a time: eight per thread
 constexpr int WS_MAX_THREADS = 1024;   // the per-pulse workgroup: L / 4, between 64 and this
 constexpr int WS_RED_BYTES = 256;      // the reductions' exchange at the head of the per-pulse LDS
-constexpr double kWsTau = 6.283185307179586476925286766559;   // math.tau (utils/private.py)
-constexpr double kWsPi = 3.14159265358979323846264338327950288;
 constexpr double kWsEps = 1e-6;        // world_synth.py:189
-
-// products, sums and differences that the compiler may not contract with their neighbours (the unit is built with -ffp-contract=on,
-// which fuses within one expression only; these are expressions of their own)
-__device__ __forceinline__ float ws_mul(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ double ws_mul(double a, double b) { return __dmul_rn(a, b); }
-__device__ __forceinline__ float ws_add(float a, float b) { return __fadd_rn(a, b); }
-__device__ __forceinline__ double ws_add(double a, double b) { return __dadd_rn(a, b); }
-__device__ __forceinline__ float ws_sub(float a, float b) { return __fsub_rn(a, b); }
-__device__ __forceinline__ double ws_sub(double a, double b) { return __dsub_rn(a, b); }
-__device__ __forceinline__ float ws_fmod(float a, float b) { return fmodf(a, b); }
-__device__ __forceinline__ double ws_fmod(double a, double b) { return fmod(a, b); }
-__device__ __forceinline__ float ws_abs(float v) { return fabsf(v); }
-__device__ __forceinline__ double ws_abs(double v) { return fabs(v); }
-__device__ __forceinline__ float ws_floor(float v) { return floorf(v); }
-__device__ __forceinline__ double ws_floor(double v) { return floor(v); }
-__device__ __forceinline__ float ws_ceil(float v) { return ceilf(v); }
-__device__ __forceinline__ double ws_ceil(double v) { return ceil(v); }
 
 // ---------------------------------------------------------------------------------------------------------------- time base
 template <typename T>
@@ -76,7 +57,7 @@ struct WsTimeBase {
     T step, sr, fmin, deflt;   // (dtype)(P / sr), (dtype) sr, (dtype)(sr / L + 1), (dtype) default_f0
     double dphase;             // tau / sr
 
-    __device__ __forceinline__ T x(long n) const { return ws_mul((T)n, step); }
+    __device__ __forceinline__ T x(long n) const { return rn_mul((T)n, step); }
     __device__ __forceinline__ T y(long n) const
     {
         const T v = f0[n];
@@ -96,12 +77,12 @@ struct WsTimeBase {
             vf = y(k == 0 ? 0 : N - 1);
             vv = T(0) < vf ? T(1) : T(0);
         } else {
-            const T x0 = x(k - 1), dx = ws_sub(x(k), x0);
+            const T x0 = x(k - 1), dx = rn_sub(x(k), x0);
             const T y0 = y(k - 1), y1 = y(k);
             const T v0 = T(0) < y0 ? T(1) : T(0), v1 = T(0) < y1 ? T(1) : T(0);
-            const T mf = ws_sub(y1, y0) / dx, mv = ws_sub(v1, v0) / dx;
-            vf = ws_add(ws_mul(mf, t), ws_sub(y0, ws_mul(mf, x0)));
-            vv = ws_add(ws_mul(mv, t), ws_sub(v0, ws_mul(mv, x0)));
+            const T mf = rn_sub(y1, y0) / dx, mv = rn_sub(v1, v0) / dx;
+            vf = rn_add(rn_mul(mf, t), rn_sub(y0, rn_mul(mf, x0)));
+            vv = rn_add(rn_mul(mv, t), rn_sub(v0, rn_mul(mv, x0)));
         }
         voiced = T(0.5) < vv;
         f = voiced ? vf : deflt;
@@ -110,32 +91,9 @@ struct WsTimeBase {
     {
         T f;
         at(i, f, voiced);
-        return ws_mul(dphase, (double)f);
+        return rn_mul(dphase, (double)f);
     }
 };
-
-// exclusive prefix over the 256 threads and the total; red: 8 slots
-template <typename V>
-__device__ __forceinline__ V ws_block_scan(V v, V* red, V& total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    V inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const V u = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += u;
-    }
-    __syncthreads();
-    if (lane == 63) red[w] = inc;
-    __syncthreads();
-    V before = 0, all = 0;
-    for (int i = 0; i < WS_THREADS / 64; ++i) {
-        if (i < w) before += red[i];
-        all += red[i];
-    }
-    total = all;
-    return before + inc - v;
-}
 
 // irec: (pulses, 4) int64 = sample index, utterance, floor frame, ceil frame; frec: (pulses, 3) of the dtype = the fractional time shift in
 // seconds, the upper weight frame - floor, the voiced flag.  Both NULL: only counts[b] is written.
@@ -152,7 +110,7 @@ __global__ __launch_bounds__(WS_THREADS) void ws_pulses_kernel(const T* __restri
     const int t = threadIdx.x;
     const long b = blockIdx.x, Tn = N * (long)P;
     const WsTimeBase<T> tb{f0 + b * N, N, P, step, sr, fmin, deflt, dphase};
-    const T tau = (T)kWsTau, pi = (T)kWsPi;
+    const T tau = (T)kTau, pi = (T)kPi;
     constexpr int PER = WS_CHUNK / WS_THREADS;
     long at = irec ? offsets[b] : 0;
     const long end = irec ? offsets[b + 1] : 0;
@@ -179,29 +137,29 @@ __global__ __launch_bounds__(WS_THREADS) void ws_pulses_kernel(const T* __restri
         unsigned hits = 0;
         for (int j = j0; j < j1; ++j) {
             if (c0 + j == 0) continue;
-            const T w0 = ws_fmod((T)ph[j], tau), w1 = ws_fmod((T)ph[1 + j], tau);
-            if (pi < ws_abs(ws_sub(w1, w0))) hits |= 1u << (j - j0);
+            const T w0 = dsa_fmod((T)ph[j], tau), w1 = dsa_fmod((T)ph[1 + j], tau);
+            if (pi < dsa_abs(rn_sub(w1, w0))) hits |= 1u << (j - j0);
         }
         int all;
-        const int before = ws_block_scan((int)__popc(hits), ired, all);
+        const int before = team_scan_excl((int)__popc(hits), ired, t, WS_THREADS, all);
         if (irec) {
             long row = at + before;
             for (int j = j0; j < j1; ++j) {
                 if (!(hits >> (j - j0) & 1u) || row >= end) continue;
                 const long i = c0 + j - 1;
-                const T w0 = ws_fmod((T)ph[j], tau), w1 = ws_fmod((T)ph[1 + j], tau);
+                const T w0 = dsa_fmod((T)ph[j], tau), w1 = dsa_fmod((T)ph[1 + j], tau);
                 T f;
                 tb.at(i, f, voiced);
-                const T y1 = ws_sub(w0, tau);
-                const T shift = (-y1 / ws_sub(w1, y1)) / sr;
-                const T frame = ws_mul(tb.time(i), rate);
-                const long fl = min((long)ws_floor(frame), N - 1), ce = min((long)ws_ceil(frame), N - 1);
+                const T y1 = rn_sub(w0, tau);
+                const T shift = (-y1 / rn_sub(w1, y1)) / sr;
+                const T frame = rn_mul(tb.time(i), rate);
+                const long fl = min((long)dsa_floor(frame), N - 1), ce = min((long)dsa_ceil(frame), N - 1);
                 irec[row * 4 + 0] = i;
                 irec[row * 4 + 1] = b;
                 irec[row * 4 + 2] = fl;
                 irec[row * 4 + 3] = ce;
                 frec[row * 3 + 0] = shift;
-                frec[row * 3 + 1] = ws_sub(frame, (T)fl);
+                frec[row * 3 + 1] = rn_sub(frame, (T)fl);
                 frec[row * 3 + 2] = voiced ? T(1) : T(0);
                 ++row;
             }
@@ -580,7 +538,7 @@ int ws_pulses(const void* f0, int64_t B, int64_t N, int32_t P, int32_t sr, int32
               void* irec, void* frec, hipStream_t st)
 {
     hipLaunchKernelGGL((ws_pulses_kernel<T>), dim3((unsigned)B), dim3(WS_THREADS), 0, st, (const T*)f0, (long)N, (int)P, (T)((double)P / (double)sr),
-                       (T)sr, (T)((double)sr / (double)L + 1.0), (T)default_f0, (T)((double)sr / (double)P), kWsTau / (double)sr,
+                       (T)sr, (T)((double)sr / (double)L + 1.0), (T)default_f0, (T)((double)sr / (double)P), kTau / (double)sr,
                        (const int64_t*)offsets, (int64_t*)counts, (int64_t*)irec, (T*)frec);
     return DSA_OK;
 }
@@ -594,7 +552,7 @@ int ws_responses(const void* ap, const void* sp, const void* noise, const void* 
         return fail(DSA_ERR_LAUNCH, "world_synth: cannot raise the dynamic LDS limit");
     hipLaunchKernelGGL((ws_responses_kernel<T>), dim3((unsigned)pulses), dim3(plan.threads), plan.lds, st, (const T*)ap, (const T*)sp, (const T*)noise,
                        (const int64_t*)irec, (const T*)frec, (const int64_t*)offsets, (const T*)remover, (const T*)tw, (long)B, (long)N, (int)L,
-                       plan.lg, (T)(kWsTau * (double)sr / (double)L), (T*)response);
+                       plan.lg, (T)(kTau * (double)sr / (double)L), (T*)response);
     return DSA_OK;
 }
 
@@ -608,7 +566,7 @@ int ws_vjp_pulses(const void* gy, const void* ap, const void* sp, const void* no
         return fail(DSA_ERR_LAUNCH, "world_synth: cannot raise the dynamic LDS limit");
     hipLaunchKernelGGL((ws_vjp_pulses_kernel<T>), dim3((unsigned)pulses), dim3(plan.threads), plan.lds, st, (const T*)gy, (const T*)ap, (const T*)sp,
                        (const T*)noise, (const int64_t*)irec, (const T*)frec, (const int64_t*)offsets, (const T*)remover, (const T*)tw, (long)B,
-                       (long)N, (long)Tout, (int)L, plan.lg, (T)(kWsTau * (double)sr / (double)L), (T*)grows);
+                       (long)N, (long)Tout, (int)L, plan.lg, (T)(kTau * (double)sr / (double)L), (T*)grows);
     return DSA_OK;
 }
 

@@ -58,29 +58,7 @@ struct YinSource {
     }
 };
 
-// The exclusive prefix of v over a team's threads (rank t of `team`, a multiple of 64) and the team's total; red: the team's YIN_RED
-// slots.  Every thread of the workgroup calls it (two barriers).
-__device__ __forceinline__ double yin_team_scan(double v, double* red, int t, int team, double& total)
-{
-    const int lane = t & 63, w = t >> 6, nw = team >> 6;
-    double inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const double u = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += u;
-    }
-    __syncthreads();   // an earlier call's slots may still be read
-    if (lane == 63) red[w] = inc;
-    __syncthreads();
-    double before = 0, all = 0;
-    for (int i = 0; i < nw; ++i) {
-        if (i < w) before += red[i];
-        all += red[i];
-    }
-    total = all;
-    return before + inc - v;
-}
-
+// (prefix sums over a team's threads: team_scan_excl, common.h; red: the team's YIN_RED slots)
 // step 2 in place: d[1 .. K-1] -> d'[1 .. K-1], d'[0] = 1.  Thread t owns the lags [lo, hi).
 template <typename T>
 __device__ __forceinline__ void yin_normalise(T* d, int K, double* red, int t, int team)
@@ -90,7 +68,7 @@ __device__ __forceinline__ void yin_normalise(T* d, int K, double* red, int t, i
     double s = 0;
     for (int k = lo; k < hi; ++k) s += (double)d[k];
     double total;
-    double run = yin_team_scan(s, red, t, team, total);
+    double run = team_scan_excl(s, red, t, team, total);
     for (int k = lo; k < hi; ++k) {
         const double v = (double)d[k];
         run += v;
@@ -147,7 +125,7 @@ __device__ __forceinline__ void yin_normalise_adjoint(const T* d, T* g, int K, d
     double s = 0;
     for (int k = lo; k < hi; ++k) s += (double)d[k];
     double total;
-    const double s0 = yin_team_scan(s, red, t, team, total);
+    const double s0 = team_scan_excl(s, red, t, team, total);
     double run = s0, qs = 0;
     for (int k = lo; k < hi; ++k) {
         const double v = (double)d[k];
@@ -156,7 +134,7 @@ __device__ __forceinline__ void yin_normalise_adjoint(const T* d, T* g, int K, d
         qs += (double)g[k] * (double)k * v / (den * den);
     }
     double qall;
-    double before = yin_team_scan(qs, red, t, team, qall);
+    double before = team_scan_excl(qs, red, t, team, qall);
     run = s0;
     for (int k = lo; k < hi; ++k) {
         const double v = (double)d[k];
@@ -350,7 +328,7 @@ __device__ __forceinline__ void yin_fft_differences(const YinRow<T>& row, int L,
             s += v * v;
         }
         double total;
-        double run = yin_team_scan(s, red, t, nt, total);
+        double run = team_scan_excl(s, red, t, nt, total);
         for (int j = lo; j < hi; ++j) {
             const double v = (double)(j & 1 ? im[j >> 1] : re[j >> 1]);
             run += v * v;
@@ -428,7 +406,7 @@ __global__ __launch_bounds__(YIN_FFT_MAX_THREADS) void yin_vjp_fft_kernel(const 
         double sum = 0;
         for (int k = lo; k < hi; ++k) sum += (double)s.buf[k];
         double total;
-        double run = yin_team_scan(sum, s.red, t, nt, total);
+        double run = team_scan_excl(sum, s.red, t, nt, total);
         for (int k = lo; k < hi; ++k) {
             run += (double)s.buf[k];
             G[k] = run;

@@ -391,6 +391,35 @@ def test_every_csrc_header_compiles_alone():
     assert not failed, failed
 
 
+def test_shared_device_helpers_are_not_copied():
+    """The builtins that the shared device helpers of csrc/common.h wrap -- wave_readlane, rn_mul / rn_add / rn_sub / rn_div,
+    fft_brev -- appear in no other file of csrc/ (read as text): a unit that needs one calls the helper and does not bring a
+    copy under a prefix of its own.  The exceptions are listed by file and builtin, each with its reason."""
+    from diffsptk_amd import _lib
+
+    primitives = {
+        "readlane": r"\b__builtin_amdgcn_readlane\b",
+        "rn": r"\b__[fd](?:mul|add|sub|div)_rn\b",
+        "brev": r"\b__brev\b",
+    }
+    allowed = {
+        # the one read of the wave's maximum inside the tuned lpc24 kernels, spelled as it was when they were tuned
+        ("lpc24.h", "readlane"),
+        # the pivot key's read in th_solve_reg: through wave_readlane the code of 25 kernels that inline it changes (two of them tuned)
+        ("th_solve_reg.h", "readlane"),
+        # pg_lane(double): with wave_readlane's spelling the compiler schedules mlpg_sweep_kernel<double, 0> differently
+        ("paramgen.hip", "readlane"),
+    }
+    files = sorted(f for f in os.listdir(_lib.CSRC) if f.endswith((".hip", ".h")))
+    assert len(files) >= 55 and "common.h" in files
+    found = set()
+    for f in files:
+        text = open(os.path.join(_lib.CSRC, f)).read()
+        found |= {(f, name) for name, pattern in primitives.items() if re.search(pattern, text)}
+    assert {name for f, name in found if f == "common.h"} == set(primitives)   # the patterns see the shared definitions
+    assert {(f, name) for f, name in found if f != "common.h"} == allowed
+
+
 def test_no_crossed_packed_float32():
     """The mechanical form of DESIGN.md 4's invariant: NO kernel of the built library contains a packed float32 instruction
     with a set op_sel bit (a low result half reading a high source half) -- the instruction class of every transient wrong
