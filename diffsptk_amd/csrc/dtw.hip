@@ -27,7 +27,7 @@
 namespace dsa {
 namespace {
 
-// dsa_last_kernel() of the three entries: [entry][route][dtype]  (these move into tests/kernel_routes.py in a follow-up)
+// dsa_last_kernel() of the three entries: [entry][route][dtype]  (tests/kernel_routes.py reads the table: PINNED_ELSEWHERE has every name)
 enum { DTW_FORWARD = 0, DTW_VJP = 1, DTW_PATH = 2 };
 enum { DTW_WAVE = 0, DTW_BLOCK = 1 };
 const char* const kDtwRoutes[3][2][2] = {

@@ -53,7 +53,6 @@ __device__ __forceinline__ void fc_fft_twiddles(const T* __restrict__ A, int H, 
         tw[2 * m + 1] = T(-0.5) * A[H + (q < 0 ? -q : q)];     // -sin = -cos(2 pi (m - L/4) / L)
     }
 }
-// (X[k] of the transform below sits at fft_brev(k, lg), common.h)
 // Round 3: the even extension of src is REAL, so the L-point transform runs as a complex transform of HALF the length on the
 // packed sequence z[n] = x[2n] + i x[2n+1], followed by the split's real part
 //   Re X[k] = (Zr[k] + Zr[L/2 - k]) / 2 + cos(2 pi k / L) (Zi[k] + Zi[L/2 - k]) / 2 - sin(2 pi k / L) (Zr[k] - Zr[L/2 - k]) / 2

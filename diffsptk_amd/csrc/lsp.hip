@@ -36,7 +36,6 @@
 namespace dsa {
 namespace {
 
-// (pi is kPi of common.h)
 constexpr int LS_LEVELS = 7;    // grid steps pi / 64 .. pi / 4096
 constexpr int LS_BISECT = 16;   // a level-0 bracket of 4.9e-2 rad shrinks to 7.5e-7 before the first Newton step
 constexpr int LS_NEWTON = 6;

@@ -92,7 +92,6 @@ __device__ __forceinline__ void md_fft_batch(float* re, float* im, int nf, int l
         __syncthreads();
     }
 }
-// (X[k] of the transform above sits at fft_brev(k, lg), common.h)
 
 // the folded frame: v_m of the windowed 2P samples u (cosine: (-c_r - d, a - b_r) of the quarters a b c d; sine: (c_r - d, a + b_r)
 // with alternating sign)

@@ -665,7 +665,6 @@ __global__ __launch_bounds__(256) void mgcep_gain_kernel(const T* __restrict__ r
         acc += r[f * (M + 1) + m + 1] * b_eps[f * M + m];
         b[f * (M + 1) + m + 1] = b_join[f * M + m];
     }
-    // lane 0 has the row's whole sum
     acc = wave_sum(acc);
     if (lane == 0) b[f * (M + 1)] = sqrt(r[f * (M + 1)] + gamma * acc);
 }

@@ -7,7 +7,11 @@ exactly one of
   PINNED_ELSEWHERE  route -> "tests/<file>.py::<test function>" that already asserts the name through last_kernel()
   EXEMPT            route -> why no case can name it (at most 5)
 
-and FORWARDED lists the names that reach check_launch() through a variable, with the source line that spells them.
+The names are the string literals inside the parentheses of a check_launch(...) call and the literals of every name table of the
+sources (`const char* const k<Name>Routes[...]` / `k<Name>Names[...]`, which a launcher indexes on its way to check_launch());
+FORWARDED lists the few that reach check_launch() as a function argument or through a local, with the function that spells them.
+Every pointer into the sources is "csrc/<file>::<function>", the host function that encloses the site, never a line number: an
+edit elsewhere in the file leaves it valid, and a renamed or removed function fails by the row's name.
 tests/test_routes_cpu.py checks, without a GPU, that nothing is missing, stale or in two places.  The same discipline holds the other
 end of every launcher: each DSA_ERR_UNSUPPORTED of the sources is claimed by exactly one of REFUSALS (the first refused shapes of
 csrc/lpc.hip), CEILINGS (every size condition that refuses or silently reshapes a launch: the last shape in by float64, the first
@@ -189,7 +193,7 @@ REFUSALS = [
 
 # ---- the size ceilings.  One row per size condition of csrc/*.hip / *.h that refuses a launch (DSA_ERR_UNSUPPORTED) or silently
 # reshapes it (fewer waves per block, a table left in global memory, the direct sum instead of the FFT: the route name stays):
-#   where     "file:line" of the condition(s)
+#   where     "csrc/<file>::<function>": the host function(s) that hold the condition
 #   says      the launcher's message, or "reshapes: ..." and what changes
 #   inside    (route, case) at the last accepted shape: every dtype, the forward, and the backward where there is one
 #   outside   the nearest shape past the condition: raises(message, shape) -- BackendError from the forward, RuntimeError from autograd
@@ -254,7 +258,7 @@ def mlsa_rows(mode, last_fwd, last_bwd, step, moves):
     def a(v):
         return dict(dict(M=24, mode=mode, n_fft=256, F=3), **{moves: v})
 
-    return ceiling("csrc/mlsacheck.hip:452", E_MC,
+    return ceiling("csrc/mlsacheck.hip::mlsacheck_generic_launch", E_MC,
                    inside=[("mlsacheck_generic_fwd", case("mlsacheck", "fwd", **a(last_fwd))),
                            ("mlsacheck_generic_bwd", case("mlsacheck", "bwd", wrt=("mc",), **a(last_bwd)))],
                    outside=[raises(E_MC, shape("mlsacheck", "fwd", BOTH, **a(last_fwd + step)), "mlsacheck_generic_fwd: the row and the bins"),
@@ -264,7 +268,7 @@ def mlsa_rows(mode, last_fwd, last_bwd, step, moves):
 def plp_waves(what, n32, n64):
     """a block of plp_fwd / plp_bwd goes from 4 waves to 2 to 1 as a wave's slice (8 (C + 194) + sizeof(T) (128 + 2 J), J = n_fft / 2 + 1)
     passes 16 KB and 32 KB: the last n_fft on one side, n_fft + 2 on the other, both under the same route name"""
-    return ceiling("csrc/plp.hip:288", "reshapes: " + what,
+    return ceiling("csrc/plp.hip::plp_geometry", "reshapes: " + what,
                    inside=per(B32_64(n32, n64), lambda dt, n: ("plp_fwd", case("plp_tail", "fwd", dt, n_fft=n, **PL, **PLP_OUT)))
                    + per(B32_64(n32, n64), lambda dt, n: ("plp_bwd", case("plp_tail", "bwd", dt, wrt=("y", "E"), n_fft=n, **PL))),
                    outside=per(B32_64(n32 + 2, n64 + 2), lambda dt, n: runs("plp_fwd", case("plp_tail", "fwd", dt, n_fft=n, **PL, **PLP_OUT)))
@@ -273,37 +277,37 @@ def plp_waves(what, n32, n64):
 
 CEILINGS = [
     # ---- csrc/lpc.hip (60 KB of LDS each).  acorr_fwd keeps the frame: sizeof(T) L
-    ceiling("csrc/lpc.hip:357", "acorr: frame too long for LDS",
+    ceiling("csrc/lpc.hip::acorr_fwd_impl", "acorr: frame too long for LDS",
             inside=per(B32_64(15360, 7680), lambda dt, L: ("acorr_fwd", case("acorr", "fwd", dt, L=L, **AC))), outside=IN_REFUSALS),
     # acorr_bwd keeps the frame (rounded up to 8 bytes) and the M + 1 cotangents as doubles: with 3 lags the frame ends 6 (float32)
     # and 3 (float64) samples sooner -- between the two ceilings Autocorrelation has a forward and no gradient
-    ceiling("csrc/lpc.hip:383", "acorr_bwd: frame too long for LDS",
+    ceiling("csrc/lpc.hip::acorr_bwd_impl", "acorr_bwd: frame too long for LDS",
             inside=per(B32_64(15354, 7677), lambda dt, L: ("acorr_bwd", case("acorr", "bwd", dt, wrt=("x",), L=L, **AC))),
             outside=per(B32_64(15355, 7678), lambda dt, L: raises("acorr_bwd: frame too long for LDS", shape("acorr", "bwd", dt, wrt=("x",), L=L, **AC)))),
     # levdur_fwd_lds: 3 (M + 1) doubles.  The autocorrelation of white noise, frames four times the order, with the module's eps: the
     # float32 restatement stays at 1e-6 of the largest entry at these orders (MEASURED), so no better-conditioned input is needed
-    ceiling("csrc/lpc.hip:372", "levdur: order too large for LDS",
+    ceiling("csrc/lpc.hip::levdur_fwd_impl", "levdur: order too large for LDS",
             inside=[("levdur_fwd_lds", case("levdur", "fwd", M=2559, **LD))], outside=IN_REFUSALS),
     # levdur_bwd_toeplitz: 7 M + 1 doubles
-    ceiling("csrc/lpc.hip:402", "levdur_bwd: order too large for LDS",
+    ceiling("csrc/lpc.hip::levdur_bwd_impl", "levdur_bwd: order too large for LDS",
             inside=[("levdur_bwd_toeplitz", case("levdur", "bwd", wrt=("r",), M=1097, **LD))], outside=IN_REFUSALS),
     # frame_window_lpc_kernel: 4 frames of sizeof(T) L per block.  Past it fuse(Frame, Window, LPC) runs the three modules
-    ceiling("csrc/lpc.hip:532", "frame_window_lpc: frame too long for LDS",
+    ceiling("csrc/lpc.hip::dsa_frame_window_lpc_fwd", "frame_window_lpc: frame too long for LDS",
             inside=per(B32_64(3840, 1920), lambda dt, L: ("frame_window_lpc_fwd", case("fwlpc", "fwd", dt, L=L, **FW))),
             outside=per(B32_64(3841, 1921), lambda dt, L: raises("frame_window_lpc: frame too long for LDS", shape("fwlpc", "fwd", dt, L=L, **FW)))
             + per(B32_64(3841, 1921), lambda dt, L: runs("levdur_fwd", case("fuse_fwlpc", "fwd", dt, L=L, **FW)))),
     # ---- csrc/spec.hip.  The direct row DFT keeps the row: sizeof(T) L <= 60 KB (fft_length 30: not a power of two)
-    ceiling("csrc/spec.hip:655", E_ROW,
+    ceiling("csrc/spec.hip::launch_row_dft", E_ROW,
             inside=per(B32_64(15360, 7680), lambda dt, L: ("row_dft_generic", case("fftr", "fwd", dt, len_in=L, nfft=30, fmt=0, F=1))),
             outside=per(B32_64(15361, 7681), lambda dt, L: raises(E_ROW, shape("fftr", "fwd", dt, len_in=L, nfft=30, fmt=0, F=1)))),
     # its backward keeps 3 (fft_length / 2 + 1) values more: 48 samples sooner at fft_length 30 (a forward and no gradient between)
-    ceiling("csrc/spec.hip:888", E_ROWB,
+    ceiling("csrc/spec.hip::launch_row_dft_bwd", E_ROWB,
             inside=per(B32_64(15312, 7632), lambda dt, L: ("row_dft_bwd_generic", case("fftr", "bwd", dt, wrt=("x",), len_in=L, nfft=30, fmt=0, F=1))),
             outside=per(B32_64(15313, 7633), lambda dt, L: raises(E_ROWB, shape("fftr", "bwd", dt, wrt=("x",), len_in=L, nfft=30, fmt=0, F=1)))),
     # the FFT in LDS: sizeof(T) (L + 2 fft_length) <= 150 KB, with the raised LDS attribute.  At fft_length 4096 the row past it is
     # too long for the direct sum as well; float64 at 8192 (float32 at 16384) falls back to the direct sum 1 sample later, under the
     # other route name; a float64 row of 8192 samples at fft_length 8192 fits neither
-    ceiling("csrc/spec.hip:645", "reshapes: the direct sum instead of the FFT in LDS, or " + E_ROW,
+    ceiling("csrc/spec.hip::launch_row_dft", "reshapes: the direct sum instead of the FFT in LDS, or " + E_ROW,
             inside=per(B32_64(30208, 11008), lambda dt, L: ("row_fft_generic", case("fftr", "fwd", dt, len_in=L, nfft=4096, fmt=0, F=1)))
             + [("row_fft_generic", case("fftr", "fwd", F64, len_in=2816, nfft=8192, fmt=0, F=1)),
                ("row_fft_generic", case("fftr", "fwd", F32, len_in=5632, nfft=16384, fmt=0, F=1))],
@@ -313,31 +317,31 @@ CEILINGS = [
                raises(E_ROW, shape("fftr", "fwd", F64, len_in=8192, nfft=8192, fmt=0, F=1))]),
     # its backward: sizeof(T) (L + 3 (fft_length / 2 + 1) + 2 fft_length) <= 150 KB, and the direct sum has no room either.  From
     # fft_length 8192 (float64) and 16384 (float32) on no row has a gradient at all, where the forward runs
-    ceiling("csrc/spec.hip:878", "reshapes: the direct sum instead of the FFT in LDS, or " + E_ROWB,
+    ceiling("csrc/spec.hip::launch_row_dft_bwd", "reshapes: the direct sum instead of the FFT in LDS, or " + E_ROWB,
             inside=per(B32_64(24061, 4861), lambda dt, L: ("row_fft_bwd_generic", case("fftr", "bwd", dt, wrt=("x",), len_in=L, nfft=4096, fmt=0, F=1))),
             outside=per(B32_64(24062, 4862), lambda dt, L: raises(E_ROWB, shape("fftr", "bwd", dt, wrt=("x",), len_in=L, nfft=4096, fmt=0, F=1)))
             + per(B32_64(16384, 8192), lambda dt, n: raises(E_ROWB, shape("fftr", "bwd", dt, wrt=("x",), len_in=16, nfft=n, fmt=0, F=1)))),
     # spec_ratio_bwd: sizeof(T) (lb + la + 5 (fft_length / 2 + 1)) <= 60 KB; the forward (two row transforms and spec_ratio) has the
     # row transform's ceilings only
-    ceiling("csrc/spec.hip:975", "spec_bwd: rows too long for LDS",
+    ceiling("csrc/spec.hip::dsa_spec_bwd", "spec_bwd: rows too long for LDS",
             inside=per(B32_64(6138, 3066), lambda dt, n: ("spec_ratio_bwd", case("spec", "bwd", dt, wrt=("b", "a"), nfft=n, **SR))),
             outside=per(B32_64(6140, 3068), lambda dt, n: raises("spec_bwd: rows too long for LDS", shape("spec", "bwd", dt, wrt=("b", "a"), nfft=n, **SR)))),
     # ---- csrc/fftcep.hip: more than 512 bins are refused in both dtypes and for every n_iter (float32 with n_iter = 0 has left the
     # matrix-core kernel at 320 bins).  The backward shares the launcher: its forward refuses first
-    ceiling("csrc/fftcep.hip:344", "fftcep: fft_length above 1022 is not supported",
+    ceiling("csrc/fftcep.hip::fftcep_launch", "fftcep: fft_length above 1022 is not supported",
             inside=[("fftcep_fwd", case("fftcep", "fwd", nfft=1022, **a, **FFTCEP)) for a in (FC0, FC2)]
             + [("fftcep_bwd", case("fftcep", "bwd", wrt=("x",), nfft=1022, **a, **FFTCEP)) for a in (FC0, FC2)],
             outside=[raises("fftcep: fft_length above 1022 is not supported", shape("fftcep", "fwd", BOTH, nfft=1024, **a)) for a in (FC0, FC2)]),
     # ---- csrc/fbank.hip.  The generic kernels: 4 waves' tiles of 4 frames and the channel ranges in 150 KB --
     # 16 sizeof(T) K + 8 C forward, (16 sizeof(T) + 8) (K + C) backward (a forward and no gradient between)
-    ceiling("csrc/fbank.hip:576", E_FB,
+    ceiling("csrc/fbank.hip::fbank_launch", E_FB,
             inside=per(B32_64(4778, 2388), lambda dt, n: ("fbank_fwd", case("fbank", "fwd", dt, nfft=n, **FB)))
             + per(B32_64(4104, 2096), lambda dt, n: ("fbank_bwd", case("fbank", "bwd", dt, wrt=("x",), nfft=n, **FB))),
             outside=per(B32_64(4780, 2390), lambda dt, n: raises(E_FB, shape("fbank", "fwd", dt, nfft=n, **FB)))
             + per(B32_64(4106, 2098), lambda dt, n: raises(E_FB, shape("fbank", "bwd", dt, wrt=("x",), nfft=n, **FB)))),
     # the filter matrix joins them in LDS while sizeof(T) K C more fits, else it stays in global memory (<T, false>: up to 16 waves
     # of tiles, above 64 KB at the ordinary fft_length 1024 / 80 channels with 64 frames)
-    ceiling("csrc/fbank.hip:577", "reshapes: the filter matrix stays in global memory",
+    ceiling("csrc/fbank.hip::fbank_launch", "reshapes: the filter matrix stays in global memory",
             inside=per(B32_64(794, 396), lambda dt, n: ("fbank_fwd", case("fbank", "fwd", dt, nfft=n, **FB)))
             + per(B32_64(752, 364), lambda dt, n: ("fbank_bwd", case("fbank", "bwd", dt, wrt=("x",), nfft=n, **FB))),
             outside=per(B32_64(796, 398), lambda dt, n: runs("fbank_fwd", case("fbank", "fwd", dt, nfft=n, **FB)))
@@ -345,18 +349,18 @@ CEILINGS = [
             + [runs("fbank_fwd", case("fbank", "fwd", F32, nfft=1024, C=80, use_power=False, gamma=0.0, F=64)),
                runs("fbank_bwd", case("fbank", "bwd", F32, wrt=("x",), nfft=1024, C=80, use_power=False, gamma=0.0, F=64))]),
     # the matrix-core launcher takes float32 up to 320 bins and 48 channels (its LDS: 163 392 of 163 840 B at 320)
-    ceiling("csrc/fbank.hip:625", "reshapes: the generic kernel instead of the matrix-core kernel",
+    ceiling("csrc/fbank.hip::dsa_fbank_fwd", "reshapes: the generic kernel instead of the matrix-core kernel",
             inside=[("fbank_mfma_fwd", case("fbank", "fwd", F32, nfft=638, C=12, use_power=False, gamma=0.0, F=5, **FBM))],
             outside=[runs("fbank_fwd", case("fbank", "fwd", F32, nfft=640, C=12, use_power=False, gamma=0.0, F=5))]),
     # MFCC: the second product costs the fused launch 3 KB more, so it ends at 309 bins; to 320 bins the two launches run
-    ceiling("csrc/fbank.hip:652", "reshapes: the filter bank and the DCT as two launches instead of one",
+    ceiling("csrc/fbank.hip::dsa_fbank_dct_fwd", "reshapes: the filter bank and the DCT as two launches instead of one",
             inside=[("fbank_dct_mfma_fwd", case("mfcc", "fwd", F32, nfft=616, C=40, M=12, F=7, **MFCC))],
             outside=[runs("freqt_lds_fwd", case("mfcc", "fwd", F32, nfft=618, C=40, M=12, F=7, **MFCC))]),
     # ---- csrc/plp.hip
     plp_waves("2 waves per block instead of 4", 3538, 1704),
     plp_waves("1 wave per block instead of 2", 7634, 3752),
     # one wave's slice against 160 KB, with the raised attribute above 64 KB; the backward has the forward's geometry
-    ceiling(("csrc/plp.hip:301", "csrc/plp.hip:317"), E_PLP,
+    ceiling(("csrc/plp.hip::plp_launch_fwd", "csrc/plp.hip::plp_launch_bwd"), E_PLP,
             inside=per(B32_64(40402, 20136), lambda dt, n: ("plp_fwd", case("plp_tail", "fwd", dt, n_fft=n, **PL, **PLP_OUT)))
             + per(B32_64(40402, 20136), lambda dt, n: ("plp_bwd", case("plp_tail", "bwd", dt, wrt=("y", "E"), n_fft=n, **PL))),
             outside=per(B32_64(40404, 20138), lambda dt, n: raises(E_PLP, shape("plp_tail", "fwd", dt, n_fft=n, **PL))),
@@ -367,13 +371,13 @@ CEILINGS = [
     mlsa_rows("clip", 18380, 18354, 2, "n_fft"),
     # ---- csrc/zerodf.hip: what is still refused behind the tap pieces (ZDF_PIECES holds the accepted side of those): a filter too
     # long for one launch with ignore_gain or a frame period that is no multiple of 4 -- 3 M + 2 + P values against 64 KB
-    ceiling("csrc/zerodf.hip:581", "zerodf: filter too long for LDS",
+    ceiling("csrc/zerodf.hip::zerodf_launch_fwd", "zerodf: filter too long for LDS",
             inside=per(B32_64(5459, 2729), lambda dt, M: ("zerodf_fwd", case("zerodf", "fwd", dt, M=M, **ZF, **ZDF_FWD))),
             outside=per(B32_64(5460, 2730), lambda dt, M: raises("zerodf: filter too long for LDS", shape("zerodf", "fwd", dt, M=M, **ZF))),
             cited=ZDF_PIECES),
     # the tap gradient of the first kernels: 4 P + M + 256 values against 64 KB, which binds before the forward only at frame periods
     # from 1421 (float64) and 2911 (float32) on
-    ceiling("csrc/zerodf.hip:836", "zerodf_bwd: filter too long for LDS",
+    ceiling("csrc/zerodf.hip::zerodf_launch_bwd", "zerodf_bwd: filter too long for LDS",
             inside=[("zerodf_bwd", case("zerodf", "bwd", F32, wrt=("x", "b"), M=4484, P=2911, **ZB, **ZDF_BWD)),
                     ("zerodf_bwd", case("zerodf", "bwd", F64, wrt=("x", "b"), M=2252, P=1421, **ZB, **ZDF_BWD))],
             outside=[raises("zerodf_bwd: filter too long for LDS", shape("zerodf", "bwd", F32, wrt=("x", "b"), M=4485, P=2911, **ZB)),
@@ -381,27 +385,27 @@ CEILINGS = [
             cited=ZDF_PIECES),
     # ---- csrc/mgc.hip, at the entries themselves (ops.gc2gc_fused / gc2gc_fn test the same sizes first and hand longer transforms to
     # the operator chain).  Forward: 2 sizeof(T) n_fft <= 150 KB; backward: 5 sizeof(T) n_fft / 2 + 64 -- one power of two sooner
-    ceiling(("csrc/mgc.hip:782", "csrc/mgc.hip:783"), E_GC,
+    ceiling("csrc/mgc.hip::dsa_gc2gc_fwd", E_GC,
             inside=per(B32_64(16384, 8192), lambda dt, n: ("gc2gc_fused", case("gc2gc_entry", "fwd", dt, n_fft=n, **GE, **GCF))),
             outside=per(B32_64(32768, 16384), lambda dt, n: raises(E_GC, shape("gc2gc_entry", "fwd", dt, n_fft=n, **GE)))),
-    ceiling(("csrc/mgc.hip:796", "csrc/mgc.hip:805"), E_GCB,
+    ceiling("csrc/mgc.hip::dsa_gc2gc_bwd", E_GCB,
             inside=per(B32_64(8192, 4096), lambda dt, n: ("gc2gc_fused_bwd", case("gc2gc_entry", "bwd", dt, wrt=("c",), n_fft=n, **GE, **GC))),
             outside=per(B32_64(16384, 8192), lambda dt, n: raises(E_GCB, shape("gc2gc_entry", "bwd", dt, wrt=("c",), n_fft=n, **GE)))),
     # (more than 2^31 - 1 rows share the message)
-    ceiling("csrc/mgc.hip:779", "gc2gc: out_order + 1 must not exceed n_fft",
+    ceiling("csrc/mgc.hip::dsa_gc2gc_fwd", "gc2gc: out_order + 1 must not exceed n_fft",
             inside=[("gc2gc_fused", case("gc2gc_entry", "fwd", g1=-0.5, g2=0.0, n_fft=4, m1=2, m2=3, F=2, **GCF))],
             outside=[raises("gc2gc: out_order + 1 must not exceed n_fft", shape("gc2gc_entry", "fwd", BOTH, g1=-0.5, g2=0.0, n_fft=4, m1=2, m2=4, F=2))]),
-    ceiling("csrc/mgc.hip:764", "mgcep_spectra: cep_order above 64",
+    ceiling("csrc/mgc.hip::dsa_mgcep_spectra", "mgcep_spectra: cep_order above 64",
             inside=[("mgcep_spectra", case("mgcep_spectra", "fwd", nfft=256, M=64, gamma=-0.5, F=3))],
             outside=[raises("mgcep_spectra: cep_order above 64", shape("mgcep_spectra", "fwd", BOTH, nfft=256, M=65, gamma=-0.5, F=3))]),
     # ---- csrc/mcep.hip, the generic pair (asked for by name: float32 geometries of this size go to the whole-batch composition):
     # sizeof(T) (3 K + M1^2 + 7 M1 - 1) <= 160 KB, the attribute set on every launch.  The backward has the forward's size
-    ceiling(("csrc/mcep.hip:313", "csrc/mcep.hip:329"), "mcep: configuration exceeds LDS",
+    ceiling(("csrc/mcep.hip::mcep_generic_fwd", "csrc/mcep.hip::mcep_generic_bwd"), "mcep: configuration exceeds LDS",
             inside=per(B32_64(27208, 13556), lambda dt, n: ("mcep_generic_fwd", case("mcep_generic", "fwd", dt, nfft=n, **MG)))
             + per(B32_64(27208, 13556), lambda dt, n: ("mcep_generic_bwd", case("mcep_generic", "bwd", dt, wrt=("X",), nfft=n, **MG))),
             outside=per(B32_64(27210, 13558), lambda dt, n: raises("mcep: configuration exceeds LDS", shape("mcep_generic", "fwd", dt, nfft=n, **MG)))),
     # ---- csrc/mdct.hip: the fast kernels end at frame length 4096 (48 KB of LDS in the synthesis: no attribute needed)
-    ceiling("csrc/mdct.hip:315", "reshapes: the generic kernels instead of the fast ones",
+    ceiling("csrc/mdct.hip::md_check", "reshapes: the generic kernels instead of the fast ones",
             inside=[("mdct_analysis_fast", case("mdct", "fwd", F32, L=4096, T=5000, B=1)), ("mdct_synthesis_fast", case("imdct", "fwd", F32, L=4096, N=3, B=1))],
             outside=[runs("mdct_analysis_generic", case("mdct", "fwd", F32, L=8192, T=9000, B=1)),
                      runs("mdct_synthesis_generic", case("imdct", "fwd", F32, L=8192, N=3, B=1))]),
@@ -457,7 +461,7 @@ NOT_A_CEILING = {
     "frame_window_lpc_bwd: frame_length + frame_period above 1024": "ops.frame_window_lpc_bwd_supported (L + P <= 1024)",
     "frame_window_lpc_bwd: this frame_length / frame_period pair does not fit the one-launch backward": "ops.frame_window_lpc_bwd_supported (the halo test)",
     "%s: the fast kernels take float32 and a power-of-two frame length in their range": "DSA_ALGO_TUNED by name only; ops.mdct passes "
-        "ALGO_AUTO, which takes the generic kernels (the CEILINGS row of csrc/mdct.hip:315 holds that edge)",
+        "ALGO_AUTO, which takes the generic kernels (the CEILINGS row of csrc/mdct.hip::md_check holds that edge)",
     "fbank: spectrum too long for the matrix-core kernel's LDS": "every caller of fbank_mfma_launch_ex tests K <= 320 first (dsa_fbank_fwd, "
         "dsa_freqt_fwd, dsa_fftcep_fwd: 163 392 B at 320), and dsa_fbank_dct_fwd tests fbank_mfma_lds_bytes(K, true) itself",
     # orders and plans: dispatch inside the library, or properties of a matrix rather than a size
@@ -568,18 +572,39 @@ PINNED_ELSEWHERE = {
        for f in ("lane", "row") for n in ("lpc2par", "par2lpc", "lpccheck") for d in ("fwd", "bwd")},
     # kernel_name(dtype, M, mode, n_fft, bwd): f"mlsacheck_{tuned or generic}_{fwd or bwd}", both sides of the boundary asserted reached
     **{f"mlsacheck_{k}_{d}": "tests/test_gpu_mlsacheck.py::test_tile_and_dispatch_edges" for k in ("tuned", "generic") for d in ("fwd", "bwd")},
+    # ---- the families whose launchers index a name table by entry, route and dtype; each pointer is the test that compares the entry
+    # with its reference and the list of its launches' names with these
+    # kDtwRoutes (csrc/dtw.hip): one wave up to 64 rows, a workgroup beyond; the path's kernel is the same on both
+    **{f"dtw_{e}{r}_{d}": "tests/test_gpu_dtw.py::test_golden_parity_paths_and_routes" for e in ("", "vjp_") for r in ("wave", "block") for d in BOTH},
+    **{f"dtw_path_{d}": "tests/test_gpu_dtw.py::test_golden_parity_paths_and_routes" for d in BOTH},
+    # kGmmRoutes (csrc/gmm.hip): the four launches of an EM iteration on the full and the diagonal route; regress and transform have one
+    **{f"gmm_{e}_{r}_{d}": "tests/test_gpu_gmm.py::test_golden_parity_and_routes"
+       for e in ("prepare", "estep", "accum", "update") for r in ("full", "diag") for d in BOTH},
+    **{f"gmm_{e}_{d}": "tests/test_gpu_gmm.py::test_transform_on_the_goldens" for e in ("regress", "transform") for d in BOTH},
+    # kYinRoutes (csrc/yingram.hip): both routes asked for by name
+    **{f"yingram_{e}{r}_{d}": "tests/test_gpu_yingram.py::test_golden_parity_and_routes" for e in ("", "vjp_") for r in ("direct", "fft") for d in BOTH},
+    **{f"frame_yingram_{r}_{d}": "tests/test_gpu_yingram.py::test_fused_equals_the_two_modules" for r in ("direct", "fft") for d in BOTH},
+    # kVqRoutes (csrc/vq.hip): the update works on float64 partial sums whatever the dtype of x
+    **{f"vq_{e}_{d}": "tests/test_gpu_lbg.py::test_vq_and_ivq_match_a_float64_composition" for e in ("search", "lookup") for d in BOTH},
+    **{f"vq_accum_{d}": "tests/test_gpu_lbg.py::test_counts_and_centroids_are_exact" for d in BOTH},
+    "vq_update": "tests/test_gpu_lbg.py::test_counts_and_centroids_are_exact",
+    **{f"vq_vjp_{d}": "tests/test_gpu_lbg.py::test_training_mode_loss_and_gradient" for d in BOTH},
+    # kWsRoutes (csrc/world_synth.hip): the module's forward ends in the overlap-add, and its backward runs on autograd's thread, so the
+    # launches between are called one by one
+    **{f"world_synth_pulses_{d}": "tests/test_gpu_world_synth.py::test_pulse_lists_are_the_references" for d in BOTH},
+    **{f"world_synth_overlap_add_{d}": "tests/test_gpu_world_synth.py::test_parity_with_the_reference" for d in BOTH},
+    **{f"world_synth_{e}_{d}": "tests/test_gpu_world_synth.py::test_every_launch_names_its_kernel" for e in ("responses", "vjp_pulses", "vjp_frames") for d in BOTH},
+    # kApRoutes (csrc/ap.hip): as WorldSynthesis -- the forward ends in the tandem kernel
+    **{f"ap_tandem_{d}": "tests/test_gpu_ap.py::test_parity_with_the_reference" for d in BOTH},
+    **{f"ap_{e}_{d}": "tests/test_gpu_ap.py::test_every_launch_names_its_kernel" for e in ("qmf", "qmf_vjp", "tandem_vjp") for d in BOTH},
 }
 
+# names passed to a shared launcher as an argument, or kept in a local before the call: name -> "csrc/<file>::<function that spells it>"
 FORWARDED = {
-    "lsp_lsp2lpc_fwd": "csrc/lsp.hip:47", "lsp_lsp2lpc_bwd": "csrc/lsp.hip:47", "lsp_lspcheck_fwd": "csrc/lsp.hip:47", "lsp_lspcheck_bwd": "csrc/lsp.hip:47",
-    "parcor_lane_lpc2par_fwd": "csrc/parcor.hip:29", "parcor_lane_lpc2par_bwd": "csrc/parcor.hip:29", "parcor_lane_par2lpc_fwd": "csrc/parcor.hip:29",
-    "parcor_lane_par2lpc_bwd": "csrc/parcor.hip:30", "parcor_lane_lpccheck_fwd": "csrc/parcor.hip:30", "parcor_lane_lpccheck_bwd": "csrc/parcor.hip:30",
-    "parcor_row_lpc2par_fwd": "csrc/parcor.hip:31", "parcor_row_lpc2par_bwd": "csrc/parcor.hip:31", "parcor_row_par2lpc_fwd": "csrc/parcor.hip:31",
-    "parcor_row_par2lpc_bwd": "csrc/parcor.hip:32", "parcor_row_lpccheck_fwd": "csrc/parcor.hip:32", "parcor_row_lpccheck_bwd": "csrc/parcor.hip:32",
-    "mlsacheck_generic_fwd": "csrc/mlsacheck.hip:449", "mlsacheck_generic_bwd": "csrc/mlsacheck.hip:449",
-    "fbank_mfma_fwd": "csrc/fbank.hip:563", "fbank_dct_mfma_fwd": "csrc/fbank.hip:654", "freqt_mfma_fwd": "csrc/mcep.hip:356",
-    "fftcep_mfma_fwd": "csrc/fftcep.hip:383",
-    "frame_window_lpc24_mfma_fwd": "csrc/lpc24.hip:374", "frame_window_lpc24_bwd_mfma": "csrc/lpc24_bwd.hip:685",
+    "mlsacheck_generic_fwd": "csrc/mlsacheck.hip::mlsacheck_generic_launch", "mlsacheck_generic_bwd": "csrc/mlsacheck.hip::mlsacheck_generic_launch",
+    "fbank_mfma_fwd": "csrc/fbank.hip::fbank_mfma_launch", "fbank_dct_mfma_fwd": "csrc/fbank.hip::dsa_fbank_dct_fwd", "freqt_mfma_fwd": "csrc/mcep.hip::dsa_freqt_fwd",
+    "fftcep_mfma_fwd": "csrc/fftcep.hip::dsa_fftcep_fwd",
+    "frame_window_lpc24_mfma_fwd": "csrc/lpc24.hip::lpc24_fwd", "frame_window_lpc24_bwd_mfma": "csrc/lpc24_bwd.hip::dsa_frame_window_lpc_bwd",
 }
 
 EXEMPT = {

@@ -302,33 +302,35 @@ def test_the_largest_workgroups(sr, P, wms):
 
 
 def test_every_launch_names_its_kernel():
-    name, dt = "bins16k", "float32"
-    m = module_of(name, dt)
-    e = m.extractor
-    x, f0 = on_gpu(Z[f"{name}_x"], dt), on_gpu(Z[f"{name}_f0"], dt)
-    T, N = x.shape[1], f0.shape[1]
+    name = "bins16k"
     n_band, _, seg = ops.ap_bands(16000)
-    lens = ops.ap_band_lengths(T, n_band)
-    p, ld = ops._p, sum(lens)
-    hp, lp = (torch.empty(1, lens[0], device="cuda", dtype=torch.float64) for _ in range(2))   # the bands are float64 whatever the dtype
-    ops._call("dsa_ap_qmf", p(x), 1, T, T, _lib.F32, p(hp), lens[0], p(lp), lens[0], ops._stream())
-    assert _lib.last_kernel() == "ap_qmf_f32"
-    gx = torch.empty_like(x)
-    ops._call("dsa_ap_qmf_vjp", p(hp), lens[0], p(lp), lens[0], 1, T, _lib.F32, p(gx), T, ops._stream())
-    assert _lib.last_kernel() == "ap_qmf_vjp_f32" and torch.isfinite(gx).all()
-    bands = torch.randn(1, ld, device="cuda", dtype=torch.float64)
-    y = torch.empty(1, N, 33, device="cuda")
-    common = (p(bands), ld, p(f0), p(e.window), p(e.window_sqrt), e.window.stride(0), p(e.interp_indices), p(e.interp_weights), 1, N, T, 80, 16000, 30.0,
-              33, 1e-5, 0.001, 0.999, 0, _lib.F32)
-    ops._call("dsa_ap_tandem", *common, p(y), ops._stream())
-    assert _lib.last_kernel() == "ap_tandem_f32" and torch.isfinite(y).all()
-    gruns = torch.empty(1, N, 3 * (sum(seg) + 2 * n_band), device="cuda")
-    starts = torch.empty(1, N, n_band, _lib.AP_START_WORDS, device="cuda", dtype=torch.int64)
-    gbands = torch.empty_like(bands)
-    ops._call("dsa_ap_tandem_vjp", p(torch.ones_like(y)), *common, p(gruns), p(starts), p(gbands), ld, ops._stream())
-    assert _lib.last_kernel() == "ap_tandem_vjp_f32" and torch.isfinite(gbands).all() and torch.isfinite(gruns).all()
-    cpos = starts[0, :, :, 3]
-    assert (cpos[1:] >= cpos[:-1]).all()   # what the gather's bisection rests on
+    p = ops._p
+    for dt, code, tag in (("float32", _lib.F32, "f32"), ("float64", _lib.F64, "f64")):
+        m = module_of(name, dt)
+        e = m.extractor
+        x, f0 = on_gpu(Z[f"{name}_x"], dt), on_gpu(Z[f"{name}_f0"], dt)
+        T, N = x.shape[1], f0.shape[1]
+        lens = ops.ap_band_lengths(T, n_band)
+        ld = sum(lens)
+        hp, lp = (torch.empty(1, lens[0], device="cuda", dtype=torch.float64) for _ in range(2))   # the bands are float64 whatever the dtype
+        ops._call("dsa_ap_qmf", p(x), 1, T, T, code, p(hp), lens[0], p(lp), lens[0], ops._stream())
+        assert _lib.last_kernel() == "ap_qmf_" + tag
+        gx = torch.empty_like(x)
+        ops._call("dsa_ap_qmf_vjp", p(hp), lens[0], p(lp), lens[0], 1, T, code, p(gx), T, ops._stream())
+        assert _lib.last_kernel() == "ap_qmf_vjp_" + tag and torch.isfinite(gx).all()
+        bands = torch.randn(1, ld, device="cuda", dtype=torch.float64)
+        y = torch.empty(1, N, 33, device="cuda", dtype=DT[dt])
+        common = (p(bands), ld, p(f0), p(e.window), p(e.window_sqrt), e.window.stride(0), p(e.interp_indices), p(e.interp_weights), 1, N, T, 80, 16000,
+                  30.0, 33, 1e-5, 0.001, 0.999, 0, code)
+        ops._call("dsa_ap_tandem", *common, p(y), ops._stream())
+        assert _lib.last_kernel() == "ap_tandem_" + tag and torch.isfinite(y).all()
+        gruns = torch.empty(1, N, 3 * (sum(seg) + 2 * n_band), device="cuda", dtype=DT[dt])
+        starts = torch.empty(1, N, n_band, _lib.AP_START_WORDS, device="cuda", dtype=torch.int64)
+        gbands = torch.empty_like(bands)
+        ops._call("dsa_ap_tandem_vjp", p(torch.ones_like(y)), *common, p(gruns), p(starts), p(gbands), ld, ops._stream())
+        assert _lib.last_kernel() == "ap_tandem_vjp_" + tag and torch.isfinite(gbands).all() and torch.isfinite(gruns).all()
+        cpos = starts[0, :, :, 3]
+        assert (cpos[1:] >= cpos[:-1]).all()   # what the gather's bisection rests on
 
 
 @pytest.mark.parametrize("dt", list(DT))

@@ -169,6 +169,8 @@ def test_vq_and_ivq_match_a_float64_composition(shape, K, dt):
     back, names = launches(lambda: dsp.InverseVectorQuantization()(idx, codebook))
     assert names == ["vq_lookup_f32"] and torch.equal(back, codebook[idx]) and back.shape == x.shape
     assert torch.equal(dsp.InverseVectorQuantization()(idx.int(), codebook), back)
+    wide, names = launches(lambda: dsp.ops.vq_lookup(idx, codebook, torch.float64))   # the float64 twin: the same rows, widened exactly
+    assert names == ["vq_lookup_f64"] and wide.dtype == torch.float64 and torch.equal(wide, codebook[idx].double())
 
 
 def test_a_tie_gives_the_first_index():

@@ -114,30 +114,31 @@ def test_parity_with_the_reference(name, dt):
 
 
 def test_every_launch_names_its_kernel():
-    name, dt = "unbatched", "float32"
+    name = "unbatched"
     c = W.CASES[name]
-    f0, ap, sp = (torch.as_tensor(a).to("cuda") for a in W.inputs(name))
-    offsets, irec, frec, pulses = ops.world_pulses(f0, c["P"], c["sr"], c["L"], c["default_f0"])
-    m = module_of(name, dt)
-    noise, tw = m._randn(pulses, c["L"]), dsp.modules.spec.device_twiddle(c["L"], f0.device, f0.dtype)
-    response = torch.empty(pulses, c["L"], device="cuda")
-    grows = torch.empty(pulses, 2, c["L"] // 2 + 1, device="cuda")
-    gy = torch.ones(1, 600, device="cuda")
     p = ops._p
-    ops._call("dsa_world_synth_responses", p(ap), p(sp), p(noise), p(irec), p(frec), p(offsets), p(m.dc_remover), p(tw), 1, 8, c["sr"], c["L"], pulses,
-              _lib.F32, p(response), ops._stream())
-    assert _lib.last_kernel() == "world_synth_responses_f32"
-    ops._call("dsa_world_synth_vjp_pulses", p(gy), p(ap), p(sp), p(noise), p(irec), p(frec), p(offsets), p(m.dc_remover), p(tw), 1, 8, 600, c["sr"],
-              c["L"], pulses, _lib.F32, p(grows), ops._stream())
-    assert _lib.last_kernel() == "world_synth_vjp_pulses_f32"
-    gap, gsp = torch.empty_like(ap), torch.empty_like(sp)
-    ops._call("dsa_world_synth_vjp_frames", p(grows), p(ap), p(sp), p(irec), p(frec), p(offsets), 1, 8, c["L"], pulses, _lib.F32, p(gap), p(gsp),
-              ops._stream())
-    assert _lib.last_kernel() == "world_synth_vjp_frames_f32" and torch.isfinite(gap).all() and torch.isfinite(gsp).all()
-    y = torch.empty(1, 600, device="cuda")
-    ops._call("dsa_world_synth_overlap_add", p(response), p(irec), p(offsets), 1, 600, c["L"], pulses, _lib.F32, p(y), ops._stream())
-    assert _lib.last_kernel() == "world_synth_overlap_add_f32"
-    assert torch.isfinite(response).all() and torch.isfinite(grows).all()
+    for dt, code, tag in (("float32", _lib.F32, "f32"), ("float64", _lib.F64, "f64")):
+        f0, ap, sp = (torch.as_tensor(a).to("cuda", DT[dt]) for a in W.inputs(name))
+        offsets, irec, frec, pulses = ops.world_pulses(f0, c["P"], c["sr"], c["L"], c["default_f0"])
+        m = module_of(name, dt)
+        noise, tw = m._randn(pulses, c["L"]), dsp.modules.spec.device_twiddle(c["L"], f0.device, f0.dtype)
+        response = torch.empty(pulses, c["L"], device="cuda", dtype=DT[dt])
+        grows = torch.empty(pulses, 2, c["L"] // 2 + 1, device="cuda", dtype=DT[dt])
+        gy = torch.ones(1, 600, device="cuda", dtype=DT[dt])
+        ops._call("dsa_world_synth_responses", p(ap), p(sp), p(noise), p(irec), p(frec), p(offsets), p(m.dc_remover), p(tw), 1, 8, c["sr"], c["L"],
+                  pulses, code, p(response), ops._stream())
+        assert _lib.last_kernel() == "world_synth_responses_" + tag
+        ops._call("dsa_world_synth_vjp_pulses", p(gy), p(ap), p(sp), p(noise), p(irec), p(frec), p(offsets), p(m.dc_remover), p(tw), 1, 8, 600,
+                  c["sr"], c["L"], pulses, code, p(grows), ops._stream())
+        assert _lib.last_kernel() == "world_synth_vjp_pulses_" + tag
+        gap, gsp = torch.empty_like(ap), torch.empty_like(sp)
+        ops._call("dsa_world_synth_vjp_frames", p(grows), p(ap), p(sp), p(irec), p(frec), p(offsets), 1, 8, c["L"], pulses, code, p(gap), p(gsp),
+                  ops._stream())
+        assert _lib.last_kernel() == "world_synth_vjp_frames_" + tag and torch.isfinite(gap).all() and torch.isfinite(gsp).all()
+        y = torch.empty(1, 600, device="cuda", dtype=DT[dt])
+        ops._call("dsa_world_synth_overlap_add", p(response), p(irec), p(offsets), 1, 600, c["L"], pulses, code, p(y), ops._stream())
+        assert _lib.last_kernel() == "world_synth_overlap_add_" + tag
+        assert torch.isfinite(response).all() and torch.isfinite(grows).all()
 
 
 @pytest.mark.parametrize("dt", ["float32", "float64"])
