@@ -492,14 +492,11 @@ int ap_launch_tandem(const ApGeom& g, const void* bands, int64_t ldb, const void
                      const void* iidx, const void* iw, int64_t B, int64_t N, int32_t P, int32_t sr, int32_t K, double eps, double lo, double hi,
                      int32_t fmt, void* y, const void* gy, void* gruns, void* starts, hipStream_t st)
 {
-    static std::atomic<uint64_t> done{0};
-    if (!ensure_dynamic_lds(reinterpret_cast<const void*>(&ap_tandem_kernel<T, VJP>), DSA_AP_MAX_LDS_BYTES, done))
-        return fail(DSA_ERR_LAUNCH, "ap: cannot raise the dynamic LDS limit");
     const size_t lds = 8 * ((size_t)AP_HEAD + (VJP ? 5 : 3) * (size_t)g.runs);
-    hipLaunchKernelGGL((ap_tandem_kernel<T, VJP>), dim3((unsigned)N, (unsigned)B), dim3(64 * g.n_band), lds, st, (const double*)bands, (long)ldb, (const T*)f0,
-                       (long)N, (const T*)window, (const T*)wsqrt, (long)ldw, (const int64_t*)iidx, (const T*)iw, (int)K, g, (T)((double)P / (double)sr),
-                       (T)eps, lo, hi, (int)fmt, (T*)y, (const T*)gy, (T*)gruns, (int64_t*)starts);
-    return DSA_OK;
+    return launch_lds<ap_tandem_kernel<T, VJP>>(DSA_AP_MAX_LDS_BYTES, "ap: cannot raise the dynamic LDS limit", dim3((unsigned)N, (unsigned)B),
+                                                dim3(64 * g.n_band), lds, st, (const double*)bands, (long)ldb, (const T*)f0, (long)N, (const T*)window,
+                                                (const T*)wsqrt, (long)ldw, (const int64_t*)iidx, (const T*)iw, (int)K, g, (T)((double)P / (double)sr),
+                                                (T)eps, lo, hi, (int)fmt, (T*)y, (const T*)gy, (T*)gruns, (int64_t*)starts);
 }
 
 template <typename T>
@@ -525,13 +522,12 @@ DSA_EXPORT int dsa_ap_qmf(const void* x, int64_t B, int64_t T, int64_t ldx, int3
     if (!(x && hp && lp)) return fail(DSA_ERR_INVALID_ARGUMENT, "ap: null pointer");
     const dim3 grid((unsigned)((To + AP_THREADS - 1) / AP_THREADS), (unsigned)B);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((ap_qmf_kernel<float>), grid, dim3(AP_THREADS), 0, st, (const float*)x, (long)T, (long)ldx, (long)To, (double*)hp, (long)ldhp,
+    return with_dtype(dtype, "ap", [&](auto tag) {
+        using V = decltype(tag);   // (T is the entry's length)
+        hipLaunchKernelGGL((ap_qmf_kernel<V>), grid, dim3(AP_THREADS), 0, st, (const V*)x, (long)T, (long)ldx, (long)To, (double*)hp, (long)ldhp,
                            (double*)lp, (long)ldlp);
-    else
-        hipLaunchKernelGGL((ap_qmf_kernel<double>), grid, dim3(AP_THREADS), 0, st, (const double*)x, (long)T, (long)ldx, (long)To, (double*)hp, (long)ldhp,
-                           (double*)lp, (long)ldlp);
-    return check_launch(kApRoutes[AP_QMF][dtype == DSA_F64]);
+        return check_launch(kApRoutes[AP_QMF][dtype == DSA_F64]);
+    });
 }
 
 DSA_EXPORT int dsa_ap_qmf_vjp(const void* ghp, int64_t ldghp, const void* glp, int64_t ldglp, int64_t B, int64_t T, int32_t dtype, void* gx, int64_t ldgx,
@@ -545,13 +541,12 @@ DSA_EXPORT int dsa_ap_qmf_vjp(const void* ghp, int64_t ldghp, const void* glp, i
     if (!(ghp && glp && gx)) return fail(DSA_ERR_INVALID_ARGUMENT, "ap: null pointer");
     const dim3 grid((unsigned)((T + AP_THREADS - 1) / AP_THREADS), (unsigned)B);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((ap_qmf_vjp_kernel<float>), grid, dim3(AP_THREADS), 0, st, (const double*)ghp, (long)ldghp, (const double*)glp, (long)ldglp,
-                           (long)T, (long)To, (float*)gx, (long)ldgx);
-    else
-        hipLaunchKernelGGL((ap_qmf_vjp_kernel<double>), grid, dim3(AP_THREADS), 0, st, (const double*)ghp, (long)ldghp, (const double*)glp, (long)ldglp,
-                           (long)T, (long)To, (double*)gx, (long)ldgx);
-    return check_launch(kApRoutes[AP_QMF_VJP][dtype == DSA_F64]);
+    return with_dtype(dtype, "ap", [&](auto tag) {
+        using V = decltype(tag);   // (T is the entry's length)
+        hipLaunchKernelGGL((ap_qmf_vjp_kernel<V>), grid, dim3(AP_THREADS), 0, st, (const double*)ghp, (long)ldghp, (const double*)glp, (long)ldglp,
+                           (long)T, (long)To, (V*)gx, (long)ldgx);
+        return check_launch(kApRoutes[AP_QMF_VJP][dtype == DSA_F64]);
+    });
 }
 
 DSA_EXPORT int dsa_ap_tandem(const void* bands, int64_t ldb, const void* f0, const void* window, const void* window_sqrt, int64_t ldw,
@@ -568,12 +563,10 @@ DSA_EXPORT int dsa_ap_tandem(const void* bands, int64_t ldb, const void* f0, con
     if (!(bands && f0 && window && window_sqrt && y) || (interp && !(interp_indices && interp_weights)))
         return fail(DSA_ERR_INVALID_ARGUMENT, "ap: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    const int rc = dtype == DSA_F32 ? ap_launch_tandem<float, false>(g, bands, ldb, f0, window, window_sqrt, ldw, interp_indices, interp_weights, B, N, P,
-                                                                     sample_rate, K, eps, lower_bound, upper_bound, out_format, y, nullptr, nullptr,
-                                                                     nullptr, st)
-                                    : ap_launch_tandem<double, false>(g, bands, ldb, f0, window, window_sqrt, ldw, interp_indices, interp_weights, B, N, P,
-                                                                      sample_rate, K, eps, lower_bound, upper_bound, out_format, y, nullptr, nullptr,
-                                                                      nullptr, st);
+    const int rc = with_dtype(dtype, "ap", [&](auto tag) {
+        return ap_launch_tandem<decltype(tag), false>(g, bands, ldb, f0, window, window_sqrt, ldw, interp_indices, interp_weights, B, N, P, sample_rate, K,
+                                                      eps, lower_bound, upper_bound, out_format, y, nullptr, nullptr, nullptr, st);
+    });
     return rc ? rc : check_launch(kApRoutes[AP_TANDEM][dtype == DSA_F64]);
 }
 
@@ -593,18 +586,15 @@ DSA_EXPORT int dsa_ap_tandem_vjp(const void* gy, const void* bands, int64_t ldb,
         return fail(DSA_ERR_INVALID_ARGUMENT, "ap: null pointer");
     hipStream_t st = (hipStream_t)stream;
     if (N > 0) {
-        const int rc = dtype == DSA_F32 ? ap_launch_tandem<float, true>(g, bands, ldb, f0, window, window_sqrt, ldw, interp_indices, interp_weights, B, N, P,
-                                                                        sample_rate, K, eps, lower_bound, upper_bound, out_format, nullptr, gy, gruns,
-                                                                        starts, st)
-                                        : ap_launch_tandem<double, true>(g, bands, ldb, f0, window, window_sqrt, ldw, interp_indices, interp_weights, B, N,
-                                                                         P, sample_rate, K, eps, lower_bound, upper_bound, out_format, nullptr, gy, gruns,
-                                                                         starts, st);
+        const int rc = with_dtype(dtype, "ap", [&](auto tag) {
+            return ap_launch_tandem<decltype(tag), true>(g, bands, ldb, f0, window, window_sqrt, ldw, interp_indices, interp_weights, B, N, P, sample_rate,
+                                                         K, eps, lower_bound, upper_bound, out_format, nullptr, gy, gruns, starts, st);
+        });
         if (rc) return rc;
         if (int rc2 = check_launch(kApRoutes[AP_TANDEM_VJP][dtype == DSA_F64])) return rc2;
     }
-    if (dtype == DSA_F32)
-        ap_launch_overlap<float>(g, gruns, starts, B, N, gbands, ldg, st);
-    else
-        ap_launch_overlap<double>(g, gruns, starts, B, N, gbands, ldg, st);
-    return check_launch(kApRoutes[AP_TANDEM_VJP][dtype == DSA_F64]);
+    return with_dtype(dtype, "ap", [&](auto tag) {
+        ap_launch_overlap<decltype(tag)>(g, gruns, starts, B, N, gbands, ldg, st);
+        return check_launch(kApRoutes[AP_TANDEM_VJP][dtype == DSA_F64]);
+    });
 }

@@ -19,6 +19,7 @@
 
 #include <atomic>
 #include <limits>
+#include <type_traits>
 
 #include "../../include/diffsptk_amd.h"
 #include "env.h"          // env_int / env_text: every DSA_* route switch is read through them, at every call
@@ -56,7 +57,7 @@ inline int check_launch(const char* name)
 }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of (kernel, DEVICE): set once per device the process
-// drives (`done` = bit mask of the devices that have it; a process may drive several GPUs).
+// drives (`done` = bit mask of the devices that have it; a process may drive several GPUs).  launch_lds's own.
 inline bool ensure_dynamic_lds(const void* kernel, int bytes, std::atomic<uint64_t>& done)
 {
     int dev = 0;
@@ -66,6 +67,33 @@ inline bool ensure_dynamic_lds(const void* kernel, int bytes, std::atomic<uint64
     if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
     if (known) done.fetch_or(bit, std::memory_order_release);
     return true;
+}
+
+// The launch of a kernel whose dynamic LDS may pass 48 KB.  reserve_bytes > 0: that much is reserved for Kernel first, once per
+// device -- the record of the devices that have it is this instantiation's, so there is one per kernel by construction.  A site that
+// needs the attribute only above a size passes `cond ? bytes : 0`.  lds_error is fail()'s FORMAT: a literal that ends in "%s", as
+// every message of the library.  The caller names the route, in a check_launch of its own right behind.
+template <auto Kernel, typename... Args>
+inline int launch_lds(int reserve_bytes, const char* lds_error, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, Args... args)
+{
+    static std::atomic<uint64_t> devices{0};
+    if (reserve_bytes > 0 && !ensure_dynamic_lds((const void*)Kernel, reserve_bytes, devices)) return fail(DSA_ERR_LAUNCH, lds_error);
+    hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, st, args...);
+    return DSA_OK;
+}
+
+// a compile-time integer as an argument: how a generic lambda takes an instantiation parameter (decltype(q)::value)
+template <int V>
+using int_c = std::integral_constant<int, V>;
+
+// f(float{}) or f(double{}) by the dtype code of an entry; f is a generic lambda that says `using T = decltype(tag);` and holds the
+// entry's argument list once.  Any other code is refused under the entry's name `what`.
+template <typename F>
+inline int with_dtype(int dtype, const char* what, F&& f)
+{
+    if (dtype == DSA_F32) return f(float{});
+    if (dtype == DSA_F64) return f(double{});
+    return fail(DSA_ERR_UNSUPPORTED, "%s: unsupported dtype", what);
 }
 
 // ---- functions one unit defines and another calls (those of the mel-cepstral families: mcep_units.h, included above) ----

@@ -454,52 +454,38 @@ int dtw_check(const char*& route, int entry, int64_t B, int64_t T1, int64_t T2, 
     return DSA_OK;
 }
 
-template <typename K>
-bool dtw_raise_lds(K kernel, std::atomic<uint64_t>& done)
-{
-    return ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), DSA_DTW_MAX_LDS_BYTES, done);
-}
+constexpr const char* kDtwLdsError = "dtw: cannot raise the dynamic LDS limit";
+inline int dtw_block_threads(int64_t T1) { return T1 >= DTW_BLOCK_THREADS ? DTW_BLOCK_THREADS : (int)((T1 + 63) / 64 * 64); }
 
 template <typename T>
 int dtw_forward(const void* x, const void* y, const void* lengths, int64_t B, int64_t T1, int64_t T2, int64_t D, int metric, const DtwSteps& st,
                 double gamma, void* R, void* Q, void* dist, hipStream_t stream)
 {
-    static std::atomic<uint64_t> done_wave{0}, done_block{0};
     const bool wave = T1 <= DTW_WAVE_ROWS;
     const size_t lds = (size_t)T1 * (D + (wave ? 0 : 2 * DTW_RING)) * sizeof(T);
     const dim3 grid((unsigned)(B < DTW_MAX_GRID ? B : DTW_MAX_GRID));
-    if (wave) {
-        if (!dtw_raise_lds(&dtw_kernel<T, true>, done_wave)) return fail(DSA_ERR_LAUNCH, "dtw: cannot raise the dynamic LDS limit");
-        hipLaunchKernelGGL((dtw_kernel<T, true>), grid, dim3(DTW_WAVE_ROWS), lds, stream, (const T*)x, (const T*)y, (const int64_t*)lengths, (long)B,
-                           (int)T1, (long)T2, (int)D, metric, st, (T)gamma, (T*)R, (T*)Q, (T*)dist);
-    } else {
-        if (!dtw_raise_lds(&dtw_kernel<T, false>, done_block)) return fail(DSA_ERR_LAUNCH, "dtw: cannot raise the dynamic LDS limit");
-        const int threads = T1 >= DTW_BLOCK_THREADS ? DTW_BLOCK_THREADS : (int)((T1 + 63) / 64 * 64);
-        hipLaunchKernelGGL((dtw_kernel<T, false>), grid, dim3(threads), lds, stream, (const T*)x, (const T*)y, (const int64_t*)lengths, (long)B,
-                           (int)T1, (long)T2, (int)D, metric, st, (T)gamma, (T*)R, (T*)Q, (T*)dist);
-    }
-    return DSA_OK;
+    auto launch = [&](auto wave_tag, int threads) {
+        return launch_lds<dtw_kernel<T, decltype(wave_tag)::value>>(DSA_DTW_MAX_LDS_BYTES, kDtwLdsError, grid, dim3(threads), lds, stream, (const T*)x,
+                                                                    (const T*)y, (const int64_t*)lengths, (long)B, (int)T1, (long)T2, (int)D, metric, st,
+                                                                    (T)gamma, (T*)R, (T*)Q, (T*)dist);
+    };
+    return wave ? launch(std::true_type{}, DTW_WAVE_ROWS) : launch(std::false_type{}, dtw_block_threads(T1));
 }
 
 template <typename T>
 int dtw_backward(const void* x, const void* y, const void* lengths, const void* R, const void* Q, const void* gdist, int64_t B, int64_t T1,
                  int64_t T2, int64_t D, int metric, const DtwSteps& st, double gamma, void* gx, void* gy, hipStream_t stream)
 {
-    static std::atomic<uint64_t> done_wave{0}, done_block{0};
     const bool wave = T1 <= DTW_WAVE_ROWS;
     const size_t lds = (size_t)T1 * (D + (wave ? 0 : 3 * DTW_RING)) * sizeof(T);
     const dim3 grid((unsigned)(B < DTW_MAX_GRID ? B : DTW_MAX_GRID));
-    if (wave) {
-        if (!dtw_raise_lds(&dtw_vjp_kernel<T, true>, done_wave)) return fail(DSA_ERR_LAUNCH, "dtw: cannot raise the dynamic LDS limit");
-        hipLaunchKernelGGL((dtw_vjp_kernel<T, true>), grid, dim3(DTW_WAVE_ROWS), lds, stream, (const T*)x, (const T*)y, (const int64_t*)lengths,
-                           (const T*)R, (const T*)Q, (const T*)gdist, (long)B, (int)T1, (long)T2, (int)D, metric, st, (T)gamma, (T*)gx, (T*)gy);
-    } else {
-        if (!dtw_raise_lds(&dtw_vjp_kernel<T, false>, done_block)) return fail(DSA_ERR_LAUNCH, "dtw: cannot raise the dynamic LDS limit");
-        const int threads = T1 >= DTW_BLOCK_THREADS ? DTW_BLOCK_THREADS : (int)((T1 + 63) / 64 * 64);
-        hipLaunchKernelGGL((dtw_vjp_kernel<T, false>), grid, dim3(threads), lds, stream, (const T*)x, (const T*)y, (const int64_t*)lengths,
-                           (const T*)R, (const T*)Q, (const T*)gdist, (long)B, (int)T1, (long)T2, (int)D, metric, st, (T)gamma, (T*)gx, (T*)gy);
-    }
-    return DSA_OK;
+    auto launch = [&](auto wave_tag, int threads) {
+        return launch_lds<dtw_vjp_kernel<T, decltype(wave_tag)::value>>(DSA_DTW_MAX_LDS_BYTES, kDtwLdsError, grid, dim3(threads), lds, stream,
+                                                                        (const T*)x, (const T*)y, (const int64_t*)lengths, (const T*)R, (const T*)Q,
+                                                                        (const T*)gdist, (long)B, (int)T1, (long)T2, (int)D, metric, st, (T)gamma,
+                                                                        (T*)gx, (T*)gy);
+    };
+    return wave ? launch(std::true_type{}, DTW_WAVE_ROWS) : launch(std::false_type{}, dtw_block_threads(T1));
 }
 
 }  // namespace
@@ -517,8 +503,9 @@ DSA_EXPORT int dsa_dtw(const void* x, const void* y, const void* lengths, int64_
     const DtwSteps st = dtw_steps(p);
     if (!(x && y && distance) || (R && st.two && !R2)) return fail(DSA_ERR_INVALID_ARGUMENT, "dtw: null pointer");
     if (!st.two || !R) R2 = nullptr;
-    const int rc = dtype == DSA_F32 ? dtw_forward<float>(x, y, lengths, B, T1, T2, D, metric, st, softness, R, R2, distance, (hipStream_t)stream)
-                                    : dtw_forward<double>(x, y, lengths, B, T1, T2, D, metric, st, softness, R, R2, distance, (hipStream_t)stream);
+    const int rc = with_dtype(dtype, "dtw", [&](auto tag) {
+        return dtw_forward<decltype(tag)>(x, y, lengths, B, T1, T2, D, metric, st, softness, R, R2, distance, (hipStream_t)stream);
+    });
     return rc ? rc : check_launch(route);
 }
 
@@ -532,9 +519,9 @@ DSA_EXPORT int dsa_dtw_vjp(const void* x, const void* y, const void* lengths, co
     if (B == 0) return DSA_OK;
     const DtwSteps st = dtw_steps(p);
     if (!(x && y && R && gdistance && gx && gy) || (st.two && !R2)) return fail(DSA_ERR_INVALID_ARGUMENT, "dtw: null pointer");
-    const int rc = dtype == DSA_F32
-                       ? dtw_backward<float>(x, y, lengths, R, R2, gdistance, B, T1, T2, D, metric, st, softness, gx, gy, (hipStream_t)stream)
-                       : dtw_backward<double>(x, y, lengths, R, R2, gdistance, B, T1, T2, D, metric, st, softness, gx, gy, (hipStream_t)stream);
+    const int rc = with_dtype(dtype, "dtw", [&](auto tag) {
+        return dtw_backward<decltype(tag)>(x, y, lengths, R, R2, gdistance, B, T1, T2, D, metric, st, softness, gx, gy, (hipStream_t)stream);
+    });
     return rc ? rc : check_launch(route);
 }
 
@@ -547,13 +534,10 @@ DSA_EXPORT int dsa_dtw_path(const void* x, const void* y, const void* lengths, c
     const DtwSteps st = dtw_steps(p);
     if (!(x && y && R && indices && count) || (st.two && !R2)) return fail(DSA_ERR_INVALID_ARGUMENT, "dtw: null pointer");
     const dim3 grid((unsigned)((B + 63) / 64));
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((dtw_path_kernel<float>), grid, dim3(64), 0, (hipStream_t)stream, (const float*)x, (const float*)y,
-                           (const int64_t*)lengths, (const float*)R, (const float*)R2, (long)B, (long)T1, (long)T2, (int)D, metric, st,
-                           (int64_t*)indices, (int32_t*)count);
-    else
-        hipLaunchKernelGGL((dtw_path_kernel<double>), grid, dim3(64), 0, (hipStream_t)stream, (const double*)x, (const double*)y,
-                           (const int64_t*)lengths, (const double*)R, (const double*)R2, (long)B, (long)T1, (long)T2, (int)D, metric, st,
-                           (int64_t*)indices, (int32_t*)count);
-    return check_launch(route);
+    return with_dtype(dtype, "dtw", [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((dtw_path_kernel<T>), grid, dim3(64), 0, (hipStream_t)stream, (const T*)x, (const T*)y, (const int64_t*)lengths, (const T*)R,
+                           (const T*)R2, (long)B, (long)T1, (long)T2, (int)D, metric, st, (int64_t*)indices, (int32_t*)count);
+        return check_launch(route);
+    });
 }

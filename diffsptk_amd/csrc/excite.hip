@@ -212,11 +212,10 @@ DSA_EXPORT int dsa_excite(const void* p, int64_t B, int64_t N, int32_t P, int32_
     if (!(p && out)) return fail(DSA_ERR_INVALID_ARGUMENT, "excite: null pointer");
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)(B < (1 << 16) ? B : (1 << 16)));
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((excite_kernel<float>), grid, dim3(EX_THREADS), 0, st, (const float*)p, (long)B, (long)N, P, type, bipolar, init_shift,
-                           (const float*)shift, (float*)out);
-    else
-        hipLaunchKernelGGL((excite_kernel<double>), grid, dim3(EX_THREADS), 0, st, (const double*)p, (long)B, (long)N, P, type, bipolar,
-                           init_shift, (const double*)shift, (double*)out);
-    return check_launch(dtype == DSA_F32 ? "excite_f32" : "excite_f64");
+    return with_dtype(dtype, "excite", [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((excite_kernel<T>), grid, dim3(EX_THREADS), 0, st, (const T*)p, (long)B, (long)N, P, type, bipolar, init_shift,
+                           (const T*)shift, (T*)out);
+        return check_launch(dtype == DSA_F32 ? "excite_f32" : "excite_f64");
+    });
 }

@@ -539,21 +539,14 @@ int fbank_mfma_launch_ex(const void* x, int64_t F, int K, const void* H, int C, 
     if (blocks > 256) blocks = 256;
     const int vec4 = (((size_t)x) & 15) == 0;
     const int nq = (4 * K + 63) / 64;
-#define DSA_FM_LAUNCH(NQ)                                                                                              \
-    do {                                                                                                               \
-        static std::atomic<uint64_t> attr_devices{0};                                                                  \
-        if (!ensure_dynamic_lds((const void*)fbank_mfma_fwd_kernel<NQ>, 160 * 1024, attr_devices))                     \
-            return fail(DSA_ERR_LAUNCH, "fbank: cannot reserve LDS for the operand images%s");                        \
-        hipLaunchKernelGGL(fbank_mfma_fwd_kernel<NQ>, dim3((unsigned)blocks), dim3(kFmWaves * 64), lds, st,            \
-                           (const float*)x, (long)F, K, (const float*)H, C, (float)floor, (float)gamma, use_power,     \
-                           (float*)y, (float*)E, nsteps, cap, tile_floats, vec4, ldh, post_mode, (float)post_scale,    \
-                           (const float*)W2, Mo, (float*)z, ldy > 0 ? ldy : C);                                       \
-    } while (0)
-    if (nq <= 5) DSA_FM_LAUNCH(5);
-    else if (nq <= 9) DSA_FM_LAUNCH(9);
-    else if (nq <= 17) DSA_FM_LAUNCH(17);
-    else DSA_FM_LAUNCH(20);
-#undef DSA_FM_LAUNCH
+    auto launch = [&](auto q) {   // q: the kernel's NQ, the spectrum's quarter-rows per lane
+        return launch_lds<fbank_mfma_fwd_kernel<decltype(q)::value>>(160 * 1024, "fbank: cannot reserve LDS for the operand images%s",
+                                                                     dim3((unsigned)blocks), dim3(kFmWaves * 64), lds, st, (const float*)x, (long)F, K,
+                                                                     (const float*)H, C, (float)floor, (float)gamma, use_power, (float*)y, (float*)E,
+                                                                     nsteps, cap, tile_floats, vec4, ldh, post_mode, (float)post_scale,
+                                                                     (const float*)W2, Mo, (float*)z, ldy > 0 ? ldy : C);
+    };
+    if (int rc = nq <= 5 ? launch(int_c<5>{}) : nq <= 9 ? launch(int_c<9>{}) : nq <= 17 ? launch(int_c<17>{}) : launch(int_c<20>{})) return rc;
     return check_launch(name);
 }
 
@@ -583,33 +576,19 @@ static int fbank_launch(bool bwd, const void* gy, const void* gE, const void* x,
     long blocks = (groups + waves - 1) / waves;
     if (blocks > 256) blocks = 256;   // one persistent workgroup per CU; H is copied once each
     const int kFbWaves = (int)waves;
-#define DSA_FB_ATTR(kern)                                                                                        \
-    do {                                                                                                         \
-        static std::atomic<uint64_t> attr_devices{0};                                                            \
-        if (lds > 48 * 1024 && !ensure_dynamic_lds((const void*)kern, 150 * 1024, attr_devices))                 \
-            return fail(DSA_ERR_LAUNCH, "fbank: cannot reserve LDS for the filter matrix%s");                   \
-    } while (0)
-    if (!bwd) {
-        if (hlds) {
-            DSA_FB_ATTR((fbank_fwd_kernel<T, true>));
-            hipLaunchKernelGGL((fbank_fwd_kernel<T, true>), dim3((unsigned)blocks), dim3(kFbWaves * 64), lds, st, (const T*)x,
-                               (long)F, K, (const T*)H, C, (T)floor, (T)gamma, use_power, (T*)y, (T*)E);
-        } else {
-            hipLaunchKernelGGL((fbank_fwd_kernel<T, false>), dim3((unsigned)blocks), dim3(kFbWaves * 64), lds, st, (const T*)x,
-                               (long)F, K, (const T*)H, C, (T)floor, (T)gamma, use_power, (T*)y, (T*)E);
-        }
-        return check_launch("fbank_fwd");
-    }
-    if (hlds) {
-        DSA_FB_ATTR((fbank_bwd_kernel<T, true>));
-        hipLaunchKernelGGL((fbank_bwd_kernel<T, true>), dim3((unsigned)blocks), dim3(kFbWaves * 64), lds, st, (const T*)gy,
-                           (const T*)gE, (const T*)x, (long)F, K, (const T*)H, C, (T)floor, (T)gamma, use_power, (T*)gx);
-    } else {
-        hipLaunchKernelGGL((fbank_bwd_kernel<T, false>), dim3((unsigned)blocks), dim3(kFbWaves * 64), lds, st, (const T*)gy,
-                           (const T*)gE, (const T*)x, (long)F, K, (const T*)H, C, (T)floor, (T)gamma, use_power, (T*)gx);
-    }
-#undef DSA_FB_ATTR
-    return check_launch("fbank_bwd");
+    const dim3 grid((unsigned)blocks), block(kFbWaves * 64);
+    auto launch = [&](auto h) {   // h: H in LDS, the form that may need more than 48 KB
+        constexpr bool HLDS = decltype(h)::value;
+        const int reserve = HLDS && lds > 48 * 1024 ? 150 * 1024 : 0;
+        const char* lds_error = "fbank: cannot reserve LDS for the filter matrix%s";
+        if (!bwd)
+            return launch_lds<fbank_fwd_kernel<T, HLDS>>(reserve, lds_error, grid, block, lds, st, (const T*)x, (long)F, K, (const T*)H, C, (T)floor,
+                                                         (T)gamma, use_power, (T*)y, (T*)E);
+        return launch_lds<fbank_bwd_kernel<T, HLDS>>(reserve, lds_error, grid, block, lds, st, (const T*)gy, (const T*)gE, (const T*)x, (long)F, K,
+                                                     (const T*)H, C, (T)floor, (T)gamma, use_power, (T*)gx);
+    };
+    if (int rc = hlds ? launch(std::true_type{}) : launch(std::false_type{})) return rc;
+    return check_launch(bwd ? "fbank_bwd" : "fbank_fwd");
 }
 
 }  // namespace dsa
@@ -624,9 +603,9 @@ DSA_EXPORT int dsa_fbank_fwd(const void* x, int64_t F, int32_t K, const void* H,
     hipStream_t st = (hipStream_t)stream;
     if (dtype == DSA_F32 && C <= 48 && K <= 16 * kFmPre && K > C && F > 0 && env_int("DSA_FBANK_GENERIC", 0) == 0)
         return fbank_mfma_launch(x, F, K, H, C, floor, gamma, use_power, y, E, st);
-    if (dtype == DSA_F32) return fbank_launch<float>(false, nullptr, nullptr, x, F, K, H, C, floor, gamma, use_power, y, E, nullptr, st);
-    if (dtype == DSA_F64) return fbank_launch<double>(false, nullptr, nullptr, x, F, K, H, C, floor, gamma, use_power, y, E, nullptr, st);
-    return fail(DSA_ERR_UNSUPPORTED, "fbank: unsupported dtype%s");
+    return with_dtype(dtype, "fbank", [&](auto tag) {
+        return fbank_launch<decltype(tag)>(false, nullptr, nullptr, x, F, K, H, C, floor, gamma, use_power, y, E, nullptr, st);
+    });
 }
 
 DSA_EXPORT int dsa_fbank_bwd(const void* gy, const void* gE, const void* x, int64_t F, int32_t K, const void* H, int32_t C,
@@ -634,9 +613,9 @@ DSA_EXPORT int dsa_fbank_bwd(const void* gy, const void* gE, const void* x, int6
 {
     DSA_REQUIRE(F >= 0 && K >= 2 && C >= 1, "fbank_bwd: sizes must be positive");
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == DSA_F32) return fbank_launch<float>(true, gy, gE, x, F, K, H, C, floor, gamma, use_power, nullptr, nullptr, gx, st);
-    if (dtype == DSA_F64) return fbank_launch<double>(true, gy, gE, x, F, K, H, C, floor, gamma, use_power, nullptr, nullptr, gx, st);
-    return fail(DSA_ERR_UNSUPPORTED, "fbank_bwd: unsupported dtype%s");
+    return with_dtype(dtype, "fbank_bwd", [&](auto tag) {
+        return fbank_launch<decltype(tag)>(true, gy, gE, x, F, K, H, C, floor, gamma, use_power, nullptr, nullptr, gx, st);
+    });
 }
 
 // MFCC front end (mfcc.py:244-256): z = glog(max(s H, floor)) W, W:(C, Mo) = DCT-II x truncation x lifter; the filter-bank

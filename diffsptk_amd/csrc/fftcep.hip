@@ -380,9 +380,9 @@ DSA_EXPORT int dsa_fftcep_fwd(const void* x, int64_t F, int32_t fft_length, int3
     // n_iter = 0: out = log(x) A[:, :N] / L with the first coefficient halved -- the matrix-core front-end kernel
     if (dtype == DSA_F32 && n_iter == 0 && N <= 48 && N < H && H <= 320 && F > 0 && env_int("DSA_FFTCEP_GENERIC", 0) == 0)
         return fbank_mfma_launch_ex(x, F, H, A, N, H, 1.0, 0.0, 2, 1, 1.0 / fft_length, out, nullptr, st, "fftcep_mfma_fwd");
-    if (dtype == DSA_F32) return fftcep_launch<float>(false, nullptr, x, F, H, N, A, accel, n_iter, out, masks, nullptr, st);
-    if (dtype == DSA_F64) return fftcep_launch<double>(false, nullptr, x, F, H, N, A, accel, n_iter, out, masks, nullptr, st);
-    return fail(DSA_ERR_UNSUPPORTED, "fftcep: unsupported dtype%s");
+    return with_dtype(dtype, "fftcep", [&](auto tag) {
+        return fftcep_launch<decltype(tag)>(false, nullptr, x, F, H, N, A, accel, n_iter, out, masks, nullptr, st);
+    });
 }
 
 DSA_EXPORT int dsa_fftcep_bwd(const void* gout, const void* x, int64_t F, int32_t fft_length, int32_t cep_order, const void* A,
@@ -393,7 +393,7 @@ DSA_EXPORT int dsa_fftcep_bwd(const void* gout, const void* x, int64_t F, int32_
     DSA_REQUIRE(F == 0 || n_iter == 0 || masks, "fftcep_bwd: the clamp masks of the forward are required when n_iter > 0");
     const int H = fft_length / 2 + 1, N = cep_order + 1;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == DSA_F32) return fftcep_launch<float>(true, gout, x, F, H, N, A, accel, n_iter, nullptr, (void*)masks, gx, st);
-    if (dtype == DSA_F64) return fftcep_launch<double>(true, gout, x, F, H, N, A, accel, n_iter, nullptr, (void*)masks, gx, st);
-    return fail(DSA_ERR_UNSUPPORTED, "fftcep_bwd: unsupported dtype%s");
+    return with_dtype(dtype, "fftcep_bwd", [&](auto tag) {
+        return fftcep_launch<decltype(tag)>(true, gout, x, F, H, N, A, accel, n_iter, nullptr, (void*)masks, gx, st);
+    });
 }

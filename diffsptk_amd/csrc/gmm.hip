@@ -561,13 +561,12 @@ int gmm_estep(const void* x, const void* mu, const void* prec, const void* cst, 
               void* post, void* ll, void* partial, void* total, void* readback, hipStream_t st)
 {
     constexpr int TILE = DSA_GMM_TILE_BYTES / sizeof(T);
-    static std::atomic<uint64_t> done{0};
-    if (!ensure_dynamic_lds(reinterpret_cast<const void*>(&gmm_estep_kernel<T, DIAG>), DSA_GMM_MAX_LDS_BYTES - 64, done))
-        return fail(DSA_ERR_LAUNCH, "gmm: cannot raise the dynamic LDS limit");
     const int64_t blocks = (Tn + TILE - 1) / TILE;
     const size_t lds = ((size_t)2 * TILE * (Lp | 1) + (DIAG ? Lp : Lp * Lp) + Lp) * sizeof(T);
-    hipLaunchKernelGGL((gmm_estep_kernel<T, DIAG>), dim3((unsigned)blocks), dim3(TILE), lds, st, (const T*)x, (const T*)mu, (const T*)prec,
-                       (const T*)cst, (long)Tn, (int)K, (int)L, (int)Lp, (T*)post, (T*)ll, (double*)partial);
+    if (int rc = launch_lds<gmm_estep_kernel<T, DIAG>>(DSA_GMM_MAX_LDS_BYTES - 64, "gmm: cannot raise the dynamic LDS limit", dim3((unsigned)blocks),
+                                                       dim3(TILE), lds, st, (const T*)x, (const T*)mu, (const T*)prec, (const T*)cst, (long)Tn, (int)K,
+                                                       (int)L, (int)Lp, (T*)post, (T*)ll, (double*)partial))
+        return rc;
     if (total || readback)
         hipLaunchKernelGGL((gmm_total_kernel<T>), dim3(1), dim3(256), 0, st, (const double*)partial, (long)blocks, (const int32_t*)failed, (int)K,
                            (T*)total, (double*)readback);
@@ -616,8 +615,9 @@ DSA_EXPORT int dsa_gmm_prepare(const void* w, const void* sigma, int64_t K, int6
     const char* route = "";
     if (int rc = gmm_check(route, GMM_PREPARE, 1, K, L, Lp, diag, dtype)) return rc;
     if (!(w && sigma && prec && cst && failed)) return fail(DSA_ERR_INVALID_ARGUMENT, "gmm: null pointer");
-    const int rc = dtype == DSA_F32 ? gmm_prepare<float>(w, sigma, K, L, Lp, diag, prec, cst, failed, (hipStream_t)stream)
-                                    : gmm_prepare<double>(w, sigma, K, L, Lp, diag, prec, cst, failed, (hipStream_t)stream);
+    const int rc = with_dtype(dtype, "gmm", [&](auto tag) {
+        return gmm_prepare<decltype(tag)>(w, sigma, K, L, Lp, diag, prec, cst, failed, (hipStream_t)stream);
+    });
     return rc ? rc : check_launch(route);
 }
 
@@ -629,13 +629,11 @@ DSA_EXPORT int dsa_gmm_estep(const void* x, const void* mu, const void* prec, co
     if (int rc = gmm_check(route, GMM_ESTEP, T, K, L, Lp, diag, dtype)) return rc;
     if (!(x && mu && prec && cst && failed && posterior && loglik && partial)) return fail(DSA_ERR_INVALID_ARGUMENT, "gmm: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    int rc;
-    if (dtype == DSA_F32)
-        rc = diag ? gmm_estep<float, true>(x, mu, prec, cst, failed, T, K, L, Lp, posterior, loglik, partial, total, readback, st)
-                  : gmm_estep<float, false>(x, mu, prec, cst, failed, T, K, L, Lp, posterior, loglik, partial, total, readback, st);
-    else
-        rc = diag ? gmm_estep<double, true>(x, mu, prec, cst, failed, T, K, L, Lp, posterior, loglik, partial, total, readback, st)
-                  : gmm_estep<double, false>(x, mu, prec, cst, failed, T, K, L, Lp, posterior, loglik, partial, total, readback, st);
+    const int rc = with_dtype(dtype, "gmm", [&](auto tag) {
+        using V = decltype(tag);   // (T is the entry's row count)
+        return diag ? gmm_estep<V, true>(x, mu, prec, cst, failed, T, K, L, Lp, posterior, loglik, partial, total, readback, st)
+                    : gmm_estep<V, false>(x, mu, prec, cst, failed, T, K, L, Lp, posterior, loglik, partial, total, readback, st);
+    });
     return rc ? rc : check_launch(route);
 }
 
@@ -652,8 +650,9 @@ DSA_EXPORT int dsa_gmm_accum(const void* x, const void* posterior, int64_t T, in
     const char* route = "";
     if (int rc = gmm_check(route, GMM_ACCUM, T, K, L, L, diag, dtype)) return rc;
     if (!(x && posterior && workspace)) return fail(DSA_ERR_INVALID_ARGUMENT, "gmm: null pointer");
-    const int rc = dtype == DSA_F32 ? gmm_accum<float>(x, posterior, T, K, L, diag, workspace, (hipStream_t)stream)
-                                    : gmm_accum<double>(x, posterior, T, K, L, diag, workspace, (hipStream_t)stream);
+    const int rc = with_dtype(dtype, "gmm", [&](auto tag) {
+        return gmm_accum<decltype(tag)>(x, posterior, T, K, L, diag, workspace, (hipStream_t)stream);
+    });
     return rc ? rc : check_launch(route);
 }
 
@@ -666,10 +665,10 @@ DSA_EXPORT int dsa_gmm_update(const void* workspace, const void* readback, const
     if (!(workspace && w && mu && sigma) || (!diag && !mask)) return fail(DSA_ERR_INVALID_ARGUMENT, "gmm: null pointer");
     if (!(alpha >= 0 && alpha <= 1 && weight_floor >= 0 && var_floor >= 0)) return fail(DSA_ERR_INVALID_ARGUMENT, "gmm: invalid options");
     if (alpha != 0 && !(ubm_w && ubm_mu && ubm_sigma)) return fail(DSA_ERR_INVALID_ARGUMENT, "gmm: alpha needs the background model");
-    const int rc = dtype == DSA_F32 ? gmm_update<float>(workspace, readback, ubm_w, ubm_mu, ubm_sigma, mask, T, K, L, diag, alpha, weight_floor,
-                                                        var_floor, w, mu, sigma, (hipStream_t)stream)
-                                    : gmm_update<double>(workspace, readback, ubm_w, ubm_mu, ubm_sigma, mask, T, K, L, diag, alpha, weight_floor,
-                                                         var_floor, w, mu, sigma, (hipStream_t)stream);
+    const int rc = with_dtype(dtype, "gmm", [&](auto tag) {
+        return gmm_update<decltype(tag)>(workspace, readback, ubm_w, ubm_mu, ubm_sigma, mask, T, K, L, diag, alpha, weight_floor, var_floor, w, mu, sigma,
+                                         (hipStream_t)stream);
+    });
     return rc ? rc : check_launch(route);
 }
 
@@ -679,15 +678,12 @@ DSA_EXPORT int dsa_gmm_regress(const void* sigma, int64_t K, int64_t L, int64_t 
     if (int rc = gmm_check(route, GMM_REGRESS, 1, K, L, Lx, 0, dtype)) return rc;
     if (Lx >= L) return fail(DSA_ERR_INVALID_ARGUMENT, "gmm: invalid sizes");
     if (!(sigma && M)) return fail(DSA_ERR_INVALID_ARGUMENT, "gmm: null pointer");
-    const size_t size = dtype == DSA_F32 ? 4 : 8, lds = (size_t)(2 * Lx * Lx + Lx) * size;
-    if (dtype == DSA_F32) {   // (2 Lx^2 + Lx elements: below 64 KiB at every Lx inside the ceiling)
-        hipLaunchKernelGGL((gmm_regress_kernel<float>), dim3((unsigned)K), dim3(256), lds, (hipStream_t)stream, (const float*)sigma, (int)L, (int)Lx,
-                           (float*)M);
-    } else {
-        hipLaunchKernelGGL((gmm_regress_kernel<double>), dim3((unsigned)K), dim3(256), lds, (hipStream_t)stream, (const double*)sigma, (int)L, (int)Lx,
-                           (double*)M);
-    }
-    return check_launch(route);
+    return with_dtype(dtype, "gmm", [&](auto tag) {
+        using T = decltype(tag);
+        const size_t lds = (size_t)(2 * Lx * Lx + Lx) * sizeof(T);   // (below 64 KiB at every Lx inside the ceiling)
+        hipLaunchKernelGGL((gmm_regress_kernel<T>), dim3((unsigned)K), dim3(256), lds, (hipStream_t)stream, (const T*)sigma, (int)L, (int)Lx, (T*)M);
+        return check_launch(route);
+    });
 }
 
 DSA_EXPORT int dsa_gmm_transform(const void* x, const void* posterior, const void* mu, const void* M, int64_t T, int64_t K, int64_t L, int64_t Lx,
@@ -697,11 +693,10 @@ DSA_EXPORT int dsa_gmm_transform(const void* x, const void* posterior, const voi
     if (int rc = gmm_check(route, GMM_TRANSFORM, T, K, L, Lx, 0, dtype)) return rc;
     if (!(posterior && indices) || (y && !(x && mu && M)) || (y && Lx >= L)) return fail(DSA_ERR_INVALID_ARGUMENT, "gmm: null pointer");
     const dim3 grid((unsigned)((T + 255) / 256));
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((gmm_transform_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)x, (const float*)posterior,
-                           (const float*)mu, (const float*)M, (long)T, (int)K, (int)L, (int)Lx, (int64_t*)indices, (float*)y);
-    else
-        hipLaunchKernelGGL((gmm_transform_kernel<double>), grid, dim3(256), 0, (hipStream_t)stream, (const double*)x, (const double*)posterior,
-                           (const double*)mu, (const double*)M, (long)T, (int)K, (int)L, (int)Lx, (int64_t*)indices, (double*)y);
-    return check_launch(route);
+    return with_dtype(dtype, "gmm", [&](auto tag) {
+        using V = decltype(tag);   // (T is the entry's row count)
+        hipLaunchKernelGGL((gmm_transform_kernel<V>), grid, dim3(256), 0, (hipStream_t)stream, (const V*)x, (const V*)posterior, (const V*)mu, (const V*)M,
+                           (long)T, (int)K, (int)L, (int)Lx, (int64_t*)indices, (V*)y);
+        return check_launch(route);
+    });
 }

@@ -86,13 +86,11 @@ DSA_EXPORT int dsa_irfft_scale(const void* y, int64_t F, int32_t nfft, int32_t d
     if (total == 0) return DSA_OK;
     hipStream_t st = (hipStream_t)stream;
     const unsigned blocks = (unsigned)((total + 255) / 256);
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((irfft_scale_kernel<float>), dim3(blocks), dim3(256), 0, st, (const float*)y, total, K, nfft, (float*)out);
-    else if (dtype == DSA_F64)
-        hipLaunchKernelGGL((irfft_scale_kernel<double>), dim3(blocks), dim3(256), 0, st, (const double*)y, total, K, nfft, (double*)out);
-    else
-        return fail(DSA_ERR_UNSUPPORTED, "irfft_scale: unsupported dtype%s");
-    return check_launch("irfft_scale");
+    return with_dtype(dtype, "irfft_scale", [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((irfft_scale_kernel<T>), dim3(blocks), dim3(256), 0, st, (const T*)y, total, K, nfft, (T*)out);
+        return check_launch("irfft_scale");
+    });
 }
 
 DSA_EXPORT int dsa_div_rows(const void* x, int64_t B, int64_t T, const void* d, double eps, int32_t dtype, void* out,
@@ -102,13 +100,11 @@ DSA_EXPORT int dsa_div_rows(const void* x, int64_t B, int64_t T, const void* d, 
     if (B * T == 0) return DSA_OK;
     hipStream_t st = (hipStream_t)stream;
     dim3 grid((unsigned)((T + 255) / 256), (unsigned)(B < 1024 ? B : 1024));
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((div_rows_kernel<float>), grid, dim3(256), 0, st, (const float*)x, (long)B, (long)T, (const float*)d, (float)eps, (float*)out);
-    else if (dtype == DSA_F64)
-        hipLaunchKernelGGL((div_rows_kernel<double>), grid, dim3(256), 0, st, (const double*)x, (long)B, (long)T, (const double*)d, eps, (double*)out);
-    else
-        return fail(DSA_ERR_UNSUPPORTED, "div_rows: unsupported dtype%s");
-    return check_launch("div_rows");
+    return with_dtype(dtype, "div_rows", [&](auto tag) {
+        using V = decltype(tag);   // (T is the entry's row length)
+        hipLaunchKernelGGL((div_rows_kernel<V>), grid, dim3(256), 0, st, (const V*)x, (long)B, (long)T, (const V*)d, (V)eps, (V*)out);
+        return check_launch("div_rows");
+    });
 }
 
 DSA_EXPORT int dsa_griffin_update(const void* t, int64_t B, int64_t Nt, int64_t N, int32_t K, const void* y, const void* phase,
@@ -122,15 +118,10 @@ DSA_EXPORT int dsa_griffin_update(const void* t, int64_t B, int64_t Nt, int64_t 
     hipStream_t st = (hipStream_t)stream;
     long blocks = (total + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((griffin_update_kernel<float>), dim3((unsigned)blocks), dim3(256), 0, st, (const float*)t, (long)B,
-                           (long)Nt, (long)N, K, (const float*)y, (const float*)phase, (float*)t_prev, (float*)d_prev, first,
-                           (float)alpha, (float)beta, (float)gamma, (float)eps, (float*)z);
-    else if (dtype == DSA_F64)
-        hipLaunchKernelGGL((griffin_update_kernel<double>), dim3((unsigned)blocks), dim3(256), 0, st, (const double*)t, (long)B,
-                           (long)Nt, (long)N, K, (const double*)y, (const double*)phase, (double*)t_prev, (double*)d_prev,
-                           first, alpha, beta, gamma, eps, (double*)z);
-    else
-        return fail(DSA_ERR_UNSUPPORTED, "griffin_update: unsupported dtype%s");
-    return check_launch("griffin_update");
+    return with_dtype(dtype, "griffin_update", [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((griffin_update_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)t, (long)B, (long)Nt, (long)N, K,
+                           (const T*)y, (const T*)phase, (T*)t_prev, (T*)d_prev, first, (T)alpha, (T)beta, (T)gamma, (T)eps, (T*)z);
+        return check_launch("griffin_update");
+    });
 }

@@ -415,9 +415,7 @@ DSA_EXPORT int dsa_acorr_fwd(const void* x, int64_t F, int32_t L, int32_t M, int
     DSA_REQUIRE(L > 0 && M >= 0 && M < L && F >= 0, "acorr: acr_order must be less than frame_length");
     DSA_REQUIRE(out_format >= 0 && out_format <= 3, "acorr: unknown out_format");
     if (F == 0) return DSA_OK;
-    if (dtype == DSA_F32) return acorr_fwd_impl<float>(x, F, L, M, out_format, r, (hipStream_t)stream);
-    if (dtype == DSA_F64) return acorr_fwd_impl<double>(x, F, L, M, out_format, r, (hipStream_t)stream);
-    return fail(DSA_ERR_UNSUPPORTED, "acorr: unsupported dtype%s");
+    return with_dtype(dtype, "acorr", [&](auto tag) { return acorr_fwd_impl<decltype(tag)>(x, F, L, M, out_format, r, (hipStream_t)stream); });
 }
 
 DSA_EXPORT int dsa_acorr_bwd(const void* gr, const void* x, int64_t F, int32_t L, int32_t M, int32_t out_format,
@@ -425,9 +423,9 @@ DSA_EXPORT int dsa_acorr_bwd(const void* gr, const void* x, int64_t F, int32_t L
 {
     DSA_REQUIRE(L > 0 && M >= 0 && M < L && F >= 0, "acorr_bwd: acr_order must be less than frame_length");
     if (F == 0) return DSA_OK;
-    if (dtype == DSA_F32) return acorr_bwd_impl<float>(gr, x, F, L, M, out_format, gx, (hipStream_t)stream);
-    if (dtype == DSA_F64) return acorr_bwd_impl<double>(gr, x, F, L, M, out_format, gx, (hipStream_t)stream);
-    return fail(DSA_ERR_UNSUPPORTED, "acorr_bwd: unsupported dtype%s");
+    return with_dtype(dtype, "acorr_bwd", [&](auto tag) {
+        return acorr_bwd_impl<decltype(tag)>(gr, x, F, L, M, out_format, gx, (hipStream_t)stream);
+    });
 }
 
 DSA_EXPORT int dsa_levdur_fwd(const void* r, int64_t F, int32_t M, double eps, int32_t dtype, void* out,
@@ -435,9 +433,7 @@ DSA_EXPORT int dsa_levdur_fwd(const void* r, int64_t F, int32_t M, double eps, i
 {
     DSA_REQUIRE(M >= 0 && F >= 0 && eps >= 0, "levdur: lpc_order and eps must be non-negative");
     if (F == 0) return DSA_OK;
-    if (dtype == DSA_F32) return levdur_fwd_impl<float>(r, F, M, eps, out, (hipStream_t)stream);
-    if (dtype == DSA_F64) return levdur_fwd_impl<double>(r, F, M, eps, out, (hipStream_t)stream);
-    return fail(DSA_ERR_UNSUPPORTED, "levdur: unsupported dtype%s");
+    return with_dtype(dtype, "levdur", [&](auto tag) { return levdur_fwd_impl<decltype(tag)>(r, F, M, eps, out, (hipStream_t)stream); });
 }
 
 DSA_EXPORT int dsa_levdur_bwd(const void* gout, const void* r, const void* out, int64_t F, int32_t M, double eps,
@@ -445,9 +441,9 @@ DSA_EXPORT int dsa_levdur_bwd(const void* gout, const void* r, const void* out, 
 {
     DSA_REQUIRE(M >= 0 && F >= 0, "levdur_bwd: lpc_order must be non-negative");
     if (F == 0) return DSA_OK;
-    if (dtype == DSA_F32) return levdur_bwd_impl<float>(gout, r, out, F, M, eps, gr, (hipStream_t)stream);
-    if (dtype == DSA_F64) return levdur_bwd_impl<double>(gout, r, out, F, M, eps, gr, (hipStream_t)stream);
-    return fail(DSA_ERR_UNSUPPORTED, "levdur_bwd: unsupported dtype%s");
+    return with_dtype(dtype, "levdur_bwd", [&](auto tag) {
+        return levdur_bwd_impl<decltype(tag)>(gout, r, out, F, M, eps, gr, (hipStream_t)stream);
+    });
 }
 
 template <typename T>
@@ -491,9 +487,7 @@ DSA_EXPORT int dsa_lpc_fwd(const void* x, int64_t F, int32_t L, int32_t M, doubl
     // (w = NULL: the window of ones; scratch = NULL: no ticket counter available, the generic kernel runs)
     if (dtype == DSA_F32 && M == 24 && L >= 25 && L <= 512 && scratch)
         return dsa_frame_window_lpc_fwd(x, 1, F * (int64_t)L, L, L, nullptr, 0, DSA_PAD_CONSTANT, M, eps, dtype, scratch, out, stream);
-    if (dtype == DSA_F32) return lpc_fwd_impl<float>(x, F, L, M, eps, out, (hipStream_t)stream);
-    if (dtype == DSA_F64) return lpc_fwd_impl<double>(x, F, L, M, eps, out, (hipStream_t)stream);
-    return fail(DSA_ERR_UNSUPPORTED, "lpc: unsupported dtype%s");
+    return with_dtype(dtype, "lpc", [&](auto tag) { return lpc_fwd_impl<decltype(tag)>(x, F, L, M, eps, out, (hipStream_t)stream); });
 }
 
 DSA_EXPORT int dsa_lpc_bwd(const void* gout, const void* x, const void* out, int64_t F, int32_t L, int32_t M,
@@ -503,9 +497,7 @@ DSA_EXPORT int dsa_lpc_bwd(const void* gout, const void* x, const void* out, int
     if (F == 0) return DSA_OK;
     if (dtype == DSA_F32 && M == 24 && L >= 25 && L <= 512)   // the tuned kernel (lpc24_bwd.hip)
         return lpc24_bwd(gout, x, F, L, eps, gx, (hipStream_t)stream);
-    if (dtype == DSA_F32) return lpc_bwd_impl<float>(gout, x, out, F, L, M, eps, gx, (hipStream_t)stream);
-    if (dtype == DSA_F64) return lpc_bwd_impl<double>(gout, x, out, F, L, M, eps, gx, (hipStream_t)stream);
-    return fail(DSA_ERR_UNSUPPORTED, "lpc_bwd: unsupported dtype%s");
+    return with_dtype(dtype, "lpc_bwd", [&](auto tag) { return lpc_bwd_impl<decltype(tag)>(gout, x, out, F, L, M, eps, gx, (hipStream_t)stream); });
 }
 
 DSA_EXPORT int dsa_frame_window_lpc_fwd(const void* x, int64_t B, int64_t T, int32_t L, int32_t P, const void* w,
@@ -531,13 +523,10 @@ DSA_EXPORT int dsa_frame_window_lpc_fwd(const void* x, int64_t B, int64_t T, int
     if (M > 63) return fail(DSA_ERR_UNSUPPORTED, "frame_window_lpc: fused kernel supports lpc_order <= 63%s");
     if (lds > 60 * 1024) return fail(DSA_ERR_UNSUPPORTED, "frame_window_lpc: frame too long for LDS%s");
     unsigned grid = (unsigned)((F + nw - 1) / nw);
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((frame_window_lpc_kernel<float>), dim3(grid), dim3(64 * nw), lds, st, (const float*)x,
-                           (long)T, (long)N, (long)F, L, P, left, pad_mode, (const float*)w, M, eps, (float*)out);
-    else if (dtype == DSA_F64)
-        hipLaunchKernelGGL((frame_window_lpc_kernel<double>), dim3(grid), dim3(64 * nw), lds, st, (const double*)x,
-                           (long)T, (long)N, (long)F, L, P, left, pad_mode, (const double*)w, M, eps, (double*)out);
-    else
-        return fail(DSA_ERR_UNSUPPORTED, "frame_window_lpc: unsupported dtype%s");
-    return check_launch("frame_window_lpc_fwd");
+    return with_dtype(dtype, "frame_window_lpc", [&](auto tag) {
+        using V = decltype(tag);   // (T is the entry's signal length)
+        hipLaunchKernelGGL((frame_window_lpc_kernel<V>), dim3(grid), dim3(64 * nw), lds, st, (const V*)x, (long)T, (long)N, (long)F, L, P, left,
+                           pad_mode, (const V*)w, M, eps, (V*)out);
+        return check_launch("frame_window_lpc_fwd");
+    });
 }

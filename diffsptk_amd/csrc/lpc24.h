@@ -210,19 +210,6 @@ __device__ __forceinline__ void lp_round_products(const lp_h8 (&ah)[2], const lp
     }
 }
 
-
-// The launch of one kernel whose dynamic LDS may pass 48 KB: reserved once per device the process drives (the record of that is the
-// instantiation's own: one per kernel), the launch, its record under `name`.  lds_error is fail()'s FORMAT: a literal that ends in
-// "%s", as every message of the library.
-template <auto Kernel, typename... Args>
-inline int lpc24_launch(const char* name, const char* lds_error, long grid, int block, size_t lds_bytes, hipStream_t st, Args... args)
-{
-    static std::atomic<uint64_t> attr_devices{0};
-    if (lds_bytes > 48 * 1024 && !ensure_dynamic_lds((const void*)Kernel, (int)lds_bytes, attr_devices)) return fail(DSA_ERR_LAUNCH, lds_error);
-    hipLaunchKernelGGL(Kernel, dim3((unsigned)grid), dim3(block), lds_bytes, st, args...);
-    return check_launch(name);
-}
-
 // Frames per work item of a launch that deals items of up to 64 consecutive frames to `grid` waves: 64 fills the lanes of the
 // one-frame-per-lane recursion, but e.g. 204 800 frames / 64 = 3200 items are 3.125 per wave of 1024 -- four rounds with the last one
 // an eighth full.  Pick the multiple of 4 (<= 64) that makes the item count a whole number of rounds (there 52 frames: 3939 items,

@@ -371,12 +371,12 @@ int lpc24_fwd(const void* x, int64_t B, int64_t T, int64_t N, int L, int P, int 
         const long wg_cap = 256L * (lds_m <= 53 * 1024 ? 3 : 2);   // workgroups of four waves per CU
         if (wgs > wg_cap) wgs = wg_cap;
         auto launch = [&](auto lc) {
-            return lpc24_launch<frame_window_lpc24_mfma_kernel<8, lc()>>("frame_window_lpc24_mfma_fwd", "frame_window_lpc: cannot reserve LDS%s", wgs, 256,
-                                                                        lds_m, st, (const float*)x, (long)T, (long)N, L, P, left, pad_mode,
-                                                                        (const float*)w, eps, (float*)out, total_sc, sc_per_utt, fpi);
+            return launch_lds<frame_window_lpc24_mfma_kernel<8, lc()>>(lds_m > 48 * 1024 ? lds_m : 0, "frame_window_lpc: cannot reserve LDS%s",
+                                                                       dim3((unsigned)wgs), dim3(256), lds_m, st, (const float*)x, (long)T, (long)N, L, P,
+                                                                       left, pad_mode, (const float*)w, eps, (float*)out, total_sc, sc_per_utt, fpi);
         };
-        return L == 400 ? launch(std::integral_constant<int, 400>{})   // the 25 ms window at 16 kHz
-                        : launch(std::integral_constant<int, 0>{});
+        if (int rc = L == 400 ? launch(int_c<400>{}) : launch(int_c<0>{})) return rc;   // (400: the 25 ms window at 16 kHz)
+        return check_launch("frame_window_lpc24_mfma_fwd");
     }
     hipLaunchKernelGGL(frame_window_lpc24_kernel, dim3((unsigned)grid), dim3(64), lds_t, st, (const float*)x,
                        (long)T, (long)N, L, P, left, pad_mode, (const float*)w, eps, (float*)out, total_sc,

@@ -682,9 +682,11 @@ DSA_EXPORT int dsa_frame_window_lpc_bwd(const void* gout, const void* x, int64_t
     if (grid > total) grid = total;
     hipStream_t st = (hipStream_t)stream;
     auto launch = [&](auto lc) {
-        return lpc24_launch<frame_window_lpc24_bwd_mfma_kernel<lc()>>("frame_window_lpc24_bwd_mfma", "frame_window_lpc_bwd: cannot reserve LDS%s", grid, 64,
-                                                                     lds, st, (const float*)gout, (const float*)x, (long)T, (long)N, L, P, left,
-                                                                     (const float*)w, eps, (float*)gx, total, (int)ipu, (int)Hc, nfr_max);
+        return launch_lds<frame_window_lpc24_bwd_mfma_kernel<lc()>>(lds > 48 * 1024 ? (int)lds : 0, "frame_window_lpc_bwd: cannot reserve LDS%s",
+                                                                    dim3((unsigned)grid), dim3(64), lds, st, (const float*)gout, (const float*)x, (long)T,
+                                                                    (long)N, L, P, left, (const float*)w, eps, (float*)gx, total, (int)ipu, (int)Hc,
+                                                                    nfr_max);
     };
-    return L == 400 ? launch(std::integral_constant<int, 400>{}) : launch(std::integral_constant<int, 0>{});
+    if (int rc = L == 400 ? launch(int_c<400>{}) : launch(int_c<0>{})) return rc;
+    return check_launch("frame_window_lpc24_bwd_mfma");
 }

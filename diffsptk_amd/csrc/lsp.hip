@@ -435,11 +435,9 @@ int lsp_lane_launch_t(const void* in0, const void* in1, int64_t F, int M, double
     const int HP = (M + 1) / 2 + 1;
     const int W = OP == LS_LSP2LPC_FWD ? 2 * HP : OP == LS_LSP2LPC_BWD ? 2 * HP + M : OP == LS_CHECK_FWD ? M : 2 * M;
     const size_t lds = 64 * (size_t)W * sizeof(double) + 64 * (size_t)((M + 1) | 1) * sizeof(T);
-    static std::atomic<uint64_t> attr{0};
-    if (!ensure_dynamic_lds(reinterpret_cast<const void*>(&lsp_lane_kernel<T, OP>), LS_MAX_LDS, attr))
-        return fail(DSA_ERR_LAUNCH, "%s: cannot reserve LDS", kLsLaneNames[OP]);
-    hipLaunchKernelGGL((lsp_lane_kernel<T, OP>), dim3((unsigned)((F + 63) / 64)), dim3(64), lds, st, (const T*)in0, (const T*)in1, (long)F, M,
-                       p, q, W, (T*)out0, (int*)unstable);
+    if (launch_lds<lsp_lane_kernel<T, OP>>(LS_MAX_LDS, "%s: cannot reserve LDS", dim3((unsigned)((F + 63) / 64)), dim3(64), lds, st, (const T*)in0,
+                                           (const T*)in1, (long)F, M, p, q, W, (T*)out0, (int*)unstable))
+        return fail(DSA_ERR_LAUNCH, "%s: cannot reserve LDS", kLsLaneNames[OP]);   // (the message again, with the name in it)
     return check_launch(kLsLaneNames[OP]);
 }
 
@@ -450,9 +448,9 @@ int lsp_lane_launch(const char* what, const void* in0, const void* in1, bool two
     if (!(F >= 0 && M >= 0 && M <= DSA_LSP_MAX_ORDER && q >= 0)) return fail(DSA_ERR_INVALID_ARGUMENT, "%s: invalid sizes", what);
     if (F == 0) return DSA_OK;
     if (!(in0 && out0 && (!two || in1))) return fail(DSA_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
-    if (dtype == DSA_F32) return lsp_lane_launch_t<float, OP>(in0, in1, F, M, p, q, out0, unstable, (hipStream_t)stream);
-    if (dtype == DSA_F64) return lsp_lane_launch_t<double, OP>(in0, in1, F, M, p, q, out0, unstable, (hipStream_t)stream);
-    return fail(DSA_ERR_UNSUPPORTED, "%s: unsupported dtype", what);
+    return with_dtype(dtype, what, [&](auto tag) {
+        return lsp_lane_launch_t<decltype(tag), OP>(in0, in1, F, M, p, q, out0, unstable, (hipStream_t)stream);
+    });
 }
 
 int lsp_wave_check(const char* what, int64_t F, int32_t M, bool pointers)
@@ -473,15 +471,12 @@ DSA_EXPORT int dsa_lpc2lsp_fwd(const void* a, int64_t F, int32_t M, int32_t log_
     if (int rc = lsp_wave_check("lpc2lsp_fwd", F, M, a && w)) return rc;
     if (F == 0) return DSA_OK;
     const dim3 grid((unsigned)(F < (1 << 20) ? F : (1 << 20)));
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((lsp_lpc2lsp_fwd_kernel<float>), grid, dim3(64), 0, (hipStream_t)stream, (const float*)a, (long)F, M, log_gain, unit,
-                           (float*)w, (int*)failed);
-    else if (dtype == DSA_F64)
-        hipLaunchKernelGGL((lsp_lpc2lsp_fwd_kernel<double>), grid, dim3(64), 0, (hipStream_t)stream, (const double*)a, (long)F, M, log_gain, unit,
-                           (double*)w, (int*)failed);
-    else
-        return fail(DSA_ERR_UNSUPPORTED, "%s: unsupported dtype", "lpc2lsp_fwd");
-    return check_launch("lsp_lpc2lsp_fwd");
+    return with_dtype(dtype, "lpc2lsp_fwd", [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((lsp_lpc2lsp_fwd_kernel<T>), grid, dim3(64), 0, (hipStream_t)stream, (const T*)a, (long)F, M, log_gain, unit, (T*)w,
+                           (int*)failed);
+        return check_launch("lsp_lpc2lsp_fwd");
+    });
 }
 
 DSA_EXPORT int dsa_lpc2lsp_bwd(const void* gw, const void* a, const void* w, int64_t F, int32_t M, int32_t log_gain, double unit, int32_t dtype,
@@ -490,15 +485,12 @@ DSA_EXPORT int dsa_lpc2lsp_bwd(const void* gw, const void* a, const void* w, int
     if (int rc = lsp_wave_check("lpc2lsp_bwd", F, M, gw && a && w && ga)) return rc;
     if (F == 0) return DSA_OK;
     const dim3 grid((unsigned)(F < (1 << 20) ? F : (1 << 20)));
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((lsp_lpc2lsp_bwd_kernel<float>), grid, dim3(64), 0, (hipStream_t)stream, (const float*)gw, (const float*)a,
-                           (const float*)w, (long)F, M, log_gain, unit, (float*)ga);
-    else if (dtype == DSA_F64)
-        hipLaunchKernelGGL((lsp_lpc2lsp_bwd_kernel<double>), grid, dim3(64), 0, (hipStream_t)stream, (const double*)gw, (const double*)a,
-                           (const double*)w, (long)F, M, log_gain, unit, (double*)ga);
-    else
-        return fail(DSA_ERR_UNSUPPORTED, "%s: unsupported dtype", "lpc2lsp_bwd");
-    return check_launch("lsp_lpc2lsp_bwd");
+    return with_dtype(dtype, "lpc2lsp_bwd", [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((lsp_lpc2lsp_bwd_kernel<T>), grid, dim3(64), 0, (hipStream_t)stream, (const T*)gw, (const T*)a, (const T*)w, (long)F, M,
+                           log_gain, unit, (T*)ga);
+        return check_launch("lsp_lpc2lsp_bwd");
+    });
 }
 
 DSA_EXPORT int dsa_lsp2lpc_fwd(const void* w, int64_t F, int32_t M, int32_t log_gain, double unit, int32_t dtype, void* a, void* stream)

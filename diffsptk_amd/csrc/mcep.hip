@@ -358,19 +358,14 @@ DSA_EXPORT int dsa_freqt_fwd(const void* c, int64_t F, int32_t L1, const void* A
         }
         return DSA_OK;
     }
-    if ((dtype == DSA_F32 && matmul_rows_lds_launch<float, false>(c, F, L1, A, L1, L2, L2, out, st)) ||
-        (dtype == DSA_F64 && matmul_rows_lds_launch<double, false>(c, F, L1, A, L1, L2, L2, out, st)))
-        return check_launch("freqt_lds_fwd");
-    int threads = L2 >= 192 ? 256 : (L2 >= 96 ? 128 : 64);
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((matmul_rows_kernel<float>), dim3((unsigned)F), dim3(threads), sizeof(float) * L1, st,
-                           (const float*)c, (long)F, L1, (const float*)A, L2, (float*)out);
-    else if (dtype == DSA_F64)
-        hipLaunchKernelGGL((matmul_rows_kernel<double>), dim3((unsigned)F), dim3(threads), sizeof(double) * L1, st,
-                           (const double*)c, (long)F, L1, (const double*)A, L2, (double*)out);
-    else
-        return fail(DSA_ERR_UNSUPPORTED, "freqt: unsupported dtype%s");
-    return check_launch("freqt_fwd");
+    return with_dtype(dtype, "freqt", [&](auto tag) {
+        using T = decltype(tag);
+        if (matmul_rows_lds_launch<T, false>(c, F, L1, A, L1, L2, L2, out, st)) return check_launch("freqt_lds_fwd");
+        const int threads = L2 >= 192 ? 256 : (L2 >= 96 ? 128 : 64);
+        hipLaunchKernelGGL((matmul_rows_kernel<T>), dim3((unsigned)F), dim3(threads), sizeof(T) * L1, st, (const T*)c, (long)F, L1, (const T*)A, L2,
+                           (T*)out);
+        return check_launch("freqt_fwd");
+    });
 }
 
 DSA_EXPORT int dsa_freqt_bwd(const void* gout, int64_t F, int32_t L1, const void* A, int32_t L2, int32_t dtype,
@@ -379,19 +374,14 @@ DSA_EXPORT int dsa_freqt_bwd(const void* gout, int64_t F, int32_t L1, const void
     DSA_REQUIRE(L1 > 0 && L2 > 0 && F >= 0, "freqt_bwd: sizes must be positive");
     if (F == 0) return DSA_OK;
     hipStream_t st = (hipStream_t)stream;
-    if ((dtype == DSA_F32 && matmul_rows_lds_launch<float, true>(gout, F, L2, A, L1, L2, L1, gc, st)) ||
-        (dtype == DSA_F64 && matmul_rows_lds_launch<double, true>(gout, F, L2, A, L1, L2, L1, gc, st)))
-        return check_launch("freqt_lds_bwd");
-    int threads = L1 >= 192 ? 256 : (L1 >= 96 ? 128 : 64);
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((matmul_rows_t_kernel<float>), dim3((unsigned)F), dim3(threads), sizeof(float) * L2, st,
-                           (const float*)gout, (long)F, L1, (const float*)A, L2, (float*)gc);
-    else if (dtype == DSA_F64)
-        hipLaunchKernelGGL((matmul_rows_t_kernel<double>), dim3((unsigned)F), dim3(threads), sizeof(double) * L2, st,
-                           (const double*)gout, (long)F, L1, (const double*)A, L2, (double*)gc);
-    else
-        return fail(DSA_ERR_UNSUPPORTED, "freqt_bwd: unsupported dtype%s");
-    return check_launch("freqt_bwd");
+    return with_dtype(dtype, "freqt_bwd", [&](auto tag) {
+        using T = decltype(tag);
+        if (matmul_rows_lds_launch<T, true>(gout, F, L2, A, L1, L2, L1, gc, st)) return check_launch("freqt_lds_bwd");
+        const int threads = L1 >= 192 ? 256 : (L1 >= 96 ? 128 : 64);
+        hipLaunchKernelGGL((matmul_rows_t_kernel<T>), dim3((unsigned)F), dim3(threads), sizeof(T) * L2, st, (const T*)gout, (long)F, L1, (const T*)A,
+                           L2, (T*)gc);
+        return check_launch("freqt_bwd");
+    });
 }
 
 DSA_EXPORT int64_t dsa_mcep_images_bytes(int32_t nfft, int32_t M, int32_t dtype)
@@ -432,9 +422,9 @@ DSA_EXPORT int dsa_mcep_fwd(const void* X, int64_t F, int32_t nfft, int32_t M, i
     if (tuned_ok && algo != DSA_ALGO_GENERIC && images && scratch)
         return mcep_mfma_fwd(X, F, n_iter, G, D, E, alpha_vec, images, scratch, mc, mc_hist, st, scratch_clean, nullptr, hist_has_rt, overlapped,
                              reserve_cus, fixed_steps, full_chains);
-    if (dtype == DSA_F32) return mcep_generic_fwd<float>(X, F, nfft, M, n_iter, G, D, E, alpha_vec, mc, mc_hist, st);
-    if (dtype == DSA_F64) return mcep_generic_fwd<double>(X, F, nfft, M, n_iter, G, D, E, alpha_vec, mc, mc_hist, st);
-    return fail(DSA_ERR_UNSUPPORTED, "mcep: unsupported dtype%s");
+    return with_dtype(dtype, "mcep", [&](auto tag) {
+        return mcep_generic_fwd<decltype(tag)>(X, F, nfft, M, n_iter, G, D, E, alpha_vec, mc, mc_hist, st);
+    });
 }
 
 // (0.2.0) dsa_stft_mcep_fwd with the framing / spectrum options of dsa_stft_fwd the one launch covers: zmean, the pad mode, the relative
@@ -493,7 +483,7 @@ DSA_EXPORT int dsa_mcep_bwd(const void* gmc, const void* X, const void* mc_hist,
         return fail(DSA_ERR_INVALID_ARGUMENT, "mcep_bwd: the tuned kernel needs the prepared images (dsa_mcep_prepare) and a scratch buffer%s");
     if (tuned_ok && algo != DSA_ALGO_GENERIC && images && scratch)
         return mcep_mfma_bwd(gmc, X, mc_hist, F, n_iter, alpha_vec, images, scratch, gX, st, has_workspace, hist_has_rt);
-    if (dtype == DSA_F32) return mcep_generic_bwd<float>(gmc, X, mc_hist, F, nfft, M, n_iter, G, D, E, alpha_vec, gX, st);
-    if (dtype == DSA_F64) return mcep_generic_bwd<double>(gmc, X, mc_hist, F, nfft, M, n_iter, G, D, E, alpha_vec, gX, st);
-    return fail(DSA_ERR_UNSUPPORTED, "mcep_bwd: unsupported dtype%s");
+    return with_dtype(dtype, "mcep_bwd", [&](auto tag) {
+        return mcep_generic_bwd<decltype(tag)>(gmc, X, mc_hist, F, nfft, M, n_iter, G, D, E, alpha_vec, gX, st);
+    });
 }

@@ -6,6 +6,61 @@
 
 namespace dsa {
 
+namespace {
+
+// what every launch of mcep_big_newton passes on
+struct BigNewtonCall {
+    const float *logx, *mc_in, *av;
+    const _Float16* images;
+    float* mc_out;
+    int K, M1, n_iter, stagger;
+    hipStream_t st;
+};
+
+// the eight-wave kernel over the frames [f0, f0 + fc)
+template <int NTV, int NGV, int NMINV, bool QUADV, bool WIDEV>
+int big_newton_launch(const BigNewtonCall& c, long f0, long fc)
+{
+    constexpr int lds_b = mbg::lds_floats<2, NTV, NGV, QUADV, WIDEV>() * 4;
+    static_assert(lds_b <= 160 * 1024, "mcep_big_newton: LDS");
+    const long tiles = (fc + (WIDEV ? 127 : 63)) / (WIDEV ? 128 : 64);
+    const long grid = tiles < 256 ? tiles : 256;   // persistent: one eight-wave workgroup per CU (105 / 148 KB of LDS)
+    return launch_lds<mcep_big_newton_kernel<2, NTV, NGV, NMINV, QUADV, WIDEV>>(
+        lds_b, "mcep_big_newton: cannot reserve LDS%s", dim3((unsigned)grid), dim3(512), lds_b, c.st, c.logx + f0 * (long)c.K, fc, c.K,
+        c.mc_in + f0 * (long)c.M1, c.M1, c.images, c.av, c.n_iter, c.mc_out + f0 * (long)c.M1);
+}
+
+// the twin four-wave kernel over the frames [f0, f0 + fc)
+template <int NTV, int NGV, int NMINV, bool QUADV>
+int big_newton4_launch(const BigNewtonCall& c, long f0, long fc)
+{
+    constexpr int lds_b = mbg4::lds_floats<2, NTV, NGV, QUADV>() * 4;
+    static_assert(lds_b <= 80 * 1024, "mcep_big_newton: two workgroups per CU");
+    const long tiles = (fc + 63) / 64;
+    const long grid = tiles < 512 ? tiles : 512;   // persistent: two four-wave workgroups per CU
+    return launch_lds<mcep_big_newton4_kernel<2, NTV, NGV, NMINV, QUADV>>(
+        lds_b, "mcep_big_newton: cannot reserve LDS%s", dim3((unsigned)grid), dim3(256), lds_b, c.st, c.logx + f0 * (long)c.K, fc, c.K,
+        c.mc_in + f0 * (long)c.M1, c.M1, c.images, c.av, c.n_iter, c.mc_out + f0 * (long)c.M1, c.stagger);
+}
+
+// the plan's launches of one instantiation: wide tiles (quad layout: twin workgroups, when asked for) over the first F_wide frames, narrow
+// tiles over the rest
+template <int NTV, int NGV, int NMINV, bool QUADV>
+int big_newton_plan(const BigNewtonCall& c, long F_wide, long F, bool twin)
+{
+    int rc = DSA_OK;
+    if constexpr (QUADV) {
+        if (F_wide > 0 && twin) rc = big_newton4_launch<NTV, NGV, NMINV, true>(c, 0L, F_wide);
+        else if (F_wide > 0) rc = big_newton_launch<NTV, NGV, NMINV, true, true>(c, 0L, F_wide);
+    } else if (F_wide > 0) {
+        rc = big_newton_launch<NTV, NGV, NMINV, false, true>(c, 0L, F_wide);
+    }
+    if (rc == DSA_OK && F_wide < F) rc = big_newton_launch<NTV, NGV, NMINV, QUADV, false>(c, F_wide, F - F_wide);
+    return rc;
+}
+
+}  // namespace
+
 // mcep.py:208-222, all n_iter steps in one persistent launch, for orders 32 .. 54 (the 48 kHz set-ups fft_length 2048 / order 49 and
 // 1024 / order 34 among them); DSA_ERR_UNSUPPORTED (no error text) otherwise --
 // the caller then runs the step as two launches.  `images`: dsa_mcep_resid_prepare's.
@@ -54,60 +109,19 @@ int mcep_big_newton(const void* logx, int64_t F, int K, const void* mc_in, int M
     }
     const long F_wide = wide_rounds * FW < F ? wide_rounds * FW : (wide_rounds > 0 ? (long)F : 0);
     const int stagger = env_int("DSA_MCEP_BIG_STAGGER", 5);   // x ~8 k cycles (measured 4 .. 6 best: profiles/r06_mcep_big_twin.txt)
-#define DSA_BIG_NEWTON_1(NTV, NGV, NMINV, QUADV, WIDEV, F0, FC)                                                                         \
-    do {                                                                                                                                \
-        constexpr int lds_b = mbg::lds_floats<2, NTV, NGV, QUADV, WIDEV>() * 4;                                                         \
-        static_assert(lds_b <= 160 * 1024, "mcep_big_newton: LDS");                                                                     \
-        static std::atomic<uint64_t> attr{0};                                                                                           \
-        if (!ensure_dynamic_lds((const void*)mcep_big_newton_kernel<2, NTV, NGV, NMINV, QUADV, WIDEV>, lds_b, attr))                    \
-            return fail(DSA_ERR_LAUNCH, "mcep_big_newton: cannot reserve LDS%s");                                                       \
-        const long tiles_ = ((FC) + (WIDEV ? 127 : 63)) / (WIDEV ? 128 : 64);                                                           \
-        const long grid_ = tiles_ < 256 ? tiles_ : 256;   /* persistent: one eight-wave workgroup per CU (105 / 148 KB of LDS) */        \
-        hipLaunchKernelGGL((mcep_big_newton_kernel<2, NTV, NGV, NMINV, QUADV, WIDEV>), dim3((unsigned)grid_), dim3(512), lds_b, st,     \
-                           (const float*)logx + (F0) * (long)K, (long)(FC), K, (const float*)mc_in + (F0) * (long)M1, M1,               \
-                           (const _Float16*)images, (const float*)av, n_iter, (float*)mc_out + (F0) * (long)M1);                        \
-    } while (0)
-#define DSA_BIG_NEWTON4_1(NTV, NGV, NMINV, QUADV, F0, FC)                                                                               \
-    do {                                                                                                                                \
-        constexpr int lds_b = mbg4::lds_floats<2, NTV, NGV, QUADV>() * 4;                                                               \
-        static_assert(lds_b <= 80 * 1024, "mcep_big_newton: two workgroups per CU");                                                    \
-        static std::atomic<uint64_t> attr{0};                                                                                           \
-        if (!ensure_dynamic_lds((const void*)mcep_big_newton4_kernel<2, NTV, NGV, NMINV, QUADV>, lds_b, attr))                          \
-            return fail(DSA_ERR_LAUNCH, "mcep_big_newton: cannot reserve LDS%s");                                                       \
-        const long tiles_ = ((FC) + 63) / 64;                                                                                           \
-        const long grid_ = tiles_ < 512 ? tiles_ : 512;   /* persistent: two four-wave workgroups per CU */                             \
-        hipLaunchKernelGGL((mcep_big_newton4_kernel<2, NTV, NGV, NMINV, QUADV>), dim3((unsigned)grid_), dim3(256), lds_b, st,           \
-                           (const float*)logx + (F0) * (long)K, (long)(FC), K, (const float*)mc_in + (F0) * (long)M1, M1,               \
-                           (const _Float16*)images, (const float*)av, n_iter, (float*)mc_out + (F0) * (long)M1, stagger);               \
-    } while (0)
-#define DSA_BIG_NEWTON_Q(NTV, NGV, NMINV)                                                                                               \
-    do {                                                                                                                                \
-        if (F_wide > 0 && twin) DSA_BIG_NEWTON4_1(NTV, NGV, NMINV, true, 0L, F_wide);                                                   \
-        else if (F_wide > 0) DSA_BIG_NEWTON_1(NTV, NGV, NMINV, true, true, 0L, F_wide);                                                 \
-        if (F_wide < (long)F) DSA_BIG_NEWTON_1(NTV, NGV, NMINV, true, false, F_wide, (long)F - F_wide);                                 \
-    } while (0)
-#define DSA_BIG_NEWTON(NTV, NGV, NMINV, QUADV)                                                                                          \
-    do {                                                                                                                                \
-        if (F_wide > 0) DSA_BIG_NEWTON_1(NTV, NGV, NMINV, QUADV, true, 0L, F_wide);                                                     \
-        if (F_wide < (long)F) DSA_BIG_NEWTON_1(NTV, NGV, NMINV, QUADV, false, F_wide, (long)F - F_wide);                                \
-    } while (0)
+    const BigNewtonCall call{(const float*)logx, (const float*)mc_in, (const float*)av, (const _Float16*)images, (float*)mc_out, K, M1, n_iter, stagger,
+                             st};
     // (M1 = order + 1; the solver's instantiations as thsolve_quadn_fwd picks them: quad <9,28> up to 35, <11,36> up to 43, <13,44> up to
     //  51, <14,52>)
-    if (quad) {
-        DSA_BIG_NEWTON_Q(5, 9, 28);
-    } else if (M1 <= 43) {
-        if (nt == 5) DSA_BIG_NEWTON(5, 11, 36, false);
-        else DSA_BIG_NEWTON(6, 11, 36, false);
-    } else if (M1 <= 51) {
-        if (nt == 6) DSA_BIG_NEWTON(6, 13, 44, false);
-        else DSA_BIG_NEWTON(7, 13, 44, false);
-    } else {
-        DSA_BIG_NEWTON(7, 14, 52, false);
-    }
-#undef DSA_BIG_NEWTON
-#undef DSA_BIG_NEWTON_Q
-#undef DSA_BIG_NEWTON_1
-#undef DSA_BIG_NEWTON4_1
+    const long Fn = (long)F;
+    int rc;
+    if (quad) rc = big_newton_plan<5, 9, 28, true>(call, F_wide, Fn, twin);
+    else if (M1 <= 43 && nt == 5) rc = big_newton_plan<5, 11, 36, false>(call, F_wide, Fn, false);
+    else if (M1 <= 43) rc = big_newton_plan<6, 11, 36, false>(call, F_wide, Fn, false);
+    else if (M1 <= 51 && nt == 6) rc = big_newton_plan<6, 13, 44, false>(call, F_wide, Fn, false);
+    else if (M1 <= 51) rc = big_newton_plan<7, 13, 44, false>(call, F_wide, Fn, false);
+    else rc = big_newton_plan<7, 14, 52, false>(call, F_wide, Fn, false);
+    if (rc) return rc;
     return check_launch("mcep_big_newton");
 }
 

@@ -41,18 +41,6 @@ int mcep_mfma_prepare(const void* G, const void* D, const void* E, void* images,
     return check_launch("mcep_prepare");
 }
 
-// One instantiation of the forward kernel: its dynamic LDS reserved (once per device the process drives), the launch, its record.
-// HIST_RT and PADM (reflect / replicate / circular padding, zmean, relative floor) are instantiations of their own.
-template <int WAVES, bool FUSED, bool HIST_RT, bool PADM, typename... Args>
-static int mcep_mfma_fwd_launch(long grid, int lds_bytes, hipStream_t st, Args... args)
-{
-    static std::atomic<uint64_t> attr_devices{0};
-    if (!ensure_dynamic_lds((const void*)mcep_mfma_fwd_kernel_h<WAVES, FUSED, HIST_RT, PADM>, lds_bytes, attr_devices))
-        return fail(DSA_ERR_LAUNCH, "mcep_mfma: cannot reserve the LDS operand images%s");
-    hipLaunchKernelGGL((mcep_mfma_fwd_kernel_h<WAVES, FUSED, HIST_RT, PADM>), dim3((unsigned)grid), dim3(WAVES * 64), lds_bytes, st, args...);
-    return check_launch(FUSED ? "stft512_mcep_fused_fwd" : "mcep_mfma_fwd");
-}
-
 // `sti`: NULL (spectra in X) or the waveform side of the fused STFT -> mel-cepstrum launch (X is then unused)
 int mcep_mfma_fwd(const void* X, int64_t F, int n_iter, const void* G, const void* D, const void* E, const void* av,
                   const void* images, void* scratch, void* mc, void* hist, hipStream_t st, bool scratch_clean, const StftIn* sti,
@@ -107,11 +95,14 @@ int mcep_mfma_fwd(const void* X, int64_t F, int n_iter, const void* G, const voi
     // DSA_MCEP_FULL_CHAINS=1 in the environment: none -- every step on three-term chains, the arithmetic of versions before 0.3.8.
     const bool three_terms = full_chains || env_int("DSA_MCEP_FULL_CHAINS", 0) != 0;
     const int n_coarse = three_terms ? 0 : (n_iter - 6 < 0 ? 0 : n_iter - 6 > 2 ? 2 : n_iter - 6);
+    // HIST_RT and PADM (reflect / replicate / circular padding, zmean, relative floor) are instantiations of their own
     auto launch = [&](auto fused, auto with_rt, auto options) {
-        return mcep_mfma_fwd_launch<WAVES, fused(), with_rt(), options()>(
-            grid, lds_bytes, st, sti ? nullptr : (const float*)X, (long)F, n_iter, (const float*)G, (const float*)D, (const float*)E,
-            (const float*)av, (float*)mc, (float*)hist, ntiles16, tiles_shared, queue, (const _Float16*)images, sti ? *sti : StftIn{},
-            hist_rt, tail_wgs, tau, n_coarse);
+        if (int rc = launch_lds<mcep_mfma_fwd_kernel_h<WAVES, fused(), with_rt(), options()>>(
+                lds_bytes, "mcep_mfma: cannot reserve the LDS operand images%s", dim3((unsigned)grid), dim3(WAVES * 64), lds_bytes, st,
+                sti ? nullptr : (const float*)X, (long)F, n_iter, (const float*)G, (const float*)D, (const float*)E, (const float*)av, (float*)mc,
+                (float*)hist, ntiles16, tiles_shared, queue, (const _Float16*)images, sti ? *sti : StftIn{}, hist_rt, tail_wgs, tau, n_coarse))
+            return rc;
+        return check_launch(fused() ? "stft512_mcep_fused_fwd" : "mcep_mfma_fwd");
     };
     constexpr std::true_type yes{};
     constexpr std::false_type no{};

@@ -17,17 +17,6 @@ void mcep_mfma_bwd_prepare_launch(const void* G, const void* D, const void* E, v
                        (const float*)G, (const float*)D, (const float*)E, (_Float16*)images);
 }
 
-// One instantiation of the one-wave-per-SIMD kernel: its dynamic LDS reserved (once per device), the launch, its record
-template <bool SAVED_RT, typename... Args>
-static int mcep_mfma_bwd_launch(long grid, int lds_bytes, hipStream_t st, Args... args)
-{
-    static std::atomic<uint64_t> attr_devices{0};
-    if (!ensure_dynamic_lds((const void*)mcep_mfma_bwd_kernel_h<SAVED_RT>, lds_bytes, attr_devices))
-        return fail(DSA_ERR_LAUNCH, "mcep_mfma_bwd: cannot reserve the LDS operand images%s");
-    hipLaunchKernelGGL(mcep_mfma_bwd_kernel_h<SAVED_RT>, dim3((unsigned)grid), dim3(256), lds_bytes, st, args...);
-    return check_launch("mcep_mfma_bwd");
-}
-
 int mcep_mfma_bwd(const void* gmc, const void* X, const void* hist, int64_t F, int n_iter, const void* av,
                   const void* images, void* scratch, void* gX, hipStream_t st, bool has_workspace, bool hist_has_rt)
 {
@@ -53,21 +42,22 @@ int mcep_mfma_bwd(const void* gmc, const void* X, const void* hist, int64_t F, i
         split_tiles = (int)rest;
         split_pieces = (int)pieces;
     }
+    const char* lds_error = "mcep_mfma_bwd: cannot reserve the LDS operand images%s";
     if (two) {
-        static std::atomic<uint64_t> attr_two{0};
-        if (!ensure_dynamic_lds((const void*)mcep_mfma_bwd2_kernel_h, lds_bytes, attr_two))
-            return fail(DSA_ERR_LAUNCH, "mcep_mfma_bwd: cannot reserve the LDS operand images%s");
-        hipLaunchKernelGGL(mcep_mfma_bwd2_kernel_h, dim3((unsigned)grid), dim3(waves * 64), lds_bytes, st, (const float*)gmc,
-                           (const float*)X, (const float*)hist, (long)F, n_iter, (const float*)av, (float*)gX, ntiles16, queue,
-                           (const _Float16*)images, hist_rt);
+        if (int rc = launch_lds<mcep_mfma_bwd2_kernel_h>(lds_bytes, lds_error, dim3((unsigned)grid), dim3(waves * 64), lds_bytes, st, (const float*)gmc,
+                                                         (const float*)X, (const float*)hist, (long)F, n_iter, (const float*)av, (float*)gX, ntiles16,
+                                                         queue, (const _Float16*)images, hist_rt))
+            return rc;
         return check_launch("mcep_mfma_bwd2");
     }
-    auto launch = [&](auto saved_rt) {
-        return mcep_mfma_bwd_launch<saved_rt()>(grid, lds_bytes, st, (const float*)gmc, (const float*)X, (const float*)hist, (long)F, n_iter,
-                                                (const float*)av, (float*)gX, ntiles16, queue, (const _Float16*)images, split_tiles, split_pieces,
-                                                reinterpret_cast<float*>(static_cast<char*>(scratch) + DSA_SCRATCH_BYTES), hist_rt);
+    auto launch = [&](auto saved_rt) {   // the one-wave-per-SIMD kernel, with or without the forward's rt rows
+        return launch_lds<mcep_mfma_bwd_kernel_h<saved_rt()>>(lds_bytes, lds_error, dim3((unsigned)grid), dim3(256), lds_bytes, st, (const float*)gmc,
+                                                              (const float*)X, (const float*)hist, (long)F, n_iter, (const float*)av, (float*)gX,
+                                                              ntiles16, queue, (const _Float16*)images, split_tiles, split_pieces,
+                                                              reinterpret_cast<float*>(static_cast<char*>(scratch) + DSA_SCRATCH_BYTES), hist_rt);
     };
-    return hist_rt ? launch(std::true_type{}) : launch(std::false_type{});
+    if (int rc = hist_rt ? launch(std::true_type{}) : launch(std::false_type{})) return rc;
+    return check_launch("mcep_mfma_bwd");
 }
 
 }  // namespace dsa

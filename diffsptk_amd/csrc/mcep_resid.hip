@@ -70,26 +70,17 @@ int mcep_resid_bwd_h(const void* logx, int64_t F, int K, const void* mc, int M1,
     const int ks1 = (M1 + 31) / 32, kse = mrb::kse_of(M1), nt3 = mrb::nt3_of(M1), N = 2 * M1 - 1;
     if (!(ks1 == 2 && M1 >= 33 && M1 <= 55 && K >= 4)) return DSA_ERR_UNSUPPORTED;
     const dim3 grid((unsigned)((F + 63) / 64));
-#define DSA_RESID_BWD(KSEV, NT3V)                                                                                                         \
-    do {                                                                                                                                  \
-        constexpr int lds_b = 2 * mrb::stage_halves_b(2, KSEV, NT3V) * 2;                                                                 \
-        static std::atomic<uint64_t> attr{0}, attr0{0};                                                                                   \
-        if (glogx) {                                                                                                                      \
-            if (!ensure_dynamic_lds((const void*)mcep_resid_bwd_h_kernel<2, KSEV, NT3V, true>, lds_b, attr))                              \
-                return fail(DSA_ERR_LAUNCH, "mcep_resid_bwd_h: cannot reserve LDS%s");                                                    \
-            hipLaunchKernelGGL((mcep_resid_bwd_h_kernel<2, KSEV, NT3V, true>), grid, dim3(256), lds_b, st, (const float*)logx, (long)F, K, \
-                               (const float*)mc, M1, (const float*)grt, N, (const _Float16*)images, (float*)glogx, (float*)gmc);          \
-        } else {                                                                                                                          \
-            if (!ensure_dynamic_lds((const void*)mcep_resid_bwd_h_kernel<2, KSEV, NT3V, false>, lds_b, attr0))                            \
-                return fail(DSA_ERR_LAUNCH, "mcep_resid_bwd_h: cannot reserve LDS%s");                                                    \
-            hipLaunchKernelGGL((mcep_resid_bwd_h_kernel<2, KSEV, NT3V, false>), grid, dim3(256), lds_b, st, (const float*)logx, (long)F, K, \
-                               (const float*)mc, M1, (const float*)grt, N, (const _Float16*)images, (float*)nullptr, (float*)gmc);        \
-        }                                                                                                                                 \
-    } while (0)
+    auto launch = [&](auto kse_, auto with_glogx) {   // (the kernel's NT3 is its KSE at every order served; without glogx: a null pointer)
+        constexpr int KSEV = decltype(kse_)::value;
+        constexpr int lds_b = 2 * mrb::stage_halves_b(2, KSEV, KSEV) * 2;
+        return launch_lds<mcep_resid_bwd_h_kernel<2, KSEV, KSEV, decltype(with_glogx)::value>>(
+            lds_b, "mcep_resid_bwd_h: cannot reserve LDS%s", grid, dim3(256), lds_b, st, (const float*)logx, (long)F, K, (const float*)mc, M1,
+            (const float*)grt, N, (const _Float16*)images, (float*)glogx, (float*)gmc);
+    };
+    auto by_glogx = [&](auto kse_) { return glogx ? launch(kse_, std::true_type{}) : launch(kse_, std::false_type{}); };
     (void)nt3;
-    if (kse == 3) DSA_RESID_BWD(3, 3);   // M1 33 .. 48: N = 2 M1 - 1 <= 95 columns of rt, three tiles of coefficients
-    else DSA_RESID_BWD(4, 4);            // M1 49 .. 55
-#undef DSA_RESID_BWD
+    // M1 33 .. 48: N = 2 M1 - 1 <= 95 columns of rt, three tiles of coefficients; M1 49 .. 55: four
+    if (int rc = kse == 3 ? by_glogx(int_c<3>{}) : by_glogx(int_c<4>{})) return rc;
     return check_launch("mcep_resid_bwd_h");
 }
 
@@ -105,17 +96,13 @@ int mcep_glogx_h(const void* logx, int64_t F, int K, const void* mcs, int M1, co
     if ((long)n_iter * mgx::step_bytes(2, kse) > mgx::kMaxLds) return DSA_ERR_UNSUPPORTED;
     const dim3 grid((unsigned)((F + 15) / 16));
     const int lds_b = n_iter * mgx::step_bytes(2, kse);
-#define DSA_GLOGX(KSEV, NT3V)                                                                                                             \
-    do {                                                                                                                                  \
-        static std::atomic<uint64_t> attr{0};                                                                                             \
-        if (!ensure_dynamic_lds((const void*)mcep_glogx_h_kernel<2, KSEV, NT3V>, mgx::kMaxLds, attr))                                     \
-            return fail(DSA_ERR_LAUNCH, "mcep_glogx_h: cannot reserve LDS%s");                                                            \
-        hipLaunchKernelGGL((mcep_glogx_h_kernel<2, KSEV, NT3V>), grid, dim3(512), lds_b, st, (const float*)logx, (long)F, K,              \
-                           (const float*)mcs, M1, (const float*)grts, N, n_iter, (const _Float16*)images, (float*)glogx);                 \
-    } while (0)
-    if (kse == 3) DSA_GLOGX(3, 3);
-    else DSA_GLOGX(4, 4);
-#undef DSA_GLOGX
+    auto launch = [&](auto kse_) {
+        constexpr int KSEV = decltype(kse_)::value;
+        return launch_lds<mcep_glogx_h_kernel<2, KSEV, KSEV>>(mgx::kMaxLds, "mcep_glogx_h: cannot reserve LDS%s", grid, dim3(512), lds_b, st,
+                                                              (const float*)logx, (long)F, K, (const float*)mcs, M1, (const float*)grts, N, n_iter,
+                                                              (const _Float16*)images, (float*)glogx);
+    };
+    if (int rc = kse == 3 ? launch(int_c<3>{}) : launch(int_c<4>{})) return rc;
     return check_launch("mcep_glogx_h");
 }
 

@@ -353,13 +353,12 @@ DSA_EXPORT int dsa_mdct_analysis(const void* x, int64_t B, int64_t T, int64_t N,
     const int64_t tiles = (N + MD_FG - 1) / MD_FG;
     if (tiles > INT32_MAX / B) return fail(DSA_ERR_INVALID_ARGUMENT, "mdct analysis: too many tiles for one launch");
     const dim3 grid((unsigned)(B * tiles));
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((mdct_analysis_generic<float>), grid, dim3(MD_THREADS), 0, st, (const float*)x, (long)T, (long)N, P, (long)tiles,
-                           (const float*)w, (const float*)basis, overlap, (float*)y);
-    else
-        hipLaunchKernelGGL((mdct_analysis_generic<double>), grid, dim3(MD_THREADS), 0, st, (const double*)x, (long)T, (long)N, P, (long)tiles,
-                           (const double*)w, (const double*)basis, overlap, (double*)y);
-    return check_launch("mdct_analysis_generic");
+    return with_dtype(dtype, "mdct analysis", [&](auto tag) {
+        using V = decltype(tag);   // (T is the entry's waveform length)
+        hipLaunchKernelGGL((mdct_analysis_generic<V>), grid, dim3(MD_THREADS), 0, st, (const V*)x, (long)T, (long)N, P, (long)tiles, (const V*)w,
+                           (const V*)basis, overlap, (V*)y);
+        return check_launch("mdct_analysis_generic");
+    });
 }
 
 DSA_EXPORT int dsa_mdct_synthesis(const void* y, int64_t B, int64_t N, int32_t L, const void* w, const void* basis_t, const void* twiddle, double z,
@@ -385,11 +384,10 @@ DSA_EXPORT int dsa_mdct_synthesis(const void* y, int64_t B, int64_t N, int32_t L
     const int64_t tiles = (T + MD_THREADS - 1) / MD_THREADS;
     if (tiles > INT32_MAX / B) return fail(DSA_ERR_INVALID_ARGUMENT, "mdct synthesis: too many tiles for one launch");
     const dim3 grid((unsigned)(B * tiles));
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((mdct_synthesis_generic<float>), grid, dim3(MD_THREADS), 0, st, (const float*)y, (long)N, P, (long)tiles, (const float*)w,
-                           (const float*)basis_t, overlap, (long)T, (float*)x);
-    else
-        hipLaunchKernelGGL((mdct_synthesis_generic<double>), grid, dim3(MD_THREADS), 0, st, (const double*)y, (long)N, P, (long)tiles,
-                           (const double*)w, (const double*)basis_t, overlap, (long)T, (double*)x);
-    return check_launch("mdct_synthesis_generic");
+    return with_dtype(dtype, "mdct synthesis", [&](auto tag) {
+        using V = decltype(tag);   // (T is the entry's waveform length)
+        hipLaunchKernelGGL((mdct_synthesis_generic<V>), grid, dim3(MD_THREADS), 0, st, (const V*)y, (long)N, P, (long)tiles, (const V*)w,
+                           (const V*)basis_t, overlap, (long)T, (V*)x);
+        return check_launch("mdct_synthesis_generic");
+    });
 }

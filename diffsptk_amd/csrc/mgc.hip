@@ -599,13 +599,12 @@ static int gc2gc_launch(const void* c1, int64_t F, int n_in, int out_order, doub
                         void* c2, hipStream_t st)
 {
     const size_t lds = sizeof(T) * (3 * (size_t)(nfft / 2) + 1);
-    static std::atomic<uint64_t> lds_set{0};
-    if (lds > 48 * 1024 && !ensure_dynamic_lds(reinterpret_cast<const void*>(&gc2gc_fused_kernel<T>), 150 * 1024, lds_set))
-        return fail(DSA_ERR_LAUNCH, "gc2gc: cannot raise the dynamic LDS limit%s");
     // short transforms: one wave per row (two butterflies per lane and pass, the passes' barriers are single-wave barriers)
     const int block = nfft <= 1024 ? 64 : 256;
-    hipLaunchKernelGGL((gc2gc_fused_kernel<T>), dim3((unsigned)F), dim3(block), lds, st, (const T*)c1, n_in, out_order, (T)g1, (T)g2, nfft,
-                       (const T*)tw, flags, (T*)c2);
+    if (int rc = launch_lds<gc2gc_fused_kernel<T>>(lds > 48 * 1024 ? 150 * 1024 : 0, "gc2gc: cannot raise the dynamic LDS limit%s", dim3((unsigned)F),
+                                                   dim3(block), lds, st, (const T*)c1, n_in, out_order, (T)g1, (T)g2, nfft, (const T*)tw, flags,
+                                                   (T*)c2))
+        return rc;
     return check_launch("gc2gc_fused");
 }
 
@@ -676,14 +675,12 @@ DSA_EXPORT int dsa_gnorm_fwd(const void* x, int64_t F, int32_t n, double gamma, 
     DSA_REQUIRE(gamma >= -1 && gamma <= 1, "gnorm: gamma must be in [-1, 1]");
     if (F == 0) return DSA_OK;
     const dim3 grid((unsigned)((F * n + 255) / 256));
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL(dsa::gnorm_rows_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)x, (long)F, (int)n,
-                           (float)gamma, (int)inverse, (float*)out);
-    else if (dtype == DSA_F64)
-        hipLaunchKernelGGL(dsa::gnorm_rows_kernel<double>, grid, dim3(256), 0, (hipStream_t)stream, (const double*)x, (long)F, (int)n, gamma,
-                           (int)inverse, (double*)out);
-    else return dsa::fail(DSA_ERR_UNSUPPORTED, "gnorm: unsupported dtype%s");
-    return dsa::check_launch(inverse ? "ignorm_fwd" : "gnorm_fwd");
+    return with_dtype(dtype, "gnorm", [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(dsa::gnorm_rows_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, (const T*)x, (long)F, (int)n, (T)gamma, (int)inverse,
+                           (T*)out);
+        return check_launch(inverse ? "ignorm_fwd" : "gnorm_fwd");
+    });
 }
 
 DSA_EXPORT int dsa_mgcep_gain(const void* r, const void* b_eps, const void* b_join, int64_t F, int32_t M, double gamma, int32_t dtype,
@@ -692,14 +689,12 @@ DSA_EXPORT int dsa_mgcep_gain(const void* r, const void* b_eps, const void* b_jo
     DSA_REQUIRE(F >= 0 && M >= 1 && (F == 0 || (r && b_eps && b_join && b)), "mgcep_gain: invalid arguments");
     if (F == 0) return DSA_OK;
     const dim3 grid((unsigned)((F + 3) / 4));
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL(dsa::mgcep_gain_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)r, (const float*)b_eps,
-                           (const float*)b_join, (long)F, (int)M, (float)gamma, (float*)b);
-    else if (dtype == DSA_F64)
-        hipLaunchKernelGGL(dsa::mgcep_gain_kernel<double>, grid, dim3(256), 0, (hipStream_t)stream, (const double*)r, (const double*)b_eps,
-                           (const double*)b_join, (long)F, (int)M, gamma, (double*)b);
-    else return dsa::fail(DSA_ERR_UNSUPPORTED, "mgcep_gain: unsupported dtype%s");
-    return dsa::check_launch("mgcep_gain");
+    return with_dtype(dtype, "mgcep_gain", [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(dsa::mgcep_gain_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, (const T*)r, (const T*)b_eps, (const T*)b_join, (long)F,
+                           (int)M, (T)gamma, (T*)b);
+        return check_launch("mgcep_gain");
+    });
 }
 
 DSA_EXPORT int dsa_mgcep_step(const void* x, const void* b1, int64_t F, int32_t fft_length, int32_t M, double gamma, const void* images,
@@ -764,9 +759,7 @@ DSA_EXPORT int dsa_mgcep_spectra(const void* x, const void* b1, int64_t F, int32
     if (F == 0) return DSA_OK;
     hipStream_t st = (hipStream_t)stream;
     const int K = fft_length / 2 + 1;
-    if (dtype == DSA_F32) return mgcep_spectra_launch<float>(x, b1, F, K, M, Cr, Ci, gamma, out, st);
-    if (dtype == DSA_F64) return mgcep_spectra_launch<double>(x, b1, F, K, M, Cr, Ci, gamma, out, st);
-    return fail(DSA_ERR_UNSUPPORTED, "mgcep_spectra: unsupported dtype%s");
+    return with_dtype(dtype, "mgcep_spectra", [&](auto tag) { return mgcep_spectra_launch<decltype(tag)>(x, b1, F, K, M, Cr, Ci, gamma, out, st); });
 }
 
 DSA_EXPORT int dsa_gc2gc_fwd(const void* c1, int64_t F, int32_t n_in, int32_t out_order, double in_gamma, double out_gamma,
@@ -792,23 +785,16 @@ DSA_EXPORT int dsa_gc2gc_bwd(const void* c1, const void* g2, int64_t F, int32_t 
     if (F == 0) return DSA_OK;
     hipStream_t st = (hipStream_t)stream;
     const int block = nfft <= 1024 ? 64 : 256;
-    if (dtype == DSA_F32 && (size_t)nfft * 10 + 64 <= 150 * 1024) {
-        const size_t lds = sizeof(float) * (5 * (size_t)(nfft / 2) + 3);
-        static std::atomic<uint64_t> lds_set{0};
-        if (lds > 48 * 1024 && !ensure_dynamic_lds(reinterpret_cast<const void*>(&gc2gc_fused_bwd_kernel<float>), 150 * 1024, lds_set))
-            return fail(DSA_ERR_LAUNCH, "gc2gc_bwd: cannot raise the dynamic LDS limit%s");
-        hipLaunchKernelGGL((gc2gc_fused_bwd_kernel<float>), dim3((unsigned)F), dim3(block), lds, st, (const float*)c1, (const float*)g2,
-                           n_in, out_order, (float)in_gamma, (float)out_gamma, nfft, (const float*)twiddle, (float*)gc1);
+    auto launch = [&](auto tag) {
+        using T = decltype(tag);
+        const size_t lds = sizeof(T) * (5 * (size_t)(nfft / 2) + 3);
+        if (int rc = launch_lds<gc2gc_fused_bwd_kernel<T>>(lds > 48 * 1024 ? 150 * 1024 : 0, "gc2gc_bwd: cannot raise the dynamic LDS limit%s",
+                                                           dim3((unsigned)F), dim3(block), lds, st, (const T*)c1, (const T*)g2, n_in, out_order,
+                                                           (T)in_gamma, (T)out_gamma, nfft, (const T*)twiddle, (T*)gc1))
+            return rc;
         return check_launch("gc2gc_fused_bwd");
-    }
-    if (dtype == DSA_F64 && (size_t)nfft * 20 + 64 <= 150 * 1024) {
-        const size_t lds = sizeof(double) * (5 * (size_t)(nfft / 2) + 3);
-        static std::atomic<uint64_t> lds_set{0};
-        if (lds > 48 * 1024 && !ensure_dynamic_lds(reinterpret_cast<const void*>(&gc2gc_fused_bwd_kernel<double>), 150 * 1024, lds_set))
-            return fail(DSA_ERR_LAUNCH, "gc2gc_bwd: cannot raise the dynamic LDS limit%s");
-        hipLaunchKernelGGL((gc2gc_fused_bwd_kernel<double>), dim3((unsigned)F), dim3(block), lds, st, (const double*)c1, (const double*)g2,
-                           n_in, out_order, in_gamma, out_gamma, nfft, (const double*)twiddle, (double*)gc1);
-        return check_launch("gc2gc_fused_bwd");
-    }
+    };
+    if (dtype == DSA_F32 && (size_t)nfft * 10 + 64 <= 150 * 1024) return launch(float{});
+    if (dtype == DSA_F64 && (size_t)nfft * 20 + 64 <= 150 * 1024) return launch(double{});
     return fail(DSA_ERR_UNSUPPORTED, "gc2gc_bwd: unsupported dtype or n_fft too long for LDS%s");
 }

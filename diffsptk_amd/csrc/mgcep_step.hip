@@ -126,15 +126,14 @@ int mgcep_step_bwd_h(const void* x, const void* b1, const void* gpt, const void*
                      const void* images, const void* gx_in, void* gx, void* gb1, hipStream_t st)
 {
     const int lds_bytes = 2 * mgh::BW_STAGE_HALVES * 2;
-    static std::atomic<uint64_t> attr{0};
-    if (!ensure_dynamic_lds((const void*)mgcep_step_bwd_h_kernel, lds_bytes, attr))
-        return fail(DSA_ERR_LAUNCH, "mgcep_step_bwd_h: cannot reserve the LDS stage buffers%s");
     const long ntiles = (long)((F + 15) / 16);
     long blocks = (ntiles + mgh::WAVES - 1) / mgh::WAVES;
     if (blocks > 256) blocks = 256;
-    hipLaunchKernelGGL(mgcep_step_bwd_h_kernel, dim3((unsigned)blocks), dim3(mgh::WAVES * 64), lds_bytes, st, (const float*)x, (const float*)b1,
-                       (const float*)gpt, (const float*)gqt, (const float*)gr, (long)F, (float)gamma, (const _Float16*)images,
-                       (const float*)gx_in, (float*)gx, (float*)gb1);
+    if (int rc = launch_lds<mgcep_step_bwd_h_kernel>(lds_bytes, "mgcep_step_bwd_h: cannot reserve the LDS stage buffers%s", dim3((unsigned)blocks),
+                                                     dim3(mgh::WAVES * 64), lds_bytes, st, (const float*)x, (const float*)b1, (const float*)gpt,
+                                                     (const float*)gqt, (const float*)gr, (long)F, (float)gamma, (const _Float16*)images,
+                                                     (const float*)gx_in, (float*)gx, (float*)gb1))
+        return rc;
     return check_launch("mgcep_step_bwd_h");
 }
 
@@ -142,14 +141,14 @@ int mgcep_step_solve_fwd(const void* x, const void* b1, int64_t F, double gamma,
                          void* pt_out, void* qt_out, int n_steps, void* b1_prev_out)
 {
     const int lds_bytes = mgh::LDS_FLOATS * 4;
-    static std::atomic<uint64_t> attr{0};
-    if (!ensure_dynamic_lds((const void*)mgcep_step_h_kernel, lds_bytes, attr))
-        return fail(DSA_ERR_LAUNCH, "mgcep_step_solve: cannot reserve the LDS stage buffers%s");
     const long ntiles = (long)((F + 15) / 16);
     long blocks = (ntiles + mgh::WAVES - 1) / mgh::WAVES;
     if (blocks > 256) blocks = 256;
-    hipLaunchKernelGGL(mgcep_step_h_kernel, dim3((unsigned)blocks), dim3(mgh::WAVES * 64), lds_bytes, st, (const float*)x, (const float*)b1,
-                       (long)F, (float)gamma, (const _Float16*)images, (float*)b1_out, (float*)r_out, (float*)pt_out, (float*)qt_out, n_steps, (float*)b1_prev_out);
+    if (int rc = launch_lds<mgcep_step_h_kernel>(lds_bytes, "mgcep_step_solve: cannot reserve the LDS stage buffers%s", dim3((unsigned)blocks),
+                                                 dim3(mgh::WAVES * 64), lds_bytes, st, (const float*)x, (const float*)b1, (long)F, (float)gamma,
+                                                 (const _Float16*)images, (float*)b1_out, (float*)r_out, (float*)pt_out, (float*)qt_out, n_steps,
+                                                 (float*)b1_prev_out))
+        return rc;
     return check_launch("mgcep_step_solve");
 }
 

@@ -450,12 +450,10 @@ int mlsacheck_generic_launch(const void* gout, const void* mc, int64_t F, int M,
     const int64_t K = mode == DSA_MLSACHECK_FAST ? 1 : n_fft / 2 + 1;
     const int64_t lds = (((int64_t)M + 1) * (BWD ? 3 : 2) + 2 * K) * (int64_t)sizeof(double);
     if (lds > MC_MAX_LDS) return fail(DSA_ERR_UNSUPPORTED, "%s: the row and the bins do not fit the LDS", name);
-    static std::atomic<uint64_t> attr{0};
-    if (!ensure_dynamic_lds(reinterpret_cast<const void*>(&mlsacheck_generic_kernel<T, BWD>), MC_MAX_LDS, attr))
-        return fail(DSA_ERR_LAUNCH, "%s: cannot reserve LDS", name);
     const dim3 grid((unsigned)(F < (1 << 16) ? F : (1 << 16)));
-    hipLaunchKernelGGL((mlsacheck_generic_kernel<T, BWD>), grid, dim3(64), (size_t)lds, st, (const T*)gout, (const T*)mc, (long)F, M, alpha, thr,
-                       mode, n_fft, (T*)out, (int*)unstable);
+    if (launch_lds<mlsacheck_generic_kernel<T, BWD>>(MC_MAX_LDS, "%s: cannot reserve LDS", grid, dim3(64), (size_t)lds, st, (const T*)gout, (const T*)mc,
+                                                     (long)F, M, alpha, thr, mode, n_fft, (T*)out, (int*)unstable))
+        return fail(DSA_ERR_LAUNCH, "%s: cannot reserve LDS", name);   // (the message again, with the name in it)
     return check_launch(name);
 }
 
@@ -480,8 +478,9 @@ int mlsacheck_launch(const void* gout, const void* mc, int64_t F, int32_t M, dou
                            mode, (float*)out, (int*)unstable);
         return check_launch(BWD ? "mlsacheck_tuned_bwd" : "mlsacheck_tuned_fwd");
     }
-    if (dtype == DSA_F32) return mlsacheck_generic_launch<float, BWD>(gout, mc, F, M, alpha, thr, mode, n_fft, out, unstable, st);
-    return mlsacheck_generic_launch<double, BWD>(gout, mc, F, M, alpha, thr, mode, n_fft, out, unstable, st);
+    return with_dtype(dtype, what, [&](auto tag) {
+        return mlsacheck_generic_launch<decltype(tag), BWD>(gout, mc, F, M, alpha, thr, mode, n_fft, out, unstable, st);
+    });
 }
 
 }  // namespace

@@ -440,22 +440,16 @@ static int delta_entry(bool bwd, const void* in, int64_t B, int64_t T, int64_t D
     unsigned grid;
     if (!pg_grid(n, PG_THREADS, grid)) return fail(DSA_ERR_INVALID_ARGUMENT, "delta: too many elements for one launch");
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == DSA_F32) {
+    return with_dtype(dtype, "delta", [&](auto tag) {
+        using V = decltype(tag);   // (T is the entry's sequence length)
         if (bwd)
-            hipLaunchKernelGGL((delta_bwd_kernel<float>), dim3(grid), dim3(PG_THREADS), 0, st, (const float*)in, n, (long)T, (long)D,
-                               (const float*)window, H, L, (float*)out);
+            hipLaunchKernelGGL((delta_bwd_kernel<V>), dim3(grid), dim3(PG_THREADS), 0, st, (const V*)in, n, (long)T, (long)D, (const V*)window, H, L,
+                               (V*)out);
         else
-            hipLaunchKernelGGL((delta_fwd_kernel<float>), dim3(grid), dim3(PG_THREADS), 0, st, (const float*)in, n, (long)T, (long)D,
-                               (const float*)window, H, L, (float*)out);
-    } else {
-        if (bwd)
-            hipLaunchKernelGGL((delta_bwd_kernel<double>), dim3(grid), dim3(PG_THREADS), 0, st, (const double*)in, n, (long)T, (long)D,
-                               (const double*)window, H, L, (double*)out);
-        else
-            hipLaunchKernelGGL((delta_fwd_kernel<double>), dim3(grid), dim3(PG_THREADS), 0, st, (const double*)in, n, (long)T, (long)D,
-                               (const double*)window, H, L, (double*)out);
-    }
-    return check_launch(bwd ? "delta_bwd" : "delta_fwd");
+            hipLaunchKernelGGL((delta_fwd_kernel<V>), dim3(grid), dim3(PG_THREADS), 0, st, (const V*)in, n, (long)T, (long)D, (const V*)window, H, L,
+                               (V*)out);
+        return check_launch(bwd ? "delta_bwd" : "delta_fwd");
+    });
 }
 
 DSA_EXPORT int dsa_delta(const void* x, int64_t B, int64_t T, int64_t D, const void* window, int32_t H, int32_t L, int32_t dtype, void* y,
@@ -484,12 +478,11 @@ DSA_EXPORT int dsa_mlpg(const void* u, int64_t B, int64_t T, int64_t D, const vo
     unsigned grid_c, grid_n;
     if (!pg_grid(cols, 64, grid_c) || !pg_grid(n, PG_THREADS, grid_n)) return fail(DSA_ERR_INVALID_ARGUMENT, "mlpg: too many elements for one launch");
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == DSA_F32)
-        mlpg_launch<float>(st, grid_n, grid_c, u, n, cols, (long)T, (long)D, window, th, H, L, factor, adjoint, work, out);
-    else
-        mlpg_launch<double>(st, grid_n, grid_c, u, n, cols, (long)T, (long)D, window, th, H, L, factor, adjoint, work, out);
-    return check_launch(L - 1 <= DSA_MLPG_MAX_REGISTER_BAND ? (adjoint ? "mlpg_adjoint_reg" : "mlpg_forward_reg")
-                                                            : (adjoint ? "mlpg_adjoint_any" : "mlpg_forward_any"));
+    return with_dtype(dtype, "mlpg", [&](auto tag) {
+        mlpg_launch<decltype(tag)>(st, grid_n, grid_c, u, n, cols, (long)T, (long)D, window, th, H, L, factor, adjoint, work, out);
+        return check_launch(L - 1 <= DSA_MLPG_MAX_REGISTER_BAND ? (adjoint ? "mlpg_adjoint_reg" : "mlpg_forward_reg")
+                                                                : (adjoint ? "mlpg_adjoint_any" : "mlpg_forward_any"));
+    });
 }
 
 static int mcpf_check(int64_t F, int32_t M1, int32_t bins, double scale, int32_t onset, int32_t dtype)
@@ -509,13 +502,12 @@ DSA_EXPORT int dsa_mcpf(const void* mc, int64_t F, int32_t M1, const void* table
     if (!(mc && table_t && out)) return fail(DSA_ERR_INVALID_ARGUMENT, "mcpf: null pointer");
     const unsigned grid = (unsigned)(F < (1 << 20) ? F : (1 << 20));
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((mcpf_fwd_kernel<float>), dim3(grid), dim3(64), 0, st, (const float*)mc, (long)F, M1, (const double*)table_t, bins, scale,
-                           onset, (float*)out);
-    else
-        hipLaunchKernelGGL((mcpf_fwd_kernel<double>), dim3(grid), dim3(64), 0, st, (const double*)mc, (long)F, M1, (const double*)table_t, bins, scale,
-                           onset, (double*)out);
-    return check_launch("mcpf_fwd");
+    return with_dtype(dtype, "mcpf", [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((mcpf_fwd_kernel<T>), dim3(grid), dim3(64), 0, st, (const T*)mc, (long)F, M1, (const double*)table_t, bins, scale, onset,
+                           (T*)out);
+        return check_launch("mcpf_fwd");
+    });
 }
 
 DSA_EXPORT int dsa_mcpf_vjp(const void* mc, const void* g, int64_t F, int32_t M1, const void* table, const void* table_t, int32_t bins, double scale,
@@ -527,11 +519,10 @@ DSA_EXPORT int dsa_mcpf_vjp(const void* mc, const void* g, int64_t F, int32_t M1
     const unsigned grid = (unsigned)(F < (1 << 20) ? F : (1 << 20));
     const size_t lds = (size_t)2 * bins * sizeof(double);   // at most 2 * DSA_MCPF_MAX_BINS * 8 = 32 784 bytes
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((mcpf_bwd_kernel<float>), dim3(grid), dim3(64), lds, st, (const float*)mc, (const float*)g, (long)F, M1, (const double*)table,
-                           (const double*)table_t, bins, scale, onset, (float*)gmc);
-    else
-        hipLaunchKernelGGL((mcpf_bwd_kernel<double>), dim3(grid), dim3(64), lds, st, (const double*)mc, (const double*)g, (long)F, M1,
-                           (const double*)table, (const double*)table_t, bins, scale, onset, (double*)gmc);
-    return check_launch("mcpf_bwd");
+    return with_dtype(dtype, "mcpf", [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((mcpf_bwd_kernel<T>), dim3(grid), dim3(64), lds, st, (const T*)mc, (const T*)g, (long)F, M1, (const double*)table,
+                           (const double*)table_t, bins, scale, onset, (T*)gmc);
+        return check_launch("mcpf_bwd");
+    });
 }

@@ -370,9 +370,9 @@ int parcor_launch(const char* what, const void* in0, const void* in1, bool two, 
     if (!(F >= 0 && M >= 0 && M <= DSA_PARCOR_ROW_MAX_ORDER)) return fail(DSA_ERR_INVALID_ARGUMENT, "%s: invalid sizes", what);
     if (F == 0) return DSA_OK;
     if (!(in0 && out0 && (!two || in1))) return fail(DSA_ERR_INVALID_ARGUMENT, "%s: null pointer", what);
-    if (dtype == DSA_F32) return parcor_launch_t<float, OP>(in0, in1, F, M, p, out0, out1, unstable, (hipStream_t)stream);
-    if (dtype == DSA_F64) return parcor_launch_t<double, OP>(in0, in1, F, M, p, out0, out1, unstable, (hipStream_t)stream);
-    return fail(DSA_ERR_UNSUPPORTED, "%s: unsupported dtype", what);
+    return with_dtype(dtype, what, [&](auto tag) {
+        return parcor_launch_t<decltype(tag), OP>(in0, in1, F, M, p, out0, out1, unstable, (hipStream_t)stream);
+    });
 }
 
 }  // namespace

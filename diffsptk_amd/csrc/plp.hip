@@ -277,8 +277,6 @@ __global__ __launch_bounds__(256) void plp_bwd_kernel(const T* __restrict__ gout
     }
 }
 
-std::atomic<uint64_t> plp_lds_fwd_f32{0}, plp_lds_fwd_f64{0}, plp_lds_bwd_f32{0}, plp_lds_bwd_f64{0};
-
 // waves per block and dynamic LDS bytes from (C, N, dtype) only; 0 when one wave's slice exceeds the CU's LDS
 template <typename T>
 int plp_geometry(int C, int N, long& lds)
@@ -299,12 +297,10 @@ int plp_launch_fwd(const void* y, const void* E, int64_t F, int C, int M, int N,
     long lds = 0;
     const int waves = plp_geometry<T>(C, N, lds);
     if (waves == 0) return fail(DSA_ERR_UNSUPPORTED, "plp: n_channel / n_fft too large for one wave's LDS%s");
-    auto kern = plp_fwd_kernel<T>;
-    if (lds > 64 * 1024 &&
-        !ensure_dynamic_lds((const void*)kern, 160 * 1024, sizeof(T) == 4 ? plp_lds_fwd_f32 : plp_lds_fwd_f64))
-        return fail(DSA_ERR_LAUNCH, "plp: cannot raise the LDS limit%s");
-    hipLaunchKernelGGL(kern, dim3((unsigned)((F + waves - 1) / waves)), dim3(64 * waves), (unsigned)lds, st, (const T*)y,
-                       (const T*)E, (long)F, C, M, N, cf, fmt, (const T*)tab, (T*)out, (T*)save);
+    if (int rc = launch_lds<plp_fwd_kernel<T>>(lds > 64 * 1024 ? 160 * 1024 : 0, "plp: cannot raise the LDS limit%s",
+                                               dim3((unsigned)((F + waves - 1) / waves)), dim3(64 * waves), (unsigned)lds, st, (const T*)y, (const T*)E,
+                                               (long)F, C, M, N, cf, fmt, (const T*)tab, (T*)out, (T*)save))
+        return rc;
     return check_launch("plp_fwd");
 }
 
@@ -315,12 +311,10 @@ int plp_launch_bwd(const void* gout, const void* y, const void* save, int64_t F,
     long lds = 0;
     const int waves = plp_geometry<T>(C, N, lds);
     if (waves == 0) return fail(DSA_ERR_UNSUPPORTED, "plp_bwd: n_channel / n_fft too large for one wave's LDS%s");
-    auto kern = plp_bwd_kernel<T>;
-    if (lds > 64 * 1024 &&
-        !ensure_dynamic_lds((const void*)kern, 160 * 1024, sizeof(T) == 4 ? plp_lds_bwd_f32 : plp_lds_bwd_f64))
-        return fail(DSA_ERR_LAUNCH, "plp_bwd: cannot raise the LDS limit%s");
-    hipLaunchKernelGGL(kern, dim3((unsigned)((F + waves - 1) / waves)), dim3(64 * waves), (unsigned)lds, st, (const T*)gout,
-                       (const T*)y, (const T*)save, (long)F, C, M, N, cf, fmt, (const T*)tab, (T*)gy, (T*)gE);
+    if (int rc = launch_lds<plp_bwd_kernel<T>>(lds > 64 * 1024 ? 160 * 1024 : 0, "plp_bwd: cannot raise the LDS limit%s",
+                                               dim3((unsigned)((F + waves - 1) / waves)), dim3(64 * waves), (unsigned)lds, st, (const T*)gout,
+                                               (const T*)y, (const T*)save, (long)F, C, M, N, cf, fmt, (const T*)tab, (T*)gy, (T*)gE))
+        return rc;
     return check_launch("plp_bwd");
 }
 
@@ -338,11 +332,9 @@ DSA_EXPORT int dsa_plp_fwd(const void* y, const void* E, int64_t F, int32_t C, i
     if (F == 0) return DSA_OK;
     DSA_REQUIRE(y && table && out, "plp: null pointer");
     DSA_REQUIRE(E || !(out_format & 1), "plp: out_format with E needs E");
-    if (dtype == DSA_F32)
-        return plp_launch_fwd<float>(y, E, F, C, M, N, compression_factor, out_format, table, out, save, (hipStream_t)stream);
-    if (dtype == DSA_F64)
-        return plp_launch_fwd<double>(y, E, F, C, M, N, compression_factor, out_format, table, out, save, (hipStream_t)stream);
-    return fail(DSA_ERR_UNSUPPORTED, "plp: unsupported dtype%s");
+    return with_dtype(dtype, "plp", [&](auto tag) {
+        return plp_launch_fwd<decltype(tag)>(y, E, F, C, M, N, compression_factor, out_format, table, out, save, (hipStream_t)stream);
+    });
 }
 
 DSA_EXPORT int dsa_plp_bwd(const void* gout, const void* y, const void* save, int64_t F, int32_t C, int32_t M, int32_t N,
@@ -354,9 +346,7 @@ DSA_EXPORT int dsa_plp_bwd(const void* gout, const void* y, const void* save, in
     DSA_REQUIRE(F <= (int64_t)INT32_MAX, "plp_bwd: too many frames");
     if (F == 0) return DSA_OK;
     DSA_REQUIRE(gout && y && save && table && gy, "plp_bwd: null pointer");
-    if (dtype == DSA_F32)
-        return plp_launch_bwd<float>(gout, y, save, F, C, M, N, compression_factor, out_format, table, gy, gE, (hipStream_t)stream);
-    if (dtype == DSA_F64)
-        return plp_launch_bwd<double>(gout, y, save, F, C, M, N, compression_factor, out_format, table, gy, gE, (hipStream_t)stream);
-    return fail(DSA_ERR_UNSUPPORTED, "plp_bwd: unsupported dtype%s");
+    return with_dtype(dtype, "plp_bwd", [&](auto tag) {
+        return plp_launch_bwd<decltype(tag)>(gout, y, save, F, C, M, N, compression_factor, out_format, table, gy, gE, (hipStream_t)stream);
+    });
 }

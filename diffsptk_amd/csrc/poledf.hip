@@ -346,18 +346,12 @@ int poledf_launch_fwd(const void* x, const void* a, int64_t B, int64_t Tlen, int
 {
     if (poledf_ring_ok(M, P)) {
         const int lds = (int)((2 * kPdE + 2 * 64 * kPdR) * sizeof(T));
-#define DSA_PD_FWD(Q)                                                                                                                  \
-    do {                                                                                                                               \
-        static std::atomic<uint64_t> attr{0};                                                                                          \
-        if (lds > 48 * 1024 && !ensure_dynamic_lds((const void*)poledf_ring_fwd_kernel<T, Q>, lds, attr))                             \
-            return fail(DSA_ERR_LAUNCH, "poledf: cannot reserve LDS%s");                                                               \
-        hipLaunchKernelGGL((poledf_ring_fwd_kernel<T, Q>), dim3((unsigned)B), dim3(64), lds, st, (const T*)x, (const T*)a, (long)Tlen, \
-                           (long)N, M, P, ig, (T*)y);                                                                                  \
-    } while (0)
-        if (M <= 32) DSA_PD_FWD(32);
-        else if (M <= 48) DSA_PD_FWD(16);
-        else DSA_PD_FWD(1);
-#undef DSA_PD_FWD
+        auto ring = [&](auto q) {   // q: the kernel's second parameter, by order bucket
+            return launch_lds<poledf_ring_fwd_kernel<T, decltype(q)::value>>(lds > 48 * 1024 ? lds : 0, "poledf: cannot reserve LDS%s", dim3((unsigned)B),
+                                                                             dim3(64), lds, st, (const T*)x, (const T*)a, (long)Tlen, (long)N, M, P, ig,
+                                                                             (T*)y);
+        };
+        if (int rc = M <= 32 ? ring(int_c<32>{}) : M <= 48 ? ring(int_c<16>{}) : ring(int_c<1>{})) return rc;
         return check_launch("poledf_ring_fwd");
     }
     hipLaunchKernelGGL((poledf_generic_fwd_kernel<T>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, (const T*)x, (const T*)a, (long)B,
@@ -372,18 +366,12 @@ int poledf_launch_bwd(const void* gy, const void* x, const void* a, const void* 
     int rc;
     if (poledf_ring_ok(M, P)) {
         const int lds = (int)((2 * kPdE + 2 * 64 * kPdR) * sizeof(T));
-#define DSA_PD_BWD(Q)                                                                                                                  \
-    do {                                                                                                                               \
-        static std::atomic<uint64_t> attr{0};                                                                                          \
-        if (lds > 48 * 1024 && !ensure_dynamic_lds((const void*)poledf_ring_bwd_kernel<T, Q>, lds, attr))                             \
-            return fail(DSA_ERR_LAUNCH, "poledf_bwd: cannot reserve LDS%s");                                                           \
-        hipLaunchKernelGGL((poledf_ring_bwd_kernel<T, Q>), dim3((unsigned)B), dim3(64), lds, st, (const T*)gy, (const T*)a,            \
-                           (long)Tlen, (long)N, M, P, ig, (T*)uo, (T*)gx);                                                             \
-    } while (0)
-        if (M <= 32) DSA_PD_BWD(32);
-        else if (M <= 48) DSA_PD_BWD(16);
-        else DSA_PD_BWD(1);
-#undef DSA_PD_BWD
+        auto ring = [&](auto q) {
+            return launch_lds<poledf_ring_bwd_kernel<T, decltype(q)::value>>(lds > 48 * 1024 ? lds : 0, "poledf_bwd: cannot reserve LDS%s",
+                                                                             dim3((unsigned)B), dim3(64), lds, st, (const T*)gy, (const T*)a, (long)Tlen,
+                                                                             (long)N, M, P, ig, (T*)uo, (T*)gx);
+        };
+        if (int rc2 = M <= 32 ? ring(int_c<32>{}) : M <= 48 ? ring(int_c<16>{}) : ring(int_c<1>{})) return rc2;
         rc = check_launch("poledf_ring_bwd");
     } else {
         hipLaunchKernelGGL((poledf_generic_bwd_kernel<T>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, (const T*)gy, (const T*)a,
@@ -410,9 +398,9 @@ DSA_EXPORT int dsa_poledf_fwd(const void* x, const void* a, int64_t B, int64_t T
     if (B * T == 0) return DSA_OK;
     DSA_REQUIRE(x && a && y, "poledf: null pointer");
     const int64_t N = T / P;
-    if (dtype == DSA_F32) return poledf_launch_fwd<float>(x, a, B, T, N, M, P, ignore_gain, y, (hipStream_t)stream);
-    if (dtype == DSA_F64) return poledf_launch_fwd<double>(x, a, B, T, N, M, P, ignore_gain, y, (hipStream_t)stream);
-    return fail(DSA_ERR_UNSUPPORTED, "poledf: unsupported dtype%s");
+    return with_dtype(dtype, "poledf", [&](auto tag) {
+        return poledf_launch_fwd<decltype(tag)>(x, a, B, T, N, M, P, ignore_gain, y, (hipStream_t)stream);
+    });
 }
 
 DSA_EXPORT int dsa_poledf_bwd(const void* gy, const void* x, const void* a, const void* y, int64_t B, int64_t T, int32_t M, int32_t P,
@@ -423,9 +411,7 @@ DSA_EXPORT int dsa_poledf_bwd(const void* gy, const void* x, const void* a, cons
     DSA_REQUIRE(gy && a && u, "poledf_bwd: gy, a and the u buffer are required");
     DSA_REQUIRE(!ga || (x && y), "poledf_bwd: ga needs the forward's x and y");
     const int64_t N = T / P;
-    if (dtype == DSA_F32)
-        return poledf_launch_bwd<float>(gy, x, a, y, B, T, N, M, P, ignore_gain, u, gx, ga, (hipStream_t)stream);
-    if (dtype == DSA_F64)
-        return poledf_launch_bwd<double>(gy, x, a, y, B, T, N, M, P, ignore_gain, u, gx, ga, (hipStream_t)stream);
-    return fail(DSA_ERR_UNSUPPORTED, "poledf_bwd: unsupported dtype%s");
+    return with_dtype(dtype, "poledf_bwd", [&](auto tag) {
+        return poledf_launch_bwd<decltype(tag)>(gy, x, a, y, B, T, N, M, P, ignore_gain, u, gx, ga, (hipStream_t)stream);
+    });
 }

@@ -603,8 +603,6 @@ bool pq_sizes_ok(int64_t B, int64_t T, int32_t K, int32_t M, int32_t P, int32_t 
            B <= (int64_t)UINT_MAX && T <= lim && (int64_t)P * T + s <= lim && B * K <= lim && B * K * ((int64_t)P * T + s + M) <= lim * 1024;
 }
 
-int pq_dtype_size(int32_t dtype) { return dtype == DSA_F32 ? 4 : dtype == DSA_F64 ? 8 : 0; }
-
 }  // namespace
 }  // namespace dsa
 
@@ -617,9 +615,9 @@ DSA_EXPORT int dsa_pqmf_fwd(const void* x, const void* f, int64_t B, int64_t T, 
     const int64_t Tout = T > start ? (T - start + period - 1) / period : 0;
     if (B * Tout == 0) return DSA_OK;
     DSA_REQUIRE(x && f && y, "pqmf: null pointer");
-    if (dtype == DSA_F32) return pqmf_launch_fwd<float>(x, f, B, T, Tout, K, M, period, start, y, (hipStream_t)stream);
-    if (dtype == DSA_F64) return pqmf_launch_fwd<double>(x, f, B, T, Tout, K, M, period, start, y, (hipStream_t)stream);
-    return fail(DSA_ERR_UNSUPPORTED, "pqmf: unsupported dtype%s");
+    return with_dtype(dtype, "pqmf", [&](auto tag) {
+        return pqmf_launch_fwd<decltype(tag)>(x, f, B, T, Tout, K, M, period, start, y, (hipStream_t)stream);
+    });
 }
 
 DSA_EXPORT int dsa_pqmf_bwd(const void* gy, const void* x, const void* f, int64_t B, int64_t T, int32_t K, int32_t M, int32_t period,
@@ -630,9 +628,9 @@ DSA_EXPORT int dsa_pqmf_bwd(const void* gy, const void* x, const void* f, int64_
     const int64_t Tout = T > start ? (T - start + period - 1) / period : 0;
     DSA_REQUIRE(f && (gy || Tout == 0), "pqmf_bwd: f and gy are required");
     DSA_REQUIRE(!gf || (x && work), "pqmf_bwd: gf needs the forward's x and the workspace");
-    if (dtype == DSA_F32) return pqmf_launch_bwd<float>(gy, x, f, B, T, Tout, K, M, period, start, gx, gf, work, (hipStream_t)stream);
-    if (dtype == DSA_F64) return pqmf_launch_bwd<double>(gy, x, f, B, T, Tout, K, M, period, start, gx, gf, work, (hipStream_t)stream);
-    return fail(DSA_ERR_UNSUPPORTED, "pqmf_bwd: unsupported dtype%s");
+    return with_dtype(dtype, "pqmf_bwd", [&](auto tag) {
+        return pqmf_launch_bwd<decltype(tag)>(gy, x, f, B, T, Tout, K, M, period, start, gx, gf, work, (hipStream_t)stream);
+    });
 }
 
 DSA_EXPORT int dsa_ipqmf_fwd(const void* y, const void* f, int64_t B, int64_t T, int32_t K, int32_t M, int32_t up, int32_t start,
@@ -641,15 +639,16 @@ DSA_EXPORT int dsa_ipqmf_fwd(const void* y, const void* f, int64_t B, int64_t T,
     DSA_REQUIRE(pq_sizes_ok(B, T, K, M, up, start), "ipqmf: invalid sizes");
     const int64_t Tu = T * up + start;
     if (B * Tu == 0) return DSA_OK;
-    const int sz = pq_dtype_size(dtype);
-    if (!sz) return fail(DSA_ERR_UNSUPPORTED, "ipqmf: unsupported dtype%s");
-    DSA_REQUIRE(f && x && (y || T == 0), "ipqmf: null pointer");
-    if (T == 0) {   // all of yu is padding: zero
-        if (hipMemsetAsync(x, 0, (size_t)(B * Tu) * sz, (hipStream_t)stream) != hipSuccess) return fail(DSA_ERR_LAUNCH, "ipqmf: memset failed%s");
-        return DSA_OK;
-    }
-    if (dtype == DSA_F32) return ipqmf_launch_fwd<float>(y, f, B, T, Tu, K, M, up, start, x, (hipStream_t)stream);
-    return ipqmf_launch_fwd<double>(y, f, B, T, Tu, K, M, up, start, x, (hipStream_t)stream);
+    return with_dtype(dtype, "ipqmf", [&](auto tag) {
+        using V = decltype(tag);   // (T is the entry's length)
+        DSA_REQUIRE(f && x && (y || T == 0), "ipqmf: null pointer");
+        if (T == 0) {   // all of yu is padding: zero
+            if (hipMemsetAsync(x, 0, (size_t)(B * Tu) * sizeof(V), (hipStream_t)stream) != hipSuccess)
+                return fail(DSA_ERR_LAUNCH, "ipqmf: memset failed%s");
+            return (int)DSA_OK;
+        }
+        return ipqmf_launch_fwd<V>(y, f, B, T, Tu, K, M, up, start, x, (hipStream_t)stream);
+    });
 }
 
 DSA_EXPORT int dsa_ipqmf_bwd(const void* gx, const void* y, const void* f, int64_t B, int64_t T, int32_t K, int32_t M, int32_t up,
@@ -658,17 +657,17 @@ DSA_EXPORT int dsa_ipqmf_bwd(const void* gx, const void* y, const void* f, int64
     DSA_REQUIRE(pq_sizes_ok(B, T, K, M, up, start), "ipqmf_bwd: invalid sizes");
     const int64_t Tu = T * up + start;
     if (B * Tu == 0) return DSA_OK;
-    const int sz = pq_dtype_size(dtype);
-    if (!sz) return fail(DSA_ERR_UNSUPPORTED, "ipqmf_bwd: unsupported dtype%s");
-    DSA_REQUIRE(f && gx, "ipqmf_bwd: f and gx are required");
-    DSA_REQUIRE(!gf || ((y || T == 0) && work), "ipqmf_bwd: gf needs the forward's y and the workspace");
-    if (T == 0) {   // no input samples: gy is empty and the filter gradient zero
-        if (gf && hipMemsetAsync(gf, 0, (size_t)K * (M + 1) * sz, (hipStream_t)stream) != hipSuccess)
-            return fail(DSA_ERR_LAUNCH, "ipqmf_bwd: memset failed%s");
-        return DSA_OK;
-    }
-    if (dtype == DSA_F32) return ipqmf_launch_bwd<float>(gx, y, f, B, T, Tu, K, M, up, start, gy, gf, work, (hipStream_t)stream);
-    return ipqmf_launch_bwd<double>(gx, y, f, B, T, Tu, K, M, up, start, gy, gf, work, (hipStream_t)stream);
+    return with_dtype(dtype, "ipqmf_bwd", [&](auto tag) {
+        using V = decltype(tag);   // (T is the entry's length)
+        DSA_REQUIRE(f && gx, "ipqmf_bwd: f and gx are required");
+        DSA_REQUIRE(!gf || ((y || T == 0) && work), "ipqmf_bwd: gf needs the forward's y and the workspace");
+        if (T == 0) {   // no input samples: gy is empty and the filter gradient zero
+            if (gf && hipMemsetAsync(gf, 0, (size_t)K * (M + 1) * sizeof(V), (hipStream_t)stream) != hipSuccess)
+                return fail(DSA_ERR_LAUNCH, "ipqmf_bwd: memset failed%s");
+            return (int)DSA_OK;
+        }
+        return ipqmf_launch_bwd<V>(gx, y, f, B, T, Tu, K, M, up, start, gy, gf, work, (hipStream_t)stream);
+    });
 }
 
 DSA_EXPORT int dsa_interpolate_fwd(const void* x, int64_t outer, int64_t T, int64_t inner, int32_t period, int32_t start, int32_t dtype,
@@ -682,13 +681,11 @@ DSA_EXPORT int dsa_interpolate_fwd(const void* x, int64_t outer, int64_t T, int6
     DSA_REQUIRE(y && (x || T == 0), "interpolate: null pointer");
     const hipStream_t st = (hipStream_t)stream;
     const unsigned nb = pq_blocks(outer * Tu * inner);
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((interp_fwd_kernel<float>), dim3(nb), dim3(256), 0, st, (const float*)x, outer, T, inner, period, start, (float*)y);
-    else if (dtype == DSA_F64)
-        hipLaunchKernelGGL((interp_fwd_kernel<double>), dim3(nb), dim3(256), 0, st, (const double*)x, outer, T, inner, period, start, (double*)y);
-    else
-        return fail(DSA_ERR_UNSUPPORTED, "interpolate: unsupported dtype%s");
-    return check_launch("interpolate_fwd");
+    return with_dtype(dtype, "interpolate", [&](auto tag) {
+        using V = decltype(tag);   // (T is the entry's length)
+        hipLaunchKernelGGL((interp_fwd_kernel<V>), dim3(nb), dim3(256), 0, st, (const V*)x, outer, T, inner, period, start, (V*)y);
+        return check_launch("interpolate_fwd");
+    });
 }
 
 DSA_EXPORT int dsa_interpolate_bwd(const void* gy, int64_t outer, int64_t T, int64_t inner, int32_t period, int32_t start, int32_t dtype,
@@ -701,11 +698,9 @@ DSA_EXPORT int dsa_interpolate_bwd(const void* gy, int64_t outer, int64_t T, int
     DSA_REQUIRE(gy && gx, "interpolate_bwd: null pointer");
     const hipStream_t st = (hipStream_t)stream;
     const unsigned nb = pq_blocks(outer * T * inner);
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((interp_bwd_kernel<float>), dim3(nb), dim3(256), 0, st, (const float*)gy, outer, T, inner, period, start, (float*)gx);
-    else if (dtype == DSA_F64)
-        hipLaunchKernelGGL((interp_bwd_kernel<double>), dim3(nb), dim3(256), 0, st, (const double*)gy, outer, T, inner, period, start, (double*)gx);
-    else
-        return fail(DSA_ERR_UNSUPPORTED, "interpolate_bwd: unsupported dtype%s");
-    return check_launch("interpolate_bwd");
+    return with_dtype(dtype, "interpolate_bwd", [&](auto tag) {
+        using V = decltype(tag);   // (T is the entry's length)
+        hipLaunchKernelGGL((interp_bwd_kernel<V>), dim3(nb), dim3(256), 0, st, (const V*)gy, outer, T, inner, period, start, (V*)gx);
+        return check_launch("interpolate_bwd");
+    });
 }

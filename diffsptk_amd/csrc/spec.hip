@@ -643,13 +643,11 @@ static int launch_row_dft(const void* x, int64_t B, int64_t Tlen, int64_t N, int
     const bool direct_only = env_int("DSA_ROWDFT_DIRECT", 0) != 0;
     const size_t lds_fft = lds + sizeof(T) * 2 * (size_t)nfft;
     if (!direct_only && nfft >= 32 && (nfft & (nfft - 1)) == 0 && lds_fft <= 150 * 1024) {
-        static std::atomic<uint64_t> lds_set{0};
-        if (lds_fft > 48 * 1024 &&
-            !ensure_dynamic_lds(reinterpret_cast<const void*>(&row_dft_kernel<T, true>), 150 * 1024, lds_set))
-            return fail(DSA_ERR_LAUNCH, "row_fft: cannot raise the dynamic LDS limit%s");
-        hipLaunchKernelGGL((row_dft_kernel<T, true>), dim3((unsigned)F), dim3(nfft >= 512 ? 256 : threads), lds_fft, st,
-                           (const T*)x, (long)Tlen, (long)N, L, P, left, mode, zmean, (const T*)w, nfft, (const T*)twiddle,
-                           out_kind, fmt, (T)eps, use_floor, floor_lin, (T*)y);
+        if (int rc = launch_lds<row_dft_kernel<T, true>>(lds_fft > 48 * 1024 ? 150 * 1024 : 0, "row_fft: cannot raise the dynamic LDS limit%s",
+                                                         dim3((unsigned)F), dim3(nfft >= 512 ? 256 : threads), lds_fft, st, (const T*)x, (long)Tlen,
+                                                         (long)N, L, P, left, mode, zmean, (const T*)w, nfft, (const T*)twiddle, out_kind, fmt, (T)eps,
+                                                         use_floor, floor_lin, (T*)y))
+            return rc;
         return check_launch("row_fft_generic");
     }
     if (lds > 60 * 1024) return fail(DSA_ERR_UNSUPPORTED, "row_dft: frame too long for LDS%s");
@@ -687,15 +685,12 @@ DSA_EXPORT int dsa_frame_fwd(const void* x, int64_t B, int64_t T, int32_t L, int
                            (long)F, L, P, left, pad_mode, src_aligned, (float*)y);
         return check_launch("frame_fwd_vec4");
     }
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((frame_fwd_kernel<float>), dim3((unsigned)F), dim3(threads), 0, st,
-                           (const float*)x, (long)T, (long)N, L, P, left, zmean, pad_mode, (float*)y);
-    else if (dtype == DSA_F64)
-        hipLaunchKernelGGL((frame_fwd_kernel<double>), dim3((unsigned)F), dim3(threads), 0, st,
-                           (const double*)x, (long)T, (long)N, L, P, left, zmean, pad_mode, (double*)y);
-    else
-        return fail(DSA_ERR_UNSUPPORTED, "frame: unsupported dtype%s");
-    return check_launch("frame_fwd");
+    return with_dtype(dtype, "frame", [&](auto tag) {
+        using V = decltype(tag);   // (T is the entry's signal length)
+        hipLaunchKernelGGL((frame_fwd_kernel<V>), dim3((unsigned)F), dim3(threads), 0, st, (const V*)x, (long)T, (long)N, L, P, left, zmean, pad_mode,
+                           (V*)y);
+        return check_launch("frame_fwd");
+    });
 }
 
 template <typename T>
@@ -731,9 +726,9 @@ DSA_EXPORT int dsa_frame_bwd(const void* gy, int64_t B, int64_t T, int32_t L, in
 {
     DSA_REQUIRE(L > 0 && P > 0 && T > 0 && B >= 0, "frame_bwd: sizes must be positive");
     if (B == 0) return DSA_OK;
-    if (dtype == DSA_F32) return frame_bwd_impl<float>(gy, B, T, L, P, center, zmean, pad_mode, gx, (hipStream_t)stream);
-    if (dtype == DSA_F64) return frame_bwd_impl<double>(gy, B, T, L, P, center, zmean, pad_mode, gx, (hipStream_t)stream);
-    return fail(DSA_ERR_UNSUPPORTED, "frame_bwd: unsupported dtype%s");
+    return with_dtype(dtype, "frame_bwd", [&](auto tag) {
+        return frame_bwd_impl<decltype(tag)>(gy, B, T, L, P, center, zmean, pad_mode, gx, (hipStream_t)stream);
+    });
 }
 
 DSA_EXPORT int dsa_window_fwd(const void* x, int64_t F, int32_t L, const void* w, int32_t L2, int32_t dtype,
@@ -744,21 +739,17 @@ DSA_EXPORT int dsa_window_fwd(const void* x, int64_t F, int32_t L, const void* w
     int64_t total = F * L2;
     unsigned grid = (unsigned)((total + 255) / 256 > 65536 ? 65536 : (total + 255) / 256);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == DSA_F32) {
-        if (window_vec4_ok(x, y, w, F, L, L2)) {
-            const unsigned n4 = (unsigned)(F * (int64_t)(L >> 2));
-            hipLaunchKernelGGL(window_vec4_kernel, dim3((n4 + 255) / 256 > 16384 ? 16384 : (n4 + 255) / 256), dim3(256), 0, st,
-                               (const float4*)x, n4, (unsigned)(L >> 2), (const float4*)w, (float4*)y);
-            return check_launch("window_vec4");
-        }
-        hipLaunchKernelGGL((window_fwd_kernel<float>), dim3(grid), dim3(256), 0, st, (const float*)x,
-                           (long)F, L, (const float*)w, L2, (float*)y);
-    } else if (dtype == DSA_F64)
-        hipLaunchKernelGGL((window_fwd_kernel<double>), dim3(grid), dim3(256), 0, st, (const double*)x,
-                           (long)F, L, (const double*)w, L2, (double*)y);
-    else
-        return fail(DSA_ERR_UNSUPPORTED, "window: unsupported dtype%s");
-    return check_launch("window_fwd");
+    if (dtype == DSA_F32 && window_vec4_ok(x, y, w, F, L, L2)) {
+        const unsigned n4 = (unsigned)(F * (int64_t)(L >> 2));
+        hipLaunchKernelGGL(window_vec4_kernel, dim3((n4 + 255) / 256 > 16384 ? 16384 : (n4 + 255) / 256), dim3(256), 0, st,
+                           (const float4*)x, n4, (unsigned)(L >> 2), (const float4*)w, (float4*)y);
+        return check_launch("window_vec4");
+    }
+    return with_dtype(dtype, "window", [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((window_fwd_kernel<T>), dim3(grid), dim3(256), 0, st, (const T*)x, (long)F, L, (const T*)w, L2, (T*)y);
+        return check_launch("window_fwd");
+    });
 }
 
 DSA_EXPORT int dsa_window_bwd(const void* gy, const void* x, int64_t F, int32_t L, const void* w, int32_t L2,
@@ -769,26 +760,17 @@ DSA_EXPORT int dsa_window_bwd(const void* gy, const void* x, int64_t F, int32_t 
     int64_t total = F * L;
     unsigned grid = (unsigned)((total + 255) / 256 > 65536 ? 65536 : (total + 255) / 256);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == DSA_F32) {
-        if (window_vec4_ok(gy, gx, w, F, L, L2)) {
+    return with_dtype(dtype, "window_bwd", [&](auto tag) {
+        using T = decltype(tag);
+        if (dtype == DSA_F32 && window_vec4_ok(gy, gx, w, F, L, L2)) {   // the float32-only vector route of the forward
             const unsigned n4 = (unsigned)(F * (int64_t)(L >> 2));
             hipLaunchKernelGGL(window_vec4_kernel, dim3((n4 + 255) / 256 > 16384 ? 16384 : (n4 + 255) / 256), dim3(256), 0, st,
                                (const float4*)gy, n4, (unsigned)(L >> 2), (const float4*)w, (float4*)gx);
         } else
-            hipLaunchKernelGGL((window_bwd_kernel<float>), dim3(grid), dim3(256), 0, st, (const float*)gy,
-                               (long)F, L, (const float*)w, L2, (float*)gx);
-        if (gw)
-            hipLaunchKernelGGL((window_gw_kernel<float>), dim3(L), dim3(256), 0, st, (const float*)gy,
-                               (const float*)x, (long)F, L, L2, (float*)gw);
-    } else if (dtype == DSA_F64) {
-        hipLaunchKernelGGL((window_bwd_kernel<double>), dim3(grid), dim3(256), 0, st, (const double*)gy,
-                           (long)F, L, (const double*)w, L2, (double*)gx);
-        if (gw)
-            hipLaunchKernelGGL((window_gw_kernel<double>), dim3(L), dim3(256), 0, st, (const double*)gy,
-                               (const double*)x, (long)F, L, L2, (double*)gw);
-    } else
-        return fail(DSA_ERR_UNSUPPORTED, "window_bwd: unsupported dtype%s");
-    return check_launch("window_bwd");
+            hipLaunchKernelGGL((window_bwd_kernel<T>), dim3(grid), dim3(256), 0, st, (const T*)gy, (long)F, L, (const T*)w, L2, (T*)gx);
+        if (gw) hipLaunchKernelGGL((window_gw_kernel<T>), dim3(L), dim3(256), 0, st, (const T*)gy, (const T*)x, (long)F, L, L2, (T*)gw);
+        return check_launch("window_bwd");
+    });
 }
 
 DSA_EXPORT int dsa_fftr_fwd(const void* x, int64_t F, int32_t len_in, int32_t nfft, int32_t out_format,
@@ -798,13 +780,9 @@ DSA_EXPORT int dsa_fftr_fwd(const void* x, int64_t F, int32_t len_in, int32_t nf
     DSA_REQUIRE(out_format >= 0 && out_format <= 4, "fftr: unknown out_format");
     hipStream_t st = (hipStream_t)stream;
     // rows are "utterances" of len_in samples holding exactly one frame each
-    if (dtype == DSA_F32)
-        return launch_row_dft<float>(x, F, len_in, 1, len_in, len_in, 0, 0, 0, nullptr, nfft, twiddle, 0,
-                                     out_format, 0.0, 0, 0.0, y, st);
-    if (dtype == DSA_F64)
-        return launch_row_dft<double>(x, F, len_in, 1, len_in, len_in, 0, 0, 0, nullptr, nfft, twiddle, 0,
-                                      out_format, 0.0, 0, 0.0, y, st);
-    return fail(DSA_ERR_UNSUPPORTED, "fftr: unsupported dtype%s");
+    return with_dtype(dtype, "fftr", [&](auto tag) {
+        return launch_row_dft<decltype(tag)>(x, F, len_in, 1, len_in, len_in, 0, 0, 0, nullptr, nfft, twiddle, 0, out_format, 0.0, 0, 0.0, y, st);
+    });
 }
 
 template <typename T>
@@ -852,11 +830,9 @@ DSA_EXPORT int dsa_spec_fwd(const void* b, int32_t lb, const void* a, int32_t la
     DSA_REQUIRE(out_format >= 0 && out_format <= 3, "spec: unknown out_format");
     if (F == 0) return DSA_OK;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == DSA_F32)
-        return spec_fwd_impl<float>(b, lb, a, la, F, nfft, eps, use_floor, relative_floor_db, out_format, twiddle, y, st);
-    if (dtype == DSA_F64)
-        return spec_fwd_impl<double>(b, lb, a, la, F, nfft, eps, use_floor, relative_floor_db, out_format, twiddle, y, st);
-    return fail(DSA_ERR_UNSUPPORTED, "spec: unsupported dtype%s");
+    return with_dtype(dtype, "spec", [&](auto tag) {
+        return spec_fwd_impl<decltype(tag)>(b, lb, a, la, F, nfft, eps, use_floor, relative_floor_db, out_format, twiddle, y, st);
+    });
 }
 
 // --------------------------------------------------------------------------- backward entries
@@ -876,13 +852,11 @@ static int launch_row_dft_bwd(const void* x, int64_t B, int64_t Tlen, int64_t N,
     const bool direct_only = env_int("DSA_ROWDFT_DIRECT", 0) != 0;
     const size_t lds_fft = lds + sizeof(T) * 2 * (size_t)nfft;
     if (!direct_only && nfft >= 32 && (nfft & (nfft - 1)) == 0 && lds_fft <= 150 * 1024) {
-        static std::atomic<uint64_t> lds_set{0};
-        if (lds_fft > 48 * 1024 &&
-            !ensure_dynamic_lds(reinterpret_cast<const void*>(&row_dft_bwd_kernel<T, true>), 150 * 1024, lds_set))
-            return fail(DSA_ERR_LAUNCH, "row_fft_bwd: cannot raise the dynamic LDS limit%s");
-        hipLaunchKernelGGL((row_dft_bwd_kernel<T, true>), dim3((unsigned)F), dim3(256), lds_fft, st, (const T*)x, (long)Tlen,
-                           (long)N, L, P, left, mode, zmean, (const T*)w, nfft, (const T*)twiddle, out_kind, fmt,
-                           (T)eps, use_floor, floor_lin, (const T*)gy, (T*)gframe, (T*)gwpart);
+        if (int rc = launch_lds<row_dft_bwd_kernel<T, true>>(lds_fft > 48 * 1024 ? 150 * 1024 : 0, "row_fft_bwd: cannot raise the dynamic LDS limit%s",
+                                                             dim3((unsigned)F), dim3(256), lds_fft, st, (const T*)x, (long)Tlen, (long)N, L, P, left,
+                                                             mode, zmean, (const T*)w, nfft, (const T*)twiddle, out_kind, fmt, (T)eps, use_floor,
+                                                             floor_lin, (const T*)gy, (T*)gframe, (T*)gwpart))
+            return rc;
         return check_launch("row_fft_bwd_generic");
     }
     if (lds > 60 * 1024) return fail(DSA_ERR_UNSUPPORTED, "row_dft_bwd: frame too long for LDS%s");
@@ -923,22 +897,19 @@ int stft_generic_fwd(int dtype, const void* x, int64_t B, int64_t Tlen, int64_t 
                      const void* w, int nfft, const void* twiddle, int fmt, double eps, int use_floor, double floor_db, void* y,
                      hipStream_t st)
 {
-    if (dtype == DSA_F32)
-        return launch_row_dft<float>(x, B, Tlen, N, L, P, left, mode, zmean, w, nfft, twiddle, 1, fmt, eps, use_floor, floor_db, y, st);
-    if (dtype == DSA_F64)
-        return launch_row_dft<double>(x, B, Tlen, N, L, P, left, mode, zmean, w, nfft, twiddle, 1, fmt, eps, use_floor, floor_db, y, st);
-    return fail(DSA_ERR_UNSUPPORTED, "stft: unsupported dtype%s");
+    return with_dtype(dtype, "stft", [&](auto tag) {
+        return launch_row_dft<decltype(tag)>(x, B, Tlen, N, L, P, left, mode, zmean, w, nfft, twiddle, 1, fmt, eps, use_floor, floor_db, y, st);
+    });
 }
 
 int stft_generic_bwd(int dtype, const void* gy, const void* x, int64_t B, int64_t Tlen, int L, int P, int nfft, const void* w,
                      const void* twiddle, int center, int zmean, int pad_mode, double eps, int use_floor, double floor_db, int fmt,
                      void* gx, void* gw, hipStream_t st)
 {
-    if (dtype == DSA_F32)
-        return stft_bwd_generic<float>(gy, x, B, Tlen, L, P, nfft, w, twiddle, center, zmean, pad_mode, eps, use_floor, floor_db, fmt, gx, gw, st);
-    if (dtype == DSA_F64)
-        return stft_bwd_generic<double>(gy, x, B, Tlen, L, P, nfft, w, twiddle, center, zmean, pad_mode, eps, use_floor, floor_db, fmt, gx, gw, st);
-    return fail(DSA_ERR_UNSUPPORTED, "stft_bwd: unsupported dtype%s");
+    return with_dtype(dtype, "stft_bwd", [&](auto tag) {
+        return stft_bwd_generic<decltype(tag)>(gy, x, B, Tlen, L, P, nfft, w, twiddle, center, zmean, pad_mode, eps, use_floor, floor_db, fmt, gx, gw,
+                                               st);
+    });
 }
 
 }  // namespace dsa
@@ -949,13 +920,10 @@ DSA_EXPORT int dsa_fftr_bwd(const void* gy, const void* x, int64_t F, int32_t le
     DSA_REQUIRE(len_in > 0 && nfft > 0 && nfft % 2 == 0, "fftr_bwd: fft_length must be positive even");
     DSA_REQUIRE(out_format >= 0 && out_format <= 4, "fftr_bwd: unknown out_format");
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == DSA_F32)
-        return launch_row_dft_bwd<float>(x, F, len_in, 1, len_in, len_in, 0, 0, 0, nullptr, nfft, twiddle, 0,
-                                         out_format, 0.0, 0, 0.0, gy, gx, nullptr, st);
-    if (dtype == DSA_F64)
-        return launch_row_dft_bwd<double>(x, F, len_in, 1, len_in, len_in, 0, 0, 0, nullptr, nfft, twiddle, 0,
-                                          out_format, 0.0, 0, 0.0, gy, gx, nullptr, st);
-    return fail(DSA_ERR_UNSUPPORTED, "fftr_bwd: unsupported dtype%s");
+    return with_dtype(dtype, "fftr_bwd", [&](auto tag) {
+        return launch_row_dft_bwd<decltype(tag)>(x, F, len_in, 1, len_in, len_in, 0, 0, 0, nullptr, nfft, twiddle, 0, out_format, 0.0, 0, 0.0, gy, gx,
+                                                 nullptr, st);
+    });
 }
 
 DSA_EXPORT int dsa_spec_bwd(const void* gy, const void* b, int32_t lb, const void* a, int32_t la, int64_t F,
@@ -974,23 +942,15 @@ DSA_EXPORT int dsa_spec_bwd(const void* gy, const void* b, int32_t lb, const voi
         const size_t lds = esz * ((size_t)lb + la + 5 * (size_t)K);
         if (lds > 60 * 1024) return fail(DSA_ERR_UNSUPPORTED, "spec_bwd: rows too long for LDS%s");
         const double fl = use_floor ? pow(10.0, relative_floor_db / 10.0) : 0.0;
-        if (dtype == DSA_F32)
-            hipLaunchKernelGGL((spec_ratio_bwd_kernel<float>), dim3((unsigned)F), dim3(128), lds, st, (const float*)gy,
-                               (const float*)b, b ? lb : 0, (const float*)a, la, nfft, (const float*)twiddle, (float)eps,
-                               use_floor, (float)fl, out_format, (float*)gb, (float*)ga);
-        else if (dtype == DSA_F64)
-            hipLaunchKernelGGL((spec_ratio_bwd_kernel<double>), dim3((unsigned)F), dim3(128), lds, st, (const double*)gy,
-                               (const double*)b, b ? lb : 0, (const double*)a, la, nfft, (const double*)twiddle, eps,
-                               use_floor, fl, out_format, (double*)gb, (double*)ga);
-        else
-            return fail(DSA_ERR_UNSUPPORTED, "spec_bwd: unsupported dtype%s");
-        return check_launch("spec_ratio_bwd");
+        return with_dtype(dtype, "spec_bwd", [&](auto tag) {
+            using T = decltype(tag);
+            hipLaunchKernelGGL((spec_ratio_bwd_kernel<T>), dim3((unsigned)F), dim3(128), lds, st, (const T*)gy, (const T*)b, b ? lb : 0, (const T*)a, la,
+                               nfft, (const T*)twiddle, (T)eps, use_floor, (T)fl, out_format, (T*)gb, (T*)ga);
+            return check_launch("spec_ratio_bwd");
+        });
     }
-    if (dtype == DSA_F32)
-        return launch_row_dft_bwd<float>(b, F, lb, 1, lb, lb, 0, 0, 0, nullptr, nfft, twiddle, 1, out_format, eps,
-                                         use_floor, relative_floor_db, gy, gb, nullptr, st);
-    if (dtype == DSA_F64)
-        return launch_row_dft_bwd<double>(b, F, lb, 1, lb, lb, 0, 0, 0, nullptr, nfft, twiddle, 1, out_format, eps,
-                                          use_floor, relative_floor_db, gy, gb, nullptr, st);
-    return fail(DSA_ERR_UNSUPPORTED, "spec_bwd: unsupported dtype%s");
+    return with_dtype(dtype, "spec_bwd", [&](auto tag) {
+        return launch_row_dft_bwd<decltype(tag)>(b, F, lb, 1, lb, lb, 0, 0, 0, nullptr, nfft, twiddle, 1, out_format, eps, use_floor,
+                                                 relative_floor_db, gy, gb, nullptr, st);
+    });
 }

@@ -872,24 +872,15 @@ static int stft_bwd_impl(const void* gy, const void* x, int64_t B, int64_t T, in
             const long wv = items < waves ? items : waves;
             const dim3 g2((unsigned)((wv + 3) / 4));
             const int lds_bb = 4 * 4 * kZS * 8 + 256 * 8 + 4 * (2 * 256 * S) * 4;
-#define DSA_BIGB_LAUNCH(SV, NRV)                                                                                                        \
-    do {                                                                                                                                \
-        static std::atomic<uint64_t> abb{0};                                                                                            \
-        if (!ensure_dynamic_lds(reinterpret_cast<const void*>(&stft_big_bwd_pk_kernel<SV, NRV>), lds_bb, abb))                          \
-            return fail(DSA_ERR_LAUNCH, "stft_bwd: cannot reserve LDS%s");                                                              \
-        hipLaunchKernelGGL((stft_big_bwd_pk_kernel<SV, NRV>), g2, dim3(256), lds_bb, st, (const float*)x, (const float*)gy, (long)T,    \
-                           (long)Nb, L, P, leftb, (const float*)w, (const float*)twiddle, (float*)gx, items, runs, ppu, warm);          \
-    } while (0)
-            if (S == 2) {
-                if (need <= 10) DSA_BIGB_LAUNCH(2, 10);
-                else if (need <= 13) DSA_BIGB_LAUNCH(2, 13);
-                else DSA_BIGB_LAUNCH(2, 16);
-            } else {
-                if (need <= 10) DSA_BIGB_LAUNCH(4, 10);
-                else if (need <= 13) DSA_BIGB_LAUNCH(4, 13);
-                else DSA_BIGB_LAUNCH(4, 16);
-            }
-#undef DSA_BIGB_LAUNCH
+            auto launch = [&](auto sv, auto nrv) {   // the kernel's S and its sample pairs per lane
+                return launch_lds<stft_big_bwd_pk_kernel<decltype(sv)::value, decltype(nrv)::value>>(
+                    lds_bb, "stft_bwd: cannot reserve LDS%s", g2, dim3(256), lds_bb, st, (const float*)x, (const float*)gy, (long)T, (long)Nb, L, P, leftb,
+                    (const float*)w, (const float*)twiddle, (float*)gx, items, runs, ppu, warm);
+            };
+            auto by_need = [&](auto sv) {
+                return need <= 10 ? launch(sv, int_c<10>{}) : need <= 13 ? launch(sv, int_c<13>{}) : launch(sv, int_c<16>{});
+            };
+            if (int rc = S == 2 ? by_need(int_c<2>{}) : by_need(int_c<4>{})) return rc;
             return check_launch(S == 2 ? "stft1024_bwd" : "stft2048_bwd");
         }
     }
@@ -992,19 +983,20 @@ static int stft_bwd_impl(const void* gy, const void* x, int64_t B, int64_t T, in
             return rc;
         }
     }
-    if (dtype != DSA_F32 && dtype != DSA_F64) return fail(DSA_ERR_UNSUPPORTED, "stft_bwd: unsupported dtype%s");
-    const size_t esz = dtype == DSA_F32 ? 4 : 8;
-    void* x0 = nullptr;
-    if (!x) {   // inverse transform through the generic kernels: they read a waveform, give them zeros
-        if (hipMallocAsync(&x0, esz * (size_t)B * T, st) != hipSuccess || hipMemsetAsync(x0, 0, esz * (size_t)B * T, st) != hipSuccess)
-            return fail(DSA_ERR_LAUNCH, "istft: workspace allocation failed%s");
-        x = x0;
-    }
-    int rc = stft_generic_bwd(dtype, gy, x, B, T, L, P, nfft, w, twiddle, center, zmean, pad_mode, eps, use_floor, relative_floor_db,
-                              out_format, gx, gw, st);
-    if (x0) (void)hipFreeAsync(x0, st);
-    if (rc == DSA_OK && div) rc = dsa_div_rows(gx, B, T, div, div_eps, dtype, gx, stream);
-    return rc;
+    return with_dtype(dtype, "stft_bwd", [&](auto tag) {   // (refused before the workspace is asked for)
+        const size_t esz = sizeof(decltype(tag));
+        void* x0 = nullptr;
+        if (!x) {   // inverse transform through the generic kernels: they read a waveform, give them zeros
+            if (hipMallocAsync(&x0, esz * (size_t)B * T, st) != hipSuccess || hipMemsetAsync(x0, 0, esz * (size_t)B * T, st) != hipSuccess)
+                return fail(DSA_ERR_LAUNCH, "istft: workspace allocation failed%s");
+            x = x0;
+        }
+        int rc = stft_generic_bwd(dtype, gy, x, B, T, L, P, nfft, w, twiddle, center, zmean, pad_mode, eps, use_floor, relative_floor_db,
+                                  out_format, gx, gw, st);
+        if (x0) (void)hipFreeAsync(x0, st);
+        if (rc == DSA_OK && div) rc = dsa_div_rows(gx, B, T, div, div_eps, dtype, gx, stream);
+        return rc;
+    });
 }
 
 DSA_EXPORT int dsa_stft_bwd(const void* gy, const void* x, int64_t B, int64_t T, int32_t L, int32_t P,

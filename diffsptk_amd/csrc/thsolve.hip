@@ -220,9 +220,9 @@ DSA_EXPORT int dsa_thsolve_fwd(const void* p, const void* q, const void* r, int6
     // dsa_mcep_newton_update: a frame's rounding must not depend on how many frames travel with it (round 6: the F >= 64 test is gone)
     if (dtype == DSA_F32 && n >= 2 && n <= 55 && quad && F > 0)
         return thsolve_quadn_fwd(p, n, q, 2 * n - 1, r, n, nullptr, nullptr, F, n, g, (hipStream_t)stream);
-    if (dtype == DSA_F32) return th_launch<float>(false, nullptr, p, q, r, F, n, g, nullptr, nullptr, (hipStream_t)stream);
-    if (dtype == DSA_F64) return th_launch<double>(false, nullptr, p, q, r, F, n, g, nullptr, nullptr, (hipStream_t)stream);
-    return fail(DSA_ERR_UNSUPPORTED, "thsolve: unsupported dtype%s");
+    return with_dtype(dtype, "thsolve", [&](auto tag) {
+        return th_launch<decltype(tag)>(false, nullptr, p, q, r, F, n, g, nullptr, nullptr, (hipStream_t)stream);
+    });
 }
 
 // mcep.py:216-222 for the geometries without a tuned kernel: mc_out = mc_in + solve(T(rt[:n]) + H(rt), rt[:n] - alpha_vec), rt:(F, 2n-1)
@@ -374,7 +374,7 @@ DSA_EXPORT int dsa_thsolve_bwd(const void* gg, const void* p, const void* q, con
                            (const float*)g, (long)F, (int)n, (float*)gp, (float*)gq);
         return check_launch("th_solve_quadn_bwd");
     }
-    if (dtype == DSA_F32) return th_launch<float>(true, gg, p, q, g, F, n, gp, gq, gr, (hipStream_t)stream);
-    if (dtype == DSA_F64) return th_launch<double>(true, gg, p, q, g, F, n, gp, gq, gr, (hipStream_t)stream);
-    return fail(DSA_ERR_UNSUPPORTED, "thsolve_bwd: unsupported dtype%s");
+    return with_dtype(dtype, "thsolve_bwd", [&](auto tag) {
+        return th_launch<decltype(tag)>(true, gg, p, q, g, F, n, gp, gq, gr, (hipStream_t)stream);
+    });
 }

@@ -31,13 +31,12 @@ static int thsolve_quadn_launch(const void* p, int ldp, const void* q, int ldq, 
 {
     constexpr int REC = ((16 * NG + 3 - 4 + 31) / 32) * 32 + 4;   // >= 16 NG + 3 and = 4 (mod 32): see the octet kernel (rounds 3-4: 16 NG + 3, odd)
     const int lds_bytes = 4 * 16 * REC * (int)sizeof(float);
-    static std::atomic<uint64_t> attr{0};
-    if (lds_bytes > 48 * 1024 && !ensure_dynamic_lds((const void*)tq::thsolve_quadn_kernel<NG, NMIN>, lds_bytes, attr))
-        return fail(DSA_ERR_LAUNCH, "thsolve_quad: cannot reserve LDS%s");
     long blocks = ((F + 15) / 16 + 3) / 4;
     if (blocks > 256) blocks = 256;   // one workgroup per CU (one wave per SIMD: the matrix takes up to 420 registers)
-    hipLaunchKernelGGL((tq::thsolve_quadn_kernel<NG, NMIN>), dim3((unsigned)blocks), dim3(256), lds_bytes, st, (const float*)p, ldp,
-                       (const float*)q, ldq, (const float*)r, ldr, (const float*)sub, (const float*)add, (long)F, n, (float*)g);
+    if (int rc = launch_lds<tq::thsolve_quadn_kernel<NG, NMIN>>(lds_bytes > 48 * 1024 ? lds_bytes : 0, "thsolve_quad: cannot reserve LDS%s",
+                                                                dim3((unsigned)blocks), dim3(256), lds_bytes, st, (const float*)p, ldp, (const float*)q,
+                                                                ldq, (const float*)r, ldr, (const float*)sub, (const float*)add, (long)F, n, (float*)g))
+        return rc;
     return check_launch("th_solve_quadn_fwd");
 }
 

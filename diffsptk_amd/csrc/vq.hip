@@ -294,13 +294,11 @@ int vq_search(const void* x, const void* cb, int64_t Tn, int64_t K, int64_t L, v
 {
     constexpr int TILE = DSA_VQ_TILE_BYTES / sizeof(T);
     constexpr int MAX_LDS = DSA_VQ_TILE_BYTES * (DSA_VQ_MAX_LENGTH | 1) + DSA_VQ_CHUNK * DSA_VQ_MAX_LENGTH * 8;
-    static std::atomic<uint64_t> done{0};
-    if (!ensure_dynamic_lds(reinterpret_cast<const void*>(&vq_search_kernel<T>), MAX_LDS, done))
-        return fail(DSA_ERR_LAUNCH, "vq: cannot raise the dynamic LDS limit");
     const int64_t blocks = (Tn + TILE - 1) / TILE;
     const size_t lds = (size_t)TILE * (L | 1) * sizeof(T) + (size_t)DSA_VQ_CHUNK * L * 8;
-    hipLaunchKernelGGL((vq_search_kernel<T>), dim3((unsigned)blocks), dim3(TILE), lds, st, (const T*)x, (const float*)cb, (long)Tn, (int)K, (int)L,
-                       (int64_t*)idx, (T*)xq, (double*)partial);
+    if (int rc = launch_lds<vq_search_kernel<T>>(MAX_LDS, "vq: cannot raise the dynamic LDS limit", dim3((unsigned)blocks), dim3(TILE), lds, st,
+                                                 (const T*)x, (const float*)cb, (long)Tn, (int)K, (int)L, (int64_t*)idx, (T*)xq, (double*)partial))
+        return rc;
     if (total)
         hipLaunchKernelGGL((vq_total_kernel<T>), dim3(1), dim3(256), 0, st, (const double*)partial, (long)blocks, scale, (T*)total);
     return DSA_OK;
@@ -332,8 +330,9 @@ DSA_EXPORT int dsa_vq_search(const void* x, const void* codebook, int64_t T, int
     if (int rc = vq_check(route, VQ_SEARCH, T, K, L, dtype)) return rc;
     if (T == 0) return DSA_OK;
     if (!(x && codebook && indices && partial)) return fail(DSA_ERR_INVALID_ARGUMENT, "vq: null pointer");
-    const int rc = dtype == DSA_F32 ? vq_search<float>(x, codebook, T, K, L, indices, xq, partial, total, scale, (hipStream_t)stream)
-                                    : vq_search<double>(x, codebook, T, K, L, indices, xq, partial, total, scale, (hipStream_t)stream);
+    const int rc = with_dtype(dtype, "vq", [&](auto tag) {
+        return vq_search<decltype(tag)>(x, codebook, T, K, L, indices, xq, partial, total, scale, (hipStream_t)stream);
+    });
     return rc ? rc : check_launch(route);
 }
 
@@ -350,8 +349,7 @@ DSA_EXPORT int dsa_vq_accum(const void* x, const void* indices, int64_t T, int64
     if (int rc = vq_check(route, VQ_ACCUM, T, K, L, dtype)) return rc;
     if (T == 0) return DSA_OK;
     if (!(x && indices && workspace)) return fail(DSA_ERR_INVALID_ARGUMENT, "vq: null pointer");
-    const int rc = dtype == DSA_F32 ? vq_accum<float>(x, indices, T, K, L, workspace, (hipStream_t)stream)
-                                    : vq_accum<double>(x, indices, T, K, L, workspace, (hipStream_t)stream);
+    const int rc = with_dtype(dtype, "vq", [&](auto tag) { return vq_accum<decltype(tag)>(x, indices, T, K, L, workspace, (hipStream_t)stream); });
     return rc ? rc : check_launch(route);
 }
 
@@ -381,13 +379,12 @@ DSA_EXPORT int dsa_vq_lookup(const void* indices, const void* codebook, int64_t 
     if (!(indices && codebook && xq)) return fail(DSA_ERR_INVALID_ARGUMENT, "vq: null pointer");
     const int64_t n = T * L;
     const dim3 grid((unsigned)((n + 255) / 256));
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((vq_lookup_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, (const int64_t*)indices, (const float*)codebook, (long)n,
-                           (int)K, (int)L, (float*)xq);
-    else
-        hipLaunchKernelGGL((vq_lookup_kernel<double>), grid, dim3(256), 0, (hipStream_t)stream, (const int64_t*)indices, (const float*)codebook, (long)n,
-                           (int)K, (int)L, (double*)xq);
-    return check_launch(route);
+    return with_dtype(dtype, "vq", [&](auto tag) {
+        using V = decltype(tag);   // (T is the entry's row count)
+        hipLaunchKernelGGL((vq_lookup_kernel<V>), grid, dim3(256), 0, (hipStream_t)stream, (const int64_t*)indices, (const float*)codebook, (long)n,
+                           (int)K, (int)L, (V*)xq);
+        return check_launch(route);
+    });
 }
 
 DSA_EXPORT int dsa_vq_vjp(const void* g_xq, const void* g_loss, const void* x, const void* xq, int64_t n, int32_t dtype, void* gx, void* stream)
@@ -397,11 +394,10 @@ DSA_EXPORT int dsa_vq_vjp(const void* g_xq, const void* g_loss, const void* x, c
     if (n == 0) return DSA_OK;
     if (!gx || (g_loss && !(x && xq))) return fail(DSA_ERR_INVALID_ARGUMENT, "vq: null pointer");
     const dim3 grid((unsigned)((n + 255) / 256));
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((vq_vjp_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)g_xq, (const float*)g_loss, (const float*)x,
-                           (const float*)xq, (long)n, (float*)gx);
-    else
-        hipLaunchKernelGGL((vq_vjp_kernel<double>), grid, dim3(256), 0, (hipStream_t)stream, (const double*)g_xq, (const double*)g_loss,
-                           (const double*)x, (const double*)xq, (long)n, (double*)gx);
-    return check_launch(route);
+    return with_dtype(dtype, "vq", [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((vq_vjp_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)g_xq, (const T*)g_loss, (const T*)x, (const T*)xq,
+                           (long)n, (T*)gx);
+        return check_launch(route);
+    });
 }

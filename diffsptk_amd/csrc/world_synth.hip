@@ -547,13 +547,10 @@ template <typename T>
 int ws_responses(const void* ap, const void* sp, const void* noise, const void* irec, const void* frec, const void* offsets, const void* remover,
                  const void* tw, int64_t B, int64_t N, int32_t sr, int32_t L, int64_t pulses, const WsPlan& plan, void* response, hipStream_t st)
 {
-    static std::atomic<uint64_t> done{0};
-    if (!ensure_dynamic_lds(reinterpret_cast<const void*>(&ws_responses_kernel<T>), DSA_WORLD_MAX_LDS_BYTES, done))
-        return fail(DSA_ERR_LAUNCH, "world_synth: cannot raise the dynamic LDS limit");
-    hipLaunchKernelGGL((ws_responses_kernel<T>), dim3((unsigned)pulses), dim3(plan.threads), plan.lds, st, (const T*)ap, (const T*)sp, (const T*)noise,
-                       (const int64_t*)irec, (const T*)frec, (const int64_t*)offsets, (const T*)remover, (const T*)tw, (long)B, (long)N, (int)L,
-                       plan.lg, (T)(kTau * (double)sr / (double)L), (T*)response);
-    return DSA_OK;
+    return launch_lds<ws_responses_kernel<T>>(DSA_WORLD_MAX_LDS_BYTES, "world_synth: cannot raise the dynamic LDS limit", dim3((unsigned)pulses),
+                                              dim3(plan.threads), plan.lds, st, (const T*)ap, (const T*)sp, (const T*)noise, (const int64_t*)irec,
+                                              (const T*)frec, (const int64_t*)offsets, (const T*)remover, (const T*)tw, (long)B, (long)N, (int)L,
+                                              plan.lg, (T)(kTau * (double)sr / (double)L), (T*)response);
 }
 
 template <typename T>
@@ -561,13 +558,10 @@ int ws_vjp_pulses(const void* gy, const void* ap, const void* sp, const void* no
                   const void* remover, const void* tw, int64_t B, int64_t N, int64_t Tout, int32_t sr, int32_t L, int64_t pulses, const WsPlan& plan,
                   void* grows, hipStream_t st)
 {
-    static std::atomic<uint64_t> done{0};
-    if (!ensure_dynamic_lds(reinterpret_cast<const void*>(&ws_vjp_pulses_kernel<T>), DSA_WORLD_MAX_LDS_BYTES, done))
-        return fail(DSA_ERR_LAUNCH, "world_synth: cannot raise the dynamic LDS limit");
-    hipLaunchKernelGGL((ws_vjp_pulses_kernel<T>), dim3((unsigned)pulses), dim3(plan.threads), plan.lds, st, (const T*)gy, (const T*)ap, (const T*)sp,
-                       (const T*)noise, (const int64_t*)irec, (const T*)frec, (const int64_t*)offsets, (const T*)remover, (const T*)tw, (long)B,
-                       (long)N, (long)Tout, (int)L, plan.lg, (T)(kTau * (double)sr / (double)L), (T*)grows);
-    return DSA_OK;
+    return launch_lds<ws_vjp_pulses_kernel<T>>(DSA_WORLD_MAX_LDS_BYTES, "world_synth: cannot raise the dynamic LDS limit", dim3((unsigned)pulses),
+                                               dim3(plan.threads), plan.lds, st, (const T*)gy, (const T*)ap, (const T*)sp, (const T*)noise,
+                                               (const int64_t*)irec, (const T*)frec, (const int64_t*)offsets, (const T*)remover, (const T*)tw, (long)B,
+                                               (long)N, (long)Tout, (int)L, plan.lg, (T)(kTau * (double)sr / (double)L), (T*)grows);
 }
 
 }  // namespace
@@ -585,8 +579,9 @@ DSA_EXPORT int dsa_world_synth_pulses(const void* f0, int64_t B, int64_t N, int3
     if (B == 0 || N == 0) return DSA_OK;
     if (!(f0 && counts) || ((irec || frec) && !(irec && frec && offsets))) return fail(DSA_ERR_INVALID_ARGUMENT, "world_synth: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    const int rc = dtype == DSA_F32 ? ws_pulses<float>(f0, B, N, P, sample_rate, L, default_f0, offsets, counts, irec, frec, st)
-                                    : ws_pulses<double>(f0, B, N, P, sample_rate, L, default_f0, offsets, counts, irec, frec, st);
+    const int rc = with_dtype(dtype, "world_synth", [&](auto tag) {
+        return ws_pulses<decltype(tag)>(f0, B, N, P, sample_rate, L, default_f0, offsets, counts, irec, frec, st);
+    });
     return rc ? rc : check_launch(kWsRoutes[WS_PULSES][dtype == DSA_F64]);
 }
 
@@ -601,10 +596,9 @@ DSA_EXPORT int dsa_world_synth_responses(const void* ap, const void* sp, const v
     if (!(ap && sp && noise && irec && frec && offsets && dc_remover && twiddle && response))
         return fail(DSA_ERR_INVALID_ARGUMENT, "world_synth: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    const int rc = dtype == DSA_F32 ? ws_responses<float>(ap, sp, noise, irec, frec, offsets, dc_remover, twiddle, B, N, sample_rate, L, pulses, plan,
-                                                          response, st)
-                                    : ws_responses<double>(ap, sp, noise, irec, frec, offsets, dc_remover, twiddle, B, N, sample_rate, L, pulses, plan,
-                                                           response, st);
+    const int rc = with_dtype(dtype, "world_synth", [&](auto tag) {
+        return ws_responses<decltype(tag)>(ap, sp, noise, irec, frec, offsets, dc_remover, twiddle, B, N, sample_rate, L, pulses, plan, response, st);
+    });
     return rc ? rc : check_launch(kWsRoutes[WS_RESPONSES][dtype == DSA_F64]);
 }
 
@@ -618,13 +612,12 @@ DSA_EXPORT int dsa_world_synth_overlap_add(const void* response, const void* ire
     if (!(offsets && y) || (pulses > 0 && !(response && irec))) return fail(DSA_ERR_INVALID_ARGUMENT, "world_synth: null pointer");
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)((T + WS_THREADS - 1) / WS_THREADS), (unsigned)B);
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((ws_overlap_kernel<float>), grid, dim3(WS_THREADS), 0, st, (const float*)response, (const int64_t*)irec,
-                           (const int64_t*)offsets, (long)T, (int)L, (float*)y);
-    else
-        hipLaunchKernelGGL((ws_overlap_kernel<double>), grid, dim3(WS_THREADS), 0, st, (const double*)response, (const int64_t*)irec,
-                           (const int64_t*)offsets, (long)T, (int)L, (double*)y);
-    return check_launch(kWsRoutes[WS_OVERLAP_ADD][dtype == DSA_F64]);
+    return with_dtype(dtype, "world_synth", [&](auto tag) {
+        using V = decltype(tag);   // (T is the entry's length)
+        hipLaunchKernelGGL((ws_overlap_kernel<V>), grid, dim3(WS_THREADS), 0, st, (const V*)response, (const int64_t*)irec, (const int64_t*)offsets,
+                           (long)T, (int)L, (V*)y);
+        return check_launch(kWsRoutes[WS_OVERLAP_ADD][dtype == DSA_F64]);
+    });
 }
 
 DSA_EXPORT int dsa_world_synth_vjp_pulses(const void* gy, const void* ap, const void* sp, const void* noise, const void* irec, const void* frec,
@@ -638,10 +631,9 @@ DSA_EXPORT int dsa_world_synth_vjp_pulses(const void* gy, const void* ap, const 
     if (!(ap && sp && noise && irec && frec && offsets && dc_remover && twiddle && grows) || (T > 0 && !gy))
         return fail(DSA_ERR_INVALID_ARGUMENT, "world_synth: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    const int rc = dtype == DSA_F32 ? ws_vjp_pulses<float>(gy, ap, sp, noise, irec, frec, offsets, dc_remover, twiddle, B, N, T, sample_rate, L, pulses,
-                                                           plan, grows, st)
-                                    : ws_vjp_pulses<double>(gy, ap, sp, noise, irec, frec, offsets, dc_remover, twiddle, B, N, T, sample_rate, L, pulses,
-                                                            plan, grows, st);
+    const int rc = with_dtype(dtype, "world_synth", [&](auto tag) {
+        return ws_vjp_pulses<decltype(tag)>(gy, ap, sp, noise, irec, frec, offsets, dc_remover, twiddle, B, N, T, sample_rate, L, pulses, plan, grows, st);
+    });
     return rc ? rc : check_launch(kWsRoutes[WS_VJP_PULSES][dtype == DSA_F64]);
 }
 
@@ -655,11 +647,10 @@ DSA_EXPORT int dsa_world_synth_vjp_frames(const void* grows, const void* ap, con
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)N, (unsigned)B);
     const int D = L / 2 + 1;
-    if (dtype == DSA_F32)
-        hipLaunchKernelGGL((ws_vjp_frames_kernel<float>), grid, dim3(WS_THREADS), 0, st, (const float*)grows, (const float*)ap, (const float*)sp,
-                           (const int64_t*)irec, (const float*)frec, (const int64_t*)offsets, (long)N, D, (float*)gap, (float*)gsp);
-    else
-        hipLaunchKernelGGL((ws_vjp_frames_kernel<double>), grid, dim3(WS_THREADS), 0, st, (const double*)grows, (const double*)ap, (const double*)sp,
-                           (const int64_t*)irec, (const double*)frec, (const int64_t*)offsets, (long)N, D, (double*)gap, (double*)gsp);
-    return check_launch(kWsRoutes[WS_VJP_FRAMES][dtype == DSA_F64]);
+    return with_dtype(dtype, "world_synth", [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((ws_vjp_frames_kernel<T>), grid, dim3(WS_THREADS), 0, st, (const T*)grows, (const T*)ap, (const T*)sp, (const int64_t*)irec,
+                           (const T*)frec, (const int64_t*)offsets, (long)N, D, (T*)gap, (T*)gsp);
+        return check_launch(kWsRoutes[WS_VJP_FRAMES][dtype == DSA_F64]);
+    });
 }

@@ -488,27 +488,23 @@ inline YinFftPlan yin_fft_plan(int64_t L, int64_t K, size_t size)
     return p;
 }
 
+constexpr const char* kYinLdsError = "yingram: cannot raise the dynamic LDS limit";
+
 template <typename T>
 int yin_forward(const YinSource<T>& src, int64_t F, int64_t L, int64_t K, int64_t M, const void* lags, const void* fl, const void* ce,
                 const void* tw, int fft, void* y, hipStream_t st)
 {
     if (fft) {
-        static std::atomic<uint64_t> done{0};
-        if (!ensure_dynamic_lds(reinterpret_cast<const void*>(&yin_fft_kernel<T>), DSA_YINGRAM_MAX_LDS_BYTES, done))
-            return fail(DSA_ERR_LAUNCH, "yingram: cannot raise the dynamic LDS limit");
         const YinFftPlan p = yin_fft_plan(L, K, sizeof(T));
-        hipLaunchKernelGGL((yin_fft_kernel<T>), dim3((unsigned)F), dim3(p.threads), p.lds, st, src, (int)L, (int)K, (int)M, p.H, p.lg,
-                           (const T*)tw, (const T*)lags, (const int64_t*)fl, (const int64_t*)ce, (T*)y);
-        return DSA_OK;
+        return launch_lds<yin_fft_kernel<T>>(DSA_YINGRAM_MAX_LDS_BYTES, kYinLdsError, dim3((unsigned)F), dim3(p.threads), p.lds, st,
+                                             src, (int)L, (int)K, (int)M, p.H, p.lg, (const T*)tw, (const T*)lags, (const int64_t*)fl, (const int64_t*)ce,
+                                             (T*)y);
     }
-    static std::atomic<uint64_t> done{0};
-    if (!ensure_dynamic_lds(reinterpret_cast<const void*>(&yin_direct_kernel<T>), DSA_YINGRAM_MAX_LDS_BYTES, done))
-        return fail(DSA_ERR_LAUNCH, "yingram: cannot raise the dynamic LDS limit");
     const int team = yin_team(K), G = YIN_DIRECT_THREADS / team;
     const size_t lds = (size_t)G * (YIN_RED * 8 + (size_t)(L + K) * sizeof(T));
-    hipLaunchKernelGGL((yin_direct_kernel<T>), dim3((unsigned)((F + G - 1) / G)), dim3(YIN_DIRECT_THREADS), lds, st, src, (long)F, (int)L, (int)K,
-                       (int)M, (const T*)lags, (const int64_t*)fl, (const int64_t*)ce, team, (T*)y);
-    return DSA_OK;
+    return launch_lds<yin_direct_kernel<T>>(DSA_YINGRAM_MAX_LDS_BYTES, kYinLdsError, dim3((unsigned)((F + G - 1) / G)),
+                                            dim3(YIN_DIRECT_THREADS), lds, st, src, (long)F, (int)L, (int)K, (int)M, (const T*)lags, (const int64_t*)fl,
+                                            (const int64_t*)ce, team, (T*)y);
 }
 
 template <typename T>
@@ -516,22 +512,16 @@ int yin_backward(const void* gy, const void* x, int64_t F, int64_t L, int64_t K,
                  const void* tw, int fft, void* gx, hipStream_t st)
 {
     if (fft) {
-        static std::atomic<uint64_t> done{0};
-        if (!ensure_dynamic_lds(reinterpret_cast<const void*>(&yin_vjp_fft_kernel<T>), DSA_YINGRAM_MAX_LDS_BYTES, done))
-            return fail(DSA_ERR_LAUNCH, "yingram: cannot raise the dynamic LDS limit");
         const YinFftPlan p = yin_fft_plan(L, K, sizeof(T));
-        hipLaunchKernelGGL((yin_vjp_fft_kernel<T>), dim3((unsigned)F), dim3(p.threads), p.lds, st, (const T*)x, (const T*)gy, (int)L, (int)K, (int)M,
-                           p.H, p.lg, (const T*)tw, (const T*)lags, (const int64_t*)fl, (const int64_t*)ce, (T*)gx);
-        return DSA_OK;
+        return launch_lds<yin_vjp_fft_kernel<T>>(DSA_YINGRAM_MAX_LDS_BYTES, kYinLdsError, dim3((unsigned)F), dim3(p.threads), p.lds,
+                                                 st, (const T*)x, (const T*)gy, (int)L, (int)K, (int)M, p.H, p.lg, (const T*)tw, (const T*)lags,
+                                                 (const int64_t*)fl, (const int64_t*)ce, (T*)gx);
     }
-    static std::atomic<uint64_t> done{0};
-    if (!ensure_dynamic_lds(reinterpret_cast<const void*>(&yin_vjp_direct_kernel<T>), DSA_YINGRAM_MAX_LDS_BYTES, done))
-        return fail(DSA_ERR_LAUNCH, "yingram: cannot raise the dynamic LDS limit");
     const int team = yin_team(K), G = YIN_DIRECT_THREADS / team;
     const size_t lds = (size_t)G * (YIN_RED * 8 + (size_t)(L + 2 * K) * sizeof(T));
-    hipLaunchKernelGGL((yin_vjp_direct_kernel<T>), dim3((unsigned)((F + G - 1) / G)), dim3(YIN_DIRECT_THREADS), lds, st, (const T*)x, (const T*)gy,
-                       (long)F, (int)L, (int)K, (int)M, (const T*)lags, (const int64_t*)fl, (const int64_t*)ce, team, (T*)gx);
-    return DSA_OK;
+    return launch_lds<yin_vjp_direct_kernel<T>>(DSA_YINGRAM_MAX_LDS_BYTES, kYinLdsError, dim3((unsigned)((F + G - 1) / G)),
+                                                dim3(YIN_DIRECT_THREADS), lds, st, (const T*)x, (const T*)gy, (long)F, (int)L, (int)K, (int)M,
+                                                (const T*)lags, (const int64_t*)fl, (const int64_t*)ce, team, (T*)gx);
 }
 
 template <typename T>
@@ -553,10 +543,10 @@ DSA_EXPORT int dsa_yingram(const void* x, int64_t F, int32_t L, int32_t lag_max,
     if (int rc = yin_check(route, fft, YIN_FWD, F, L, lag_max, M, algo, dtype)) return rc;
     if (F == 0 || M == 0) return DSA_OK;
     if (!(x && lags && lags_floor && lags_ceil && y) || (fft && !twiddle)) return fail(DSA_ERR_INVALID_ARGUMENT, "yingram: null pointer");
-    const int rc = dtype == DSA_F32 ? yin_forward<float>(yin_source<float>(x, 0, 1, L, 1, 0, 0), F, L, lag_max, M, lags, lags_floor, lags_ceil,
-                                                         twiddle, fft, y, (hipStream_t)stream)
-                                    : yin_forward<double>(yin_source<double>(x, 0, 1, L, 1, 0, 0), F, L, lag_max, M, lags, lags_floor, lags_ceil,
-                                                          twiddle, fft, y, (hipStream_t)stream);
+    const int rc = with_dtype(dtype, "yingram", [&](auto tag) {
+        using T = decltype(tag);
+        return yin_forward<T>(yin_source<T>(x, 0, 1, L, 1, 0, 0), F, L, lag_max, M, lags, lags_floor, lags_ceil, twiddle, fft, y, (hipStream_t)stream);
+    });
     return rc ? rc : check_launch(route);
 }
 
@@ -569,8 +559,9 @@ DSA_EXPORT int dsa_yingram_vjp(const void* gy, const void* x, int64_t F, int32_t
     if (F == 0) return DSA_OK;
     if (!(x && gx) || (M > 0 && !(gy && lags && lags_floor && lags_ceil)) || (fft && !twiddle))
         return fail(DSA_ERR_INVALID_ARGUMENT, "yingram: null pointer");
-    const int rc = dtype == DSA_F32 ? yin_backward<float>(gy, x, F, L, lag_max, M, lags, lags_floor, lags_ceil, twiddle, fft, gx, (hipStream_t)stream)
-                                    : yin_backward<double>(gy, x, F, L, lag_max, M, lags, lags_floor, lags_ceil, twiddle, fft, gx, (hipStream_t)stream);
+    const int rc = with_dtype(dtype, "yingram", [&](auto tag) {
+        return yin_backward<decltype(tag)>(gy, x, F, L, lag_max, M, lags, lags_floor, lags_ceil, twiddle, fft, gx, (hipStream_t)stream);
+    });
     return rc ? rc : check_launch(route);
 }
 
@@ -588,9 +579,9 @@ DSA_EXPORT int dsa_frame_yingram(const void* x, int64_t B, int64_t T, int32_t L,
     if (F == 0 || M == 0) return DSA_OK;
     if (!(x && lags && lags_floor && lags_ceil && y) || (fft && !twiddle)) return fail(DSA_ERR_INVALID_ARGUMENT, "yingram: null pointer");
     const int left = center ? L / 2 : 0;
-    const int rc = dtype == DSA_F32 ? yin_forward<float>(yin_source<float>(x, T, N, L, P, left, 1), F, L, lag_max, M, lags, lags_floor, lags_ceil,
-                                                         twiddle, fft, y, (hipStream_t)stream)
-                                    : yin_forward<double>(yin_source<double>(x, T, N, L, P, left, 1), F, L, lag_max, M, lags, lags_floor,
-                                                          lags_ceil, twiddle, fft, y, (hipStream_t)stream);
+    const int rc = with_dtype(dtype, "yingram", [&](auto tag) {
+        using V = decltype(tag);   // (T is the entry's signal length)
+        return yin_forward<V>(yin_source<V>(x, T, N, L, P, left, 1), F, L, lag_max, M, lags, lags_floor, lags_ceil, twiddle, fft, y, (hipStream_t)stream);
+    });
     return rc ? rc : check_launch(route);
 }

@@ -851,9 +851,9 @@ DSA_EXPORT int dsa_zerodf_fwd(const void* x, const void* b, int64_t B, int64_t T
     DSA_REQUIRE(T % P == 0, "zerodf: the sequence length must be frames x frame_period");
     if (B * T == 0) return DSA_OK;
     const int64_t N = T / P;
-    if (dtype == DSA_F32) return zerodf_launch_fwd<float>(x, b, B, T, N, M, P, zeroth_index, ignore_gain, y, (hipStream_t)stream);
-    if (dtype == DSA_F64) return zerodf_launch_fwd<double>(x, b, B, T, N, M, P, zeroth_index, ignore_gain, y, (hipStream_t)stream);
-    return fail(DSA_ERR_UNSUPPORTED, "zerodf: unsupported dtype%s");
+    return with_dtype(dtype, "zerodf", [&](auto tag) {
+        return zerodf_launch_fwd<decltype(tag)>(x, b, B, T, N, M, P, zeroth_index, ignore_gain, y, (hipStream_t)stream);
+    });
 }
 
 DSA_EXPORT int dsa_zerodf_taylor_fwd(const void* x, const void* b, int64_t B, int64_t T, int32_t M, int32_t P, int32_t zeroth_index,
@@ -865,11 +865,9 @@ DSA_EXPORT int dsa_zerodf_taylor_fwd(const void* x, const void* b, int64_t B, in
     DSA_REQUIRE((acc != nullptr) == (ysum != nullptr), "zerodf_taylor: acc and ysum come together");
     DSA_REQUIRE(y != nullptr || ysum != nullptr, "zerodf_taylor: no output");
     const int64_t N = T / P;
-    if (dtype == DSA_F32)
-        return zerodf_launch_fwd<float>(x, b, B, T, N, M, P, zeroth_index, 0, y, (hipStream_t)stream, scale, acc, ysum);
-    if (dtype == DSA_F64)
-        return zerodf_launch_fwd<double>(x, b, B, T, N, M, P, zeroth_index, 0, y, (hipStream_t)stream, scale, acc, ysum);
-    return fail(DSA_ERR_UNSUPPORTED, "zerodf_taylor: unsupported dtype%s");
+    return with_dtype(dtype, "zerodf_taylor", [&](auto tag) {
+        return zerodf_launch_fwd<decltype(tag)>(x, b, B, T, N, M, P, zeroth_index, 0, y, (hipStream_t)stream, scale, acc, ysum);
+    });
 }
 
 DSA_EXPORT int dsa_zerodf_bwd(const void* gy, const void* x, const void* b, const void* y, int64_t B, int64_t T, int32_t M, int32_t P,
@@ -878,11 +876,9 @@ DSA_EXPORT int dsa_zerodf_bwd(const void* gy, const void* x, const void* b, cons
     DSA_REQUIRE(M >= 0 && P > 0 && B >= 0 && T >= 0 && zeroth_index >= 0 && zeroth_index <= M && T % P == 0, "zerodf_bwd: invalid sizes");
     if (B * T == 0) return DSA_OK;
     const int64_t N = T / P;
-    if (dtype == DSA_F32)
-        return zerodf_launch_bwd<float>(gy, x, b, y, B, T, N, M, P, zeroth_index, ignore_gain, gx, gb, (hipStream_t)stream);
-    if (dtype == DSA_F64)
-        return zerodf_launch_bwd<double>(gy, x, b, y, B, T, N, M, P, zeroth_index, ignore_gain, gx, gb, (hipStream_t)stream);
-    return fail(DSA_ERR_UNSUPPORTED, "zerodf_bwd: unsupported dtype%s");
+    return with_dtype(dtype, "zerodf_bwd", [&](auto tag) {
+        return zerodf_launch_bwd<decltype(tag)>(gy, x, b, y, B, T, N, M, P, zeroth_index, ignore_gain, gx, gb, (hipStream_t)stream);
+    });
 }
 
 DSA_EXPORT int dsa_zerodf_taylor_bwd(const void* G, const void* x, const void* b, int64_t B, int64_t T, int32_t M, int32_t P,
@@ -893,9 +889,7 @@ DSA_EXPORT int dsa_zerodf_taylor_bwd(const void* G, const void* x, const void* b
     if (B * T == 0) return DSA_OK;
     DSA_REQUIRE(G_out != nullptr && G_out != G, "zerodf_taylor_bwd: G_out must be a buffer of its own");
     const int64_t N = T / P;
-    if (dtype == DSA_F32)
-        return zerodf_launch_bwd<float>(G, x, b, nullptr, B, T, N, M, P, zeroth_index, 0, G_out, gb, (hipStream_t)stream, scale, gy, true);
-    if (dtype == DSA_F64)
-        return zerodf_launch_bwd<double>(G, x, b, nullptr, B, T, N, M, P, zeroth_index, 0, G_out, gb, (hipStream_t)stream, scale, gy, true);
-    return fail(DSA_ERR_UNSUPPORTED, "zerodf_taylor_bwd: unsupported dtype%s");
+    return with_dtype(dtype, "zerodf_taylor_bwd", [&](auto tag) {
+        return zerodf_launch_bwd<decltype(tag)>(G, x, b, nullptr, B, T, N, M, P, zeroth_index, 0, G_out, gb, (hipStream_t)stream, scale, gy, true);
+    });
 }

@@ -423,12 +423,8 @@ LDS_FIXED = {
 # can reach meets it.  tests/test_routes_cpu.py holds the three tables against the sources.
 DTYPE = "ops._core._dtype_code raises TypeError for anything but float32 / float64 before the entry is called"
 NOT_A_CEILING = {
-    **{f"{n}: unsupported dtype": DTYPE for n in (
-        "fbank", "fbank_bwd", "fftcep", "fftcep_bwd", "irfft_scale", "div_rows", "griffin_update", "acorr", "acorr_bwd", "levdur", "levdur_bwd",
-        "lpc", "lpc_bwd", "frame_window_lpc", "freqt", "freqt_bwd", "mcep", "mcep_bwd", "gnorm", "mgcep_gain", "mgcep_spectra", "plp", "plp_bwd",
-        "poledf", "poledf_bwd", "pqmf", "pqmf_bwd", "ipqmf", "ipqmf_bwd", "interpolate", "interpolate_bwd", "frame", "frame_bwd", "window",
-        "window_bwd", "fftr", "fftr_bwd", "spec", "spec_bwd", "stft", "stft_bwd", "thsolve", "thsolve_bwd", "zerodf", "zerodf_taylor", "zerodf_bwd",
-        "zerodf_taylor_bwd", "%s")},   # ("%s": the shared launchers of csrc/lsp.hip and csrc/parcor.hip)
+    # with_dtype of csrc/common.h, which speaks every entry's dtype refusal under the entry's name (tests/test_dtype_refusals_cpu.py calls each)
+    "%s: unsupported dtype": DTYPE,
     "fbank_bins_bwd: float32 only (the fused forward it differentiates is)": "ops.StftFbankFn is the only caller and FusedSTFTFilterBank._fusable "
         "admits float32 only",
     "mcep_newton_update: float32 only": "ops.mcep._mcep_composed_applies admits float32 only",
@@ -604,7 +600,6 @@ FORWARDED = {
     "mlsacheck_generic_fwd": "csrc/mlsacheck.hip::mlsacheck_generic_launch", "mlsacheck_generic_bwd": "csrc/mlsacheck.hip::mlsacheck_generic_launch",
     "fbank_mfma_fwd": "csrc/fbank.hip::fbank_mfma_launch", "fbank_dct_mfma_fwd": "csrc/fbank.hip::dsa_fbank_dct_fwd", "freqt_mfma_fwd": "csrc/mcep.hip::dsa_freqt_fwd",
     "fftcep_mfma_fwd": "csrc/fftcep.hip::dsa_fftcep_fwd",
-    "frame_window_lpc24_mfma_fwd": "csrc/lpc24.hip::lpc24_fwd", "frame_window_lpc24_bwd_mfma": "csrc/lpc24_bwd.hip::dsa_frame_window_lpc_bwd",
 }
 
 EXEMPT = {

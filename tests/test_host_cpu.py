@@ -394,13 +394,17 @@ def test_every_csrc_header_compiles_alone():
 def test_shared_device_helpers_are_not_copied():
     """The builtins that the shared device helpers of csrc/common.h wrap -- wave_readlane, rn_mul / rn_add / rn_sub / rn_div,
     fft_brev -- appear in no other file of csrc/ (read as text): a unit that needs one calls the helper and does not bring a
-    copy under a prefix of its own.  The exceptions are listed by file and builtin, each with its reason."""
+    copy under a prefix of its own.  The same for the host helpers: the dynamic-LDS attribute and its per-device record belong to
+    launch_lds, the dtype refusal to with_dtype.  The exceptions are listed by file and pattern, each with its reason."""
     from diffsptk_amd import _lib
 
     primitives = {
         "readlane": r"\b__builtin_amdgcn_readlane\b",
         "rn": r"\b__[fd](?:mul|add|sub|div)_rn\b",
         "brev": r"\b__brev\b",
+        "lds_attribute": r"\bhipFuncAttributeMaxDynamicSharedMemorySize\b",
+        "lds_record": r"\bensure_dynamic_lds\(",
+        "dtype_refusal": r': unsupported dtype(?:%s)?"',
     }
     allowed = {
         # the one read of the wave's maximum inside the tuned lpc24 kernels, spelled as it was when they were tuned
@@ -409,6 +413,9 @@ def test_shared_device_helpers_are_not_copied():
         ("th_solve_reg.h", "readlane"),
         # pg_lane(double): with wave_readlane's spelling the compiler schedules mlpg_sweep_kernel<double, 0> differently
         ("paramgen.hip", "readlane"),
+        # mcep_generic_fwd / _bwd: a size that grows with the call, set again on every launch above 48 KB -- launch_lds reserves one
+        # size once per device, which a later, larger call would not raise
+        ("mcep.hip", "lds_attribute"),
     }
     files = sorted(f for f in os.listdir(_lib.CSRC) if f.endswith((".hip", ".h")))
     assert len(files) >= 55 and "common.h" in files

@@ -210,7 +210,8 @@ def test_the_site_pattern_still_finds_the_messages(texts=TEXTS):
     # every other mention of the status in code (not behind //) is a comparison `== DSA_ERR_UNSUPPORTED)`: a site spelled in a way the
     # patterns above do not know would show as a difference here
     n_all = sum(len(re.findall(r"^[^/\n]*?(?<![=!] )\bDSA_ERR_UNSUPPORTED\b(?! *\))", text, re.M)) for text in texts.values())
-    assert n_found > 100 and n_found == n_all, (n_found, n_all)
+    # (73 sites since the 55 spellings of the dtype refusal became the one of csrc/common.h; the floor only says that the pattern works)
+    assert n_found > 60 and n_found == n_all, (n_found, n_all)
 
 
 def test_every_unsupported_site_is_in_exactly_one_table(texts=TEXTS):
