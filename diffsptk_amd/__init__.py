@@ -22,6 +22,7 @@ from .modules import __all__ as _module_names
 # exported from here and not from diffsptk_amd.modules: every name of modules.__all__ needs a row in the alignment sweep's table
 # (tests/alignment_rows.py); the change that adds that row moves the name into modules.__all__
 from .modules.ap import Aperiodicity
+from .modules.pitch_spec import PitchAdaptiveSpectralAnalysis
 from .modules.delta import Delta
 from .modules.dtw import DynamicTimeWarping
 from .modules.dtw import DynamicTimeWarping as DTW
@@ -52,4 +53,4 @@ __all__ = [*_module_names, "functional", "get_alpha", "read", "write", "Graphed"
            "ExcitationGeneration", "mseq", "mseq_like", "nrand", "MDCT", "IMDCT", "MDST", "IMDST", "ModifiedDiscreteCosineTransform",
            "InverseModifiedDiscreteCosineTransform", "ModifiedDiscreteSineTransform", "InverseModifiedDiscreteSineTransform", "Delta", "MLPG",
            "MaximumLikelihoodParameterGeneration", "MelCepstrumPostfiltering", "DynamicTimeWarping", "DTW", "GaussianMixtureModeling", "GMM", "Yingram",
-           "VectorQuantization", "InverseVectorQuantization", "LindeBuzoGrayAlgorithm", "LBG", "WorldSynthesis", "Aperiodicity"]
+           "VectorQuantization", "InverseVectorQuantization", "LindeBuzoGrayAlgorithm", "LBG", "WorldSynthesis", "Aperiodicity", "PitchAdaptiveSpectralAnalysis"]

@@ -19,7 +19,7 @@ LIB_DIR = os.path.join(_PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libdiffsptk_amd.so")
 SOURCES = ("core.hip", "stft.hip", "spec.hip", "griffin.hip", "mcep.hip", "mcep_mfma.hip", "mcep_mfma_bwd.hip", "mgcep_step.hip", "mcep_resid.hip", "mcep_big.hip", "lpc.hip", "lpc24.hip", "lpc24_bwd.hip", "fbank.hip", "fftcep.hip", "mgc.hip", "thsolve.hip",
            "zerodf.hip", "rows_gemm.hip", "thsolve_quad.hip", "poledf.hip", "plp.hip", "pqmf.hip", "parcor.hip", "lsp.hip", "mlsacheck.hip", "excite.hip", "mdct.hip",
-           "paramgen.hip", "dtw.hip", "gmm.hip", "yingram.hip", "vq.hip", "world_synth.hip", "ap.hip")
+           "paramgen.hip", "dtw.hip", "gmm.hip", "yingram.hip", "vq.hip", "world_synth.hip", "ap.hip", "pitch_spec.hip")
 HIPCC_FLAGS = (
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
     "-mcode-object-version=5", "-Wno-unused-value", "-ffp-contract=on",
@@ -56,6 +56,7 @@ SOURCE_FLAGS = {
     "vq.hip": _NO_PK,
     "world_synth.hip": _NO_PK,
     "ap.hip": _NO_PK,
+    "pitch_spec.hip": _NO_PK,
     # the mel-cepstral units: their kernels carry DSA_PK_TARGET -- measured faster with the compiler's pairing -- except mgcep_step_h
     "mcep_mfma.hip": _NO_PK,
     "mcep_mfma_bwd.hip": _NO_PK,

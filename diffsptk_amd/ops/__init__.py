@@ -7,7 +7,7 @@ section 3.5, is replaced by the hand-written backward kernels).
 `ops.<name>` resolves for every name of every module below.  That is a copy of the binding: to CHANGE a tunable that is read at
 call time (MCEP_GLOGX_MIN_FRAMES, MCEP_HIST_RT_MAX_BYTES), set it on the module that reads it, `ops.mcep`.
 """
-from . import _core, rows, stft, fbank, lpc, filters, mgc, mcep, mdct, paramgen, dtw, gmm, yingram, vq, world, ap   # import order: _core <- the families <- mcep (uses rows, mgc)
+from . import _core, rows, stft, fbank, lpc, filters, mgc, mcep, mdct, paramgen, dtw, gmm, yingram, vq, world, ap, pitch_spec   # import order: _core <- the families <- mcep (uses rows, mgc)
 
-for _m in (_core, rows, stft, fbank, lpc, filters, mgc, mcep, mdct, paramgen, dtw, gmm, yingram, vq, world, ap):
+for _m in (_core, rows, stft, fbank, lpc, filters, mgc, mcep, mdct, paramgen, dtw, gmm, yingram, vq, world, ap, pitch_spec):
     globals().update({_n: _v for _n, _v in vars(_m).items() if not _n.startswith("__")})
