@@ -16,7 +16,7 @@
 //               cotangent to the bin of the maximum), 2 X g through a fourth ... sixth transform, the mean removal and the window.  The frame's
 //               cotangent, L float64 values that are zero outside |j| <= h, goes to the caller's scratch.
 //   gather      one thread per waveform sample adds, in ascending frame order, the frames that cover it; two more workgroups sum what the
-//               replicate padding sent to the first and the last sample.  No atomics.
+//               replicate padding sent to the first and the last sample (with one sample, the first of the two sums all L columns).  No atomics.
 //
 // LDS, in float64 words: the transform's two arrays of L, the kept spectrum (2 K), the smoothed spectrum (K) and 32 words for the reductions:
 // DSA_PITCH_SPEC_LDS_BYTES(L) = 28 L + 280.
@@ -299,7 +299,8 @@ __global__ __launch_bounds__(PS_THREADS) void ps_gather_kernel(const double* __r
         return;
     }
     const bool head = blockIdx.x == blocks;
-    if (!head && Tlen == 1) return;   // one sample: the head's workgroup has it all
+    const bool one = Tlen == 1;   // one sample: the padding clamps every column to it, on both sides, and the head's workgroup takes them all
+    if (!head && one) return;
     long n0 = 0, n1 = half / P;
     if (!head) {
         n0 = Tlen - half <= 0 ? 0 : (Tlen - half + P - 1) / P;
@@ -310,7 +311,7 @@ __global__ __launch_bounds__(PS_THREADS) void ps_gather_kernel(const double* __r
     double acc = 0;
     for (long i = threadIdx.x; i < items; i += PS_THREADS) {
         const long n = n0 + i / L, c = i % L, at = n * P + c - half;
-        if (head ? at <= 0 : at >= Tlen - 1) acc += g[n * L + c];
+        if (head ? at <= 0 || one : at >= Tlen - 1) acc += g[n * L + c];
     }
     acc = block_sum(acc, red);
     if (threadIdx.x == 0) out[head ? 0 : Tlen - 1] = (T)acc;

@@ -50,7 +50,7 @@
 extern "C" {
 #endif
 
-#define DSA_VERSION 147 /* 0.4.1: + dsa_pitch_spec / dsa_pitch_spec_vjp_frames / dsa_pitch_spec_vjp_gather (the pitch-adaptive spectral envelope of CheapTrick: a frame from the waveform to the formatted envelope in one workgroup and one launch, float64 inside, and the adjoint down to the waveform in two launches without atomics); 0.4.0: + dsa_ap_qmf / dsa_ap_qmf_vjp / dsa_ap_tandem / dsa_ap_tandem_vjp (band aperiodicity by TANDEM-STRAIGHT: a level of the QMF pyramid and its transpose, the per-band least-squares fits of a frame with their own regulariser escalation and the interpolated, clipped output in one launch, and the adjoint down to the band signals without atomics); 0.3.9: + dsa_world_synth_pulses / dsa_world_synth_responses / dsa_world_synth_overlap_add / dsa_world_synth_vjp_pulses / dsa_world_synth_vjp_frames (WORLD synthesis: the time base and pulse list of an utterance in one workgroup, a pulse's periodic and aperiodic response through four complex transforms in LDS, the overlap-add as a gather, and the adjoint down to sp and ap in two launches); 0.3.8: + DSA_ALGO_FULL_CHAINS (the tuned mel-cepstral forward runs the first clamp(n_iter - 6, 0, 2) Newton steps on one-term binary16 chains; the flag keeps every step on three terms); 0.3.7: + dsa_vq_search / dsa_vq_accum / dsa_vq_update / dsa_vq_lookup / dsa_vq_vjp (vector quantisation and the Linde-Buzo-Gray codebook design: nearest-codeword search on float64 sums, per-codeword counts and float64 sums in fixed-order segments without atomics, centroids with the iteration's three scalars, the lookup and the quantiser's adjoint); 0.3.6: + dsa_yingram / dsa_yingram_vjp / dsa_frame_yingram (Yingram: YIN's cumulative-mean-normalised difference function on a semitone grid, from frames or from the waveform in one launch, and its adjoint; lag sums directly or through the LDS transform); 0.3.5: + dsa_gmm_prepare / dsa_gmm_estep / dsa_gmm_accum / dsa_gmm_update / dsa_gmm_regress / dsa_gmm_transform (Gaussian mixture models: one EM iteration as factorisation, E-step, weighted moment sums and M-step on the device, and the conversion of a joint-density model); 0.3.4: + dsa_dtw / dsa_dtw_vjp / dsa_dtw_path (dynamic time warping with a soft minimum: the aligned distance of two vector sequences by an anti-diagonal wavefront, its gradient by the reverse sweep, the Viterbi path from the saved tables); 0.3.3: + DSA_ALGO_FIXED_STEPS (the tuned mel-cepstral forward stops a frame's Newton iteration once its update is rounding noise; the flag runs every step); 0.3.2: + dsa_delta / dsa_delta_vjp, dsa_mlpg, dsa_mcpf / dsa_mcpf_vjp (parameter generation: delta features, maximum likelihood parameter generation by a banded Cholesky solve, mel-cepstrum postfiltering in closed form); 0.3.1: + dsa_mdct_analysis / dsa_mdct_synthesis (MDCT / MDST and their inverses: window, fold, DCT-IV through a quarter-length complex FFT and overlap-add in one launch each way; each is the other's adjoint); 0.3.0: + dsa_excite (pitch to excitation: the voiced shapes of ExcitationGeneration on a segmented float64 phase sum, one launch); 0.2.9: + dsa_mlsacheck / dsa_mlsacheck_vjp (the stability check of the MLSA filter: the mel-cepstrum scaled or clipped where the amplitude of its gain-free part passes the threshold of the Pade approximation, forward and adjoint); 0.2.8: + dsa_lpc2lsp_fwd / _bwd, dsa_lsp2lpc_fwd / _bwd, dsa_lspcheck_fwd / _bwd (line spectral pairs by a Chebyshev-series root search, back by a product of real sections, and their stability check, forward and adjoint); 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
+#define DSA_VERSION 148 /* 0.4.2: dsa_pitch_spec_vjp_gather with T = 1 sums every column of the one frame (the replicate padding clamps them all to the one sample; 147 dropped the columns behind the middle); 0.4.1: + dsa_pitch_spec / dsa_pitch_spec_vjp_frames / dsa_pitch_spec_vjp_gather (the pitch-adaptive spectral envelope of CheapTrick: a frame from the waveform to the formatted envelope in one workgroup and one launch, float64 inside, and the adjoint down to the waveform in two launches without atomics); 0.4.0: + dsa_ap_qmf / dsa_ap_qmf_vjp / dsa_ap_tandem / dsa_ap_tandem_vjp (band aperiodicity by TANDEM-STRAIGHT: a level of the QMF pyramid and its transpose, the per-band least-squares fits of a frame with their own regulariser escalation and the interpolated, clipped output in one launch, and the adjoint down to the band signals without atomics); 0.3.9: + dsa_world_synth_pulses / dsa_world_synth_responses / dsa_world_synth_overlap_add / dsa_world_synth_vjp_pulses / dsa_world_synth_vjp_frames (WORLD synthesis: the time base and pulse list of an utterance in one workgroup, a pulse's periodic and aperiodic response through four complex transforms in LDS, the overlap-add as a gather, and the adjoint down to sp and ap in two launches); 0.3.8: + DSA_ALGO_FULL_CHAINS (the tuned mel-cepstral forward runs the first clamp(n_iter - 6, 0, 2) Newton steps on one-term binary16 chains; the flag keeps every step on three terms); 0.3.7: + dsa_vq_search / dsa_vq_accum / dsa_vq_update / dsa_vq_lookup / dsa_vq_vjp (vector quantisation and the Linde-Buzo-Gray codebook design: nearest-codeword search on float64 sums, per-codeword counts and float64 sums in fixed-order segments without atomics, centroids with the iteration's three scalars, the lookup and the quantiser's adjoint); 0.3.6: + dsa_yingram / dsa_yingram_vjp / dsa_frame_yingram (Yingram: YIN's cumulative-mean-normalised difference function on a semitone grid, from frames or from the waveform in one launch, and its adjoint; lag sums directly or through the LDS transform); 0.3.5: + dsa_gmm_prepare / dsa_gmm_estep / dsa_gmm_accum / dsa_gmm_update / dsa_gmm_regress / dsa_gmm_transform (Gaussian mixture models: one EM iteration as factorisation, E-step, weighted moment sums and M-step on the device, and the conversion of a joint-density model); 0.3.4: + dsa_dtw / dsa_dtw_vjp / dsa_dtw_path (dynamic time warping with a soft minimum: the aligned distance of two vector sequences by an anti-diagonal wavefront, its gradient by the reverse sweep, the Viterbi path from the saved tables); 0.3.3: + DSA_ALGO_FIXED_STEPS (the tuned mel-cepstral forward stops a frame's Newton iteration once its update is rounding noise; the flag runs every step); 0.3.2: + dsa_delta / dsa_delta_vjp, dsa_mlpg, dsa_mcpf / dsa_mcpf_vjp (parameter generation: delta features, maximum likelihood parameter generation by a banded Cholesky solve, mel-cepstrum postfiltering in closed form); 0.3.1: + dsa_mdct_analysis / dsa_mdct_synthesis (MDCT / MDST and their inverses: window, fold, DCT-IV through a quarter-length complex FFT and overlap-add in one launch each way; each is the other's adjoint); 0.3.0: + dsa_excite (pitch to excitation: the voiced shapes of ExcitationGeneration on a segmented float64 phase sum, one launch); 0.2.9: + dsa_mlsacheck / dsa_mlsacheck_vjp (the stability check of the MLSA filter: the mel-cepstrum scaled or clipped where the amplitude of its gain-free part passes the threshold of the Pade approximation, forward and adjoint); 0.2.8: + dsa_lpc2lsp_fwd / _bwd, dsa_lsp2lpc_fwd / _bwd, dsa_lspcheck_fwd / _bwd (line spectral pairs by a Chebyshev-series root search, back by a product of real sections, and their stability check, forward and adjoint); 0.2.7: + dsa_lpc2par_fwd / _bwd, dsa_par2lpc_fwd / _bwd, dsa_lpccheck_fwd / _bwd (the step-down and step-up recursions between LPC and PARCOR coefficients and the stability check built from them, forward and adjoint); 0.2.6: + dsa_pqmf_fwd / _bwd, dsa_ipqmf_fwd / _bwd (pseudo-QMF analysis and synthesis with decimation / interpolation folded in), dsa_interpolate_fwd / _bwd; 0.2.5: + dsa_plp_fwd / dsa_plp_bwd (PLP after the filter bank, forward and adjoint); 0.2.4: + dsa_poledf_fwd / dsa_poledf_bwd (the time-variant all-pole filter, forward and adjoint); 0.2.3: + DSA_ALGO_RESERVE_CUS; a zero count is a no-op before any pointer check; 0.2.2: + dsa_mcep_newton_glogx_h (glogx of the 48 kHz analysis in one pass after the sweep; dsa_mcep_newton_resid_h_bwd takes glogx = NULL); twin workgroups in dsa_mcep_newton_steps; 0.2.1: + dsa_mcep_resid_bwd_images_bytes / _prepare, dsa_mcep_newton_resid_h_bwd (the 48 kHz analysis with a gradient: the step's backward in two launches); wide tiles in dsa_mcep_newton_steps; 0.2.0: + dsa_mcep_newton_steps, dsa_stft_mcep_opts_fwd, DSA_ALGO_OVERLAPPED_LAUNCHES, DSA_ALGO_PAD_MODE, packed STFT kernels for fft_length 1024 / 2048 and for every pad mode at 512; 0.1.9: + dsa_mgcep_step_solve, dsa_mgcep_step_bwd_h, dsa_mcep_resid_images_bytes / _prepare, dsa_mcep_newton_resid_h; 0.1.8: + dsa_frame_window_lpc_bwd, DSA_LPC_EXACT_LAGSUMS, DSA_ALGO_HIST_HAS_RT; 0.1.7: + dsa_gnorm_fwd, dsa_mgcep_gain, DSA_LPC_SCRATCH_IS_CLEAN; 0.1.6: + dsa_mcep_newton_update_bwd; 0.1.5: + dsa_mcep_newton_resid; 0.1.4: dsa_stft_mcep_fwd (STFT -> mel-cepstrum in one launch), dsa_rows_gemm, dsa_rows_ew, dsa_mcep_newton_update */
 
 typedef enum {
     DSA_OK = 0,
@@ -1163,6 +1163,7 @@ int dsa_ap_tandem_vjp(const void* gy, const void* bands, int64_t ldb, const void
  *                              the eight steps for the cotangent gy:(B,N,K); a frame's row is zero outside |j| <= h.  No gradient reaches f0.
  *   dsa_pitch_spec_vjp_gather  gx:(B,T) of the dtype, every element written: one thread per sample adds, in ascending frame order, the frames
  *                              that cover it; samples 0 and T - 1 also collect what the replicate padding sent to them, a workgroup each.
+ *                              T = 1 (one frame): the padding clamps all L columns to the one sample, and gx is their sum (since 0.4.2).
  * dsa_last_kernel(): "pitch_spec_f32", "pitch_spec_vjp_frames_f32", "pitch_spec_vjp_gather_f32" and the same with f64.
  * DSA_ERR_INVALID_ARGUMENT with a message that names "pitch_spec": a negative size, an unknown dtype, an L that is no power of two (the
  * reference takes any length >= 1024; WORLD itself uses powers of two) or below 16, DSA_PITCH_SPEC_LDS_BYTES(L) >

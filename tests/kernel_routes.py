@@ -593,6 +593,9 @@ PINNED_ELSEWHERE = {
     # kApRoutes (csrc/ap.hip): as WorldSynthesis -- the forward ends in the tandem kernel
     **{f"ap_tandem_{d}": "tests/test_gpu_ap.py::test_parity_with_the_reference" for d in BOTH},
     **{f"ap_{e}_{d}": "tests/test_gpu_ap.py::test_every_launch_names_its_kernel" for e in ("qmf", "qmf_vjp", "tandem_vjp") for d in BOTH},
+    # csrc/pitch_spec.hip keeps no table: each entry picks its pair into a local and hands it to ps_launch (FORWARDED below).  The backward
+    # runs on autograd's thread, so the test calls the three entries one by one
+    **{f"pitch_spec{e}_{d}": "tests/test_gpu_pitch_spec.py::test_every_launch_names_its_kernel" for e in ("", "_vjp_frames", "_vjp_gather") for d in BOTH},
 }
 
 # names passed to a shared launcher as an argument, or kept in a local before the call: name -> "csrc/<file>::<function that spells it>"
@@ -600,6 +603,7 @@ FORWARDED = {
     "mlsacheck_generic_fwd": "csrc/mlsacheck.hip::mlsacheck_generic_launch", "mlsacheck_generic_bwd": "csrc/mlsacheck.hip::mlsacheck_generic_launch",
     "fbank_mfma_fwd": "csrc/fbank.hip::fbank_mfma_launch", "fbank_dct_mfma_fwd": "csrc/fbank.hip::dsa_fbank_dct_fwd", "freqt_mfma_fwd": "csrc/mcep.hip::dsa_freqt_fwd",
     "fftcep_mfma_fwd": "csrc/fftcep.hip::dsa_fftcep_fwd",
+    **{f"pitch_spec{e}_{d}": f"csrc/pitch_spec.hip::dsa_pitch_spec{e}" for e in ("", "_vjp_frames", "_vjp_gather") for d in BOTH},
 }
 
 EXEMPT = {

@@ -103,22 +103,41 @@ def one_frame(xrow, n, f, P, sr, L, eps, floor, q1, fmt, n1, n2, noise_eps, gy):
     return y, gu * w * mask
 
 
-def pitch_spec(x, f0, P, sr, L, *, default_f0=500, q1=-0.15, eps=0.0, relative_floor=None, out_format=3, noise1=None, noise2=None,
-               noise_eps=float(np.finfo(np.float64).eps), gy=None):
-    """x:(B, T), f0:(B, N), noise1:(B, N, L), noise2:(B, N, K) -> (y:(B, N, K), gx:(B, T) or None), float64"""
-    x, f0 = np.asarray(x, np.float64), np.asarray(f0, np.float64)
+def _frames(x, f0, P, sr, L, default_f0, q1, eps, relative_floor, out_format, noise1, noise2, noise_eps, gy):
+    """(y:(B, N, K), cot:(B, N, L) or None): one_frame over every frame of x:(B, T), f0:(B, N)"""
     (B, T), N, K = x.shape, f0.shape[1], L // 2 + 1
     fmt = FORMATS[out_format]
     floor = 0.0 if relative_floor is None else 10 ** (relative_floor / 10)
     f_min = 3 * sr / (L - 3)
     y = np.zeros((B, N, K))
-    gx = None if gy is None else np.zeros((B, T))
+    cot = None if gy is None else np.zeros((B, N, L))
     for bi in range(B):
         for n in range(N):
             f = default_f0 if f0[bi, n] <= f_min else f0[bi, n]
             n1 = np.zeros(L) if noise1 is None else np.asarray(noise1[bi, n], np.float64)
             n2 = np.zeros(K) if noise2 is None else np.asarray(noise2[bi, n], np.float64)
-            y[bi, n], cot = one_frame(x[bi], n, float(f), P, sr, L, eps, floor, q1, fmt, n1, n2, noise_eps, None if gy is None else gy[bi, n])
-            if cot is not None:
-                np.add.at(gx[bi], np.clip(n * P + np.arange(L) - L // 2, 0, T - 1), cot)
+            y[bi, n], c = one_frame(x[bi], n, float(f), P, sr, L, eps, floor, q1, fmt, n1, n2, noise_eps, None if gy is None else gy[bi, n])
+            if c is not None:
+                cot[bi, n] = c
+    return y, cot
+
+
+def pitch_spec(x, f0, P, sr, L, *, default_f0=500, q1=-0.15, eps=0.0, relative_floor=None, out_format=3, noise1=None, noise2=None,
+               noise_eps=float(np.finfo(np.float64).eps), gy=None):
+    """x:(B, T), f0:(B, N), noise1:(B, N, L), noise2:(B, N, K) -> (y:(B, N, K), gx:(B, T) or None), float64"""
+    x, f0 = np.asarray(x, np.float64), np.asarray(f0, np.float64)
+    (B, T), N = x.shape, f0.shape[1]
+    y, cot = _frames(x, f0, P, sr, L, default_f0, q1, eps, relative_floor, out_format, noise1, noise2, noise_eps, gy)
+    gx = None if gy is None else np.zeros((B, T))
+    for bi in range(B if gy is not None else 0):
+        for n in range(N):
+            np.add.at(gx[bi], np.clip(n * P + np.arange(L) - L // 2, 0, T - 1), cot[bi, n])
     return y, gx
+
+
+def frame_cotangents(x, f0, P, sr, L, gy, *, default_f0=500, q1=-0.15, eps=0.0, relative_floor=None, out_format=3, noise1=None, noise2=None,
+                     noise_eps=float(np.finfo(np.float64).eps)):
+    """(B, N, L) float64: every frame's cotangent before the clamp, one_frame's second result -- what dsa_pitch_spec_vjp_frames writes
+    to its scratch and pitch_spec() above adds into gx"""
+    x, f0 = np.asarray(x, np.float64), np.asarray(f0, np.float64)
+    return _frames(x, f0, P, sr, L, default_f0, q1, eps, relative_floor, out_format, noise1, noise2, noise_eps, np.asarray(gy, np.float64))[1]

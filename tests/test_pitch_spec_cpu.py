@@ -87,6 +87,47 @@ def test_the_tie_margins():
     assert (f0 <= 3 * 16000 / 1021).any() and (f0 > 3 * 16000 / 1021).any()
 
 
+@pytest.mark.parametrize("name", list(A.EDGE_CASES))
+def test_the_edge_cases_keep_their_margins_and_a_bound_that_says_something(name):
+    """the cases below 1024 points and up to Nyquist (tests/test_gpu_pitch_spec_edges.py runs the kernels on them): what they are meant
+    to reach, the three tie margins, and -- so that 64 D_ulp cannot go vacuous -- a finite restatement whose float64 bounds are at most
+    1e-10, for y and gx and for the frames' cotangents, in both modes"""
+    B, N, T, L, K = A.edge_sizes(name)
+    c = A.EDGE_CASES[name]
+    sr, P = c["sr"], c["P"]
+    x, f0 = A.edge_inputs(name)
+    assert (B, N) == (2, 7) and x.shape == (2, T) and f0.shape == (2, 7) and T == N * P and N == (T - 1) // P + 1
+    assert np.array_equal(np.round(f0.astype(np.float64) * 8), f0.astype(np.float64) * 8) and f0.max() <= 0.49 * sr
+    assert min(A.edge_margins(name)) >= A.MARGIN, A.edge_margins(name)
+    assert (sr / 4) / (sr / L) == L // 4   # the default F0 is a bin exactly: `k rate < f` is exactly false there in every precision
+    f_min = 3 * sr / (L - 3)
+    f = np.where(f0 <= f_min, sr / 4, f0.astype(np.float64))
+    assert (f0 <= f_min).any() and (f0 > f_min).sum() >= 4 and (name != "L16" or (f0 <= f_min).sum() >= 4)
+    # near Nyquist the DC mask covers nearly every bin and the mirror is a third of the spectrum; just above f_min the window is widest
+    consts = [pitch_spec_ref.frame_constants(float(v), sr, L) for v in f.flatten()]
+    top = pitch_spec_ref.frame_constants(float(f.max()), sr, L)
+    assert top[1] >= 0.43 * L and top[3] >= 0.32 * L and all(0 <= t[0] <= L // 2 - 1 and t[3] <= K - 1 and t[6] + 1 <= 2 * t[3] for t in consts)
+    assert max(t[0] for t in consts) >= 0.8 * (L // 2 - 1)
+    for mode in A.EDGE_MODES:
+        r = A.edge_reference(name, mode)
+        assert r["y"].shape == (B, N, K) and r["gx"].shape == (B, T) and r["cot"].shape == (B, N, L)
+        assert all(np.isfinite(r[k]).all() and np.abs(r[k]).max() > 0 for k in ("y", "gx", "cot"))
+        print(f"{name} {mode}: D_ulp {r['D_ulp']:.3g} (bound {r['bound']:.3g}), on the frames' cotangents {r['D_cot']:.3g} (bound {r['bound_cot']:.3g})")
+        assert 64 * 2.0 ** -53 <= r["bound"] <= 1e-10 and 64 * 2.0 ** -53 <= r["bound_cot"] <= 1e-10
+        # the helper returns what pitch_spec() adds into gx: the clipped scatter-add of the rows is gx to the bit
+        gx = np.zeros((B, T))
+        for b in range(B):
+            for n in range(N):
+                np.add.at(gx[b], np.clip(n * P + np.arange(L) - L // 2, 0, T - 1), r["cot"][b, n])
+        assert np.array_equal(gx, r["gx"])
+
+
+def test_the_edge_cases_cover_the_workgroup_size():
+    """256 threads: L / 4 butterflies, K bins and L samples below it (16, 64), L at it (256), K above it (512), L / 4 at it (1024)"""
+    assert [c["L"] for c in A.EDGE_CASES.values()] == [16, 64, 256, 512, 1024]
+    assert re.search(r"constexpr int PS_THREADS = 256;", UNIT) and "L >= 16" in UNIT
+
+
 def signature(f):
     return [[p.name, p.kind.name, None if p.default is inspect._empty else repr(p.default)] for p in inspect.signature(f).parameters.values()]
 
@@ -155,12 +196,21 @@ def test_the_two_ceilings():
     assert lib.dsa_pitch_spec(*args(8192)) == _lib.ERR_INVALID_ARGUMENT
     assert "DSA_PITCH_SPEC_LDS_BYTES(fft_length) = 28 fft_length + 280 bytes exceed DSA_PITCH_SPEC_MAX_LDS_BYTES" in lib.dsa_last_error().decode()
     assert lib.dsa_pitch_spec(*args(3000)) == _lib.ERR_INVALID_ARGUMENT and "power of two" in lib.dsa_last_error().decode()
+    # the batch is the grid's y: 65535 utterances pass the sizes (and stop at the null pointer), 65536 are refused before any pointer
+    gather = lambda B: lib.dsa_pitch_spec_vjp_gather(None, B, 3, 5, 2, 16, _lib.F64, None, None)  # noqa: E731
+    assert gather(65535) == _lib.ERR_INVALID_ARGUMENT and lib.dsa_last_error().decode() == "pitch_spec: null pointer"
+    assert gather(65536) == _lib.ERR_INVALID_ARGUMENT
+    assert lib.dsa_last_error().decode() == "pitch_spec: invalid sizes (B N frames must fit one grid dimension)"
+    small = (None, None, None, None, None, 65536, 3, 5, 2, 256, 16, 64.0, -0.15, 0.0, 0.0, 3, _lib.F64, None, None)
+    assert lib.dsa_pitch_spec(*small) == _lib.ERR_INVALID_ARGUMENT
+    assert lib.dsa_last_error().decode() == "pitch_spec: invalid sizes (B N frames must fit one grid dimension)"
 
 
 def test_the_header_has_the_section():
     header = open(_lib.HEADER).read()
-    assert int(re.search(r"#define DSA_VERSION (\d+)", header).group(1)) >= 147 and _lib.VERSION >= 147
+    assert int(re.search(r"#define DSA_VERSION (\d+)", header).group(1)) >= 148 and _lib.VERSION >= 148
     assert re.search(r"a26\s+Pitch-adaptive spectral envelope", header)
+    assert re.search(r"T = 1 \(one frame\): the padding clamps all L columns to the one sample, and gx is their sum", header)   # 148
     for name, n_args in (("dsa_pitch_spec", 19), ("dsa_pitch_spec_vjp_frames", 20), ("dsa_pitch_spec_vjp_gather", 9)):
         assert re.search(rf"\bint {name}\(", header) and name in _lib.SIGNATURES and hasattr(_lib.load(), name), name
         assert len(_lib.SIGNATURES[name][1]) == n_args, name
@@ -217,7 +267,11 @@ def test_the_unit_fits_in():
     assert re.search(r"int ps_launch\(const char\* route\b[^{]*\{[^}]*check_launch\(route\)", UNIT)
     import kernel_routes as KR
 
-    assert not set(ROUTES) & (set(KR.ROUTES) | set(KR.PINNED_ELSEWHERE) | set(KR.EXEMPT) | set(KR.FORWARDED))   # the table is as it was
+    # the six names are registered: pinned by the test that calls the three entries, and forwarded from the entry that spells each
+    assert all(KR.PINNED_ELSEWHERE[r] == "tests/test_gpu_pitch_spec.py::test_every_launch_names_its_kernel" for r in ROUTES)
+    assert all(KR.FORWARDED[r] == "csrc/pitch_spec.hip::dsa_" + r[:-4] for r in ROUTES)
+    assert not set(ROUTES) & (set(KR.ROUTES) | set(KR.EXEMPT))
+    assert RC.argument_problems({"pitch_spec.hip": UNIT}, KR.FORWARDED) == []
 
 
 def test_every_route_name_is_pinned_by_a_gpu_test_that_reads_last_kernel():

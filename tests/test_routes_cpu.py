@@ -1,6 +1,7 @@
 """Completeness of the kernel-route table (tests/kernel_routes.py), checked without a GPU: every name a launcher of
 diffsptk_amd/csrc hands to check_launch() is a key of exactly one of ROUTES, PINNED_ELSEWHERE and EXEMPT; a pointer of
-PINNED_ELSEWHERE names a test function that reads last_kernel(); every measured tolerance has its base values in the table; and the
+PINNED_ELSEWHERE names a test function that reads last_kernel(); every check_launch() argument that is neither a literal nor a name
+table is followed to the literals assigned to it, or to a FORWARDED anchor in its file; every measured tolerance has its base values in the table; and the
 inputs of every case keep the float64 restatement itself well inside the case's bound (tests/routes_ref.py evaluated twice).  The
 same for the refusals: every DSA_ERR_UNSUPPORTED of the sources is claimed by exactly one of REFUSALS, CEILINGS and NOT_A_CEILING.
 
@@ -127,6 +128,60 @@ def test_every_route_is_in_exactly_one_table(texts=TEXTS):
     for a, b in (("ROUTES", "PINNED_ELSEWHERE"), ("ROUTES", "EXEMPT"), ("PINNED_ELSEWHERE", "EXEMPT")):
         assert not tables[a] & tables[b], f"in both {a} and {b}: {sorted(tables[a] & tables[b])}"
     assert all(cases for cases in KR.ROUTES.values()), "a route of ROUTES without a case"
+
+
+def argument_problems(texts, forwarded):
+    """What test_every_check_launch_argument_is_accounted_for reports, as sentences that name the file and the route: every argument of
+    a check_launch(...) call either holds a literal or names a name table (collected() has those), or is an identifier V.  If the file
+    assigns V (`V = ...;`, a declaration included), every literal of the right-hand sides is a collected name or a key of `forwarded`;
+    a name table there counts as collected.  If the file never assigns V, V is a parameter, and an anchor of `forwarded` points into
+    the file: the callers' names are then held by test_forwarded_names_are_spelled_where_the_table_says."""
+    names, out = collected(texts), []
+    for file, text in sorted(texts.items()):
+        code = re.sub(r"//[^\n]*", "", text)
+        tables = name_tables(code)
+        for arg in sorted(set(launch_arguments(code))):
+            arg = arg[:-1].strip()
+            if re.fullmatch(r"const\s+char\s*\*\s*\w+", arg):   # the definition of check_launch itself (csrc/common.h)
+                continue
+            if '"' in arg or any(re.search(r"\b%s\b" % t, arg) for t in tables):
+                continue
+            if not re.fullmatch(r"[A-Za-z_]\w*", arg):
+                out.append(f"{file}: check_launch({arg}) holds no literal, names no name table and is no identifier")
+                continue
+            assigned = re.findall(r"\b%s\s*=(?!=)([^;]*);" % arg, code)
+            if not assigned and not any(where.startswith(f"csrc/{file}::") for where in forwarded.values()):
+                out.append(f"{file}: check_launch({arg}) gets a parameter, and no FORWARDED anchor points into {file}")
+            for rhs in assigned:
+                for name in re.findall(r'"([^"]+)"', rhs):
+                    if name not in names and name not in forwarded:
+                        out.append(f"{file}: \"{name}\" reaches check_launch({arg}) through `{arg} = ...` and is neither collected nor in FORWARDED")
+    return out
+
+
+def test_every_check_launch_argument_is_accounted_for(texts=TEXTS):
+    """collected() reads literals inside check_launch(...) and inside name tables only: a launcher that keeps its names in a local was
+    invisible to test_every_route_is_in_exactly_one_table (csrc/pitch_spec.hip went in that way, with none of its six names in a table)"""
+    problems = argument_problems(texts, KR.FORWARDED)
+    assert not problems, "\n".join(problems)
+    # the tables as they were before the six names of csrc/pitch_spec.hip were registered: exactly those six, by file and name
+    six = sorted(f"pitch_spec{e}_{d}" for e in ("", "_vjp_frames", "_vjp_gather") for d in ("f32", "f64"))
+    before = {name: where for name, where in KR.FORWARDED.items() if name not in six}
+    assert len(before) == len(KR.FORWARDED) - 6
+    assert sorted(argument_problems(texts, before)) == [
+        f'pitch_spec.hip: "{name}" reaches check_launch(route) through `route = ...` and is neither collected nor in FORWARDED' for name in six]
+    # doctored sources: a local with an unregistered name beside a registered table, a parameter in a file nothing points into, a call
+    launcher = 'const char* const kAbNames[] = {"n0", "n1"};\nint f(int dtype)\n{\n    const char* route = dtype ? "new_f64" : "n0";\n' \
+               '    // route = "in_a_comment";\n    if (route == nullptr) route = kAbNames[1];\n    return check_launch(route);\n}\n'
+    assert argument_problems({"new.hip": launcher}, {}) == [
+        'new.hip: "new_f64" reaches check_launch(route) through `route = ...` and is neither collected nor in FORWARDED']
+    assert argument_problems({"new.hip": launcher}, {"new_f64": "csrc/new.hip::f"}) == []
+    shared = "int launch(const char* name)\n{\n    return check_launch(name);\n}\n"
+    assert argument_problems({"new.hip": shared}, {"x": "csrc/other.hip::f"}) == [
+        "new.hip: check_launch(name) gets a parameter, and no FORWARDED anchor points into new.hip"]
+    assert argument_problems({"new.hip": shared}, {"x": "csrc/new.hip::g"}) == []
+    assert argument_problems({"new.hip": "int f() { return check_launch(pick(1)); }\ninline int check_launch(const char* name);\n"}, {}) == [
+        "new.hip: check_launch(pick(1)) holds no literal, names no name table and is no identifier"]
 
 
 def test_exemptions_are_few_and_reasoned():
@@ -271,7 +326,7 @@ def test_shifted_sources_pass():
     assert unsupported_sites(moved) == down and collected(moved) == collected(TEXTS)
     _, first, last = function_span(TEXTS, "csrc/lpc.hip::acorr_fwd_impl", "-")
     assert function_span(moved, "csrc/lpc.hip::acorr_fwd_impl", "-") == ("lpc.hip", first + 3, last + 3)
-    assert len(SOURCE_CHECKS) == 8   # every test above that reads the sources takes them as `texts`
+    assert len(SOURCE_CHECKS) == 9   # every test above that reads the sources takes them as `texts`
     for check in SOURCE_CHECKS:
         check(moved)
 
